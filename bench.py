@@ -13,14 +13,18 @@ generated on the device and its phase guesses are formed the way pptoas forms th
 (dedispersed mean profile -> fit_phase_shift -> phase_transform, pptoas.py:421-457)
 before the timed region.  The TOA records of every step stay in HBM and are gathered
 ONCE, at the end of the timed region (RCCL gather of device tensors).  Rank 0 prints
-ONE JSON line; at N = 1 it also carries the other workloads (--other-steps timed
-steps after --other-warmup untimed ones each, same process), the CPU baseline of the
-headline shape and of configs[1..3] (1 core and a one-worker-per-core pool each), and,
-as its LAST key, a compact {workload: fits/s} summary of everything it measured.
+ONE JSON line.  A plain run times the headline workload alone; with --full, at N = 1,
+the line also carries the other workloads (--other-steps timed steps after
+--other-warmup untimed ones each, same process), configs[4]'s strong flow at 3000
+subints, the CPU baseline of the headline shape and of configs[1..3] (1 core and a
+one-worker-per-core pool each).  As its LAST key the line holds a compact
+{workload: fits/s} summary of everything it measured.
 
     --total-nsub 100000   configs[4] as written: the subints are dealt in contiguous
                           shards to the ranks (strong scaling) and fitted in
                           device-generated sub-batches of --nsub
+    --full                the other workloads and the CPU baseline as well (above)
+    --dump-outputs DIR    what the last timed step computed, as DIR/<name>.npy
 """
 import argparse
 import gc
@@ -406,6 +410,13 @@ def main():
                     help="--total-nsub: rank 0 saves the gathered [total, 18] records there (.npy)")
     ap.add_argument("--harm-eps", type=float, default=None,
                     help="override the harmonic-truncation threshold (experiments)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline also the other workloads, configs[4]'s strong flow at 3000 "
+                         "subints and the CPU baseline (--no-other-workloads / --no-cpu-baseline leave parts out); "
+                         "without it a run times the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed -- the fit's result arrays and TOA "
+                         "records -- as DIR/<name>.npy (float64, at most 64 MB: dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -416,7 +427,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     pool = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         pool = start_cpu_pool()         # before anything initialises the GPU
 
     import torch
@@ -535,6 +546,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         timed.piped = piped
+        timed.last_records = recs[-1]
         return res, gathered, elapsed, eng.kernel_times()
 
     def summary(batch, res, elapsed, ktimes, steps, nfits):
@@ -582,6 +594,8 @@ def main():
                   seed_ns=max(args.seed_ns, 0), reseed=(args.seed_ns < 0),
                   variant=VARIANTS[args.variant] if args.variant else None)
     res, gathered, elapsed, ktimes = timed(batch, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, timed.last_records)
 
     line = None
     if rank == 0:
@@ -650,8 +664,8 @@ def main():
                                 "return_codes": summ["return_codes"]},
                 "gathered_records": {"rows": int(rec.shape[0]),
                                      "checksum": ppdist.records_checksum(rec)["column_sums"][:3]}}
-    # ---- the other workloads, same process, --other-steps timed steps each (N = 1 only) ----
-    if world == 1 and not args.no_other_workloads:
+    # ---- the other workloads, same process, --other-steps timed steps each (N = 1 and --full only) ----
+    if world == 1 and args.full and not args.no_other_workloads:
         cpu_cases = {}
         if pool is not None:
             cpu_cases["headline"] = cpu_case(batch, res, 64)
@@ -722,7 +736,7 @@ def main():
         try:
             import copy
             sargs = copy.copy(args)
-            sargs.total_nsub, sargs.nsub, sargs.dump_records = 3000, 1024, None
+            sargs.total_nsub, sargs.nsub, sargs.dump_records, sargs.dump_outputs = 3000, 1024, None, None
             sl = strong_scaling(sargs, make_batch, sync, fence, device, rank, world, use_dist,
                                 collect=eng.collect if args.pipeline > 1 else None)
             others["strong_3000"] = {"fits_per_s": sl["value"], "ms_total": sl["ms_per_step"],
@@ -761,6 +775,45 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, res, records, limit=60e6):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy in float64 -- the step's
+    TOA records [nsub, 18] and the arrays of Engine.fit_batch's result (`res`, without its wall time and the fit
+    flags it echoes); every array runs over the subints along its first axis.  The per-channel arrays the fit
+    leaves in HBM ([nsub, nchan] each, 100 MB for the headline's three) are cut to a fixed, seeded sample of
+    subints, listed in per_channel_rows.npy, that keeps the whole under `limit` bytes; so are the per-subint
+    arrays (subint_rows.npy) should they alone not fit.  The same arguments make the same inputs, so two builds
+    can be compared file by file."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    nsub = int(records.shape[0])
+    narrow, wide = {"records": records}, {}
+    for k, v in res.items():
+        if k not in ("duration", "fit_flags"):
+            (wide if torch.is_tensor(v) else narrow)[k] = v
+
+    def save(group, tag, room):
+        row_bytes = sum(8 * int(np.prod(v.shape[1:])) for v in group.values())
+        k = min(nsub, max(1, int(room - 8 * nsub) // max(1, row_bytes)))     # (8 * nsub: the list of rows)
+        rows = np.arange(nsub)
+        if k < nsub:
+            rows = np.sort(np.random.default_rng(20260101).choice(nsub, k, replace=False))
+            np.save(os.path.join(out_dir, tag + "_rows.npy"), rows.astype(np.float64))
+        idx = None
+        for name, v in group.items():
+            if torch.is_tensor(v):
+                if idx is None:
+                    idx = torch.from_numpy(rows).to(v.device)
+                a = v.index_select(0, idx).cpu().numpy()
+            else:
+                a = np.asarray(v)[rows]
+            np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+        return k * row_bytes + (8 * nsub if k < nsub else 0)
+
+    used = save(narrow, "subint", limit)
+    if wide:
+        save(wide, "per_channel", limit - used)
 
 
 def strong_scaling(args, make_batch, sync, fence, device, rank, world, use_dist, collect=None):
@@ -864,6 +917,8 @@ def strong_scaling(args, make_batch, sync, fence, device, rank, world, use_dist,
     rec = gathered.cpu().numpy() if hasattr(gathered, "cpu") else np.asarray(gathered)
     if getattr(args, "dump_records", None):
         np.save(args.dump_records, rec)
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {}, rec)        # (the job's one step: what the caller gets is the gathered records)
     cs = ppdist.records_checksum(rec)
     return {
         "metric": "subint_fits_per_sec", "value": round(args.total_nsub / total_s, 2),

@@ -82,6 +82,8 @@ def pytest_collection_finish(session):
                    "--gpus", "1", "--no-cpu-baseline"] + extra
             if tag == "strong":
                 cmd += ["--dump-records", r1]
+            else:
+                cmd += ["--dump-outputs", os.path.join(tmp, "outputs1_weak")]
             env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
             env.pop("PP_BENCH_SHARE_GPU", None)
             p1 = subprocess.Popen(cmd, stdout=o, stderr=e, cwd=ROOT, env=env)

@@ -249,6 +249,44 @@ def test_bench_main_takes_the_self_launch_branch_before_torch():
     assert "start_cpu_pool()" in body and body.index("self_launch(args.gpus") < body.index("start_cpu_pool()")
 
 
+def test_dump_outputs_keeps_a_fixed_sample_under_64_mb(tmp_path):
+    """bench.dump_outputs (--dump-outputs): the headline step's result arrays as float64 .npy files under 64 MB --
+    the per-subint arrays whole, the per-channel ones the fit leaves in HBM cut to a seeded sample of subints that
+    is the same from run to run; the wall time and the echoed fit flags are no outputs.  A records-only dump that
+    is too large (the strong flow) is sampled the same way."""
+    import torch
+    import bench
+    nsub, nchan = 1024, 4096
+    rng = np.random.default_rng(7)
+    res = dict(params=rng.random((nsub, 5)), cov=rng.random((nsub, 5, 5)), nfeval=np.arange(nsub, dtype=np.int32),
+               duration=1.5, fit_flags=[1, 1, 0, 0, 0],
+               **{k: torch.from_numpy(rng.random((nsub, nchan))) for k in ("scales", "scale_errs", "channel_snrs")})
+    records = torch.from_numpy(rng.random((nsub, ppdist.RECORD_WIDTH)))
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        bench.dump_outputs(str(d), res, records)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(["records.npy", "params.npy", "cov.npy", "nfeval.npy", "scales.npy", "scale_errs.npy",
+                            "channel_snrs.npy", "per_channel_rows.npy"])
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64e6
+    for n in names:
+        a = np.load(dirs[0] / n)
+        assert a.dtype == np.float64
+        np.testing.assert_array_equal(a, np.load(dirs[1] / n))
+    np.testing.assert_array_equal(np.load(dirs[0] / "records.npy"), records.numpy())
+    np.testing.assert_array_equal(np.load(dirs[0] / "cov.npy"), res["cov"])
+    np.testing.assert_array_equal(np.load(dirs[0] / "nfeval.npy"), np.arange(nsub))
+    rows = np.load(dirs[0] / "per_channel_rows.npy").astype(np.int64)
+    assert 256 <= len(rows) < nsub and (np.diff(rows) > 0).all() and rows[-1] < nsub
+    for k in ("scales", "scale_errs", "channel_snrs"):
+        np.testing.assert_array_equal(np.load(dirs[0] / (k + ".npy")), res[k].numpy()[rows])
+    big = rng.random((500000, ppdist.RECORD_WIDTH))
+    bench.dump_outputs(str(tmp_path / "strong"), {}, big)
+    rows = np.load(tmp_path / "strong" / "subint_rows.npy").astype(np.int64)
+    np.testing.assert_array_equal(np.load(tmp_path / "strong" / "records.npy"), big[rows])
+    assert sum(os.path.getsize(tmp_path / "strong" / n) for n in os.listdir(tmp_path / "strong")) <= 64e6
+
+
 def test_record_layout_matches_the_c_abi():
     """RECORD_FIELDS is the layout k_finalize writes into pp_fit_out.records_dev
     (include/pp_toas.h PP_RECORD_WIDTH)."""

@@ -170,6 +170,17 @@ def test_rccl_backend_with_one_rank():
     np.testing.assert_allclose(2.0 * mine[:, :3].sum(axis=0), w["gathered_records"]["checksum"], rtol=1e-12)
     np.testing.assert_allclose(mine[:, :13], rec[:256, :13], rtol=1e-13, atol=1e-15)
     np.testing.assert_allclose(mine[:, 13:16], rec[:256, 13:16], rtol=1e-11)
+    # the weak job's --dump-outputs: its last timed step's records and result arrays (float64), which are those fits
+    d = os.path.join(BENCH_CHILD["tmp"], "outputs1_weak")
+    drec = np.load(os.path.join(d, "records.npy"))
+    assert drec.dtype == np.float64 and drec.shape == (256, ppdist.RECORD_WIDTH)
+    np.testing.assert_allclose(2.0 * drec[:, :3].sum(axis=0), w["gathered_records"]["checksum"], rtol=1e-12)
+    np.testing.assert_array_equal(np.load(os.path.join(d, "params.npy")), drec[:, :5])
+    np.testing.assert_allclose(mine[:, :13], drec[:, :13], rtol=1e-13, atol=1e-15)
+    np.testing.assert_allclose(mine[:, 13:16], drec[:, 13:16], rtol=1e-11)
+    scales = np.load(os.path.join(d, "scales.npy"))       # (256 x 4096 x 3 per-channel values: no sample needed)
+    assert scales.shape == (256, w["config"]["nchan"]) and np.isfinite(scales).all()
+    assert not os.path.exists(os.path.join(d, "per_channel_rows.npy"))
     b.free()
     b = bench.Batch(eng, ns, dev, s["config"]["workload"], 220, "f64", 1280)
     out = torch.zeros((220, ppdist.RECORD_WIDTH), dtype=torch.float64, device=dev)

@@ -8,8 +8,8 @@ export TMPDIR=/tmp
 R=${1:-r03}
 O=gpurun_out/profiles_$R
 rm -rf $O; mkdir -p $O/raw
-# the driver's command: headline + other workloads + CPU baseline in one line
-python3 bench.py > $O/${R}_bench.json 2> $O/raw/bench.err
+# the full benchmark: headline + other workloads + CPU baseline in one line
+python3 bench.py --full > $O/${R}_bench.json 2> $O/raw/bench.err
 # profiled passes: headline only (no CPU pool: nothing may be spawned under rocprofv3)
 B="python3 bench.py --no-cpu-baseline --no-other-workloads"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw/trace -- $B --steps 3 --warmup 1 > $O/${R}_bench_under_rocprof.json 2> $O/raw/trace.err
