@@ -246,6 +246,145 @@ def _take_subints(subints, ok_isubs):
     return np.ascontiguousarray(a[idx, 0])
 
 
+def _load_or_skip(datafile, quiet):
+    """(DataBunch, name) of an archive, or None for one get_TOAs skips: it cannot be
+    loaded, or it has no subint to fit."""
+    try:
+        data, fname = _load(datafile)
+    except RuntimeError as err:
+        if not quiet:
+            print("Cannot load_data(%s).  Skipping it." % datafile)
+            print(err)
+        return None
+    if not len(data.ok_isubs):
+        if not quiet:
+            print("No subints to fit for %s.  Skipping it." % fname)
+        return None
+    return data, fname
+
+
+def _good_channel_counts(datafile):
+    """Good-channel counts of an archive's good subints, from its weights alone (the
+    portraits are not read); [] for an archive get_TOAs cannot load."""
+    if isinstance(datafile, dict):
+        return [len(datafile["ok_ichans"][i]) for i in datafile["ok_isubs"]]
+    if not str(datafile).endswith(".npz"):
+        return []
+    with np.load(datafile, allow_pickle=True) as z:
+        if "weights" in z.files:
+            counts = (np.asarray(z["weights"], dtype=np.float64) > 0).sum(axis=-1)
+        else:               # (data_from_arrays: every channel of every subint is good)
+            with z.zip.open("subints.npy") as f:
+                version = np.lib.format.read_magic(f)
+                read = np.lib.format.read_array_header_1_0 if version == (1, 0) else \
+                    np.lib.format.read_array_header_2_0
+                shape = read(f)[0]
+            counts = np.full(shape[0], shape[-2])
+    return [int(c) for c in np.atleast_1d(counts) if c > 0]
+
+
+def subint_fit_flags(nchans, fit_flags, carry=None):
+    """The fit flags of a run of good subints with `nchans` good channels each, as the
+    reference sets them (pptoas.py:475-486): a one-channel subint is fitted for phase
+    only; a two-channel subint under fit_DM and fit_GM takes the list LEFT OVER from the
+    subint before it (`carry`, across archives too) with GM dropped -- the flags asked
+    for with GM dropped when there is none (the first subint of a call, where the
+    reference raises NameError).  Returns (list of flag tuples, carry-out)."""
+    out = []
+    for n in nchans:
+        if n == 1:
+            fl = [1, 0, 0, 0, 0]
+        elif n == 2 and fit_flags[1] and fit_flags[2]:
+            # (SURVEY App. C-8: right after a one-channel subint the left-over list is [1,0,0,0,0] and the
+            # two-channel subint is fitted for phase only; after a normal one it becomes phase + DM)
+            fl = list(carry) if carry is not None else list(fit_flags)
+            fl[2] = 0
+        else:
+            fl = list(fit_flags)
+        carry = fl
+        out.append(tuple(fl))
+    return out, carry
+
+
+def deltadm_mean(DMs, DM_errs, DM0, ok_isubs):
+    """Weighted mean DM offset of an archive and its error (pptoas.py:665-682)."""
+    DeltaDMs = DMs - DM0
+    if np.all(DM_errs[ok_isubs]):
+        DM_weights = DM_errs[ok_isubs] ** -2
+    else:
+        DM_weights = np.ones(len(ok_isubs))
+    DeltaDM_mean, DeltaDM_var = np.average(DeltaDMs[ok_isubs], weights=DM_weights,
+                                           returned=True)
+    DeltaDM_var = DeltaDM_var ** -1
+    if len(ok_isubs) > 1:
+        DeltaDM_var *= np.sum(((DeltaDMs[ok_isubs] - DeltaDM_mean) ** 2) *
+                              DM_weights) / (len(ok_isubs) - 1)
+    return DeltaDM_mean, DeltaDM_var ** 0.5
+
+
+def shard_plan(n_archives, rank, world):
+    """What a rank of a sharded get_TOAs walks: ("archives", lo, hi) -- a contiguous
+    block of whole archives -- when there are at least as many archives as ranks, else
+    ("subints", 0, n_archives): every archive, fitting shard_subints of each."""
+    from .dist import shard_range
+    if n_archives >= world:
+        return ("archives",) + shard_range(n_archives, rank, world)
+    return ("subints", 0, n_archives)
+
+
+def shard_subints(mode, nok, rank, world):
+    """[j0, j1) of an archive's `nok` good subints that a rank fits under `mode`."""
+    from .dist import shard_range
+    return (0, nok) if mode == "archives" else shard_range(nok, rank, world)
+
+
+def _process_group():
+    try:
+        import torch.distributed as tdist
+    except ImportError:
+        tdist = None
+    if tdist is None or not (tdist.is_available() and tdist.is_initialized()):
+        raise ValueError("get_TOAs(distributed=True) needs an initialised torch.distributed "
+                         "process group")
+    return tdist.get_rank(), tdist.get_world_size()
+
+
+def _archive_meta(d, fname, DM0):
+    """The per-archive entries of the result lists that do not come from the fit."""
+    return dict(fname=fname, obs=DataBunch(telescope=d.telescope, backend=d.backend, frontend=d.frontend),
+                doppler_fs=d.doppler_factors, nu0=d.nu0, ok_isubs=np.asarray(d.ok_isubs, dtype=int),
+                epochs=d.epochs, MJDs=np.array([e.in_days() for e in d.epochs], dtype=np.double),
+                Ps=d.Ps, DM0=d.DM if DM0 is None else DM0)
+
+
+# the result lists that hold one per-subint array (or list) per archive, filled by the bookkeeping
+_ARCHIVE_ARRAYS = ("nu_fits", "nu_refs", "phis", "phi_errs", "TOAs", "TOA_errs", "DMs", "DM_errs", "GMs",
+                   "GM_errs", "taus", "tau_errs", "alphas", "alpha_errs", "scales", "scale_errs", "snrs",
+                   "channel_snrs", "profile_fluxes", "profile_flux_errs", "fluxes", "flux_errs", "flux_freqs",
+                   "covariances", "red_chi2s", "nfevals", "rcs")
+
+
+def merge_blocks(blocks):
+    """One archive rebuilt from the blocks of the ranks that fitted its subints (in rank
+    order, i.e. subint order): each block carries its subints' rows of the per-subint
+    arrays.  Returns (arrays, TOAs, summed fit duration, meta)."""
+    meta, nsub = blocks[0]["meta"], blocks[0]["nsub"]
+    arrays = {}
+    for name, v in blocks[0]["arrays"].items():
+        if isinstance(v, list):
+            full = list(np.zeros([nsub, 3]))
+            for b in blocks:
+                for i, row in zip(b["rows"], b["arrays"][name]):
+                    full[i] = row
+        else:
+            full = np.zeros((nsub,) + v.shape[1:], dtype=v.dtype)
+            for b in blocks:
+                full[b["rows"]] = b["arrays"][name]
+        arrays[name] = full
+    toas = [t for b in blocks for t in b["toas"]]
+    return arrays, toas, sum(b["fit_duration"] for b in blocks), meta
+
+
 class GetTOAs(object):
     """Measure wideband TOAs and DMs (pptoas.py:75-1419, the get_TOAs path)."""
 
@@ -387,10 +526,10 @@ class GetTOAs(object):
                  print_phase=False, print_flux=False, print_parangle=False,
                  add_instrumental_response=False, addtnl_toa_flags={},
                  method='trust-ncg', bounds=None, nu_fits=None, show_plot=False,
-                 quiet=None, seed='reference'):
-        """Same arguments as the reference (pptoas.py:150-156), plus `seed`.  Not
-        supported here: tscrunch and show_plot (they raise) -- they live in PSRCHIVE /
-        the plotting code.
+                 quiet=None, seed='reference', distributed=False):
+        """Same arguments as the reference (pptoas.py:150-156), plus `seed` and
+        `distributed`.  Not supported here: tscrunch and show_plot (they raise) -- they
+        live in PSRCHIVE / the plotting code.
 
         seed='reference' (default -- a drop-in returns the reference's numbers): the
         reference's initial guesses, formed the way it forms them (pptoas.py:421-457:
@@ -404,13 +543,30 @@ class GetTOAs(object):
         the fit (the exact maximum of the channel-summed cross-correlation on a pilot subset
         of the channels) and every `method` runs the Newton solver to the rounding of the
         objective -- the optimum itself, within ~1e-9 rot of wherever SciPy's iteration
-        stops from the reference's own starting point."""
+        stops from the reference's own starting point.
+
+        distributed=True shards the work over the ranks of an initialised
+        torch.distributed process group (ValueError if there is none; a world of one is
+        the single-process path).  Every rank fits on
+        default_engine(LOCAL_RANK % torch.cuda.device_count()).  With at least as many
+        archives as ranks, each rank takes a contiguous block of archives
+        (dist.shard_range); otherwise every rank reads every archive and fits a
+        contiguous block of its good subints.  Each rank does the TOA bookkeeping of its
+        own subints; one gather brings the per-archive blocks to rank 0, which rebuilds
+        every archive, forms DeltaDM_means / DeltaDM_errs from the merged DMs and fills
+        the result lists and TOA_list exactly as a one-process run would
+        (fit_durations: the sum over the ranks).  On the other ranks the result lists
+        stay EMPTY.  A rank that raises reaches the gather with an error record: rank 0
+        then raises RuntimeError naming it, and the failing rank re-raises its own error.
+        Bit equality with the one-process run rests on a subint's answer not depending
+        on the batch it is fitted in."""
         if quiet is None:
             quiet = self.quiet
         if tscrunch or show_plot:
             raise NotImplementedError("tscrunch / plots are outside the accelerated path")
         if seed not in ('device', 'reference'):
             raise ValueError("seed must be 'device' or 'reference'")
+        rank, world = _process_group() if distributed else (0, 1)
         use_ird = bool(add_instrumental_response and
                        (self.ird['DM'] or len(self.ird['wids'])))
         if method not in ('trust-ncg', 'Newton-CG', 'TNC'):
@@ -425,180 +581,26 @@ class GetTOAs(object):
                           int(self.fit_alpha)]
         self.log10_tau = log10_tau if fit_scat else False
         log10_tau = self.log10_tau
-        if (self.fit_GM or fit_scat) and not quiet:
+        if (self.fit_GM or fit_scat) and not quiet and rank == 0:
             print("You are using an experimental functionality of pptoas!")
         self.scat_guess = scat_guess
         self.DM0, self.bary = DM0, bary
         self.tscrunch = tscrunch
         self.add_instrumental_response = add_instrumental_response
-        start = time.time()
-        datafiles = self.datafiles if datafile is None else [datafile]
-        eng = default_engine()
-        last_fl = None          # (the reference's `fit_flags` variable lives across subints AND archives of one call)
-        for iarch, datafile in enumerate(datafiles):
-            try:
-                data, fname = _load(datafile)
-            except RuntimeError as err:
-                if not quiet:
-                    print("Cannot load_data(%s).  Skipping it." % datafile)
-                    print(err)
-                continue
-            if not len(data.ok_isubs):
-                if not quiet:
-                    print("No subints to fit for %s.  Skipping it." % fname)
-                continue
-            self.ok_idatafiles.append(iarch)
-            d = data
+        opt = DataBunch(nu_refs=nu_refs, nu_fits=nu_fits, bary=bary, fit_scat=fit_scat,
+                        log10_tau=log10_tau, use_ird=use_ird, seed=seed, method=method,
+                        print_phase=print_phase, print_flux=print_flux,
+                        print_parangle=print_parangle, addtnl_toa_flags=addtnl_toa_flags)
+        # (stage 3 lives in this body: its flags are set in the reference's statement order)
+        def archive_entries(d, fname, a, res, slot_means):
+            """Stage 3 of an archive: the TOA bookkeeping on the host (pptoas.py:528-721) for
+            the subints a.isubs -- their rows of the archive's per-subint result arrays
+            (nsub long; the rows of other subints stay zero) and their TOA objects, in subint
+            order.  Returns (arrays, toas); `arrays` is keyed by the result list's name."""
+            nu_refs, log10_tau = opt.nu_refs, opt.log10_tau
+            print_phase, print_flux, print_parangle = opt.print_phase, opt.print_flux, opt.print_parangle
             nsub, nchan, nbin = d.nsub, d.nchan, d.nbin
-            ok_isubs = np.asarray(d.ok_isubs, dtype=int)
-            source = d.source if d.source is not None else "noname"
-            obs = DataBunch(telescope=d.telescope, backend=d.backend, frontend=d.frontend)
-            DM_stored = d.DM
-            DM0_arch = DM_stored if self.DM0 is None else self.DM0
-            MJDs = np.array([e.in_days() for e in d.epochs], dtype=np.double)
-
-            # ---- batch marshalling: good subints, channel masks, templates ----
-            nok = len(ok_isubs)
-            mask = np.zeros((nok, nchan), dtype=np.uint8)
-            nu_fit_arr = np.zeros((nok, 3))
-            nu_ref_arr = np.full((nok, 3), np.nan)
-            x0 = np.zeros((nok, 5))
-            flags_per = []
-            slots, slot_of = {}, np.zeros(nok, dtype=np.int32)
-            errs = None if d.noise_stds is None else \
-                np.ascontiguousarray(np.asarray(d.noise_stds)[ok_isubs, 0], dtype=np.float64)
-            for j, isub in enumerate(ok_isubs):
-                ich = np.asarray(d.ok_ichans[isub], dtype=int)
-                mask[j, ich] = 1
-                freqsx = d.freqs[isub, ich]
-                key = d.freqs[isub].tobytes() + np.float64(d.Ps[isub]).tobytes() \
-                    if (fit_scat or use_ird) else d.freqs[isub].tobytes()
-                if use_ird:
-                    key += ich.tobytes()    # the smearing width uses the good channels' spacing
-                if key not in slots:
-                    if len(slots) >= 64:
-                        raise NotImplementedError("more than 64 distinct templates in one archive")
-                    slots[key] = len(slots)
-                    self._load_template(eng, slots[key], d.freqs[isub], nbin, d.Ps[isub],
-                                        unscattered=fit_scat)
-                    if use_ird:
-                        # template x instrumental response of the good channels
-                        # (pptoas.py:388-394), multiplied in the Fourier domain on the
-                        # device: constant responses x per-channel dispersive smearing
-                        from .pptoaslib import instrumental_response_device_args
-                        rconst, smear = instrumental_response_device_args(
-                            nbin, freqsx, self.ird['DM'], d.Ps[isub], self.ird['wids'],
-                            self.ird['irf_types'], nchan=nchan, ichans=ich)
-                        eng.apply_response(slots[key], rconst, smear)
-                slot_of[j] = slots[key]
-                if nu_fits is None:
-                    nu_fit = guess_fit_freq(freqsx, d.SNRs[isub, 0, ich])
-                    nu_fit_arr[j] = nu_fit
-                else:
-                    nu_fit_arr[j] = [nu_fits[0], nu_fits[0], nu_fits[-1]]
-                if nu_refs is not None:
-                    nu_ref_arr[j] = [nu_refs[0], nu_refs[0], nu_refs[-1]]
-                    if bary and nu_refs[-1]:
-                        nu_ref_arr[j, 2] = nu_refs[-1] / d.doppler_factors[isub]
-                # initial guesses (pptoas.py:421-460); the phase comes from the
-                # device seed
-                tau_guess, alpha_guess = 0.0, 0.0
-                if j == 0:
-                    tau_lin = np.zeros(nok)      # tau_guess [rot] before any log10 (seed='reference')
-                if fit_scat:
-                    P = d.Ps[isub]
-                    if self.scat_guess is not None:
-                        tau_s, tau_ref, alpha_guess = self.scat_guess
-                        tau_guess = (tau_s / P) * (nu_fit_arr[j, 2] / tau_ref) ** alpha_guess
-                    else:
-                        alpha_guess = self.alpha if hasattr(self, 'alpha') else scattering_alpha
-                        if hasattr(self, 'gparams'):
-                            tau_guess = (self.gparams[1] / P) * \
-                                (nu_fit_arr[j, 2] / self.model_nu_ref) ** alpha_guess
-                        else:
-                            tau_guess = 0.0
-                    tau_lin[j] = tau_guess
-                    if log10_tau:
-                        if tau_guess == 0.0:
-                            tau_guess = nbin ** -1
-                        tau_guess = np.log10(tau_guess)
-                x0[j] = [0.0, DM_stored, 0.0, tau_guess, alpha_guess]
-                if len(freqsx) == 1:
-                    fl = [1, 0, 0, 0, 0]
-                elif len(freqsx) == 2 and self.fit_DM and self.fit_GM:
-                    # the reference writes `fit_flags[2] = 0` into the list LEFT OVER from the subint before
-                    # (pptoas.py:479-481): right after a one-channel subint that list is [1,0,0,0,0] and the
-                    # two-channel subint is fitted for phase only; after a normal one it becomes phase + DM.
-                    # Reproduced -- but for the very first subint of a call, where the
-                    # reference has no list yet and raises NameError: the flags asked for, GM dropped.
-                    fl = list(last_fl) if last_fl is not None else list(self.fit_flags)
-                    fl[2] = 0
-                else:
-                    fl = list(self.fit_flags)
-                last_fl = fl
-                flags_per.append(tuple(fl))
-            port = _dededisperse(eng, _take_subints(d.subints, ok_isubs), d, ok_isubs)
-            ref_in = None
-            if seed == 'reference':
-                # (batches without a single-pass path read the portraits twice -- seed, fit --:
-                # hand them to the device once)
-                port = _to_device_once(eng, port)
-                ref_in = self._reference_seed_inputs(port, d, ok_isubs, mask, tau_lin, nu_fit_arr[:, 2],
-                                                     fit_scat, use_ird)
-            # ---- one device call per distinct flag set (normally one) ----
-            res = None
-            for fl in sorted(set(flags_per)):
-                sel = np.array([k for k, f in enumerate(flags_per) if f == fl])
-                # (all subints in one call is the normal case: no gather copy then)
-                if len(sel) == nok:
-                    psel = port
-                elif hasattr(port, "is_cuda"):       # (device tensor: gather on the device)
-                    import torch
-                    psel = port[torch.as_tensor(sel, device=port.device)].contiguous()
-                else:
-                    psel = np.ascontiguousarray(port[sel])
-                fkw = dict(errs=None if errs is None else errs[sel], nu_fits=nu_fit_arr[sel],
-                           nu_outs=nu_ref_arr[sel], fit_flags=fl, log10_tau=log10_tau, option=0, is_toa=True,
-                           model_slot=slot_of[sel], chan_mask=mask[sel], seed_ns=100 if seed == 'device' else 0,
-                           method='newton' if seed == 'device' else method)
-                fsel, Psel = d.freqs[ok_isubs][sel], np.asarray(d.Ps, dtype=np.float64)[ok_isubs][sel]
-                r = None
-                if ref_in is not None:
-                    # the reference's own guess: formed inside the fit's single pass over the
-                    # portraits where the library has that path, else in a pass of its own
-                    w_, numean_, mprofs_ = (a[sel] for a in ref_in)
-                    try:
-                        r = eng.fit_batch(psel, fsel, Psel, x0[sel], ref_seed=dict(
-                            weights=w_, model_profs=mprofs_, nu_mean=numean_, Ns=100, finish='simplex'), **fkw)
-                    except EngineNotSupported:
-                        x0[sel, 0] = self._reference_phase_seeds(eng, psel, fsel, Psel, w_, numean_, mprofs_,
-                                                                 nu_fit_arr[sel, 0], DM_stored)
-                if r is None:
-                    r = eng.fit_batch(psel, fsel, Psel, x0[sel], **fkw)
-                    if ref_in is not None:
-                        # (the fallback route formed the guess in a pass of its own: report it like
-                        # the single-pass route does, so every group carries the same keys)
-                        r["seed_phase"] = x0[sel, 0].copy()
-                if res is None:
-                    res = {"duration": 0.0}
-                for k, v in r.items():
-                    if isinstance(v, np.ndarray):
-                        # (groups may return different key sets: allocate on first sight)
-                        if k not in res:
-                            res[k] = np.zeros((nok,) + v.shape[1:], dtype=v.dtype)
-                        res[k][sel] = v
-                    elif k != "duration":
-                        res.setdefault(k, v)
-                res["duration"] += r["duration"]
-            fit_duration = res["duration"]
-            # template profile means per slot, for the flux estimate (the scattering
-            # kernel leaves the mean of a profile unchanged: B_0 = 1)
-            slot_means = {}
-            if print_flux:
-                for sl in set(slots.values()):
-                    slot_means[sl] = eng.model_means(sl, nchan, nbin)
-
-            # ---- TOA bookkeeping on the host (pptoas.py:528-721) ----
+            flags_per, slot_of, nu_fit_arr = a.flags_per, a.slot_of, a.nu_fit_arr
             phis = np.zeros(nsub); phi_errs = np.zeros(nsub)
             TOAs = np.zeros(nsub, dtype="object"); TOA_errs = np.zeros(nsub, dtype="object")
             DMs = np.zeros(nsub); DM_errs = np.zeros(nsub)
@@ -613,7 +615,8 @@ class GetTOAs(object):
             covariances = np.zeros([nsub, self.nfit, self.nfit])
             nfevals = np.zeros(nsub, dtype="int"); rcs = np.zeros(nsub, dtype="int")
             nu_fits_out = list(np.zeros([nsub, 3])); nu_refs_out = list(np.zeros([nsub, 3]))
-            for j, isub in enumerate(ok_isubs):
+            toas = []
+            for j, isub in enumerate(a.isubs):
                 fl = flags_per[j]
                 P = d.Ps[isub]
                 p, e = res["params"][j].copy(), res["param_errs"][j]
@@ -706,73 +709,303 @@ class GetTOAs(object):
                     toa_flags['flux_ref_freq'] = flux_freqs[isub]
                 if print_parangle:
                     toa_flags['par_angle'] = d.parallactic_angles[isub]
-                for k, v in addtnl_toa_flags.items():
+                for k, v in opt.addtnl_toa_flags.items():
                     toa_flags[k] = v
-                self.TOA_list.append(TOA(fname, res["nu_refs"][j, 0], TOA_MJD, TOA_err,
-                                         d.telescope, d.telescope_code, DM_flag,
-                                         DM_err_flag, toa_flags))
-            # mean DM offset of the archive (pptoas.py:665-682)
-            DeltaDMs = DMs - DM0_arch
-            if np.all(DM_errs[ok_isubs]):
-                DM_weights = DM_errs[ok_isubs] ** -2
+                toas.append(TOA(fname, res["nu_refs"][j, 0], TOA_MJD, TOA_err,
+                                d.telescope, d.telescope_code, DM_flag,
+                                DM_err_flag, toa_flags))
+            arrays = dict(nu_fits=nu_fits_out, nu_refs=nu_refs_out, phis=phis, phi_errs=phi_errs,
+                          TOAs=TOAs, TOA_errs=TOA_errs, DMs=DMs, DM_errs=DM_errs, GMs=GMs,
+                          GM_errs=GM_errs, taus=taus, tau_errs=tau_errs, alphas=alphas,
+                          alpha_errs=alpha_errs, scales=scales, scale_errs=scale_errs, snrs=snrs,
+                          channel_snrs=channel_snrs, profile_fluxes=profile_fluxes,
+                          profile_flux_errs=profile_flux_errs, fluxes=fluxes, flux_errs=flux_errs,
+                          flux_freqs=flux_freqs, covariances=covariances, red_chi2s=red_chi2s,
+                          nfevals=nfevals, rcs=rcs)
+            return arrays, toas
+
+        start = time.time()
+        datafiles = self.datafiles if datafile is None else [datafile]
+        if world > 1:
+            self._get_TOAs_sharded(datafiles, opt, rank, world, quiet, archive_entries)
+            self._print_total(start, quiet or rank != 0)
+            return
+        eng = self._engine(False)
+        last_fl = None          # (the reference's `fit_flags` variable lives across subints AND archives of one call)
+        for iarch, datafile in enumerate(datafiles):
+            loaded = _load_or_skip(datafile, quiet)
+            if loaded is None:
+                continue
+            d, fname = loaded
+            self.ok_idatafiles.append(iarch)
+            ok_isubs = np.asarray(d.ok_isubs, dtype=int)
+            a = self._archive_inputs(eng, d, ok_isubs, last_fl, opt)
+            last_fl = a.carry
+            res, fit_duration, slot_means = self._archive_fit(eng, d, a, opt)
+            arrays, toas = archive_entries(d, fname, a, res, slot_means)
+            self.TOA_list.extend(toas)
+            self._append_archive(_archive_meta(d, fname, self.DM0), arrays, fit_duration, quiet)
+        self._print_total(start, quiet)
+
+    # -- get_TOAs in stages ---------------------------------------------------
+    def _engine(self, distributed):
+        """The engine this process fits on: device 0, or LOCAL_RANK's device (modulo the
+        visible devices) for a rank of a sharded call.  Under the "nccl" backend the
+        device is also made current, where gather_object stages its tensors."""
+        if not distributed:
+            return default_engine()
+        import os
+        import torch
+        import torch.distributed as tdist
+        ndev = torch.cuda.device_count()
+        if ndev < 1:
+            raise RuntimeError("get_TOAs(distributed=True): no GPU visible to this rank")
+        dev = int(os.environ.get("LOCAL_RANK", "0")) % ndev
+        if tdist.get_backend() == "nccl":
+            torch.cuda.set_device(dev)
+        return default_engine(dev)
+
+    def _archive_inputs(self, eng, d, isubs, carry, opt):
+        """Stage 1 of an archive: everything the device calls need for the good subints
+        `isubs` (all of an archive's, or a rank's contiguous slice of them) -- channel
+        masks, fit and reference frequencies, initial guesses, templates in the engine's
+        model slots, the fit flags (subint_fit_flags from the carry-in `carry`), the
+        portraits and, for seed='reference', the inputs of the reference's phase guess."""
+        fit_scat, use_ird, log10_tau = opt.fit_scat, opt.use_ird, opt.log10_tau
+        nu_refs, nu_fits, bary = opt.nu_refs, opt.nu_fits, opt.bary
+        nchan, nbin = d.nchan, d.nbin
+        DM_stored = d.DM
+        isubs = np.asarray(isubs, dtype=int)
+        nok = len(isubs)
+        flags_per, carry = subint_fit_flags([len(d.ok_ichans[isub]) for isub in isubs],
+                                            self.fit_flags, carry)
+        mask = np.zeros((nok, nchan), dtype=np.uint8)
+        nu_fit_arr = np.zeros((nok, 3))
+        nu_ref_arr = np.full((nok, 3), np.nan)
+        x0 = np.zeros((nok, 5))
+        slots, slot_of = {}, np.zeros(nok, dtype=np.int32)
+        errs = None if d.noise_stds is None else \
+            np.ascontiguousarray(np.asarray(d.noise_stds)[isubs, 0], dtype=np.float64)
+        tau_lin = np.zeros(nok)      # tau_guess [rot] before any log10 (seed='reference')
+        for j, isub in enumerate(isubs):
+            ich = np.asarray(d.ok_ichans[isub], dtype=int)
+            mask[j, ich] = 1
+            freqsx = d.freqs[isub, ich]
+            key = d.freqs[isub].tobytes() + np.float64(d.Ps[isub]).tobytes() \
+                if (fit_scat or use_ird) else d.freqs[isub].tobytes()
+            if use_ird:
+                key += ich.tobytes()    # the smearing width uses the good channels' spacing
+            if key not in slots:
+                if len(slots) >= 64:
+                    raise NotImplementedError("more than 64 distinct templates in one archive")
+                slots[key] = len(slots)
+                self._load_template(eng, slots[key], d.freqs[isub], nbin, d.Ps[isub],
+                                    unscattered=fit_scat)
+                if use_ird:
+                    # template x instrumental response of the good channels
+                    # (pptoas.py:388-394), multiplied in the Fourier domain on the
+                    # device: constant responses x per-channel dispersive smearing
+                    from .pptoaslib import instrumental_response_device_args
+                    rconst, smear = instrumental_response_device_args(
+                        nbin, freqsx, self.ird['DM'], d.Ps[isub], self.ird['wids'],
+                        self.ird['irf_types'], nchan=nchan, ichans=ich)
+                    eng.apply_response(slots[key], rconst, smear)
+            slot_of[j] = slots[key]
+            if nu_fits is None:
+                nu_fit = guess_fit_freq(freqsx, d.SNRs[isub, 0, ich])
+                nu_fit_arr[j] = nu_fit
             else:
-                DM_weights = np.ones(len(ok_isubs))
-            DeltaDM_mean, DeltaDM_var = np.average(DeltaDMs[ok_isubs], weights=DM_weights,
-                                                   returned=True)
-            DeltaDM_var = DeltaDM_var ** -1
-            if len(ok_isubs) > 1:
-                DeltaDM_var *= np.sum(((DeltaDMs[ok_isubs] - DeltaDM_mean) ** 2) *
-                                      DM_weights) / (len(ok_isubs) - 1)
-            self.order.append(fname)
-            self.obs.append(obs)
-            self.doppler_fs.append(d.doppler_factors)
-            self.nu0s.append(d.nu0)
-            self.nu_fits.append(nu_fits_out)
-            self.nu_refs.append(nu_refs_out)
-            self.ok_isubs.append(ok_isubs)
-            self.epochs.append(d.epochs)
-            self.MJDs.append(MJDs)
-            self.Ps.append(d.Ps)
-            self.phis.append(phis)
-            self.phi_errs.append(phi_errs)
-            self.TOAs.append(TOAs)
-            self.TOA_errs.append(TOA_errs)
-            self.DM0s.append(DM0_arch)
-            self.DMs.append(DMs)
-            self.DM_errs.append(DM_errs)
-            self.DeltaDM_means.append(DeltaDM_mean)
-            self.DeltaDM_errs.append(DeltaDM_var ** 0.5)
-            self.GMs.append(GMs)
-            self.GM_errs.append(GM_errs)
-            self.taus.append(taus)
-            self.tau_errs.append(tau_errs)
-            self.alphas.append(alphas)
-            self.alpha_errs.append(alpha_errs)
-            self.scales.append(scales)
-            self.scale_errs.append(scale_errs)
-            self.snrs.append(snrs)
-            self.channel_snrs.append(channel_snrs)
-            self.profile_fluxes.append(profile_fluxes)
-            self.profile_flux_errs.append(profile_flux_errs)
-            self.fluxes.append(fluxes)
-            self.flux_errs.append(flux_errs)
-            self.flux_freqs.append(flux_freqs)
-            self.covariances.append(covariances)
-            self.red_chi2s.append(red_chi2s)
-            self.nfevals.append(nfevals)
-            self.rcs.append(rcs)
-            self.fit_durations.append(fit_duration)
-            if not quiet:
-                print("--------------------------")
-                print(fname)
-                print("~%.6f sec/TOA" % (fit_duration / len(ok_isubs)))
-                print("Med. TOA error is %.3f us" % (np.median(phi_errs[ok_isubs]) *
-                                                     d.Ps.mean() * 1e6))
+                nu_fit_arr[j] = [nu_fits[0], nu_fits[0], nu_fits[-1]]
+            if nu_refs is not None:
+                nu_ref_arr[j] = [nu_refs[0], nu_refs[0], nu_refs[-1]]
+                if bary and nu_refs[-1]:
+                    nu_ref_arr[j, 2] = nu_refs[-1] / d.doppler_factors[isub]
+            # initial guesses (pptoas.py:421-460); the phase comes from the
+            # device seed
+            tau_guess, alpha_guess = 0.0, 0.0
+            if fit_scat:
+                P = d.Ps[isub]
+                if self.scat_guess is not None:
+                    tau_s, tau_ref, alpha_guess = self.scat_guess
+                    tau_guess = (tau_s / P) * (nu_fit_arr[j, 2] / tau_ref) ** alpha_guess
+                else:
+                    alpha_guess = self.alpha if hasattr(self, 'alpha') else scattering_alpha
+                    if hasattr(self, 'gparams'):
+                        tau_guess = (self.gparams[1] / P) * \
+                            (nu_fit_arr[j, 2] / self.model_nu_ref) ** alpha_guess
+                    else:
+                        tau_guess = 0.0
+                tau_lin[j] = tau_guess
+                if log10_tau:
+                    if tau_guess == 0.0:
+                        tau_guess = nbin ** -1
+                    tau_guess = np.log10(tau_guess)
+            x0[j] = [0.0, DM_stored, 0.0, tau_guess, alpha_guess]
+        port = _dededisperse(eng, _take_subints(d.subints, isubs), d, isubs)
+        ref_in = None
+        if opt.seed == 'reference':
+            # (batches without a single-pass path read the portraits twice -- seed, fit --:
+            # hand them to the device once)
+            port = _to_device_once(eng, port)
+            ref_in = self._reference_seed_inputs(port, d, isubs, mask, tau_lin, nu_fit_arr[:, 2],
+                                                 fit_scat, use_ird)
+        return DataBunch(isubs=isubs, mask=mask, nu_fit_arr=nu_fit_arr, nu_ref_arr=nu_ref_arr,
+                         x0=x0, flags_per=flags_per, carry=carry, slots=slots, slot_of=slot_of,
+                         errs=errs, port=port, ref_in=ref_in)
+
+    def _archive_fit(self, eng, d, a, opt):
+        """Stage 2 of an archive: one device call per distinct flag set (normally one)
+        over the inputs of _archive_inputs.  Returns (res, fit_duration, slot_means)."""
+        seed, method, log10_tau = opt.seed, opt.method, opt.log10_tau
+        isubs, port, errs, x0, ref_in = a.isubs, a.port, a.errs, a.x0, a.ref_in
+        flags_per, slot_of, mask = a.flags_per, a.slot_of, a.mask
+        nok = len(isubs)
+        res = None
+        for fl in sorted(set(flags_per)):
+            sel = np.array([k for k, f in enumerate(flags_per) if f == fl])
+            # (all subints in one call is the normal case: no gather copy then)
+            if len(sel) == nok:
+                psel = port
+            elif hasattr(port, "is_cuda"):       # (device tensor: gather on the device)
+                import torch
+                psel = port[torch.as_tensor(sel, device=port.device)].contiguous()
+            else:
+                psel = np.ascontiguousarray(port[sel])
+            fkw = dict(errs=None if errs is None else errs[sel], nu_fits=a.nu_fit_arr[sel],
+                       nu_outs=a.nu_ref_arr[sel], fit_flags=fl, log10_tau=log10_tau, option=0, is_toa=True,
+                       model_slot=slot_of[sel], chan_mask=mask[sel], seed_ns=100 if seed == 'device' else 0,
+                       method='newton' if seed == 'device' else method)
+            fsel, Psel = d.freqs[isubs][sel], np.asarray(d.Ps, dtype=np.float64)[isubs][sel]
+            r = None
+            if ref_in is not None:
+                # the reference's own guess: formed inside the fit's single pass over the
+                # portraits where the library has that path, else in a pass of its own
+                w_, numean_, mprofs_ = (v[sel] for v in ref_in)
+                try:
+                    r = eng.fit_batch(psel, fsel, Psel, x0[sel], ref_seed=dict(
+                        weights=w_, model_profs=mprofs_, nu_mean=numean_, Ns=100, finish='simplex'), **fkw)
+                except EngineNotSupported:
+                    x0[sel, 0] = self._reference_phase_seeds(eng, psel, fsel, Psel, w_, numean_, mprofs_,
+                                                             a.nu_fit_arr[sel, 0], d.DM)
+            if r is None:
+                r = eng.fit_batch(psel, fsel, Psel, x0[sel], **fkw)
+                if ref_in is not None:
+                    # (the fallback route formed the guess in a pass of its own: report it like
+                    # the single-pass route does, so every group carries the same keys)
+                    r["seed_phase"] = x0[sel, 0].copy()
+            if res is None:
+                res = {"duration": 0.0}
+            for k, v in r.items():
+                if isinstance(v, np.ndarray):
+                    # (groups may return different key sets: allocate on first sight)
+                    if k not in res:
+                        res[k] = np.zeros((nok,) + v.shape[1:], dtype=v.dtype)
+                    res[k][sel] = v
+                elif k != "duration":
+                    res.setdefault(k, v)
+            res["duration"] += r["duration"]
+        fit_duration = res["duration"]
+        # template profile means per slot, for the flux estimate (the scattering
+        # kernel leaves the mean of a profile unchanged: B_0 = 1)
+        slot_means = {}
+        if opt.print_flux:
+            for sl in set(a.slots.values()):
+                slot_means[sl] = eng.model_means(sl, d.nchan, d.nbin)
+        return res, fit_duration, slot_means
+
+    def _append_archive(self, meta, arrays, fit_duration, quiet):
+        """One archive's entries of the result lists; its mean DM offset is formed here
+        from the (merged) per-subint DMs (deltadm_mean)."""
+        ok_isubs = meta["ok_isubs"]
+        DeltaDM_mean, DeltaDM_err = deltadm_mean(arrays["DMs"], arrays["DM_errs"], meta["DM0"],
+                                                 ok_isubs)
+        self.order.append(meta["fname"])
+        self.obs.append(meta["obs"])
+        self.doppler_fs.append(meta["doppler_fs"])
+        self.nu0s.append(meta["nu0"])
+        self.ok_isubs.append(ok_isubs)
+        self.epochs.append(meta["epochs"])
+        self.MJDs.append(meta["MJDs"])
+        self.Ps.append(meta["Ps"])
+        self.DM0s.append(meta["DM0"])
+        self.DeltaDM_means.append(DeltaDM_mean)
+        self.DeltaDM_errs.append(DeltaDM_err)
+        for name in _ARCHIVE_ARRAYS:
+            getattr(self, name).append(arrays[name])
+        self.fit_durations.append(fit_duration)
+        if not quiet:
+            print("--------------------------")
+            print(meta["fname"])
+            print("~%.6f sec/TOA" % (fit_duration / len(ok_isubs)))
+            print("Med. TOA error is %.3f us" % (np.median(arrays["phi_errs"][ok_isubs]) *
+                                                 meta["Ps"].mean() * 1e6))
+
+    def _print_total(self, start, quiet):
         tot_duration = time.time() - start
         if not quiet and len(self.ok_isubs):
             print("--------------------------")
             print("Total time: %.2f sec, ~%.4f sec/TOA" %
                   (tot_duration, tot_duration / sum(len(o) for o in self.ok_isubs)))
+
+    def _get_TOAs_sharded(self, datafiles, opt, rank, world, quiet, archive_entries):
+        """get_TOAs over the ranks of a process group (see its docstring): this rank's
+        blocks, ONE gather_object to rank 0, and rank 0's merge."""
+        import torch.distributed as tdist
+        blocks, error, exc = [], None, None
+        try:
+            eng = self._engine(True)
+            mode, lo, hi = shard_plan(len(datafiles), rank, world)
+            walk_quiet = quiet or rank != 0
+            carry = None
+            if mode == "archives" and self.fit_DM and self.fit_GM:
+                # the flags left over from the archives before this rank's (their weights only)
+                for df_ in datafiles[:lo]:
+                    carry = subint_fit_flags(_good_channel_counts(df_), self.fit_flags, carry)[1]
+            for iarch in range(lo, hi):
+                loaded = _load_or_skip(datafiles[iarch], walk_quiet)
+                if loaded is None:
+                    continue
+                d, fname = loaded
+                ok_isubs = np.asarray(d.ok_isubs, dtype=int)
+                nchx = [len(d.ok_ichans[isub]) for isub in ok_isubs]
+                j0, j1 = shard_subints(mode, len(ok_isubs), rank, world)
+                carry_in = subint_fit_flags(nchx[:j0], self.fit_flags, carry)[1]
+                carry = subint_fit_flags(nchx, self.fit_flags, carry)[1]
+                if j0 == j1:
+                    continue            # (an empty slice of this archive: nothing to send)
+                a = self._archive_inputs(eng, d, ok_isubs[j0:j1], carry_in, opt)
+                res, fit_duration, slot_means = self._archive_fit(eng, d, a, opt)
+                arrays, toas = archive_entries(d, fname, a, res, slot_means)
+                rows = a.isubs
+                blocks.append(dict(
+                    iarch=iarch, meta=_archive_meta(d, fname, self.DM0), nsub=int(d.nsub), rows=rows,
+                    arrays={k: ([v[i] for i in rows] if isinstance(v, list) else v[rows])
+                            for k, v in arrays.items()},
+                    toas=toas, fit_duration=fit_duration))
+        except Exception as err:        # (every rank must reach the gather)
+            exc = err
+            error = "%s: %s" % (type(err).__name__, err)
+            blocks = []
+        payload = dict(rank=rank, error=error, blocks=blocks)
+        got = [None] * world if rank == 0 else None
+        tdist.gather_object(payload, got, dst=0)
+        if exc is not None:
+            raise exc
+        if rank != 0:
+            return
+        failed = [p for p in got if p["error"] is not None]
+        if failed:
+            raise RuntimeError("get_TOAs: rank %d failed: %s" % (failed[0]["rank"], failed[0]["error"])
+                               + "".join("; rank %d failed: %s" % (p["rank"], p["error"]) for p in failed[1:]))
+        by_arch = {}
+        for p in got:                    # (rank order: within an archive, subint order)
+            for b in p["blocks"]:
+                by_arch.setdefault(b["iarch"], []).append(b)
+        for iarch in sorted(by_arch):
+            arrays, toas, fit_duration, meta = merge_blocks(by_arch[iarch])
+            self.ok_idatafiles.append(iarch)
+            self.TOA_list.extend(toas)
+            self._append_archive(meta, arrays, fit_duration, quiet)
 
     def get_narrowband_TOAs(self, datafile=None, tscrunch=False, fit_scat=False,
                             log10_tau=True, scat_guess=None, print_phase=False,
