@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 5
+#define PP_ABI_VERSION 6
 
 /* status codes */
 #define PP_OK 0
@@ -69,6 +69,14 @@ extern "C" {
  * objective in fewer evaluations (what 'Newton-CG' and 'TNC' also aim at). */
 #define PP_METHOD_TRUST_NCG 0
 #define PP_METHOD_NEWTON 1
+
+/* normalisation of pp_channel_noise: normalize_portrait's methods (pplib.py:2462-2507) */
+#define PP_NORM_NONE 0
+#define PP_NORM_MEAN 1
+#define PP_NORM_MAX 2
+#define PP_NORM_PROF 3    /* the caller's divisor per row */
+#define PP_NORM_RMS 4
+#define PP_NORM_ABS 5
 
 typedef struct pp_ctx pp_ctx;
 
@@ -477,6 +485,25 @@ int pp_channel_red_chi2(pp_ctx* ctx, const void* src, int dtype, int on_device,
                         const double* freqs, int64_t freqs_stride, const double* P,
                         const double* params5, const double* nu_refs3,
                         const double* scales, const double* errs, double* red_chi2);
+
+/* ---- ppzap ---------------------------------------------------------------- */
+/* The channel noise of ppzap's noise method (ppzap.py:200-241): for every row of src
+ * [nrows][nbin] (`dtype`, host or device) the norm of normalize_portrait (pplib.py:2462-2507)
+ * by `norm_method` (PP_NORM_*; PP_NORM_PROF takes divisor[nrows], the fit_phase_shift scale
+ * of each row against its subint's mean profile) and get_noise_PS(row / norm, frac=4)
+ * (pplib.py:2227-2253), formed as noise(row) / |norm|.  Rows with no non-zero sample keep
+ * norm 1 and noise 0.  norms and noise: [nrows] host arrays.  nbin: even, 8 ... 4096. */
+int pp_channel_noise(pp_ctx* ctx, const void* src, int dtype, int on_device, int nrows,
+                     int nbin, int norm_method, const double* divisor, double* norms,
+                     double* noise);
+
+/* get_zap_channels (ppzap.py:18-47) of nsub subints at once: over the channels with
+ * good[i][n] != 0, drop every channel whose noise exceeds median + nstd * std (NumPy's
+ * median and population std) and repeat until a round drops none or none is left.
+ * noise, good, zap: [nsub][nchan] host arrays (nchan <= 4096); zap[i][n] = 1 for every
+ * dropped channel, 0 elsewhere. */
+int pp_zap_median(pp_ctx* ctx, const double* noise, const unsigned char* good, int nsub,
+                  int nchan, double nstd, unsigned char* zap);
 
 /* Fill dst[nsub][nchan][nbin] (device pointer, dtype) with
  *   gains[i][n] * rotate(model slot, -phi_i, -DM_i, -GM_i) + N(0, sigma)

@@ -2149,3 +2149,4 @@ extern "C" int pp_fit_wait(pp_ctx* c) {
 }
 
 #include "pp_extra_api.h"
+#include "pp_zap.h"

@@ -684,6 +684,88 @@ class Engine(object):
             _dp(params), _dp(nu_refs), _dp(scales), _dp(errs), _dp(out)), "pp_channel_red_chi2")
         return out
 
+    def channel_noise(self, ports, norm=None, weights=None):
+        """ppzap's channel noise (ppzap.py:222-230): every row normalised as
+        normalize_portrait(port, method=norm, weights) does (pplib.py:2462-2507), then
+        get_noise_PS(row, frac=4).  ports: [nsub,nchan,nbin] or [nrows,nbin] (one
+        portrait), NumPy or a device tensor; weights: [nsub,nchan] (norm 'prof').
+        Returns (noise, norms) shaped like ports without the bin axis; rows with no
+        non-zero sample keep norm 1 and noise 0."""
+        if norm not in _lib.PP_NORMS:
+            raise ValueError("norm must be one of None, 'mean', 'max', 'prof', 'rms', 'abs'")
+        shape = tuple(int(v) for v in ports.shape)
+        if len(shape) not in (2, 3):
+            raise ValueError("ports must be [nsub,nchan,nbin] or [nrows,nbin]")
+        nbin = shape[-1]
+        nrows = int(np.prod(shape[:-1]))
+        if _is_device_array(ports):
+            if not ports.is_contiguous():
+                raise EngineError("channel_noise: device ports must be contiguous")
+            src, on_dev = C.c_void_p(ports.data_ptr()), 1
+            dtype = PP_F64 if ports.element_size() == 8 else PP_F32
+        else:
+            keep = np.asarray(ports)
+            if keep.dtype != np.float32:
+                keep = keep.astype(np.float64, copy=False)
+            keep = np.ascontiguousarray(keep)
+            src, on_dev = C.c_void_p(keep.ctypes.data), 0
+            dtype = PP_F64 if keep.dtype == np.float64 else PP_F32
+        div = None
+        if norm == 'prof':
+            div = self._prof_norms(ports, weights)
+        norms, noise = np.empty(nrows), np.empty(nrows)
+        _check(self._lib.pp_channel_noise(self._ctx, src, dtype, on_dev, nrows, nbin, _lib.PP_NORMS[norm],
+                                          _dp(div), _dp(norms), _dp(noise)), "pp_channel_noise")
+        return noise.reshape(shape[:-1]), norms.reshape(shape[:-1])
+
+    # host bytes of f64 rows _prof_norms holds at a time (and as many again for their mean profiles)
+    PROF_RUN_BYTES = 256 << 20
+
+    def _prof_norms(self, ports, weights):
+        """normalize_portrait's 'prof' norms (pplib.py:2478-2495): each portrait's mean
+        profile over its channels of non-zero sum, weighted, on the host as np.average
+        forms it; then fit_phase_shift(row, mean_prof).scale of every non-zero row on the
+        device (brute grid + the reference's simplex finish).  Zero rows get 1.  Runs of
+        whole portraits of at most PROF_RUN_BYTES go through the host at a time (a device
+        tensor's run is copied over); a row's norm does not depend on its run."""
+        dev = _is_device_array(ports)
+        shape = tuple(int(v) for v in ports.shape)
+        nchan, nbin = (shape[1], shape[2]) if len(shape) == 3 else (shape[0], shape[1])
+        nsub = shape[0] if len(shape) == 3 else 1
+        view = ports.reshape(nsub, nchan, nbin)
+        w = np.ones((nsub, nchan)) if weights is None else \
+            np.asarray(weights, dtype=np.float64).reshape(nsub, nchan)
+        div = np.ones((nsub, nchan))
+        run = max(1, self.PROF_RUN_BYTES // (nchan * nbin * 8))
+        for s0 in range(0, nsub, run):
+            part = view[s0:s0 + run]
+            a = np.asarray(part.detach().cpu().numpy() if dev else part, dtype=np.float64)
+            n = len(a)
+            rows = a.reshape(n * nchan, nbin)
+            live = rows.any(axis=1)
+            if not live.any():
+                continue
+            means = np.empty((n, nbin))
+            for i in range(n):
+                good = np.where(a[i].sum(axis=1) != 0.0)[0]
+                means[i] = np.average(a[i][good], axis=0, weights=w[s0 + i][good])
+            sub_of = np.repeat(np.arange(n), nchan)[live]
+            div[s0:s0 + n].reshape(-1)[live] = \
+                self.fit_phase_shift_batch(rows[live], means[sub_of], finish='simplex')[:, 2]
+        return div.reshape(-1)
+
+    def zap_median(self, noise, good, nstd):
+        """get_zap_channels' clip (ppzap.py:18-47) of every subint at once: noise and
+        good [nsub,nchan] (good != 0: a channel in ok_ichans).  Returns the uint8
+        [nsub,nchan] mask of the channels it zaps."""
+        nz = _f64(np.atleast_2d(noise))
+        nsub, nchan = nz.shape
+        g = np.ascontiguousarray(np.broadcast_to(np.asarray(good) != 0, (nsub, nchan)), dtype=np.uint8)
+        zap = np.empty((nsub, nchan), dtype=np.uint8)
+        _check(self._lib.pp_zap_median(self._ctx, _dp(nz), g.ctypes.data_as(c_uint8_p), nsub, nchan, float(nstd),
+                                       zap.ctypes.data_as(c_uint8_p)), "pp_zap_median")
+        return zap
+
     def synth_portraits(self, dst, freqs, P, inj, sigma, seed, first_subint=0,
                         slot=0, gains=None):
         """Fill a CUDA tensor dst[nsub,nchan,nbin] with synthetic subints; gains[nsub,nchan]
