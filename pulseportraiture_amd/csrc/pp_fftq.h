@@ -55,12 +55,17 @@ constexpr int FFTQ_LDS_ELEMS = 4 * 272;      // four rows of 16 lanes x (16 x 17
 // dead: WHEN = 0 a quarter into stage 1, 1 after the stage-1 twiddles (their powers no
 // longer live), 2 after the lane swaps, 3 after the transpose (before the last stage).  power (optional) += this lane's share of
 // sum_{k=1}^{M-1} |Z_k|^2 + (Re Z_0 - Im Z_0)^2.
-template <int WHEN = 0, typename Mid>
-__device__ __forceinline__ void fftq1024(cplx (&v)[16], cplx* lds, const cplx t1, const cplx t2, int tid,
-                                         double* power, Mid mid) {
+//
+// fftq1024_from takes the two twiddles as callables, each called ONCE where its value is first wanted (in front of
+// the second half of stage 1's butterflies; in front of the lane swaps): a kernel that keeps its lane constants in
+// LDS reads them there instead of holding eight registers from the top of the row.
+template <int WHEN = 0, typename T1, typename T2, typename Mid>
+__device__ __forceinline__ void fftq1024_from(cplx (&v)[16], cplx* lds, T1 get_t1, T2 get_t2, int tid,
+                                              double* power, Mid mid) {
     // ---- stage 1 ----
     dft16_first(v);
     if (WHEN == 0) mid();
+    const cplx t1 = get_t1();
     dft16_second(v);
     {
         // v[j] *= t1^j, every power formed once (product tree, as stage_finish<TREE>)
@@ -77,6 +82,7 @@ __device__ __forceinline__ void fftq1024(cplx (&v)[16], cplx* lds, const cplx t1
         for (int j = 1; j < 16; ++j) v[j] = cmul(v[j], wq[j]);
     }
     if (WHEN == 1) mid();
+    const cplx t2 = get_t2();
     // ---- lane bits 5,4 <-> register bits 3,2 ----
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -125,6 +131,12 @@ __device__ __forceinline__ void fftq1024(cplx (&v)[16], cplx* lds, const cplx t1
         }
         *power += acc;
     }
+}
+
+template <int WHEN = 0, typename Mid>
+__device__ __forceinline__ void fftq1024(cplx (&v)[16], cplx* lds, const cplx t1, const cplx t2, int tid,
+                                         double* power, Mid mid) {
+    fftq1024_from<WHEN>(v, lds, [&]() { return t1; }, [&]() { return t2; }, tid, power, mid);
 }
 
 // --------------------------------------------------------------------------

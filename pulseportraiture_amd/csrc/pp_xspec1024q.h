@@ -57,12 +57,94 @@
                                    // (profiles/r05_publish_kept_ab.txt): the scalar jump costs what the stores save
 #endif
 
+// The constants of a lane that an f64 row needs (stage twiddles t1, t2, split twiddle wb0) are kept in the wave's own
+// LDS and read back, per row, where they are first used; phi_n is fetched by the scalar unit.  0 = the three
+// L1-resident vector loads and the one-word vector load of phi_n at the top of every row.  See TWL below.
+#ifndef PP_LANE_CONSTS_LDS
+#define PP_LANE_CONSTS_LDS 1
+#endif
+// the kernel that also measures the noise (TAIL): which of the above it takes.  Its LDS is full (two template slots), so
+// only t2 has a place there, and t1 and wb0 stay vector loads at the top of the row.  Measured: each option alone and
+// both together lose 0.2 - 0.3 % (profiles/r07_lane_consts_ab.txt) -- off, the kernel is the one it was
+#ifndef PP_TAIL_T2_LDS
+#define PP_TAIL_T2_LDS 0
+#endif
+#ifndef PP_TAIL_ROW_TOP
+#define PP_TAIL_ROW_TOP 0
+#endif
+// timing-only build (results WRONG): the three constants are a register copy of wbT, no load of any kind; phi_n by the
+// scalar unit.  Useless as a ceiling while the launch carries the previous step's solve as tickets -- on wrong sums that
+// solve does not converge and the kernel it rides in takes three times as long (profiles/r07_row_wait_ceiling.txt);
+// the LDS build, which has no small vector load left in the row either, is the measurement
+#ifndef PP_ROW_WAIT_CEILING
+#define PP_ROW_WAIT_CEILING 0
+#endif
+
 namespace pp {
+
+// the free element of the transpose image (pitch 17: element 16 of every lane's run is never written or read) of lane
+// l of the LAST row of 16 lanes -- beyond what the partner exchange (elements 0..447, 0..767 when the noise is measured)
+// and the reduction publish
+constexpr int FFTQ_FREE_ELEM0 = 3 * 272 + 16, FFTQ_FREE_PITCH = 17;
+
+// The results of a row -- the 12 Taylor sums, S_d and (TAIL) the measured noise, wave totals as wave_reduce_lds leaves
+// them -- to memory.  All four lanes of quad q hold total q and the quads past the last total hold the last one, so EVERY
+// lane has a value and a place for it: the results leave in ONE store that no branch skips, and the compiler can count
+// it.  (Stores that only some lanes issue are branched around when none does; behind them the number of accesses in
+// flight is unknown, and the next row's wait for its data has to be one for the store's acknowledgement as well.)
+// 0 = the two or three one-lane stores.
+#ifndef PP_ROW_RESULTS_ONE_STORE
+#define PP_ROW_RESULTS_ONE_STORE 1
+#endif
+template <int M, bool TAIL, bool ONE = true>
+__device__ __forceinline__ void store_row_results(const XspecArgs& a, const size_t rc, const int tid, double tv) {
+    constexpr int H = M + 1, kc = (int)(0.75 * H);   // get_noise_PS: int((1 - 1/4) * len(pows))
+  if constexpr (ONE && PP_ROW_RESULTS_ONE_STORE) {
+    const int q = wave_reduce16_index(tid);
+    const double th = 0.5 * tv;
+    // Re(i^q z): +Re, -Im, -Re, +Im, ...   (x 1/2: unhalved template against 2 d_k)
+    double val = (q <= PP_TJ && ((q & 3) == 1 || (q & 3) == 2)) ? -th : th;
+    double* dst = a.tay + tay_idx(rc, q < PP_TSTRIDE ? q : 0);
+    if (q >= PP_TSTRIDE) { val = tv; dst = a.sdraw + rc; }
+    if (TAIL) {
+        const double nz = sqrt(tv / (2.0 * M) / (double)(H - kc));
+        if (q > PP_TSTRIDE) { val = nz; dst = a.noise + rc; }
+    }
+    typedef double __attribute__((address_space(1)))* gdp_t;
+    *(gdp_t)(uintptr_t)dst = val;
+  } else {
+    if ((tid & 3) == 0) {
+        const int q = wave_reduce16_index(tid);
+        if (q < PP_TSTRIDE) {
+            // Re(i^q z): +Re, -Im, -Re, +Im, ...   (x 1/2: unhalved template against 2 d_k)
+            tv *= 0.5;
+            a.tay[tay_idx(rc, q)] = (q <= PP_TJ && ((q & 3) == 1 || (q & 3) == 2)) ? -tv : tv;
+        }
+    }
+    if (tid == 4 * PP_TSTRIDE) a.sdraw[rc] = tv;
+    if (TAIL && tid == 4 * (PP_TSTRIDE + 1)) a.noise[rc] = sqrt(tv / (2.0 * M) / (double)(H - kc));
+  }
+}
+
+// The first row is waited for in front of the row loop, with a wait the compiler knows (vmcnt(0), the other counters
+// left alone).  Its count at the top of a row has to hold on every way into the loop: coming from the kernel's start the
+// row's last load was the youngest access in flight, coming from the previous row there is one younger, the result
+// store -- so the top of EVERY row waited for vmcnt(0), the acknowledgement of a store issued a few instructions
+// earlier.  With nothing in flight on entry the wait at the top is vmcnt(1): the row's data, and the store stays under way.
+#ifndef PP_FIRST_ROW_LANDED
+#define PP_FIRST_ROW_LANDED 1
+#endif
+__device__ __forceinline__ void first_row_landed() {
+#if PP_FIRST_ROW_LANDED
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
+}
 
 // Where the next row's loads are queued (measured choices, profiles/README.md): f64 rows in two
 // halves -- eight registers' worth after the stage-1 twiddles (fftq1024's WHEN = 1), the rest
-// behind the partner exchange -- and with the stage twiddles re-read per row; f32 rows whole, a
-// quarter into stage 1 (WHEN = 0), twiddles held.
+// behind the partner exchange -- and with the stage twiddles not held through the row (Q_TW_RELOAD:
+// read back from the wave's LDS where they are used, see TWL in k_xspec_q1024; a vector load per
+// row before); f32 rows whole, a quarter into stage 1 (WHEN = 0), twiddles held.
 constexpr bool Q_SPLIT_PREFETCH = true, Q_TW_RELOAD = true;
 constexpr int Q_PREFETCH_F64 = 1, Q_PREFETCH_F32 = 0;
 // TAIL: also measure the noise from the top quarter of the power spectrum (errs == NULL,
@@ -84,23 +166,48 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     // (with them held the kernel spilled one of them + three dwords to scratch, and the scratch reload in the middle
     // of the row queues behind the prefetched half row: vector memory returns in order)
     constexpr int NML = ((PP_TAIL_M_LDS && TAIL) || (PP_MAIN_M_LDS && !TAIL)) && sizeof(Tin) == 8 ? 2 : 0;
-    __shared__ cplx lds[LDSN + 64 * NML];
+    // f64 rows: the lane's constants live in LDS (TWL, below).  t2 (16 distinct values) takes free elements of the
+    // transpose image; t1 and wb0 take two tables of 64 beside it where the template slots have not taken that room
+    // (eight workgroups per CU: 8 x 19 456 B of the CU's 160 KB -- at seven the kernel loses more than any wait costs)
+    constexpr bool TWL = PP_LANE_CONSTS_LDS && !PP_ROW_WAIT_CEILING && Q_TW_RELOAD && sizeof(Tin) == 8 && (!TAIL || PP_TAIL_T2_LDS);
+    // phi_n through the scalar cache, one result store, the first row waited for in front of the loop
+    constexpr bool ROWTOP = !TAIL || PP_TAIL_ROW_TOP;
+    constexpr int NTW = (TWL && NML == 0) ? 2 : 0;
+    __shared__ cplx lds[LDSN + 64 * (NML + NTW)];
+    static_assert(sizeof(lds) <= 19456, "eight workgroups per CU");
+    static_assert(FFTQ_FREE_ELEM0 + 15 * FFTQ_FREE_PITCH < FFTQ_LDS_ELEMS && FFTQ_FREE_ELEM0 >= 64 * (TAIL ? 12 : 7) &&
+                  2 * FFTQ_FREE_ELEM0 >= PP_WRED_DOUBLES(NRED), "t2's elements are outside everything a row writes");
     cplx* const ldsm = lds + LDSN + threadIdx.x;
     int tid = threadIdx.x;
     const long long nrows = (long long)a.nsub * a.nchan;
     Raw cur[PER1][R1];
     // stage twiddles: W_1024^tid, W_64^(tid & 15)
-    // f64 rows re-read them every row (three L1-resident loads, older than the prefetch)
-    // instead of holding 12 registers through the whole row: with them held, three of the
+    // f64 rows do not hold them (12 registers) through the whole row: with them held, three of the
     // template values spill to scratch, and a scratch reload queues BEHIND the prefetched
     // row (vector memory returns in order) -- the split then waits for the next row's HBM
-    // data (15.1 -> 14.1 ms per 1024 fits)
+    // data (15.1 -> 14.1 ms per 1024 fits).  TWR: they were re-read at the top of every row instead, three L1-resident
+    // vector loads -- which come back behind every row piece the CU's other seven waves have queued (the vector-memory
+    // path returns in order).  TWL: the wave writes the three values to its own LDS once (and again after tail_work,
+    // which uses the whole LDS) and the row reads them back with ds_read_b128 where they are used -- LDS returns on
+    // lgkmcnt, not through that queue --; phi_n, one word for the whole wave, comes through the scalar cache (k_setup /
+    // k_phase0 wrote it in an earlier launch; the tickets this launch carries belong to another work set).  The row
+    // loop's vector memory is then the row stream, one result store and the per-chunk / per-channel reads, and nothing
+    // else.  Worth 0.3 % by itself (profiles/r07_row_wait_ceiling.txt): the wait at the top of a row is for the row.
     constexpr bool TWR = Q_TW_RELOAD && sizeof(Tin) == 8;
     cplx t1 = a.twB[2 * tid], t2 = a.twB[32 * (tid & 15)];
     // this lane's harmonics k = kb + 64 j; split twiddle W_B^kb, stepped by W_B^64
     const int lam0 = fftq_lambda(tid);
     cplx wb0 = a.twB[lam0 ? lam0 : 64];
     const cplx wbT = a.twB[64];
+    cplx* const ldt2 = lds + FFTQ_FREE_ELEM0;          // [17 (tid & 15)]
+    cplx* const ldtw = lds + LDSN + 64 * NML;          // t1 [tid] | wb0 [64 + tid]
+    auto put_lane_consts = [&](const cplx p1, const cplx p2, const cplx pb) {
+        if (!TWL) return;
+        ldt2[FFTQ_FREE_PITCH * (tid & 15)] = p2;       // (four lanes, the same value)
+        if (NTW) { ldtw[tid] = p1; ldtw[64 + tid] = pb; }
+        lds_sync<T>();
+    };
+    put_lane_consts(t1, t2, wb0);
     // (the previous batch's solve + post-fit stage, see tail_work: this wave draws ONE ticket after tail_after rows --
     // a different count for every wave, spread over the first three quarters of its share, so that at any time a
     // few per cent of the waves are out of the transform instead of half of them for the first millisecond --
@@ -136,6 +243,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     const cplx* mrow = nullptr;    // the template row and cut of the channel in hand (channel_lookup)
     int n_held = -1, ktn = 0;
     int i_nx = i, n_nx = n;
+    if (ROWTOP) first_row_landed();
 #pragma unroll 1
     for (int phase = 0; phase < 2; ++phase) {
     if (phase == 1) {
@@ -143,6 +251,10 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         // (between two rows: the next row's loads are in flight, the call keeps what it must across itself)
         tail_work(a.tail, reinterpret_cast<double*>(lds), 2 * (LDSN + 64 * NML), tid, 1);
         tail_after = 0x7fffffff;
+        if (TWL) {      // (its layout covers the image: the lane constants again)
+            const int lamr = fftq_lambda(tid);
+            put_lane_consts(as_global(a.twB)[2 * tid], as_global(a.twB)[32 * (tid & 15)], as_global(a.twB)[lamr ? lamr : 64]);
+        }
     }
     for (; rw.more && tail_after != 0; rw.advance(), row = rw.row, i = i_nx, n = n_nx, --tail_after) {
         rw.draw(a.ticket);
@@ -153,7 +265,13 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         const int lam = fftq_lambda(tid);
         const bool l0 = (lam == 0);
         const int kb = l0 ? 64 : lam;
-        if (TWR) {
+        if (PP_ROW_WAIT_CEILING && TWR) {
+            t1 = t2 = wb0 = wbT;
+            asm volatile("" : "+v"(t1.x), "+v"(t1.y), "+v"(t2.x), "+v"(t2.y), "+v"(wb0.x), "+v"(wb0.y));
+        } else if (TWL) {
+            // (read where they are used; without the two tables t1 and wb0 stay vector loads)
+            if (!NTW) { t1 = as_global(a.twB)[2 * tid]; wb0 = as_global(a.twB)[kb]; }
+        } else if (TWR) {
             t1 = as_global(a.twB)[2 * tid];
             t2 = as_global(a.twB)[32 * (tid & 15)];
             wb0 = as_global(a.twB)[kb];
@@ -172,7 +290,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
             }
             mheld = mrow;
         }
-        const double phin = a.ph0[rc];
+        const double phin = ROWTOP ? load_uniform(a.ph0 + rc) : a.ph0[rc];
         double sd = 0.0;
         cplx v[R1];
 #pragma unroll
@@ -216,7 +334,9 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
             load_some(0, HALVES ? R1 / 2 : R1);
             __builtin_amdgcn_sched_barrier(0);
         };
-        fftq1024<(sizeof(Tin) == 8 ? Q_PREFETCH_F64 : Q_PREFETCH_F32)>(v, lds, t1, t2, tid, &sd, prefetch);
+        fftq1024_from<(sizeof(Tin) == 8 ? Q_PREFETCH_F64 : Q_PREFETCH_F32)>(
+            v, lds, [&]() { return NTW ? ldtw[tid] : t1; }, [&]() { return TWL ? ldt2[FFTQ_FREE_PITCH * (tid & 15)] : t2; },
+            tid, &sd, prefetch);
         __builtin_amdgcn_sched_barrier(0);
         // ---- partners through LDS: registers 9..15 out, seven values back ----
         {
@@ -240,6 +360,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
             }
             lds_sync<T>();
         }
+        if (NTW) wb0 = ldtw[64 + tid];
         double tail = 0.0;
         if (TAIL) {
             // |2 d_k|^2 for k = lam + 64 kd, kd = 12..15; W_B^k = W_B^kb0 W_B^(64 kd) with
@@ -340,19 +461,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         if (TAIL) tr[NRED - 1] = tail;
         lds_sync<T>();      // (the partner reads are older than the reduction's writes)
         double tv = wave_reduce_lds(tr, tid, reinterpret_cast<double*>(lds));
-        if ((tid & 3) == 0) {
-            const int q = wave_reduce16_index(tid);
-            if (q < PP_TSTRIDE) {
-                // Re(i^q z): +Re, -Im, -Re, +Im, ...   (x 1/2: unhalved template against 2 d_k)
-                tv *= 0.5;
-                a.tay[tay_idx(rc, q)] = (q <= PP_TJ && ((q & 3) == 1 || (q & 3) == 2)) ? -tv : tv;
-            }
-        }
-        if (tid == 4 * PP_TSTRIDE) a.sdraw[rc] = tv;
-        if (TAIL && tid == 4 * (PP_TSTRIDE + 1)) {
-            constexpr int H = M + 1, kc = (int)(0.75 * H);   // get_noise_PS: int((1 - 1/4) * len(pows))
-            a.noise[rc] = sqrt(tv / (2.0 * M) / (double)(H - kc));
-        }
+        store_row_results<M, TAIL, ROWTOP>(a, rc, tid, tv);
         lds_sync<T>();
     }
     }
@@ -381,6 +490,16 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
 #ifndef PP_QF512_HOLD_TEMPLATE
 #define PP_QF512_HOLD_TEMPLATE 1
 #endif
+// k_xspec_qf: phi_n through the scalar cache, the row's results in one store, the first row waited for in front of the
+// loop (see store_row_results, first_row_landed): +0.5 % for 2048-bin rows with the noise given; -0.6 % for 1024-bin
+// rows (three waves per SIMD hide the wait already) and -0.3 % for 2048-bin rows whose noise is measured (as in
+// k_xspec_q1024; profiles/r07_lane_consts_ab.txt) -- PP_QF_ROW_TOP_ALL, off.  The stage twiddles stay where they are (Q::run)
+#ifndef PP_QF_ROW_TOP
+#define PP_QF_ROW_TOP 1
+#endif
+#ifndef PP_QF_ROW_TOP_ALL
+#define PP_QF_ROW_TOP_ALL 0
+#endif
 #ifndef PP_QF512_WPS
 #define PP_QF512_WPS 3
 #endif
@@ -399,6 +518,7 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
     static_assert(M != 1024 || 2 * LDSN >= PP_TAIL_LDS_DOUBLES, "tail_work's layout of this kernel's LDS");
     __shared__ cplx lds[LDSN];
     int tid = threadIdx.x;
+    constexpr bool QTOP = PP_QF_ROW_TOP && ((M == 1024 && !TAIL) || PP_QF_ROW_TOP_ALL);
     const long long nrows = (long long)a.nsub * a.nchan;
     Raw cur[PER1][R1];
     const cplx wbT = a.twB[64];
@@ -425,6 +545,7 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
     constexpr bool MHOLD = PP_QF512_HOLD_TEMPLATE && M == 512;
     cplx mv[NSL];
     const cplx* mheld = nullptr;
+    if (QTOP) first_row_landed();
 #pragma unroll 1
     for (int phase = 0; phase < 2; ++phase) {
     if (phase == 1) {
@@ -448,7 +569,7 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
             for (int j = 0; j < NSL; ++j) mv[j] = mrow[kb + 64 * j - 1];
             mheld = mrow;
         }
-        const double phin = a.ph0[rc];
+        const double phin = QTOP ? load_uniform(a.ph0 + rc) : a.ph0[rc];
         double sd = 0.0;
         cplx v[R1];
 #pragma unroll
@@ -573,18 +694,7 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
         if (TAIL) tr[NRED - 1] = 0.25 * tail;
         lds_sync<T>();      // (the partner reads are older than the reduction's writes)
         double tv = wave_reduce_lds(tr, tid, reinterpret_cast<double*>(lds));
-        if ((tid & 3) == 0) {
-            const int q = wave_reduce16_index(tid);
-            if (q < PP_TSTRIDE) {
-                tv *= 0.5;
-                a.tay[tay_idx(rc, q)] = (q <= PP_TJ && ((q & 3) == 1 || (q & 3) == 2)) ? -tv : tv;
-            }
-        }
-        if (tid == 4 * PP_TSTRIDE) a.sdraw[rc] = tv;
-        if (TAIL && tid == 4 * (PP_TSTRIDE + 1)) {
-            constexpr int H = M + 1, kc = (int)(0.75 * H);   // get_noise_PS: int((1 - 1/4) * len(pows))
-            a.noise[rc] = sqrt(tv / (2.0 * M) / (double)(H - kc));
-        }
+        store_row_results<M, TAIL, QTOP>(a, rc, tid, tv);
         lds_sync<T>();
     }
     }

@@ -84,6 +84,71 @@ def loop_scratch(so=None, pat=""):
         return out
 
 
+def row_loop(so=None, kernel=""):
+    """The instructions (text, operands included) of the ROW LOOP of the kernel whose short demangled name is `kernel`:
+    the widest call-free loop that holds the 16 once-read (`nt`) loads of the next row (the compiler closes the loop with
+    more than one backward branch, one of them into the middle of the row; the loop around the call to tail_work and the
+    loops inside the row -- ticket draws, mask words -- are not it)."""
+    so = so or os.path.join(ROOT, "pulseportraiture_amd", "csrc", "libpptoas_hip.so")
+    with tempfile.TemporaryDirectory() as tmp:
+        co = code_object(so, tmp)
+        full = subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True,
+                              check=True).stdout
+    syms = re.findall(r"^[0-9a-f]+ <(_ZN2pp[^>]+)>:", full, re.M)
+    dem = subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True).stdout.split("\n")
+    want = [sy for sy, name in zip(syms, dem) if re.sub(r"\(.*\)$", "", re.sub(r"^(void )?pp::", "", name)) == kernel]
+    if len(want) != 1:
+        raise KeyError(kernel)
+    ins, start, on = [], None, False          # (address, text, branch target or None)
+    for ln in full.splitlines():
+        m = re.match(r"^([0-9a-f]+) <([^>]+)>:", ln)
+        if m:
+            on = (m.group(2) == want[0])
+            start = int(m.group(1), 16)
+            continue
+        m = re.match(r"^\s+(\S.*?)\s*//\s*([0-9A-Fa-f]+):", ln)
+        if not on or not m:
+            continue
+        text, addr = m.group(1), int(m.group(2), 16)
+        mnem, tgt = text.split()[0], None
+        if mnem.startswith("s_cbranch") or mnem == "s_branch":
+            t = re.search(r"<[^>]*\+0x([0-9a-f]+)>", ln)
+            tgt = start + int(t.group(1), 16) if t else start
+        ins.append((addr, text, tgt))
+    calls = [a for a, tx, t in ins if tx.startswith("s_swappc")]
+    loops = [(lo, hi) for hi, tx, lo in ins if lo is not None and lo <= hi and not any(lo <= c <= hi for c in calls)]
+    is_row = lambda tx: tx.startswith("global_load_dwordx") and tx.endswith(" nt")
+    best = None
+    for lo, hi in loops:
+        if sum(1 for a, tx, t in ins if lo <= a <= hi and is_row(tx)) >= 16 and (best is None or hi - lo > best[1] - best[0]):
+            best = (lo, hi)
+    if best is None:
+        raise ValueError("no row loop in " + kernel)
+    return [tx for a, tx, t in ins if best[0] <= a <= best[1]]
+
+
+def metadata(so=None, pat=""):
+    """{kernel (demangled, short): dict(vgpr, agpr, sgpr, vspill, sspill, lds, scratch)} from the code object's notes."""
+    so = so or os.path.join(ROOT, "pulseportraiture_amd", "csrc", "libpptoas_hip.so")
+    with tempfile.TemporaryDirectory() as tmp:
+        notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", code_object(so, tmp)], capture_output=True, text=True,
+                               check=True).stdout
+    keys = dict(vgpr="vgpr_count", agpr="agpr_count", sgpr="sgpr_count", vspill="vgpr_spill_count",
+                sspill="sgpr_spill_count", lds="group_segment_fixed_size", scratch="private_segment_fixed_size")
+    rows = []
+    for e in re.split(r"\n  - ", notes):
+        m = re.search(r"\.name:\s+(\S+)", e)
+        if m and ".vgpr_count" in e:
+            rows.append((m.group(1), {k: int(re.search(r"\.%s:\s+(\d+)" % v, e).group(1)) for k, v in keys.items()}))
+    names = subprocess.run(["c++filt"], input="\n".join(r[0] for r in rows), capture_output=True, text=True).stdout.split("\n")
+    out = {}
+    for (sym, d), n in zip(rows, names):
+        n = re.sub(r"\(.*\)$", "", re.sub(r"^(void )?pp::", "", n))
+        if not pat or pat in n:
+            out[n] = d
+    return out
+
+
 def main():
     so = os.path.join(ROOT, "pulseportraiture_amd", "csrc", "libpptoas_hip.so")
     if len(sys.argv) > 1 and sys.argv[1] == "--loops":

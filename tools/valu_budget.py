@@ -142,7 +142,7 @@ def main():
                         if i > lo_ and pat in l:
                             return i
                 raise KeyError(pats)
-            xq = {"fft": after("fftq1024<", "Q::template run<")}
+            xq = {"fft": after("fftq1024<", "fftq1024_from<", "Q::template run<")}
             xq["partners"] = after("// ---- partners through LDS", start=xq["fft"])
             xq["phasors"] = after("// ---- phasors:", "const cplx* pc = lds + Q::lane_of", start=xq["partners"])
             xq["reduce"] = after("// ---- the 12 sums and S_d", "double tr[NRED];", start=xq["phasors"])
