@@ -116,6 +116,7 @@ __global__ __launch_bounds__(FftPlan<L>::T) void k_any(XspecArgs a, AnyArgs g) {
                 acc[2] = fma(kk * kk, z.x, acc[2]);
             } else {
                 static_assert(PP_TJ == 10, "power ladder written for order 10");
+                // (taylor_terms' sums in running form, written out: the call moves k_any's register allocation)
                 const double kap = PP_TWO_PI * (double)k;
                 const double p2 = kap * kap, p4 = p2 * p2, p6 = p4 * p2, p8 = p4 * p4, p10 = p8 * p2;
                 const double ui = z.y * kap;

@@ -14,10 +14,6 @@ namespace pp {
 
 typedef double2 cplx;
 
-#ifndef PP_FAST_SINCOS
-#define PP_FAST_SINCOS 1
-#endif
-
 __device__ __forceinline__ cplx cmul(cplx a, cplx b) {
     return make_double2(fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x));
 }
@@ -122,11 +118,7 @@ __device__ __forceinline__ cplx unit_phasor(double k, double phi) {
     double err = fma(k, pfrac, -prod);       // exact residual of the product
     double r = (prod - rint(prod)) + err;
     double s, c;
-#if PP_FAST_SINCOS
     sincos_turns<SC>(r, &s, &c);
-#else
-    sincospi(2.0 * r, &s, &c);
-#endif
     return make_double2(c, s);
 }
 
@@ -291,33 +283,19 @@ struct SubState {
 #define PP_NACC 21
 // channels per workgroup of the kernels that sum over channels (evaluators, seed accumulation, moments):
 // a property of the band, never of the batch (see fit_chunk's `chunking`)
-#ifndef PP_CHUNK_CHANNELS
-#define PP_CHUNK_CHANNELS 256
-#endif
+constexpr int PP_CHUNK_CHANNELS = 256;
 // raw per-channel sums kept for the post-fit stage
 #define PP_NCS 9   // A0 A1 A2 T1 T2 A1T S0 S1 S2
 // order of the per-channel Taylor model of C_n(phi_n) about the initial point:
 // A_0 .. A_PP_TJ (derivatives) + a rigorous remainder coefficient
 #define PP_TJ 10
 #define PP_TSTRIDE (PP_TJ + 2)
-// The Taylor rows in HBM.  Row-major (default): 12 doubles per row, 96 B apart -- the transform writes a row as one
-// 96-byte piece.  PP_TAY_BLOCKED = 1: blocks of 64 rows with the coefficients in pairs, [row / 64][pair 0..5][row % 64][2],
-// so that the solve, where lane l works on row r0 + l, reads 1 KB contiguous per load instruction and its evaluation at
-// the expansion point only two of the six pairs.  Measured (profiles/README.md, round 4): the solve at 4096 channels is
-// bound by the bytes it re-reads, not by how it touches the lines (0.44 against 0.45-0.46 ms), while the transform pays
-// 6 more VALU instructions per row for the addresses and writes six pieces instead of one: +1 % of 14.4 ms.  Kept as a
-// build option; the buffer holds a multiple of 64 rows either way.
-#ifndef PP_TAY_BLOCKED
-#define PP_TAY_BLOCKED 0
-#endif
-#if PP_TAY_BLOCKED
-#define PP_TAY_PAIR_STRIDE 128     // doubles between the coefficient pairs of a row
-__device__ __forceinline__ size_t tay_idx(size_t row, int q) {
-    return (row >> 6) * (size_t)(64 * PP_TSTRIDE) + (size_t)(q >> 1) * 128 + (row & 63) * 2 + (q & 1);
-}
-#else
-#define PP_TAY_PAIR_STRIDE 2
+// The Taylor rows in HBM, row-major: 12 doubles per row, 96 B apart -- the transform writes a row as one 96-byte piece.
+// (Blocks of 64 rows with the coefficients in pairs, 1 KB contiguous per load of the solve, were built and measured in
+// round 4, profiles/README.md: the solve at 4096 channels is bound by the bytes it re-reads, not by how it touches the
+// lines, while the transform paid 6 more VALU instructions per row and six pieces instead of one, +1 % of 14.4 ms.)
+// The buffer holds a multiple of 64 rows.
+#define PP_TAY_PAIR_STRIDE 2       // doubles between the coefficient pairs of a row
 __device__ __forceinline__ size_t tay_idx(size_t row, int q) { return row * PP_TSTRIDE + (size_t)q; }
-#endif
 
 }  // namespace pp

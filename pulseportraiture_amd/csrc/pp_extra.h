@@ -333,14 +333,8 @@ __global__ __launch_bounds__(64, 2) void k_rot_mean_q1024(RotMeanArgs a) {
         const cplx z0 = v[0];      // (lane 0: Z_0)
 #pragma unroll
         for (int kd = 0; kd < 16; ++kd) {
-            const cplx zk = v[kd];
-            cplx zc = pc[64 * (15 - kd)];
-            zc.y = -zc.y;
-            // 2 d_k = E - i W^k O with E, O unhalved; the half goes into the weight (exact)
-            const cplx E = make_double2(zk.x + zc.x, zk.y + zc.y);
-            const cplx O = make_double2(zk.x - zc.x, zk.y - zc.y);
-            const cplx wo = cmul(wb, O);
-            cplx y = cmul(make_double2(E.x + wo.y, E.y - wo.x), e);
+            // 2 d_k, unhalved; the half goes into the weight (exact)
+            cplx y = cmul(split_pair(v[kd], pc[64 * (15 - kd)], wb), e);
             if (kd == 0) {
                 // harmonic 0 of lane 0: d_0 = Re Z_0 + Im Z_0
                 y.x = l0 ? 2.0 * (z0.x + z0.y) : y.x;

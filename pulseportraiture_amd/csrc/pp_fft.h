@@ -115,9 +115,6 @@ __device__ __forceinline__ int lds_pad(int i) { return i + (i >> PADLOG); }
 // `s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier`, which would stall on the
 // prefetched HBM loads of the next row.  A one-wave workgroup (T == 64) needs
 // no barrier at all: its LDS operations retire in order.
-#ifndef PP_WAVE_SYNC_WAITS
-#define PP_WAVE_SYNC_WAITS 0    // 1: a one-wave workgroup still drains lgkmcnt at every sync
-#endif
 template <int T>
 __device__ __forceinline__ void lds_sync() {
     if (T == 64) {
@@ -126,8 +123,7 @@ __device__ __forceinline__ void lds_sync() {
         // has to be kept from reordering.  (Waiting here for lgkmcnt(0) would stop
         // the wave until EVERY outstanding read has returned, where the compiler's
         // own counted waits let the first butterfly start as its operands arrive.)
-        if (PP_WAVE_SYNC_WAITS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        else asm volatile("" ::: "memory");
+        asm volatile("" ::: "memory");
     } else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
@@ -160,12 +156,8 @@ __device__ __forceinline__ cplx to_cplx(float2 v) { return make_double2((double)
 // A portrait row is read exactly once per pass: its loads are marked non-temporal so that
 // the stream does not displace the template rows, twiddles and per-channel tables the
 // same CU keeps re-reading (k_xspec_q1024: 14.3-14.6 -> 14.0-14.1 ms per 1024 fits).
-#ifndef PP_NT_ROW_LOADS
-#define PP_NT_ROW_LOADS 1
-#endif
 template <typename Raw>
 __device__ __forceinline__ Raw load_row_once(const char* pa) {
-#if PP_NT_ROW_LOADS
     // (the builtin takes native vectors)
     typedef double nvd2 __attribute__((ext_vector_type(2)));
     typedef float nvf2 __attribute__((ext_vector_type(2)));
@@ -178,9 +170,6 @@ __device__ __forceinline__ Raw load_row_once(const char* pa) {
         r.x = t.x; r.y = t.y;
     }
     return r;
-#else
-    return *reinterpret_cast<const Raw*>(pa);
-#endif
 }
 
 template <int M, int T, int R, typename Tin, typename Raw, int PER>
@@ -252,10 +241,7 @@ __device__ __forceinline__ void stage_finish(cplx (&v)[PER][R], cplx* lds, const
             const int q = t & (S - 1);
             const int ob = q + S * R * (t / S);
             if constexpr (!LAST) {
-#ifndef PP_TWIDDLE_TREE
-#define PP_TWIDDLE_TREE 1
-#endif
-                if (PP_TWIDDLE_TREE && TREE) {
+                if (TREE) {
                     // v[j] *= w^j with every power formed once, w^j = (w^(j/2))^2 or
                     // w^(j-1) w: R - 2 products for the powers + R - 1 for the elements
                     // (29 for R = 16 where the bitwise scheme below takes 35), at most
@@ -353,9 +339,7 @@ PP_PLAN(64, 64, 8, 8, 1, 1, 3);
 PP_PLAN(128, 64, 8, 4, 4, 1, 3);
 PP_PLAN(256, 64, 8, 8, 4, 1, 3);
 PP_PLAN(512, 64, 8, 8, 8, 1, 3);
-#ifndef PP_PLAN1024
 #define PP_PLAN1024 64, 16, 8, 8, 1, 4
-#endif
 #define PP_PLAN_X(M_, ...) PP_PLAN(M_, __VA_ARGS__)
 PP_PLAN_X(1024, PP_PLAN1024);
 PP_PLAN(2048, 256, 8, 8, 8, 4, 3);

@@ -283,4 +283,68 @@ template <> struct FftQ<512> {
     }
 };
 
+// --------------------------------------------------------------------------
+// Row code the transform kernels share: the arithmetic that is the same in all of them.  Where each kernel calls it --
+// between which scheduling barriers, prefetch halves and LDS syncs -- is that kernel's own, measured, business.
+// --------------------------------------------------------------------------
+
+// The even/odd split of a harmonic pair: 2 d_k = E - i W^k O with E, O = Z_k +- conj Z_{M-k} (unhalved), from this
+// lane's Z_k, the partner's Z_{M-k} (zc, conjugated here) and the split twiddle wb = W_B^k.
+__device__ __forceinline__ cplx split_pair(const cplx zk, cplx zc, const cplx wb) {
+    zc.y = -zc.y;
+    const cplx E = make_double2(zk.x + zc.x, zk.y + zc.y);
+    const cplx O = make_double2(zk.x - zc.x, zk.y - zc.y);
+    const cplx wo = cmul(wb, O);
+    return make_double2(E.x + wo.y, E.y - wo.x);
+}
+
+// One harmonic's terms of the 12 Taylor sums (A_0 .. A_10 of the channel's model about the expansion point and the
+// remainder coefficient): x = X_k, z = X_k e^{i kappa phi}, kap = kappa_k.  kappa^2, ^4 .. ^10 once per harmonic, every
+// sum is then one FMA.  first (a compile-time value at every call site): the sums START from this harmonic -- no zeroing.
+template <int N>
+__device__ __forceinline__ void taylor_terms(const bool first, double (&tm)[N], const cplx x, const cplx z, const double kap) {
+    static_assert(PP_TJ == 10 && N >= PP_TSTRIDE, "power ladder written for order 10");
+    const double p2 = kap * kap, p4 = p2 * p2, p6 = p4 * p2, p8 = p4 * p4, p10 = p8 * p2;
+    const double ui = z.y * kap;
+    const double ax = fabs(x.x) + fabs(x.y);
+    if (first) {
+        tm[0] = z.x;
+        tm[1] = ui;
+        tm[2] = p2 * z.x;
+        tm[3] = p2 * ui;
+        tm[4] = p4 * z.x;
+        tm[5] = p4 * ui;
+        tm[6] = p6 * z.x;
+        tm[7] = p6 * ui;
+        tm[8] = p8 * z.x;
+        tm[9] = p8 * ui;
+        tm[10] = p10 * z.x;
+        tm[11] = (p10 * kap) * ax;
+    } else {
+        tm[0] += z.x;
+        tm[1] += ui;
+        tm[2] = fma(p2, z.x, tm[2]);
+        tm[3] = fma(p2, ui, tm[3]);
+        tm[4] = fma(p4, z.x, tm[4]);
+        tm[5] = fma(p4, ui, tm[5]);
+        tm[6] = fma(p6, z.x, tm[6]);
+        tm[7] = fma(p6, ui, tm[7]);
+        tm[8] = fma(p8, z.x, tm[8]);
+        tm[9] = fma(p8, ui, tm[9]);
+        tm[10] = fma(p10, z.x, tm[10]);
+        tm[11] = fma(p10 * kap, ax, tm[11]);
+    }
+}
+
+// Pieces k0 .. k1 - 1 of the row at nxrow (piece k = elements 64 k .. 64 k + 63, one per lane) into the registers of
+// the next row, read once (load_row_once).  k0 and k1 are compile-time values at every call site.
+template <typename Raw, int R>
+__device__ __forceinline__ void load_row_pieces(Raw (&cur)[1][R], const void* nxrow, const int tid, const int k0, const int k1) {
+    const char* gb = reinterpret_cast<const char*>(nxrow);
+    const unsigned boff = (unsigned)tid * (unsigned)sizeof(Raw);
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+        if (k >= k0 && k < k1) cur[0][k] = load_row_once<Raw>(gb + (size_t)(k * 64) * sizeof(Raw) + boff);
+}
+
 }  // namespace pp

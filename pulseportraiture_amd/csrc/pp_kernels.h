@@ -165,12 +165,9 @@ __device__ __forceinline__ const P* uniform_ptr(const P* p) {
 // other rows' prefetches have in flight: a memory latency per wait, two waits per row.  With the lookups inside this
 // branch a row that does not take it waits for nothing but its own data (profiles/r05_quiet_row_top_ab.txt: +3.5 %).
 // Returns true when it looked.
-#ifndef PP_STICKY_LOOKUP
-#define PP_STICKY_LOOKUP 1
-#endif
 __device__ __forceinline__ bool channel_lookup(const XspecArgs& a, int ia, int n, int ne, int M, int& n_held,
                                                const cplx*& mrow, int& ktn) {
-    if (PP_STICKY_LOOKUP && !a.slot && n == n_held) return false;
+    if (!a.slot && n == n_held) return false;
     const cplx* m = as_global(a.slot ? a.mft[a.slot[ia]] : a.mft0) + (size_t)ne * M;
     const int k = a.ktab ? as_global(a.slot ? a.ktab[a.slot[ia]] : a.kt0)[ne] : a.Kt;
     mrow = uniform_ptr(m);
@@ -262,9 +259,7 @@ __global__ void k_model_kcut(const cplx* mft, const double* mmax, int /*nchan*/,
 // counter is never reset: a launch consumes exactly one ticket per chunk, which the
 // host adds to the base it passes to the next launch (32 bits, wrapping: only the
 // difference is used).  The template row is re-read (L2) once per chunk.
-#ifndef PP_ROW_CHUNK
-#define PP_ROW_CHUNK 32
-#endif
+constexpr int PP_ROW_CHUNK = 32;
 // DYN = false (workgroups of several waves: the ticket would have to cross waves):
 // chunk c goes to workgroup c mod G; the tickets are then not drawn at all.
 // Rows in use (XspecArgs::mwords): one 32-bit word per chunk, bit b set = row 32 c + b is to be
@@ -399,12 +394,7 @@ struct RowWalk {
     }
 };
 
-#ifndef PP_SPLIT_U
-#define PP_SPLIT_U 4          // harmonics per thread processed together in the split loop
-#endif
-#ifndef PP_OPAQUE_ROW
-#define PP_OPAQUE_ROW 2         // 0 never, 1 always, 2 only in MODE 2 (register-bound)
-#endif
+constexpr int PP_SPLIT_U = 4;          // harmonics per thread processed together in the split loop
 // MODE 0: store X.  MODE 1: store X and the sums A0, A1, A2 at the initial
 // parameters.  MODE 2: store NO cross-spectrum, only the Taylor model of every
 // channel about the initial parameters (A_0..A_PP_TJ + remainder coefficient,
@@ -471,8 +461,9 @@ __global__ __launch_bounds__(FftPlan<M>::T, (FftPlan<M>::T >= 256 ? 1 : 2)) void
         // Everything derived from the thread index and the twiddles is invariant
         // over this loop, and the compiler hoists all of it (LDS addresses of every
         // stage, twiddle powers: ~50 VGPRs held across the whole row).  Recomputing
-        // them per row frees those registers; it only pays where that buys occupancy.
-        if (PP_OPAQUE_ROW == 1 || (PP_OPAQUE_ROW == 2 && M2)) {
+        // them per row frees those registers; it only pays where that buys occupancy:
+        // in MODE 2 / 3 (register-bound).
+        if (M2) {
             asm volatile("" : "+v"(tid));
             opaque_twiddles<M>(tw);
             asm volatile("" : "+v"(wb0.x), "+v"(wb0.y));   // or all of wb0 wbT^j are hoisted
@@ -579,7 +570,9 @@ __global__ __launch_bounds__(FftPlan<M>::T, (FftPlan<M>::T >= 256 ? 1 : 2)) void
                 for (int j = 0; j < PP_TSTRIDE; ++j) tm[j] = 0.0;
             }
             // kappa^2, ^4 .. ^10 once per harmonic; every sum is then one FMA
-            // (first: the sums start from this harmonic)
+            // (first: the sums start from this harmonic).  taylor_terms (pp_fftq.h) is this ladder for the one-wave
+            // kernels; called from here it costs k_xspec<1024, double, true, 3> eight spilled registers and
+            // k_xspec<256, float, false, 3> its fourth wave per SIMD (profiles/r08_refactor_isa.txt)
             auto taylor_sums = [&](const cplx& x, const cplx& z, double kap, bool first) {
                 const double p2 = kap * kap, p4 = p2 * p2, p6 = p4 * p2, p8 = p4 * p4, p10 = p8 * p2;
                 const double ui = z.y * kap;
@@ -1016,9 +1009,6 @@ __device__ __forceinline__ void accumulate_channel(const Local& L, const ChanGeo
 // --------------------------------------------------------------------------
 // chi^2 evaluators: k_eval_fast below (no scattering) and k_eval_scat (pp_evalscat.h).
 // --------------------------------------------------------------------------
-#ifndef PP_FAST_RECIP
-#define PP_FAST_RECIP 1       // |B_nk|^2 = 1/(1 + u^2) by rcp + 2 Newton steps (~1 ulp)
-#endif
 
 // First evaluation when k_xspec already produced the per-channel sums (FUSE):
 // only the O(nchan) chain rule + reduction remains.  grid = (nchunk, nsub).
@@ -1641,12 +1631,8 @@ __device__ __forceinline__ void taylor_shift_reg(const double (&t)[PP_TSTRIDE], 
 // rows the subints in flight re-read on every evaluation -- 393 KB each at 4096 channels -- stay inside the
 // Infinity Cache).  (Rows held in registers over the evaluations: measured slower in round 3, profiles/README.md.)
 #define PP_SOLVE_CACHE_MAX 4096   // channels whose invariants k_taylor_solve can keep in LDS (32 B each: 512 per wave of the block)
-#ifndef PP_SOLVE_PF
-#define PP_SOLVE_PF 2         // Taylor rows a thread keeps on their way (24 registers each)
-#endif
-#ifndef PP_TAYLOR_WAVES
-#define PP_TAYLOR_WAVES 2     // waves per SIMD the kernel is compiled for (register cap 512 / n)
-#endif
+constexpr int PP_SOLVE_PF = 2;         // Taylor rows a thread keeps on their way (24 registers each)
+constexpr int PP_TAYLOR_WAVES = 2;     // waves per SIMD the kernel is compiled for (register cap 512 / n)
 // The body serves two kernels.  NVW = 1: NT real threads, one subint per workgroup (k_taylor_solve).  NVW = NT / 64:
 // ONE real wave walks the NT / 64 waves of that kernel in turn -- lane l plays threads l, l + 64, ... -- and forms
 // every block-wide sum from the same per-wave totals in the same order (vblock_sum): bitwise the results of the
@@ -1772,9 +1758,6 @@ __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i,
     };
     // f, g, H of the model at displacement dx from x0 (identical in every thread);
     // returns the largest per-channel phase displacement
-#ifdef PP_SOLVE_CLOCKS
-    long long ck_loop = 0, ck_red = 0, ck_start = clock64(), ck_n = 0;
-#endif
     // ... and at the expansion point itself (the first evaluation of the ordinary flow: d = 0 in every channel,
     // where Horner's rule returns A0, A1, A2 = t[0], t[1], t[2] exactly) only the first two coefficient pairs
     // of a row are read: 32 of its 96 bytes (which saves HBM traffic with the blocked row layout only)
@@ -1795,9 +1778,6 @@ __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i,
         }
     };
     auto evalm = [&](const double* dx, double& f, double* g, double* H, bool at_origin = false) -> double {
-#ifdef PP_SOLVE_CLOCKS
-        const long long ck0 = clock64();
-#endif
         double acc[10];
         double dmax = 0.0;
         // (a channel out of the fit adds zeros instead of branching around the work: the two channels a thread
@@ -1830,12 +1810,6 @@ __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i,
                     add(w, p1, p2, S0, A0, A1, A2);
                 });
         });
-#ifdef PP_SOLVE_CLOCKS
-        const long long ck1 = clock64();
-#endif
-#ifdef PP_SOLVE_CLOCKS
-        ck_loop += ck1 - ck0; ck_red += clock64() - ck1; ++ck_n;
-#endif
         f = acc[0];
         // (phi, DM, GM) block only: 3 + 9 numbers per thread instead of 5 + 25
         g[0] = fl[0] ? acc[1] : 0.0; g[1] = fl[1] ? acc[2] : 0.0; g[2] = fl[2] ? acc[3] : 0.0;
@@ -1969,9 +1943,6 @@ __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i,
     // ---- certificate (truncation error of the gradient, in parameter units) and the
     // sums of the accepted point x0 + dx for the post-fit stage, in ONE pass over the
     // model (they go to the buffer that only becomes current if the certificate holds)
-#ifdef PP_SOLVE_CLOCKS
-    const long long ck_cert = clock64();
-#endif
     const int buf = 1 - st.cur;
     if (ok) {
         double* csum = a.csum + ((size_t)buf * a.nsub + i) * a.nchan * a.ncs;
@@ -2037,13 +2008,6 @@ __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i,
             atomicSub(a.nactive, 1);
         }
     }
-#ifdef PP_SOLVE_CLOCKS
-    if (tid == 0 && (i % 200) == 0) {
-        const long long e = clock64();
-        printf("solve %d: total %lld loop %lld red %lld cert %lld evals %lld -> serial %lld\n", i, e - ck_start, ck_loop, ck_red,
-               e - ck_cert, ck_n, (e - ck_start) - ck_loop - ck_red - (e - ck_cert));
-    }
-#endif
     // Not ok.  The tentative answer x0 + dx is usually still far better than x0 (the
     // harmonics that carry the power are within the model's reach long after the
     // highest ones have left it): expand again about it -- one more pass over this
@@ -2452,9 +2416,6 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
             for (int j = 0; j < PP_NCS; ++j) cs[j] = csum[(size_t)n * PP_NCS + j];
         }
     };
-#ifdef PP_SOLVE_CLOCKS
-    const long long fk0 = clock64();
-#endif
     // ---- pass 0: Sd, mean frequency, used channels -------------------------
     double v3[3];
     vblock_sum<3, 31, NT, NVW>(v3, scratch, flip, nullptr, tid, [&](const int vt, double (&u3)[3], double&) __attribute__((always_inline)) {
@@ -2466,9 +2427,6 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
         });
     });
     const double Sd = v3[0], nused = v3[2], fmean = v3[1] / v3[2];
-#ifdef PP_SOLVE_CLOCKS
-    const long long fk1 = clock64();
-#endif
     int pat = 0;
     for (int j = 0; j < 5; ++j) pat = pat * 2 + (fl[j] ? 1 : 0);
     if (pat == 0x1F) pat = 0x1B;  // [1,1,1,1,1] is approximated by [1,1,0,1,1] (:893-901)
@@ -2552,9 +2510,6 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
             }
         });
         });
-#ifdef PP_SOLVE_CLOCKS
-        if (tid == 0 && (i % 200) == 0) printf("fin %d: zero-loop %lld\n", i, clock64() - fk1);
-#endif
         switch (pat) {
         case 0x18: nzDM = 1.0 / sqrt(v[0] / v[1]); break;
         case 0x14: nzGM = pow(v[0] / v[1], -0.25); break;
@@ -2630,9 +2585,6 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
     // ---- covariance with the amplitude parameters at the output references --
     // A_ij (15 upper) + Schur correction sum_n U_i U_j/(2 S_n) (15) -> 30 sums,
     // then snr^2
-#ifdef PP_SOLVE_CLOCKS
-    const long long fk2 = clock64();
-#endif
     double m[31];
     vblock_sum<31, 31, NT, NVW>(m, scratch, flip, nullptr, tid, [&](const int vt, double (&m)[31], double&) __attribute__((always_inline)) {
     for_channels(vt, [&](int n, int q) {
@@ -2668,12 +2620,6 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
         m[30] += w * A0 * r;      // (a_n sqrt(S_n))^2 = w A0^2/S0
     });
     });
-#ifdef PP_SOLVE_CLOCKS
-    const long long fk3 = clock64();
-#endif
-#ifdef PP_SOLVE_CLOCKS
-    const long long fk4 = clock64();
-#endif
     // positions of the fitted parameters, and everything that works on the fit subspace -- the inverse, the
     // per-channel scale errors, the covariance outputs -- with its dimension a compile-time number (PP_FOR_N):
     // no dynamically indexed array (those live in scratch memory), same operations in the same order
@@ -2702,9 +2648,6 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
     auto sel5 = [](double v0, double v1, double v2, double v3, double v4, int k) {
         return k == 0 ? v0 : k == 1 ? v1 : k == 2 ? v2 : k == 3 ? v3 : v4;
     };
-#ifdef PP_SOLVE_CLOCKS
-    long long fk5 = 0;
-#endif
     auto on_subspace = [&](auto NC) {
         constexpr int N = decltype(NC)::value;
         double Xs[N * N];
@@ -2718,9 +2661,6 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
             for (int c2 = 0; c2 < N; ++c2) Xs[r * N + c2] = sel5(row[0], row[1], row[2], row[3], row[4], ix[c2]);
         }
         const bool inv_ok = mat_inverse<N>(Xs);
-#ifdef PP_SOLVE_CLOCKS
-        fk5 = clock64();
-#endif
         // ---- per-channel outputs -------------------------------------------------
 #pragma unroll 1
         for (int kv = 0; kv < NVW; ++kv)
@@ -2769,11 +2709,6 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
     // (the register-cached variants serve fits without scattering: at most phi, DM, GM)
     if constexpr (CPT > 0) { PP_FOR_N3(nfit, on_subspace(std::integral_constant<int, N_>{})); }
     else { PP_FOR_N(nfit, on_subspace(std::integral_constant<int, N_>{})); }
-#ifdef PP_SOLVE_CLOCKS
-    if (tid == 0 && (i % 200) == 0)
-        printf("fin %d: pass0 %lld zero %lld covloop %lld covred %lld inv %lld chan %lld\n", i, fk1 - fk0, fk2 - fk1, fk3 - fk2,
-               fk4 - fk3, fk5 - fk4, clock64() - fk5);
-#endif
     if (tid == 0) {
         double* op = a.o_params + (size_t)i * 5;
         op[0] = phi_out; op[1] = DM; op[2] = GM;

@@ -32,9 +32,7 @@
 // (the state is that of the ordinary path at every moment).
 #pragma once
 
-#ifndef PP_MP
 #define PP_MP 8                 // total degree of the per-channel model
-#endif
 #define PP_MNG ((PP_MP + 1) * (PP_MP + 2) / 2)       // G[q][c], c <= q <= P, at q(q+1)/2 + c
 #define PP_MROW ((PP_MNG + PP_MP + 4 + 1) & ~1)       // + Sc[0..P], W_0, tau_n, W_(P+1) (even)
 static_assert(PP_MROW % 2 == 0, "rows of the scattering model are moved in pairs");
@@ -367,9 +365,6 @@ __global__ __launch_bounds__(256) void k_scat_model_solve(FitArgs a) {
     const double tau_c = a.log10_tau ? pow(10.0, xc[3]) : xc[3];
     const double kmax = PP_TWO_PI * (double)a.Kt;
     const double tol[5] = {1e-13, 1e-11, 1e-8, a.log10_tau ? 4e-11 : 1e-10 * tau_c, 1e-9};
-#ifdef PP_SOLVE_TIMING
-    long long tA = 0, tB = 0, tC = 0, t0 = clock64(), t1;
-#endif
     for (int round = 0;; ++round) {
         double xe[5];
         // (after the iteration has ended: one more sweep at the accepted point, which
@@ -447,18 +442,12 @@ __global__ __launch_bounds__(256) void k_scat_model_solve(FitArgs a) {
                 acc[PP_NACC + 5] += 2.0 * w * r * W0 * series_tail(PP_MP + 1, x, 0.5 * rho) * fma(y, y, 1.0 + y);
             }
         }
-#ifdef PP_SOLVE_TIMING
-        t1 = clock64(); tA += t1 - t0; t0 = t1;
-#endif
         if (publish) break;
         block_sum<PP_NACC + 6>(acc, scratch);
         if (tid == 0) flag = 0;
         __syncthreads();
         if (!inside) flag = 1;               // (any thread)
         __syncthreads();
-#ifdef PP_SOLVE_TIMING
-        t1 = clock64(); tB += t1 - t0; t0 = t1;
-#endif
         if (tid == 0) {
             double f, g[5], H[25];
             unpack_acc(acc, a.flags, f, g, H);
@@ -492,10 +481,6 @@ __global__ __launch_bounds__(256) void k_scat_model_solve(FitArgs a) {
             }
         }
         __syncthreads();
-#ifdef PP_SOLVE_TIMING
-        t1 = clock64(); tC += t1 - t0; t0 = t1;
-        if (flag >= 2 && tid == 0 && i == 0) printf("solve i=0 rounds %d: loop %lld  sum %lld  logic %lld cycles\n", round + 1, tA, tB, tC);
-#endif
         if (flag == 2) break;
         // (flag == 3: the loop comes round once more to publish)
     }

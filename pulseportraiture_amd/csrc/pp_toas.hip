@@ -17,6 +17,7 @@
 #include <atomic>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "pp_kernels.h"
@@ -304,20 +305,6 @@ extern "C" int pp_abi_version(void) { return PP_ABI_VERSION; }
 extern "C" const char* pp_last_error(void) { return g_err.c_str(); }
 
 static int ctx_init(pp_ctx* c) {
-    // PP_CU_EXCLUDE=n (experiments): the context's stream may not use the last n compute units
-    // (hipExtStreamCreateWithCUMask) and the persistent grids are sized for the rest -- measures what
-    // the transform loses when a few CUs are set aside for other work (profiles/README.md, round 4)
-    const char* ex = getenv("PP_CU_EXCLUDE");
-    const int nex = ex ? atoi(ex) : 0;
-    if (nex > 0) {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-        const int ncu = prop.multiProcessorCount;
-        std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-        for (int i = 0; i < ncu - nex; ++i) mask[i / 32] |= 1u << (i % 32);
-        HIP_TRY(hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)mask.size(), mask.data()));
-        c->ncu = ncu - nex;
-    } else
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     {
         // the stream of the solve / post-fit stage of deferred batches: OLDER work, dispatched first where the
@@ -825,12 +812,20 @@ static int resident_grid(pp_ctx* c, K kernel, int T, long long nrows, int fallba
         c->ncu = (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
                      ? prop.multiProcessorCount : 256;
     }
-    long long g = per_cu > 0 ? (long long)per_cu * c->ncu : (long long)fallback;
-    // PP_GRID_SCALE=f (experiments): the persistent grids at a fraction f of their residency -- what the transform
-    // loses when wave slots are left free for other work (profiles/README.md, round 5)
-    static const double scale = [] { const char* e = getenv("PP_GRID_SCALE"); return e ? atof(e) : 1.0; }();
-    if (scale > 0.0 && scale != 1.0) g = std::max(1LL, (long long)std::llround((double)g * scale));
+    const long long g = per_cu > 0 ? (long long)per_cu * c->ncu : (long long)fallback;
     return (int)std::max(1LL, std::min(nrows, g));
+}
+
+// f(std::bool_constant<b>) / f(std::integral_constant<int, mode>): a run-time flag or mode (1..MAX, anything else
+// is 0) as the compile-time value a kernel's template parameter wants
+template <typename F>
+static void with_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int MAX, typename F>
+static void with_mode(int mode, F f) {
+    if constexpr (MAX > 0) {
+        if (mode == MAX) f(std::integral_constant<int, MAX>{});
+        else with_mode<MAX - 1>(mode, f);
+    } else f(std::integral_constant<int, 0>{});
 }
 
 template <int MM, typename TIN>
@@ -842,76 +837,36 @@ static void launch_xspec(pp_ctx* c, const XspecArgs& xa_in, bool tail, int mode)
     xa.ticket = c->ticket.as<unsigned>();
     xa.ticket_base = c->ticket_base;
     if (T == 64) c->ticket_base += (unsigned)((nrows + PP_ROW_CHUNK - 1) / PP_ROW_CHUNK);
-    const dim3 blk(T);
+    auto launch = [&](auto kernel) {
+        const dim3 grid(resident_grid(c, kernel, T, nrows, fft_grid(T, nrows)));
+        hipLaunchKernelGGL(kernel, grid, dim3(T), 0, c->stream, xa);
+    };
     if constexpr (MM == 1024) {
         // 2048-bin rows, Taylor sums only (noise given or measured): the one-exchange transform
         // (pp_xspec1024q.h) -- a third of the LDS traffic of the general kernel
-        if (c->one_exchange && mode == 2 && 2 * xa.Kt < MM) {
-            if (tail) {
-                const dim3 grid(resident_grid(c, k_xspec_q1024<TIN, true>, T, nrows, fft_grid(T, nrows)));
-                hipLaunchKernelGGL((k_xspec_q1024<TIN, true>), grid, blk, 0, c->stream, xa);
-            } else {
-                const dim3 grid(resident_grid(c, k_xspec_q1024<TIN, false>, T, nrows, fft_grid(T, nrows)));
-                hipLaunchKernelGGL((k_xspec_q1024<TIN, false>), grid, blk, 0, c->stream, xa);
-            }
-            return;
-        }
-    }
-    if constexpr (MM == 1024) {
+        if (c->one_exchange && mode == 2 && 2 * xa.Kt < MM)
+            return with_flag(tail, [&](auto TL) { launch(k_xspec_q1024<TIN, decltype(TL)::value>); });
         // ... and with a template that keeps 512 harmonics or more (mode 3)
-        if (c->one_exchange && mode == 3) {
-            if (tail) {
-                const dim3 grid(resident_grid(c, k_xspec_qf<1024, TIN, true>, T, nrows, fft_grid(T, nrows)));
-                hipLaunchKernelGGL((k_xspec_qf<1024, TIN, true>), grid, blk, 0, c->stream, xa);
-            } else {
-                const dim3 grid(resident_grid(c, k_xspec_qf<1024, TIN, false>, T, nrows, fft_grid(T, nrows)));
-                hipLaunchKernelGGL((k_xspec_qf<1024, TIN, false>), grid, blk, 0, c->stream, xa);
-            }
-            return;
-        }
+        if (c->one_exchange && mode == 3)
+            return with_flag(tail, [&](auto TL) { launch(k_xspec_qf<1024, TIN, decltype(TL)::value>); });
     }
     if constexpr (MM == 512) {
         // 1024-bin rows, Taylor sums only: the one-exchange transform of pp_fftq.h (plan 8.4.2.8),
         // whatever the template keeps
-        if (c->one_exchange && (mode == 2 || mode == 3)) {
-            if (tail) {
-                const dim3 grid(resident_grid(c, k_xspec_qf<512, TIN, true>, T, nrows, fft_grid(T, nrows)));
-                hipLaunchKernelGGL((k_xspec_qf<512, TIN, true>), grid, blk, 0, c->stream, xa);
-            } else {
-                const dim3 grid(resident_grid(c, k_xspec_qf<512, TIN, false>, T, nrows, fft_grid(T, nrows)));
-                hipLaunchKernelGGL((k_xspec_qf<512, TIN, false>), grid, blk, 0, c->stream, xa);
-            }
-            return;
-        }
+        if (c->one_exchange && (mode == 2 || mode == 3))
+            return with_flag(tail, [&](auto TL) { launch(k_xspec_qf<512, TIN, decltype(TL)::value>); });
     }
     if constexpr (MM == 1024 && sizeof(TIN) == 4) {
         // 2048-bin rows whose template keeps fewer than 512 harmonics: last stage
         // and split in registers (pp_xspec1024.h)
         // (f32 portraits only: with f64 rows the 64 prefetch registers on top of the
         // 16 held outputs push the kernel over 256 VGPRs -- it spills and loses)
-        if (c->paired_split && 2 * xa.Kt < MM && mode <= 2 && !xa.act && xa.cstep == 1) {
-#define PP_XP(TL, MD)                                                                                  \
-    do {                                                                                               \
-        const dim3 grid(resident_grid(c, k_xspec_p1024<TIN, TL, MD>, T, nrows, fft_grid(T, nrows)));   \
-        hipLaunchKernelGGL((k_xspec_p1024<TIN, TL, MD>), grid, blk, 0, c->stream, xa);                 \
-    } while (0)
-            if (tail) { if (mode == 2) PP_XP(true, 2); else if (mode == 1) PP_XP(true, 1); else PP_XP(true, 0); }
-            else { if (mode == 2) PP_XP(false, 2); else if (mode == 1) PP_XP(false, 1); else PP_XP(false, 0); }
-#undef PP_XP
-            return;
-        }
+        if (c->paired_split && 2 * xa.Kt < MM && mode <= 2 && !xa.act && xa.cstep == 1)
+            return with_flag(tail, [&](auto TL) {
+                with_mode<2>(mode, [&](auto MD) { launch(k_xspec_p1024<TIN, decltype(TL)::value, decltype(MD)::value>); });
+            });
     }
-#define PP_XS(TL, MD)                                                                                  \
-    do {                                                                                               \
-        const dim3 grid(resident_grid(c, k_xspec<MM, TIN, TL, MD>, T, nrows, fft_grid(T, nrows)));     \
-        hipLaunchKernelGGL((k_xspec<MM, TIN, TL, MD>), grid, blk, 0, c->stream, xa);                   \
-    } while (0)
-    if (tail) {
-        if (mode == 3) PP_XS(true, 3); else if (mode == 2) PP_XS(true, 2); else if (mode == 1) PP_XS(true, 1); else PP_XS(true, 0);
-    } else {
-        if (mode == 3) PP_XS(false, 3); else if (mode == 2) PP_XS(false, 2); else if (mode == 1) PP_XS(false, 1); else PP_XS(false, 0);
-    }
-#undef PP_XS
+    with_flag(tail, [&](auto TL) { with_mode<3>(mode, [&](auto MD) { launch(k_xspec<MM, TIN, decltype(TL)::value, decltype(MD)::value>); }); });
 }
 
 // the packed per-subint outputs of a batch, from its host staging block to the caller's arrays

@@ -18,6 +18,7 @@
 // Split twiddles W_B^k = W_B^l * W_B^(128 j): the second factor is exp(-i pi j/8), a
 // compile-time constant; phasors advance by e^{2 pi i 128 phi}.
 #pragma once
+#include "pp_fftq.h"
 
 namespace pp {
 
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_p1024(XspecArgs a) {
     for (; rw.more; rw.advance(), row = rw.row, i = i_nx, n = n_nx) {
         rw.draw(a.ticket);
         rw.peek(nrows, a.ticket_base, a.mwords);
-        if (PP_OPAQUE_ROW == 1 || (PP_OPAQUE_ROW == 2 && M2)) asm volatile("" : "+v"(tid));
+        if (M2) asm volatile("" : "+v"(tid));
         // stage twiddles are re-read every row (three L1-resident loads, issued before
         // the prefetch) instead of living in 12 registers through the harmonic phase,
         // where the 16 outputs of the last stage, the template row and the 12 sums
@@ -187,28 +188,11 @@ __global__ __launch_bounds__(64, 2) void k_xspec_p1024(XspecArgs a) {
             eB = csel(l0, e64, cmulc(e128, el));
         }
         if (M2) {
-            static_assert(PP_TJ == 10, "power ladder written for order 10");
 #pragma unroll
             for (int j = 0; j < PP_TSTRIDE; ++j) tm[j] = 0.0;
         }
-        auto taylor_sums = [&](const cplx& x, const cplx& z, double kap) {
-            const double p2 = kap * kap, p4 = p2 * p2, p6 = p4 * p2, p8 = p4 * p4, p10 = p8 * p2;
-            const double ui = z.y * kap;
-            tm[0] += z.x;
-            tm[1] += ui;
-            tm[2] = fma(p2, z.x, tm[2]);
-            tm[3] = fma(p2, ui, tm[3]);
-            tm[4] = fma(p4, z.x, tm[4]);
-            tm[5] = fma(p4, ui, tm[5]);
-            tm[6] = fma(p6, z.x, tm[6]);
-            tm[7] = fma(p6, ui, tm[7]);
-            tm[8] = fma(p8, z.x, tm[8]);
-            tm[9] = fma(p8, ui, tm[9]);
-            tm[10] = fma(p10, z.x, tm[10]);
-            tm[11] = fma(p10 * kap, fabs(x.x) + fabs(x.y), tm[11]);
-        };
         auto consume = [&](const cplx& x, const cplx& e, int k) {
-            if (M2) taylor_sums(x, cmul(x, e), PP_TWO_PI * (double)k);
+            if (M2) taylor_terms(false, tm, x, cmul(x, e), PP_TWO_PI * (double)k);
             else {
                 if (k >= 1 && k <= ktn) store_x(a, rc, k, x);
                 if (MODE == 1) {

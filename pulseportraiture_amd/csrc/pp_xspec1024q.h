@@ -20,67 +20,33 @@
 // elements and reads contiguously; the partner map sends every aligned group of eight
 // lanes to eight lanes with distinct low three bits.
 #pragma once
-#ifndef PP_TAIL_M_LDS
-#define PP_TAIL_M_LDS 1
-#endif
-#ifndef PP_MAIN_M_LDS
-#define PP_MAIN_M_LDS 0     // (the noise-given kernel does not spill: measured, no gain)
-#endif
 #include "pp_fftq.h"
 
 // The harmonics a lane works on come in slots of 64 (k = kb + 64 j) and a channel's template keeps a PREFIX of them
-// (kt_n is a multiple of 64, wave-uniform).  Round 5: the slot loop ends with the last kept slot instead of walking
-// the dropped ones for their two recurrences (split twiddle W^k and phasor e^{i kappa phi}: 8 f64 instructions a
-// slot) and their partner read from LDS: the example template keeps 4.5 of 7 (of 8 at 1024 bins) slots on average.
-// Same sums, same bits.
-#ifndef PP_SLOT_EARLY_EXIT
-#define PP_SLOT_EARLY_EXIT 1
-#endif
-#ifndef PP_TICKET_SPREAD
-#define PP_TICKET_SPREAD 0
-#endif
-// a wave asks for its ticket after a wave-specific number of rows, uniform over this fraction of its share of the launch
-// (every wave asks, the first `tickets` to ask get one: with 3/4 and four waves per ticket they are gone after the first fifth)
-#ifndef PP_TICKET_WINDOW_NUM
-#define PP_TICKET_WINDOW_NUM 3u
-#define PP_TICKET_WINDOW_DEN 4u
-#endif
-#ifndef PP_TAIL_HOOKS
-#define PP_TAIL_HOOKS 1            // the transform kernels of 2048-bin rows can work off the previous batch's solve / post-fit
-                                   // tickets (tail_work).  Not the 1024-bin kernel: it is compiled for three waves per SIMD
-                                   // (168 registers), and a function called from it inherits that budget -- the tail's code
-                                   // then spills, in EVERY carrier: configs[1] lost 6 % with it, the headline gained less
-#endif
-#ifndef PP_SLOT_PUBLISH_KEPT
-#define PP_SLOT_PUBLISH_KEPT 0     // k_xspec_q1024: 1 = only the kept slots' partner registers are published to LDS (2.5 fewer
-                                   // ds_write_b128 of 65 LDS instructions a row).  Measured neutral to -0.5 %
-                                   // (profiles/r05_publish_kept_ab.txt): the scalar jump costs what the stores save
-#endif
-
-// The constants of a lane that an f64 row needs (stage twiddles t1, t2, split twiddle wb0) are kept in the wave's own
-// LDS and read back, per row, where they are first used; phi_n is fetched by the scalar unit.  0 = the three
-// L1-resident vector loads and the one-word vector load of phi_n at the top of every row.  See TWL below.
-#ifndef PP_LANE_CONSTS_LDS
-#define PP_LANE_CONSTS_LDS 1
-#endif
-// the kernel that also measures the noise (TAIL): which of the above it takes.  Its LDS is full (two template slots), so
-// only t2 has a place there, and t1 and wb0 stay vector loads at the top of the row.  Measured: each option alone and
-// both together lose 0.2 - 0.3 % (profiles/r07_lane_consts_ab.txt) -- off, the kernel is the one it was
-#ifndef PP_TAIL_T2_LDS
-#define PP_TAIL_T2_LDS 0
-#endif
-#ifndef PP_TAIL_ROW_TOP
-#define PP_TAIL_ROW_TOP 0
-#endif
-// timing-only build (results WRONG): the three constants are a register copy of wbT, no load of any kind; phi_n by the
-// scalar unit.  Useless as a ceiling while the launch carries the previous step's solve as tickets -- on wrong sums that
-// solve does not converge and the kernel it rides in takes three times as long (profiles/r07_row_wait_ceiling.txt);
-// the LDS build, which has no small vector load left in the row either, is the measurement
-#ifndef PP_ROW_WAIT_CEILING
-#define PP_ROW_WAIT_CEILING 0
-#endif
+// (kt_n is a multiple of 64, wave-uniform).  The slot loop ends with the last kept slot instead of walking the dropped
+// ones for their two recurrences (split twiddle W^k and phasor e^{i kappa phi}: 8 f64 instructions a slot) and their
+// partner read from LDS: the example template keeps 4.5 of 7 (of 8 at 1024 bins) slots on average.  Same sums, same
+// bits (profiles/r05_slot_exit_ab.txt).  Every slot's partner register is published, kept or not: publishing only the
+// kept ones costs a scalar jump that eats what the stores save (profiles/r05_publish_kept_ab.txt).
 
 namespace pp {
+
+// a wave asks for its ticket after a wave-specific number of rows, uniform over this fraction of its share of the launch
+// (every wave asks, the first `tickets` to ask get one: with 3/4 and four waves per ticket they are gone after the first fifth)
+constexpr unsigned PP_TICKET_WINDOW_NUM = 3u, PP_TICKET_WINDOW_DEN = 4u;
+__device__ __forceinline__ int ticket_moment(const long long nrows) {
+    const unsigned share = (unsigned)(nrows / (long long)gridDim.x) + 1u;
+    return 1 + (int)(((blockIdx.x * 2654435761u) >> 8) % (share * PP_TICKET_WINDOW_NUM / PP_TICKET_WINDOW_DEN + 1u));
+}
+
+// where the row after this one starts: (subint i_nx of the list, channel n_nx of the subset), or this row again (rc)
+// when the walk has run out -- the prefetch is unconditional
+template <int M, typename Tin>
+__device__ __forceinline__ const Tin* next_row_of(const XspecArgs& a, const unsigned more_nx, const int i_nx, const int n_nx,
+                                                  const size_t rc) {
+    const size_t rn = more_nx ? (size_t)sub_of(a.act, i_nx) * a.nchan_full + (a.coff + n_nx * a.cstep) : rc;
+    return reinterpret_cast<const Tin*>(a.data) + rn * (2 * M);
+}
 
 // the free element of the transpose image (pitch 17: element 16 of every lane's run is never written or read) of lane
 // l of the LAST row of 16 lanes -- beyond what the partner exchange (elements 0..447, 0..767 when the noise is measured)
@@ -92,14 +58,11 @@ constexpr int FFTQ_FREE_ELEM0 = 3 * 272 + 16, FFTQ_FREE_PITCH = 17;
 // lane has a value and a place for it: the results leave in ONE store that no branch skips, and the compiler can count
 // it.  (Stores that only some lanes issue are branched around when none does; behind them the number of accesses in
 // flight is unknown, and the next row's wait for its data has to be one for the store's acknowledgement as well.)
-// 0 = the two or three one-lane stores.
-#ifndef PP_ROW_RESULTS_ONE_STORE
-#define PP_ROW_RESULTS_ONE_STORE 1
-#endif
+// ONE = false (the kernels that also measure the noise): the two or three one-lane stores.
 template <int M, bool TAIL, bool ONE = true>
 __device__ __forceinline__ void store_row_results(const XspecArgs& a, const size_t rc, const int tid, double tv) {
     constexpr int H = M + 1, kc = (int)(0.75 * H);   // get_noise_PS: int((1 - 1/4) * len(pows))
-  if constexpr (ONE && PP_ROW_RESULTS_ONE_STORE) {
+  if constexpr (ONE) {
     const int q = wave_reduce16_index(tid);
     const double th = 0.5 * tv;
     // Re(i^q z): +Re, -Im, -Re, +Im, ...   (x 1/2: unhalved template against 2 d_k)
@@ -131,21 +94,13 @@ __device__ __forceinline__ void store_row_results(const XspecArgs& a, const size
 // row's last load was the youngest access in flight, coming from the previous row there is one younger, the result
 // store -- so the top of EVERY row waited for vmcnt(0), the acknowledgement of a store issued a few instructions
 // earlier.  With nothing in flight on entry the wait at the top is vmcnt(1): the row's data, and the store stays under way.
-#ifndef PP_FIRST_ROW_LANDED
-#define PP_FIRST_ROW_LANDED 1
-#endif
-__device__ __forceinline__ void first_row_landed() {
-#if PP_FIRST_ROW_LANDED
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
-}
+__device__ __forceinline__ void first_row_landed() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
 // Where the next row's loads are queued (measured choices, profiles/README.md): f64 rows in two
 // halves -- eight registers' worth after the stage-1 twiddles (fftq1024's WHEN = 1), the rest
-// behind the partner exchange -- and with the stage twiddles not held through the row (Q_TW_RELOAD:
-// read back from the wave's LDS where they are used, see TWL in k_xspec_q1024; a vector load per
-// row before); f32 rows whole, a quarter into stage 1 (WHEN = 0), twiddles held.
-constexpr bool Q_SPLIT_PREFETCH = true, Q_TW_RELOAD = true;
+// behind the partner exchange -- and with the stage twiddles not held through the row (read back
+// where they are used, see TWL in k_xspec_q1024); f32 rows whole, a quarter into stage 1
+// (WHEN = 0), twiddles held.
 constexpr int Q_PREFETCH_F64 = 1, Q_PREFETCH_F32 = 0;
 // TAIL: also measure the noise from the top quarter of the power spectrum (errs == NULL,
 // get_noise_PS): harmonics 768..1023 are this lane's registers 12..15 against the
@@ -158,21 +113,25 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     typedef typename RawOf<Tin>::type Raw;
     constexpr int NRED = PP_TSTRIDE + (TAIL ? 2 : 1);       // the 12 Taylor sums, S_d (and the noise tail)
     static_assert(NRED <= 16, "wave_reduce_lds takes 16 values");
-    static_assert(PP_TJ == 10, "power ladder written for order 10");
     constexpr int WRED = PP_WRED_DOUBLES(NRED) / 2;   // in cplx
     constexpr int LDSN = WRED > FFTQ_LDS_ELEMS ? WRED : FFTQ_LDS_ELEMS;
     static_assert(2 * LDSN >= PP_TAIL_LDS_DOUBLES, "tail_work's layout of this kernel's LDS");
     // TAIL, f64 rows: the template values of the last NML slots live in LDS beside the image instead of in registers
     // (with them held the kernel spilled one of them + three dwords to scratch, and the scratch reload in the middle
-    // of the row queues behind the prefetched half row: vector memory returns in order)
-    constexpr int NML = ((PP_TAIL_M_LDS && TAIL) || (PP_MAIN_M_LDS && !TAIL)) && sizeof(Tin) == 8 ? 2 : 0;
-    // f64 rows: the lane's constants live in LDS (TWL, below).  t2 (16 distinct values) takes free elements of the
-    // transpose image; t1 and wb0 take two tables of 64 beside it where the template slots have not taken that room
-    // (eight workgroups per CU: 8 x 19 456 B of the CU's 160 KB -- at seven the kernel loses more than any wait costs)
-    constexpr bool TWL = PP_LANE_CONSTS_LDS && !PP_ROW_WAIT_CEILING && Q_TW_RELOAD && sizeof(Tin) == 8 && (!TAIL || PP_TAIL_T2_LDS);
+    // of the row queues behind the prefetched half row: vector memory returns in order).  The noise-given kernel does
+    // not spill and keeps them in registers.
+    constexpr bool F64 = sizeof(Tin) == 8;
+    constexpr int NML = (F64 && TAIL) ? 2 : 0;
+    // f64 rows, noise given: the lane's constants (stage twiddles t1, t2, split twiddle wb0) live in the wave's own LDS
+    // and are read back, per row, where they are first used (TWL).  t2 (16 distinct values) takes free elements of the
+    // transpose image; t1 and wb0 take two tables of 64 beside it (eight workgroups per CU: 8 x 19 456 B of the CU's
+    // 160 KB -- at seven the kernel loses more than any wait costs).  With the noise measured the template slots have
+    // taken that room and the three stay vector loads at the top of the row (TWR): t2 alone in LDS loses 0.2 - 0.3 %
+    // (profiles/r07_lane_consts_ab.txt).
+    constexpr bool TWL = F64 && !TAIL, TWR = F64 && TAIL;
     // phi_n through the scalar cache, one result store, the first row waited for in front of the loop
-    constexpr bool ROWTOP = !TAIL || PP_TAIL_ROW_TOP;
-    constexpr int NTW = (TWL && NML == 0) ? 2 : 0;
+    constexpr bool ROWTOP = !TAIL;
+    constexpr int NTW = TWL ? 2 : 0;
     __shared__ cplx lds[LDSN + 64 * (NML + NTW)];
     static_assert(sizeof(lds) <= 19456, "eight workgroups per CU");
     static_assert(FFTQ_FREE_ELEM0 + 15 * FFTQ_FREE_PITCH < FFTQ_LDS_ELEMS && FFTQ_FREE_ELEM0 >= 64 * (TAIL ? 12 : 7) &&
@@ -185,15 +144,14 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     // f64 rows do not hold them (12 registers) through the whole row: with them held, three of the
     // template values spill to scratch, and a scratch reload queues BEHIND the prefetched
     // row (vector memory returns in order) -- the split then waits for the next row's HBM
-    // data (15.1 -> 14.1 ms per 1024 fits).  TWR: they were re-read at the top of every row instead, three L1-resident
-    // vector loads -- which come back behind every row piece the CU's other seven waves have queued (the vector-memory
-    // path returns in order).  TWL: the wave writes the three values to its own LDS once (and again after tail_work,
-    // which uses the whole LDS) and the row reads them back with ds_read_b128 where they are used -- LDS returns on
-    // lgkmcnt, not through that queue --; phi_n, one word for the whole wave, comes through the scalar cache (k_setup /
-    // k_phase0 wrote it in an earlier launch; the tickets this launch carries belong to another work set).  The row
-    // loop's vector memory is then the row stream, one result store and the per-chunk / per-channel reads, and nothing
-    // else.  Worth 0.3 % by itself (profiles/r07_row_wait_ceiling.txt): the wait at the top of a row is for the row.
-    constexpr bool TWR = Q_TW_RELOAD && sizeof(Tin) == 8;
+    // data (15.1 -> 14.1 ms per 1024 fits).  TWL: the wave writes the three values to its own LDS once (and again after
+    // tail_work, which uses the whole LDS) and the row reads them back with ds_read_b128 where they are used -- LDS
+    // returns on lgkmcnt, not through the vector-memory queue, where an L1-resident load comes back behind every row
+    // piece the CU's other seven waves have queued --; phi_n, one word for the whole wave, comes through the scalar
+    // cache (k_setup / k_phase0 wrote it in an earlier launch; the tickets this launch carries belong to another work
+    // set).  The row loop's vector memory is then the row stream, one result store and the per-chunk / per-channel
+    // reads, and nothing else.  Worth 0.3 % by itself (profiles/r07_row_wait_ceiling.txt): the wait at the top of a
+    // row is for the row.
     cplx t1 = a.twB[2 * tid], t2 = a.twB[32 * (tid & 15)];
     // this lane's harmonics k = kb + 64 j; split twiddle W_B^kb, stepped by W_B^64
     const int lam0 = fftq_lambda(tid);
@@ -204,7 +162,8 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     auto put_lane_consts = [&](const cplx p1, const cplx p2, const cplx pb) {
         if (!TWL) return;
         ldt2[FFTQ_FREE_PITCH * (tid & 15)] = p2;       // (four lanes, the same value)
-        if (NTW) { ldtw[tid] = p1; ldtw[64 + tid] = pb; }
+        ldtw[tid] = p1;
+        ldtw[64 + tid] = pb;
         lds_sync<T>();
     };
     put_lane_consts(t1, t2, wb0);
@@ -213,19 +172,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     // few per cent of the waves are out of the transform instead of half of them for the first millisecond --
     // and whatever is left once it has run out of rows)
     int tail_after = 0x7fffffff;
-    if (PP_TAIL_HOOKS && a.tail) {
-        const unsigned share = (unsigned)(nrows / (long long)gridDim.x) + 1u;
-        tail_after = 1 + (int)(((blockIdx.x * 2654435761u) >> 8) % (share * PP_TICKET_WINDOW_NUM / PP_TICKET_WINDOW_DEN + 1u));
-#if PP_TICKET_SPREAD
-        // (experiment: only as many waves ask as there are tickets -- every (grid / tickets)-th one --, so that the tickets
-        // are spread over the first three quarters of the launch instead of being gone after its first fifth)
-        {
-            const unsigned nt = (unsigned)a.tail_nsub;
-            const unsigned div = nt ? gridDim.x / nt : 1u;
-            if (div > 1u && (((blockIdx.x * 2246822519u) >> 11) % div) != 0u) tail_after = 0x7fffffff;   // (hashed: blockIdx mod 8 is the XCD)
-        }
-#endif
-    }
+    if (a.tail) tail_after = ticket_moment(nrows);
     RowWalk<true> rw;
     rw.start(nrows, a.mwords, a.ticket, a.ticket_base);
     long long row = rw.row;
@@ -247,7 +194,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
 #pragma unroll 1
     for (int phase = 0; phase < 2; ++phase) {
     if (phase == 1) {
-        if (!(PP_TAIL_HOOKS && a.tail)) break;
+        if (!a.tail) break;
         // (between two rows: the next row's loads are in flight, the call keeps what it must across itself)
         tail_work(a.tail, reinterpret_cast<double*>(lds), 2 * (LDSN + 64 * NML), tid, 1);
         tail_after = 0x7fffffff;
@@ -265,17 +212,11 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         const int lam = fftq_lambda(tid);
         const bool l0 = (lam == 0);
         const int kb = l0 ? 64 : lam;
-        if (PP_ROW_WAIT_CEILING && TWR) {
-            t1 = t2 = wb0 = wbT;
-            asm volatile("" : "+v"(t1.x), "+v"(t1.y), "+v"(t2.x), "+v"(t2.y), "+v"(wb0.x), "+v"(wb0.y));
-        } else if (TWL) {
-            // (read where they are used; without the two tables t1 and wb0 stay vector loads)
-            if (!NTW) { t1 = as_global(a.twB)[2 * tid]; wb0 = as_global(a.twB)[kb]; }
-        } else if (TWR) {
+        if (TWR) {
             t1 = as_global(a.twB)[2 * tid];
             t2 = as_global(a.twB)[32 * (tid & 15)];
             wb0 = as_global(a.twB)[kb];
-        } else {
+        } else if (!TWL) {      // (TWL: read where they are used)
             asm volatile("" : "+v"(t1.x), "+v"(t1.y), "+v"(t2.x), "+v"(t2.y), "+v"(wb0.x), "+v"(wb0.y));
         }
         const int ia = sub_of(a.act, i), ne = a.coff + n * a.cstep;   // true subint, channel
@@ -301,36 +242,20 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         // rest once the second half of this row's outputs has been published: with the
         // whole next row in flight from the start, 64 + 64 row registers on top of the
         // template row and the sums do not fit the 256 of two waves per SIMD
-        constexpr bool HALVES = Q_SPLIT_PREFETCH && sizeof(Tin) == 8;
+        constexpr bool HALVES = F64;
         const Tin* nxrow = nullptr;
-        auto load_some = [&](int k0, int k1) {
-            const char* gb = reinterpret_cast<const char*>(nxrow);
-            const unsigned boff = (unsigned)tid * (unsigned)sizeof(Raw);
-#pragma unroll
-            for (int k = 0; k < R1; ++k)
-                if (k >= k0 && k < k1)
-                    cur[0][k] = load_row_once<Raw>(gb + (size_t)(k * 64) * sizeof(Raw) + boff);
-        };
+        // (pieces k0 .. k1 - 1 of the next row.  A lambda over the kernel's own variables in every kernel that queues a
+        // row in pieces, not a direct call: k_xspec_qf<1024> keeps three more scalar registers alive across its call
+        // to tail_work with the direct call -- profiles/r08_refactor_isa.txt)
+        auto load_some = [&](int k0, int k1) { load_row_pieces<Raw>(cur, nxrow, tid, k0, k1); };
         // (the row after this one is decided HERE, outside the lambda: a walk captured by reference is not
         // split into registers -- its flags went through scratch memory, whose loads queue behind the
         // prefetched row -- and at the top of a row everything older than this row's own data has landed,
         // the ticket of the chunk's first row included)
-#ifndef PP_NEXT_IN_LAMBDA
         rw.next(i, n, i_nx, n_nx, nrows, a.nsub, a.ticket_base, a.ticket, a.mwords);
-        {
-            const size_t rn = rw.more_nx
-                ? (size_t)sub_of(a.act, i_nx) * a.nchan_full + (a.coff + n_nx * a.cstep) : rc;
-            nxrow = reinterpret_cast<const Tin*>(a.data) + rn * (2 * M);
-        }
-#endif
+        nxrow = next_row_of<M, Tin>(a, rw.more_nx, i_nx, n_nx, rc);
         auto prefetch = [&]() {
             __builtin_amdgcn_sched_barrier(0);
-#ifdef PP_NEXT_IN_LAMBDA
-            rw.next(i, n, i_nx, n_nx, nrows, a.nsub, a.ticket_base, a.ticket, a.mwords);
-            const size_t rn = rw.more_nx
-                ? (size_t)sub_of(a.act, i_nx) * a.nchan_full + (a.coff + n_nx * a.cstep) : rc;
-            nxrow = reinterpret_cast<const Tin*>(a.data) + rn * (2 * M);
-#endif
             load_some(0, HALVES ? R1 / 2 : R1);
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -341,19 +266,8 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         // ---- partners through LDS: registers 9..15 out, seven values back ----
         {
             cplx* pub = lds + tid;
-            // (slot j reads the partner's register 15 - j = published piece 6 - j: only the pieces of the KEPT slots
-            // are published -- one scalar jump into the run of stores)
-            const int nk = PP_SLOT_PUBLISH_KEPT ? max(1, min(NSL, __builtin_amdgcn_readfirstlane(ktn) >> 6)) : NSL;
-            switch (NSL - nk) {
-                case 0: pub[64 * 0] = v[9];  [[fallthrough]];
-                case 1: pub[64 * 1] = v[10]; [[fallthrough]];
-                case 2: pub[64 * 2] = v[11]; [[fallthrough]];
-                case 3: pub[64 * 3] = v[12]; [[fallthrough]];
-                case 4: pub[64 * 4] = v[13]; [[fallthrough]];
-                case 5: pub[64 * 5] = v[14]; [[fallthrough]];
-                default: pub[64 * 6] = v[15];
-            }
-            static_assert(NSL == 7, "the run of stores above is written for seven slots");
+#pragma unroll
+            for (int r = 0; r < NSL; ++r) pub[64 * r] = v[9 + r];
             if (TAIL) {
 #pragma unroll
                 for (int r = 0; r < 5; ++r) pub[64 * (NSL + r)] = v[r];
@@ -373,13 +287,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
             cplx wt = l0 ? make_double2(-h, -h) : cmul(wb0, make_double2(-h, -h));
 #pragma unroll
             for (int kd = 12; kd < 16; ++kd) {
-                const cplx zk = v[kd];
-                cplx zc = pt[64 * (NSL + 15 - kd)];
-                zc.y = -zc.y;
-                const cplx E = make_double2(zk.x + zc.x, zk.y + zc.y);
-                const cplx O = make_double2(zk.x - zc.x, zk.y - zc.y);
-                const cplx wo = cmul(wt, O);
-                tail += cnorm(make_double2(E.x + wo.y, E.y - wo.x));
+                tail += cnorm(split_pair(v[kd], pt[64 * (NSL + 15 - kd)], wt));
                 wt = cmul(wt, wbT);
             }
             tail *= 0.25;
@@ -401,54 +309,19 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         cplx zc_nx = pc[64 * 6];
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
-            if (PP_SLOT_EARLY_EXIT && j > 0 && !(64 * j < ktu)) break;     // (kept slots are a prefix)
-            cplx zc = zc_nx;
-            if (j + 1 < NSL && (!PP_SLOT_EARLY_EXIT || 64 * (j + 1) < ktu)) zc_nx = pc[64 * (5 - j)];
+            if (j > 0 && !(64 * j < ktu)) break;     // (kept slots are a prefix)
+            const cplx zc = zc_nx;
+            if (j + 1 < NSL && 64 * (j + 1) < ktu) zc_nx = pc[64 * (5 - j)];
             // the template cut is a multiple of 64: a slot is kept or dropped as a whole
             if (j == 0 || 64 * j < ktu) {
-                const cplx zk = csel(l0, v[j + 1], v[j]);
-                zc.y = -zc.y;
-                const cplx E = make_double2(zk.x + zc.x, zk.y + zc.y);
-                const cplx O = make_double2(zk.x - zc.x, zk.y - zc.y);
-                const cplx wo = cmul(wb, O);
-                // 2 d_k = E - i W^k O
+                const cplx dd = split_pair(csel(l0, v[j + 1], v[j]), zc, wb);
                 const cplx mj = (j < NSL - NML) ? mv2[j < NSL - NML ? j : 0] : ldsm[64 * (j - (NSL - NML))];
-                const cplx x = cmulc(make_double2(E.x + wo.y, E.y - wo.x), mj);
+                const cplx x = cmulc(dd, mj);
                 const cplx z = cmul(x, e);
                 const double kap = j == 0 ? kap0 : kap0 + kconst<true>(PP_TWO_PI * (double)(64 * j));
-                // kappa^2, ^4 .. ^10 once per harmonic; every sum is then one FMA
-                const double p2 = kap * kap, p4 = p2 * p2, p6 = p4 * p2, p8 = p4 * p4, p10 = p8 * p2;
-                const double ui = z.y * kap;
-                const double ax = fabs(x.x) + fabs(x.y);
-                if (j == 0) {
-                    tm[0] = z.x;
-                    tm[1] = ui;
-                    tm[2] = p2 * z.x;
-                    tm[3] = p2 * ui;
-                    tm[4] = p4 * z.x;
-                    tm[5] = p4 * ui;
-                    tm[6] = p6 * z.x;
-                    tm[7] = p6 * ui;
-                    tm[8] = p8 * z.x;
-                    tm[9] = p8 * ui;
-                    tm[10] = p10 * z.x;
-                    tm[11] = (p10 * kap) * ax;
-                } else {
-                    tm[0] += z.x;
-                    tm[1] += ui;
-                    tm[2] = fma(p2, z.x, tm[2]);
-                    tm[3] = fma(p2, ui, tm[3]);
-                    tm[4] = fma(p4, z.x, tm[4]);
-                    tm[5] = fma(p4, ui, tm[5]);
-                    tm[6] = fma(p6, z.x, tm[6]);
-                    tm[7] = fma(p6, ui, tm[7]);
-                    tm[8] = fma(p8, z.x, tm[8]);
-                    tm[9] = fma(p8, ui, tm[9]);
-                    tm[10] = fma(p10, z.x, tm[10]);
-                    tm[11] = fma(p10 * kap, ax, tm[11]);
-                }
+                taylor_terms(j == 0, tm, x, z, kap);
             }
-            if (!PP_SLOT_EARLY_EXIT || (j + 1 < NSL && 64 * (j + 1) < ktu)) {
+            if (j + 1 < NSL && 64 * (j + 1) < ktu) {
                 wb = cmul(wb, wbT);
                 e = cmul(e, wst);
             }
@@ -466,7 +339,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     }
     }
     // (out of rows: the tickets of the previous batch's tail that are left)
-    if (PP_TAIL_HOOKS && a.tail) tail_work(a.tail, reinterpret_cast<double*>(lds), 2 * (LDSN + 64 * NML), tid, 1 << 30);
+    if (a.tail) tail_work(a.tail, reinterpret_cast<double*>(lds), 2 * (LDSN + 64 * NML), tid, 1 << 30);
 }
 
 
@@ -487,22 +360,11 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
 // template keeps them.
 // M = 512 (1024-bin rows, plan 8.4.2.8 of pp_fftq.h): the same with 8 harmonics per lane; serves every
 // template cut (slots beyond it are skipped) -- configs[1]'s template keeps 448 of 512 harmonics.
-#ifndef PP_QF512_HOLD_TEMPLATE
-#define PP_QF512_HOLD_TEMPLATE 1
-#endif
-// k_xspec_qf: phi_n through the scalar cache, the row's results in one store, the first row waited for in front of the
-// loop (see store_row_results, first_row_landed): +0.5 % for 2048-bin rows with the noise given; -0.6 % for 1024-bin
-// rows (three waves per SIMD hide the wait already) and -0.3 % for 2048-bin rows whose noise is measured (as in
-// k_xspec_q1024; profiles/r07_lane_consts_ab.txt) -- PP_QF_ROW_TOP_ALL, off.  The stage twiddles stay where they are (Q::run)
-#ifndef PP_QF_ROW_TOP
-#define PP_QF_ROW_TOP 1
-#endif
-#ifndef PP_QF_ROW_TOP_ALL
-#define PP_QF_ROW_TOP_ALL 0
-#endif
-#ifndef PP_QF512_WPS
-#define PP_QF512_WPS 3
-#endif
+// k_xspec_qf, 2048-bin rows with the noise given: phi_n through the scalar cache, the row's results in one store, the
+// first row waited for in front of the loop (QTOP; see store_row_results, first_row_landed): +0.5 %.  Not the others:
+// -0.6 % for 1024-bin rows (three waves per SIMD hide the wait already) and -0.3 % for 2048-bin rows whose noise is
+// measured (as in k_xspec_q1024; profiles/r07_lane_consts_ab.txt).  The stage twiddles stay where they are (Q::run)
+constexpr int PP_QF512_WPS = 3;      // waves per SIMD the 1024-bin kernel is compiled for
 template <int M, typename Tin, bool TAIL>
 __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf(XspecArgs a) {
     typedef FftQ<M> Q;
@@ -518,15 +380,15 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
     static_assert(M != 1024 || 2 * LDSN >= PP_TAIL_LDS_DOUBLES, "tail_work's layout of this kernel's LDS");
     __shared__ cplx lds[LDSN];
     int tid = threadIdx.x;
-    constexpr bool QTOP = PP_QF_ROW_TOP && ((M == 1024 && !TAIL) || PP_QF_ROW_TOP_ALL);
+    constexpr bool QTOP = M == 1024 && !TAIL;
     const long long nrows = (long long)a.nsub * a.nchan;
     Raw cur[PER1][R1];
     const cplx wbT = a.twB[64];
-    int tail_after = 0x7fffffff;         // (as k_xspec_q1024)
-    if (PP_TAIL_HOOKS && M == 1024 && a.tail) {
-        const unsigned share = (unsigned)(nrows / (long long)gridDim.x) + 1u;
-        tail_after = 1 + (int)(((blockIdx.x * 2654435761u) >> 8) % (share * PP_TICKET_WINDOW_NUM / PP_TICKET_WINDOW_DEN + 1u));
-    }
+    // (tickets as in k_xspec_q1024, for 2048-bin rows only: the 1024-bin kernel is compiled for three waves per SIMD, 168
+    // registers, and a function called from it inherits that budget -- tail_work then spills, in every carrier:
+    // configs[1] lost 6 % with it)
+    int tail_after = 0x7fffffff;
+    if (M == 1024 && a.tail) tail_after = ticket_moment(nrows);
     RowWalk<true> rw;
     rw.start(nrows, a.mwords, a.ticket, a.ticket_base);
     long long row = rw.row;
@@ -542,14 +404,14 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
     int n_held = -1, ktn = 0;
     // 1024-bin rows: the lane's 8 template values are HELD while the channel does not change (32 registers; the 16
     // values of a 2048-bin row's lane do not fit beside two rows and are read every row)
-    constexpr bool MHOLD = PP_QF512_HOLD_TEMPLATE && M == 512;
+    constexpr bool MHOLD = M == 512;
     cplx mv[NSL];
     const cplx* mheld = nullptr;
     if (QTOP) first_row_landed();
 #pragma unroll 1
     for (int phase = 0; phase < 2; ++phase) {
     if (phase == 1) {
-        if (!(PP_TAIL_HOOKS && M == 1024 && a.tail)) break;
+        if (!(M == 1024 && a.tail)) break;
         tail_work(a.tail, reinterpret_cast<double*>(lds), 2 * LDSN, tid, 1);
         tail_after = 0x7fffffff;
     }
@@ -593,19 +455,11 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
         }
         // ---- the next row: first half now (behind the template reads), second half after slot 7 ----
         const Tin* nxrow;
-        auto load_some = [&](int k0, int k1) {
-            const char* gb = reinterpret_cast<const char*>(nxrow);
-            const unsigned boff = (unsigned)tid * (unsigned)sizeof(Raw);
-#pragma unroll
-            for (int k = 0; k < R1; ++k)
-                if (k >= k0 && k < k1) cur[0][k] = load_row_once<Raw>(gb + (size_t)(k * 64) * sizeof(Raw) + boff);
-        };
+        auto load_some = [&](int k0, int k1) { load_row_pieces<Raw>(cur, nxrow, tid, k0, k1); };
         {
             __builtin_amdgcn_sched_barrier(0);
             rw.next(i, n, i_nx, n_nx, nrows, a.nsub, a.ticket_base, a.ticket, a.mwords);
-            const size_t rn = rw.more_nx
-                ? (size_t)sub_of(a.act, i_nx) * a.nchan_full + (a.coff + n_nx * a.cstep) : rc;
-            nxrow = reinterpret_cast<const Tin*>(a.data) + rn * (2 * M);
+            nxrow = next_row_of<M, Tin>(a, rw.more_nx, i_nx, n_nx, rc);
             load_some(0, R1 / 2);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -624,9 +478,9 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
             // the second half of the next row's loads has been queued, at slot NSL / 2 -- a copy of those loads at
             // every earlier exit cost the kernel its register allocation: 54 / 123 spilled VGPRs --; before that a
             // dropped slot just skips its body, its recurrences and its partner read)
-            if (PP_SLOT_EARLY_EXIT && !TAIL && j > NSL / 2 && !(64 * j < ktu)) break;
-            cplx zc = zc_nx;
-            if (j + 1 < NSL && (!PP_SLOT_EARLY_EXIT || TAIL || 64 * (j + 1) < ktu)) zc_nx = pc[64 * (NSL - 2 - j)];
+            if (!TAIL && j > NSL / 2 && !(64 * j < ktu)) break;
+            const cplx zc = zc_nx;
+            if (j + 1 < NSL && (TAIL || 64 * (j + 1) < ktu)) zc_nx = pc[64 * (NSL - 2 - j)];
             if (j == NSL / 2) {
                 __builtin_amdgcn_sched_barrier(0);
                 load_some(R1 / 2, R1);
@@ -635,13 +489,7 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
             // the template cut is a multiple of 64: a slot is kept or dropped as a whole
             const bool keep = (j == 0 || 64 * j < ktu);
             if (keep || (TAIL && j >= JT - 1)) {
-                const cplx zk = csel(l0, v[(j + 1) & (NSL - 1)], v[j]);
-                zc.y = -zc.y;
-                const cplx E = make_double2(zk.x + zc.x, zk.y + zc.y);
-                const cplx O = make_double2(zk.x - zc.x, zk.y - zc.y);
-                const cplx wo = cmul(wb, O);
-                // 2 d_k = E - i W^k O
-                const cplx dd = make_double2(E.x + wo.y, E.y - wo.x);
+                const cplx dd = split_pair(csel(l0, v[(j + 1) & (NSL - 1)], v[j]), zc, wb);
                 if (TAIL && j >= JT - 1) {
                     const double pw = cnorm(dd);
                     tail += (j >= JT || l0) ? pw : 0.0;
@@ -650,39 +498,10 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
                 const cplx x = cmulc(dd, mv[j]);
                 const cplx z = cmul(x, e);
                 const double kap = j == 0 ? kap0 : kap0 + kconst<true>(PP_TWO_PI * (double)(64 * j));
-                const double p2 = kap * kap, p4 = p2 * p2, p6 = p4 * p2, p8 = p4 * p4, p10 = p8 * p2;
-                const double ui = z.y * kap;
-                const double ax = fabs(x.x) + fabs(x.y);
-                if (j == 0) {
-                    tm[0] = z.x;
-                    tm[1] = ui;
-                    tm[2] = p2 * z.x;
-                    tm[3] = p2 * ui;
-                    tm[4] = p4 * z.x;
-                    tm[5] = p4 * ui;
-                    tm[6] = p6 * z.x;
-                    tm[7] = p6 * ui;
-                    tm[8] = p8 * z.x;
-                    tm[9] = p8 * ui;
-                    tm[10] = p10 * z.x;
-                    tm[11] = (p10 * kap) * ax;
-                } else {
-                    tm[0] += z.x;
-                    tm[1] += ui;
-                    tm[2] = fma(p2, z.x, tm[2]);
-                    tm[3] = fma(p2, ui, tm[3]);
-                    tm[4] = fma(p4, z.x, tm[4]);
-                    tm[5] = fma(p4, ui, tm[5]);
-                    tm[6] = fma(p6, z.x, tm[6]);
-                    tm[7] = fma(p6, ui, tm[7]);
-                    tm[8] = fma(p8, z.x, tm[8]);
-                    tm[9] = fma(p8, ui, tm[9]);
-                    tm[10] = fma(p10, z.x, tm[10]);
-                    tm[11] = fma(p10 * kap, ax, tm[11]);
-                }
+                taylor_terms(j == 0, tm, x, z, kap);
               }
             }
-            if (!PP_SLOT_EARLY_EXIT || TAIL || (j + 1 < NSL && 64 * (j + 1) < ktu)) {
+            if (TAIL || (j + 1 < NSL && 64 * (j + 1) < ktu)) {
                 wb = cmul(wb, wbT);
                 e = cmul(e, wst);
             }
@@ -698,7 +517,7 @@ __global__ __launch_bounds__(64, (M == 1024 ? 2 : PP_QF512_WPS)) void k_xspec_qf
         lds_sync<T>();
     }
     }
-    if (PP_TAIL_HOOKS && M == 1024 && a.tail) tail_work(a.tail, reinterpret_cast<double*>(lds), 2 * LDSN, tid, 1 << 30);
+    if (M == 1024 && a.tail) tail_work(a.tail, reinterpret_cast<double*>(lds), 2 * LDSN, tid, 1 << 30);
 }
 
 }  // namespace pp

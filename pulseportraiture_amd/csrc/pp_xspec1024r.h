@@ -54,7 +54,6 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
     constexpr int NSL = 7;
     typedef typename RawOf<Tin>::type Raw;
     constexpr int NRED = PP_TSTRIDE + 1;
-    static_assert(PP_TJ == 10, "power ladder written for order 10");
     constexpr int WRED = PP_WRED_DOUBLES(NRED) / 2;
     constexpr int LDSN = WRED > FFTQ_LDS_ELEMS ? WRED : FFTQ_LDS_ELEMS;
     // f64 rows: three of the four tail accumulators live in the LDS a wave has left beside its
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
     // there is no room for them in the register file
     // (f32 rows that carry tickets: two of them -- the call's bookkeeping costs the row loop the registers of one
     // accumulator, which otherwise goes to scratch memory and is read, updated and written back every row)
-    constexpr int NLA = (sizeof(Tin) == 8) ? 3 : ((PP_TAIL_HOOKS && !STORE) ? 2 : 0);
+    constexpr int NLA = (sizeof(Tin) == 8) ? 3 : (!STORE ? 2 : 0);
     __shared__ cplx lds[LDSN + 64 * NLA];
     int tid = threadIdx.x;
     cplx* const lacc = lds + LDSN + threadIdx.x;
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
     // after tail_after rows, at the next chunk boundary -- there the channel sums in hand have just been written out
     // and the ticket may use the whole image --, a different count for every wave as in k_xspec_q1024; what is left
     // is drawn by the waves that have run out of rows)
-    constexpr bool HOOK = PP_TAIL_HOOKS && !STORE;
+    constexpr bool HOOK = !STORE;
     static_assert(!HOOK || 2 * LDSN >= PP_TAIL_LDS_DOUBLES, "tail_work's layout of this kernel's LDS");
     // (the only state the hook carries through the row loop is `phase` -- this kernel has neither a vector nor a
     // scalar register to spare: a row count per wave, as k_xspec_q1024 keeps, cost it a spilled accumulator per row.
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
         // rows: this kernel has no register to spare)
         const cplx* mrow;
         int ktn;
-        if (PP_STICKY_LOOKUP && !a.slot) {
+        if (!a.slot) {
             mrow = as_global(a.mft0) + (size_t)ne * M;
             ktn = a.ktab ? load_uniform(a.kt0 + ne) : a.Kt;
         } else {
@@ -146,14 +145,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
         for (int k = 0; k < R1; ++k) v[k] = to_cplx(cur[0][k]);
         constexpr bool HALVES = sizeof(Tin) == 8;
         const Tin* nxrow = nullptr;
-        auto load_some = [&](int k0, int k1) {
-            const char* gb = reinterpret_cast<const char*>(nxrow);
-            const unsigned boff = (unsigned)tid * (unsigned)sizeof(Raw);
-#pragma unroll
-            for (int k = 0; k < R1; ++k)
-                if (k >= k0 && k < k1)
-                    cur[0][k] = load_row_once<Raw>(gb + (size_t)(k * 64) * sizeof(Raw) + boff);
-        };
+        auto load_some = [&](int k0, int k1) { load_row_pieces<Raw>(cur, nxrow, tid, k0, k1); };
         // (the row after this one is decided here, outside the lambda: see k_xspec_q1024)
         rw.next_row(nrows, a.ticket_base, a.ticket, a.mwords);
         {
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
         cplx zc_nx = pc[64 * 6];
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
-            cplx zc = zc_nx;
+            const cplx zc = zc_nx;
             if (j + 1 < NSL) zc_nx = pc[64 * (5 - j)];
             if (HALVES && j == NSL - 1) {
                 // the second half of the next row: queued before the last kept slot (earlier, the
@@ -212,12 +204,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
             // (the channel sum takes every harmonic ANY template row keeps; the Taylor sums only
             // those this channel's row keeps -- both cuts are multiples of 64, wave-uniform)
             if (j == 0 || 64 * j < ktg) {
-                const cplx zk = csel(l0, v[j + 1], v[j]);
-                zc.y = -zc.y;
-                const cplx E = make_double2(zk.x + zc.x, zk.y + zc.y);
-                const cplx O = make_double2(zk.x - zc.x, zk.y - zc.y);
-                const cplx wo = cmul(wb, O);
-                const cplx dd = make_double2(E.x + wo.y, E.y - wo.x);     // 2 d_k = E - i W^k O
+                const cplx dd = split_pair(csel(l0, v[j + 1], v[j]), zc, wb);
                 // the rotated channel sum: w_n d_k e^{i kap phi_n}
                 const cplx y = cmul(dd, e);
                 acc[j].x = fma(hw, y.x, acc[j].x);
@@ -234,36 +221,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
                 const cplx x = cmulc(dd, mv2[j]);
                 const cplx z = cmul(x, e);
                 const double kap = j == 0 ? kap0 : kap0 + kconst<true>(PP_TWO_PI * (double)(64 * j));
-                const double p2 = kap * kap, p4 = p2 * p2, p6 = p4 * p2, p8 = p4 * p4, p10 = p8 * p2;
-                const double ui = z.y * kap;
-                const double ax = fabs(x.x) + fabs(x.y);
-                if (j == 0) {
-                    tm[0] = z.x;
-                    tm[1] = ui;
-                    tm[2] = p2 * z.x;
-                    tm[3] = p2 * ui;
-                    tm[4] = p4 * z.x;
-                    tm[5] = p4 * ui;
-                    tm[6] = p6 * z.x;
-                    tm[7] = p6 * ui;
-                    tm[8] = p8 * z.x;
-                    tm[9] = p8 * ui;
-                    tm[10] = p10 * z.x;
-                    tm[11] = (p10 * kap) * ax;
-                } else {
-                    tm[0] += z.x;
-                    tm[1] += ui;
-                    tm[2] = fma(p2, z.x, tm[2]);
-                    tm[3] = fma(p2, ui, tm[3]);
-                    tm[4] = fma(p4, z.x, tm[4]);
-                    tm[5] = fma(p4, ui, tm[5]);
-                    tm[6] = fma(p6, z.x, tm[6]);
-                    tm[7] = fma(p6, ui, tm[7]);
-                    tm[8] = fma(p8, z.x, tm[8]);
-                    tm[9] = fma(p8, ui, tm[9]);
-                    tm[10] = fma(p10, z.x, tm[10]);
-                    tm[11] = fma(p10 * kap, ax, tm[11]);
-                }
+                taylor_terms(j == 0, tm, x, z, kap);
               }
             }
             wb = cmul(wb, PP_WBT);
@@ -284,13 +242,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
             const cplx* pt = lds + fftq_lane_of((64 - lam) & 63) + (l0 ? 64 : 0);
 #pragma unroll
             for (int kd = 12; kd < 16; ++kd) {
-                const cplx zk = v[kd];
-                cplx zc = pt[64 * (NSL + 15 - kd)];
-                zc.y = -zc.y;
-                const cplx E = make_double2(zk.x + zc.x, zk.y + zc.y);
-                const cplx O = make_double2(zk.x - zc.x, zk.y - zc.y);
-                const cplx wo = cmul(wt, O);
-                const cplx y = cmul(make_double2(E.x + wo.y, E.y - wo.x), et);
+                const cplx y = cmul(split_pair(v[kd], pt[64 * (NSL + 15 - kd)], wt), et);
                 constexpr int NRT = 4 - NLA;      // tail accumulators in registers
                 if (kd - 12 < NRT) {
                     acc[7 + kd - 12].x = fma(hw, y.x, acc[7 + kd - 12].x);
@@ -324,6 +276,9 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qr1024(XspecArgs a, RefSeedArgs
             tr[PP_TSTRIDE] = sd;
             lds_sync<T>();
             double tv = wave_reduce_lds(tr, tid, reinterpret_cast<double*>(lds));
+            // (store_row_results<M, false, false>, written out: with the call the ticket-carrying kernels' allocation
+            // moves -- two SGPR spills fewer, other scratch traffic -- and this kernel is at 256 registers, where nothing
+            // may move unmeasured: profiles/r08_refactor_isa.txt)
             if ((tid & 3) == 0) {
                 const int q = wave_reduce16_index(tid);
                 if (q < PP_TSTRIDE) {

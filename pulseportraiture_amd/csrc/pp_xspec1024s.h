@@ -66,14 +66,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qs1024(XspecArgs a, const doubl
         for (int k = 0; k < R1; ++k) v[k] = to_cplx(cur[0][k]);
         constexpr bool HALVES = sizeof(Tin) == 8;
         const Tin* nxrow = nullptr;
-        auto load_some = [&](int k0, int k1) {
-            const char* gb = reinterpret_cast<const char*>(nxrow);
-            const unsigned boff = (unsigned)tid * (unsigned)sizeof(Raw);
-#pragma unroll
-            for (int k = 0; k < R1; ++k)
-                if (k >= k0 && k < k1)
-                    cur[0][k] = load_row_once<Raw>(gb + (size_t)(k * 64) * sizeof(Raw) + boff);
-        };
+        auto load_some = [&](int k0, int k1) { load_row_pieces<Raw>(cur, nxrow, tid, k0, k1); };
         // (the row after this one is decided outside the lambda: see k_xspec_q1024)
         rw.next(i, n, i_nx, n_nx, nrows, a.nsub, a.ticket_base, a.ticket, a.mwords);
         {
@@ -108,17 +101,12 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qs1024(XspecArgs a, const doubl
         cplx zc_nx = pc[64 * 6];
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
-            if (PP_SLOT_EARLY_EXIT && j > 0 && !(64 * j < ktu)) break;     // (kept slots are a prefix: pp_xspec1024q.h)
-            cplx zc = zc_nx;
-            if (j + 1 < NSL && (!PP_SLOT_EARLY_EXIT || 64 * (j + 1) < ktu)) zc_nx = pc[64 * (5 - j)];
+            if (j > 0 && !(64 * j < ktu)) break;     // (kept slots are a prefix: pp_xspec1024q.h)
+            const cplx zc = zc_nx;
+            if (j + 1 < NSL && 64 * (j + 1) < ktu) zc_nx = pc[64 * (5 - j)];
             if (j == 0 || 64 * j < ktu) {
-                const cplx zk = csel(l0, v[j + 1], v[j]);
-                zc.y = -zc.y;
-                const cplx E = make_double2(zk.x + zc.x, zk.y + zc.y);
-                const cplx O = make_double2(zk.x - zc.x, zk.y - zc.y);
-                const cplx wo = cmul(wb, O);
                 // X_k = d_k conj(m_k) with 2 d_k = E - i W^k O (the half is exact)
-                cplx x = cmulc(make_double2(E.x + wo.y, E.y - wo.x), mv2[j]);
+                cplx x = cmulc(split_pair(csel(l0, v[j + 1], v[j]), zc, wb), mv2[j]);
                 x.x *= 0.5; x.y *= 0.5;
                 store_x(a, rc, kb + 64 * j, x);
                 const cplx z = cmul(x, e);
@@ -141,7 +129,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_qs1024(XspecArgs a, const doubl
                 S1 = fma(kap * u * D2, Mk, S1);
                 S2 = fma(k2 * D2 * fma(4.0 * u * u, D, -1.0), Mk, S2);
             }
-            if (!PP_SLOT_EARLY_EXIT || (j + 1 < NSL && 64 * (j + 1) < ktu)) {
+            if (j + 1 < NSL && 64 * (j + 1) < ktu) {
                 wb = cmul(wb, wbT);
                 e = cmul(e, wst);
             }

@@ -2,7 +2,7 @@
 alone (PP_CHUNK_CHANNELS = 256, whatever the batch: a subint's answer must not depend on its neighbours), so a lone
 4096-channel subint launches 16 evaluator workgroups where round 4 launched up to 64.  Times 1 / 2 / 4 / 8 subints of
 4096 x 2048 and 2048 x 2048, scattering (evaluation loop) and phase + DM (one pass), device-resident portraits, best of
-5 calls:   PP_TOAS_LIB=variants/chunk64.so python tools/dev_small_batch_latency.py    for the 64-channel chunk build."""
+5 calls (PP_TOAS_LIB=<library> times another build, e.g. one with PP_CHUNK_CHANNELS edited to 64: profiles/r06_chunk_ab.txt)."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

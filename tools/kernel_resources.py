@@ -8,7 +8,10 @@ ticket a wave draws) from spills inside the row loop (executed per row, and a sc
 the prefetched row like every other vector-memory access).  A loop is a backward branch; a scratch
 instruction, or an SGPR spill to a VGPR lane (v_writelane / v_readlane), counts as "in a loop" when
 some loop that contains NO call (s_swappc) spans it -- the phase loop around the call site is not one.
-    python tools/kernel_resources.py --loops [filter]"""
+    python tools/kernel_resources.py --loops [filter]
+
+... and whether two builds are the same kernels: symbols, resource notes and instruction text, kernel by kernel
+    python tools/kernel_resources.py --compare A.so B.so"""
 import os
 import re
 import subprocess
@@ -149,8 +152,93 @@ def metadata(so=None, pat=""):
     return out
 
 
+def disassembly(so):
+    """{kernel symbol (mangled): [instruction text, ...]} of the code object, addresses stripped."""
+    with tempfile.TemporaryDirectory() as tmp:
+        full = subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", code_object(so, tmp)],
+                              capture_output=True, text=True, check=True).stdout
+    out, cur = {}, None
+    for ln in full.splitlines():
+        m = re.match(r"^[0-9a-f]+ <([^>]+)>:", ln)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+            continue
+        m = re.match(r"^\s+(\S.*?)\s*//\s*[0-9A-Fa-f]+:", ln)
+        if m and cur is not None:
+            cur.append(m.group(1))
+    return out
+
+
+# the mnemonics whose counts may not change where the text of a kernel does: memory, LDS, f64 arithmetic, lane spills, calls
+COUNTED = re.compile(r"^(global_|scratch_|ds_|v_\w+_f64|v_fma|v_readlane|v_writelane|s_swappc)")
+
+
+def masked(text):
+    """An instruction with register numbers and branch-target offsets masked."""
+    text = re.sub(r"<[^>]*>", "<>", text)
+    text = re.sub(r"\b([vsa])\[\d+:\d+\]", r"\1[]", text)
+    return re.sub(r"\b([vsa])\d+\b", r"\1", text)
+
+
+def waves_per_simd(vgpr):
+    return 4 if vgpr <= 128 else 3 if vgpr <= 168 else 2
+
+
+def compare(so_a, so_b):
+    """One line per kernel of B that differs from A's (symbols, resource notes, instruction text) and a summary.
+    Returns the number of kernels that break the rules of an instruction-preserving refactor: a symbol gone or new,
+    a resource note changed (VGPR / SGPR counts may move where nothing spills and the waves per SIMD stay), or a text
+    that differs in more than order (counts of the COUNTED mnemonics unequal, total off by more than 0.5 %)."""
+    import collections
+    import difflib
+    ma, mb = metadata(so_a), metadata(so_b)
+    da, db = disassembly(so_a), disassembly(so_b)
+    short = lambda n: re.sub(r"\(.*\)$", "", re.sub(r"^(void )?pp::", "", n))
+    syms = sorted(set(da) | set(db))
+    names = dict(zip(syms, (short(n) for n in subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True,
+                                                             text=True).stdout.split("\n"))))
+    bad = differ = moved = 0
+    for n in sorted(set(ma) ^ set(mb)):
+        print("SYMBOL   %-70s only in %s" % (n[:70], "A" if n in ma else "B"))
+        bad += 1
+    for n in sorted(set(ma) & set(mb)):
+        if ma[n] == mb[n]:
+            continue
+        ch = {k: (ma[n][k], mb[n][k]) for k in ma[n] if ma[n][k] != mb[n][k]}
+        clean = all(d[k] == 0 for d in (ma[n], mb[n]) for k in ("vspill", "sspill", "scratch"))
+        ok = clean and set(ch) <= {"vgpr", "sgpr"} and waves_per_simd(ma[n]["vgpr"]) == waves_per_simd(mb[n]["vgpr"])
+        print("%-8s %-70s %s" % ("moved" if ok else "NOTES", n[:70], " ".join("%s %d->%d" % (k, x, y) for k, (x, y) in ch.items())))
+        moved += ok
+        bad += not ok
+    for sy in sorted(set(da) & set(db)):
+        ta, tb = da[sy], db[sy]
+        if ta == tb:
+            continue
+        differ += 1
+        xa, xb = [masked(t) for t in ta], [masked(t) for t in tb]
+        nd = sum(max(i2 - i1, j2 - j1) for tag, i1, i2, j1, j2 in
+                 difflib.SequenceMatcher(None, xa, xb, autojunk=False).get_opcodes() if tag != "equal")
+        ca = collections.Counter(t.split()[0] for t in ta)
+        cb = collections.Counter(t.split()[0] for t in tb)
+        cnt = {k: (ca[k], cb[k]) for k in sorted(set(ca) | set(cb)) if ca[k] != cb[k]}
+        ok = not any(COUNTED.match(k) for k in cnt) and abs(len(tb) - len(ta)) <= 0.005 * len(ta)
+        print("%-8s %-70s %d -> %d instructions, %d masked lines differ; counts: %s" %
+              ("text" if ok else "TEXT", names[sy][:70], len(ta), len(tb), nd,
+               " ".join("%s %d->%d" % (k, x, y) for k, (x, y) in cnt.items()) or "equal"))
+        bad += not ok
+    for sy in sorted(set(da) ^ set(db)):
+        if names[sy] not in ma and names[sy] not in mb:      # (a function that is no kernel: no notes of its own)
+            print("SYMBOL   %-70s only in %s" % (names[sy][:70], "A" if sy in da else "B"))
+            bad += 1
+    print("%d symbols (%d kernels) in A, %d (%d) in B; resource notes: %d moved within the rule; instruction text: %d differ; "
+          "%d break the rules" % (len(da), len(ma), len(db), len(mb), moved, differ, bad))
+    return bad
+
+
 def main():
     so = os.path.join(ROOT, "pulseportraiture_amd", "csrc", "libpptoas_hip.so")
+    if len(sys.argv) > 1 and sys.argv[1] == "--compare":
+        sys.exit(1 if compare(sys.argv[2], sys.argv[3]) else 0)
     if len(sys.argv) > 1 and sys.argv[1] == "--loops":
         res = loop_scratch(so, sys.argv[2] if len(sys.argv) > 2 else "")
         print("%-60s %8s %8s %8s %8s %6s %6s" % ("kernel", "scratch", "in-loop", "lanespl", "in-loop", "calls", "loops"))
@@ -159,33 +247,10 @@ def main():
                                                       v["lane_spills_in_loops"], v["calls"], v["loops"]))
         return
     pat = sys.argv[1] if len(sys.argv) > 1 else ""
-    with tempfile.TemporaryDirectory() as tmp:
-        fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")
-        subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", so, fat], check=True)
-        subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
-        notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], capture_output=True, text=True,
-                               check=True).stdout
-    rows = []
-    for e in re.split(r"\n  - ", notes):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        if not m or ".vgpr_count" not in e:
-            continue
-
-        def g(k):
-            mm = re.search(r"\.%s:\s+(\d+)" % k, e)
-            return int(mm.group(1)) if mm else -1
-        rows.append((m.group(1), g("vgpr_count"), g("agpr_count"), g("sgpr_count"), g("vgpr_spill_count"),
-                     g("sgpr_spill_count"), g("group_segment_fixed_size"), g("private_segment_fixed_size")))
-    names = subprocess.run(["c++filt"], input="\n".join(r[0] for r in rows), capture_output=True,
-                           text=True).stdout.split("\n")
     print("%-84s %5s %5s %5s %6s %6s %7s %7s" % ("kernel", "vgpr", "agpr", "sgpr", "vspill", "sspill", "lds", "scratch"))
-    for r, n in zip(rows, names):
-        n = re.sub(r"^void pp::", "", n)
-        n = re.sub(r"\(.*\)$", "", n)
-        if pat and pat not in n:
-            continue
-        print("%-84s %5d %5d %5d %6d %6d %7d %7d" % ((n[:84],) + r[1:]))
+    for n, d in metadata(so, pat).items():
+        print("%-84s %5d %5d %5d %6d %6d %7d %7d" % (n[:84], d["vgpr"], d["agpr"], d["sgpr"], d["vspill"], d["sspill"],
+                                                     d["lds"], d["scratch"]))
 
 
 if __name__ == "__main__":
