@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 6
+#define PP_ABI_VERSION 7
 
 /* status codes */
 #define PP_OK 0
@@ -504,6 +504,40 @@ int pp_channel_noise(pp_ctx* ctx, const void* src, int dtype, int on_device, int
  * dropped channel, 0 elsewhere. */
 int pp_zap_median(pp_ctx* ctx, const double* noise, const unsigned char* good, int nsub,
                   int nchan, double nstd, unsigned char* zap);
+
+/* ---- ppspline --------------------------------------------------------------- */
+/* pplib.get_SNR(row, fudge) (pplib.py:2289-2308) of every row of src [nrows][nbin] (`dtype`, host or
+ * device): sum / (noise sqrt(Weq)) / fudge with Weq = sum / max (1, and a zero result, where that is not
+ * positive) and the get_noise_PS noise of pp_channel_noise; sum, maximum and noise come from one pass over
+ * the row.  snrs: [nrows] host array. */
+int pp_channel_snrs(pp_ctx* ctx, const void* src, int dtype, int on_device, int nrows,
+                    int nbin, double fudge, double* snrs);
+
+/* The device side of pplib.pca (pplib.py:1497-1534) up to the eigen-solve, for the portrait src
+ * [nchan][nbin] (`dtype`, host or device) and the weights w[nchan] (host; sumw = sum w, fact = sumw -
+ * sum w^2 / sumw, np.cov's normalisation with aweights and ddof = 1):
+ *   mean_prof = sum_n w_n src_n / sumw                                      (ppspline.py:70)
+ *   delta = src - mean_prof, re-centred by its weighted average as np.cov does (pplib.py:1528)
+ *   gram  = the nbin x nbin covariance when nchan >= nbin, else the nchan x nchan dual
+ *           sqrt(w_i) sqrt(w_j) delta_i . delta_j / fact, which has the covariance's non-zero spectrum
+ * on v_mfma_f64_16x16x4_f64 in a fixed summation order (the same bits on every run).  mean_prof [nbin] and
+ * gram [n][n], n = min-side as above, are host arrays.  The centred rows stay resident for pp_pca_basis
+ * and pp_pca_project.  nbin: even, 8 ... 4096. */
+int pp_pca_gram(pp_ctx* ctx, const void* src, int dtype, int on_device, int nchan, int nbin,
+                const double* w, double sumw, double fact, double* mean_prof, double* gram);
+
+/* The leading eigenvectors of the covariance and what find_significant_eigvec (pplib.py:1555-1619) measures
+ * of them without smoothing.  vecs [nvec][n] are the host's leading eigenvectors of gram (one per row,
+ * eigenvalues lam[nvec], descending; nvec <= 16); on the dual side each is mapped back to a profile,
+ * delta^T sqrt(w) u / sqrt(lam fact), scaled to unit length.  basis [nvec][nbin]; stats [nvec][4] = { sum_{k>=1} |rfft(ev)_k|^2,
+ * get_noise_PS(ev) (pplib.py:2249-2253), max |ev|, count_crossings(|ev|, 0.1 max |ev|) (pplib.py:686-694) }.
+ * The basis stays resident. */
+int pp_pca_basis(pp_ctx* ctx, const double* vecs, const double* lam, int nvec, double* basis,
+                 double* stats);
+
+/* proj [nchan][ncomp] = delta . basis[ieig] and reconst [nchan][nbin] = proj . basis[ieig]^T + mean_prof
+ * (ppspline.py:119-129; reconstruct_portrait, pplib.py:1536-1553) from the resident rows and basis. */
+int pp_pca_project(pp_ctx* ctx, const int32_t* ieig, int ncomp, double* proj, double* reconst);
 
 /* Fill dst[nsub][nchan][nbin] (device pointer, dtype) with
  *   gains[i][n] * rotate(model slot, -phi_i, -DM_i, -GM_i) + N(0, sigma)

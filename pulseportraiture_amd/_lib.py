@@ -16,7 +16,7 @@ PP_OK, PP_EINVAL, PP_EHIP, PP_ENOMEM, PP_ESTATE, PP_ENOTSUP = 0, -1, -2, -3, -4,
 PP_F64, PP_F32 = 0, 1
 PP_MAX_SLOTS = 64
 PP_RECORD_WIDTH = 18
-ABI_VERSION = 6
+ABI_VERSION = 7
 PP_METHOD_TRUST_NCG, PP_METHOD_NEWTON = 0, 1
 PP_NORMS = {None: 0, 'mean': 1, 'max': 2, 'prof': 3, 'rms': 4, 'abs': 5}
 
@@ -117,6 +117,12 @@ SYMBOLS = {
                                    c_double_p, c_double_p, c_double_p]),
     "pp_zap_median": (C.c_int, [C.c_void_p, c_double_p, c_uint8_p, C.c_int, C.c_int, C.c_double,
                                 c_uint8_p]),
+    "pp_channel_snrs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                  c_double_p]),
+    "pp_pca_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p,
+                              C.c_double, C.c_double, c_double_p, c_double_p]),
+    "pp_pca_basis": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p]),
+    "pp_pca_project": (C.c_int, [C.c_void_p, c_int32_p, C.c_int, c_double_p, c_double_p]),
     "pp_kernel_times": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p),
                                   c_double_p, C.POINTER(C.c_int64)]),
     "pp_kernel_times_reset": (C.c_int, [C.c_void_p]),

@@ -97,9 +97,9 @@ __global__ void k_copy_words(unsigned long long* dst, const unsigned long long* 
 static int staged_copy(pp_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st = nullptr);
 __global__ void k_publish_int(int* host_dst, const int* dev_src) { *host_dst = *dev_src; }
 static int publish_int(pp_ctx* c, int* host_dst, const int* dev_src);
-enum KernelFamily { KF_MODEL = 0, KF_XSPEC, KF_PREP, KF_SEED, KF_ACCUM, KF_EVAL, KF_TAYLOR, KF_STEP, KF_FINAL, KF_SYNTH, KF_FPS, KF_SCATMODEL, KF_COUNT };
+enum KernelFamily { KF_MODEL = 0, KF_XSPEC, KF_PREP, KF_SEED, KF_ACCUM, KF_EVAL, KF_TAYLOR, KF_STEP, KF_FINAL, KF_SYNTH, KF_FPS, KF_SCATMODEL, KF_PCA, KF_COUNT };
 static const char* kFamilyNames[KF_COUNT] = {"model_fft", "xspec", "prep", "seed", "accum", "eval", "taylor_solve", "step", "finalize",
-                                            "synth", "fit_phase_shift", "scat_model"};
+                                            "synth", "fit_phase_shift", "scat_model", "pca_gram"};
 
 #define PP_NSTAGE 3     // enqueued batches that may be pending at once (staging blocks, work-buffer sets)
 struct pp_ctx {
@@ -151,6 +151,13 @@ struct pp_ctx {
                                      // with registers as the binding resource the two do not co-reside, they alternate.
                                      // Kept as an option: the work-set / two-stream plumbing is what a fused tail would use.
     DevBuf inpack;   // (aux entry points)
+    // ppspline (pp_pca.h): what pp_pca_gram leaves resident for pp_pca_basis and pp_pca_project
+    struct Pca {
+        DevBuf w, vec, part, D, S, G, U, B, small, idx, proj;   // vec: mean profile, then np.cov's weighted row average
+        int nchan = 0, nbin = 0, dual = 0, pitch = 0, nvec = 0;
+        double fact = 0.0;
+        void release() { for (DevBuf* b : {&w, &vec, &part, &D, &S, &G, &U, &B, &small, &idx, &proj}) b->release(); }
+    } pca;
     // pinned host staging of the small inputs / the packed outputs of a batch: two sets, so that a
     // deferred batch (pp_fit_enqueue) keeps its own while the next one is being queued
     struct Stage { void* in_host = nullptr; size_t in_cap = 0; void* o_host = nullptr; size_t o_cap = 0;
@@ -378,6 +385,7 @@ extern "C" int pp_destroy(pp_ctx* c) {
         if (sg.done) (void)hipEventDestroy(sg.done);
     }
     c->inpack.release();
+    c->pca.release();
     c->refbuf.release();
     c->mwords.release();
     DevBuf* bufs[] = {&c->ticket, &c->o_pack, &c->mft_table, &c->msum_table, &c->kt_table, &c->mdc_table, &c->msq_table, &c->data, &c->X, &c->sdraw, &c->noise, &c->wts, &c->freqs,
@@ -2105,3 +2113,4 @@ extern "C" int pp_fit_wait(pp_ctx* c) {
 
 #include "pp_extra_api.h"
 #include "pp_zap.h"
+#include "pp_pca.h"

@@ -13,6 +13,8 @@ struct ChanNoiseArgs {
     double* noise;            // [nrows] noise of the normalised row: noise / |norm|
     long long nrows;
     int M, method;
+    double* snr;              // [nrows] get_SNR of the row (pp_channel_snrs), or nullptr
+    double fudge;
 };
 
 // workgroup totals of the lanes' v = {sum, maximum, sum of squares, max |x| (!= 0 iff row.any()), power of
@@ -56,6 +58,14 @@ __device__ __forceinline__ void chan_noise_store(const ChanNoiseArgs& a, long lo
     }
     a.norms[r] = norm;
     a.noise[r] = noise / fabs(norm);
+    if (a.snr) {
+        // get_SNR (pplib.py:2289-2308; its dc is 0): the equivalent width sum / max, 1 and a zero result where
+        // that is not positive
+        double Weq = v[0] / v[1];
+        const double keep = Weq <= 0.0 ? 0.0 : 1.0;
+        if (Weq <= 0.0) Weq = 1.0;
+        a.snr[r] = v[0] / (noise * sqrt(Weq)) * keep / a.fudge;
+    }
 }
 
 __device__ __forceinline__ void chan_noise_start(double v[5]) {
@@ -202,8 +212,9 @@ __global__ __launch_bounds__(PP_ZAP_T) void k_zap_median(const double* noise, co
 // ---- ppzap: channel noise and norms ------------------------------------------
 // pplib.get_noise_PS(row, frac=4) (pplib.py:2227-2253) of every row, with the norm of
 // normalize_portrait (pplib.py:2462-2507) that ppzap applies before it (ppzap.py:222-230)
-extern "C" int pp_channel_noise(pp_ctx* c, const void* src, int dtype, int on_device, int nrows, int nbin,
-                                int norm_method, const double* divisor, double* norms, double* noise) {
+// (snrs: pp_channel_snrs' output of the same pass, or nullptr)
+static int channel_noise_rows(pp_ctx* c, const void* src, int dtype, int on_device, int nrows, int nbin, int norm_method,
+                              const double* divisor, double* norms, double* noise, double* snrs, double fudge) {
     if (int busy_ = ctx_busy(c, "pp_channel_noise")) return busy_;
     if (!c || !src || !norms || !noise) return fail(PP_EINVAL, "pp_channel_noise: null argument");
     if (!nbin_any_ok(nbin) || nbin > 4096) return fail(PP_EINVAL, "pp_channel_noise: nbin %d must be even and in [8, 4096]", nbin);
@@ -224,8 +235,9 @@ extern "C" int pp_channel_noise(pp_ctx* c, const void* src, int dtype, int on_de
         if (nrows > cap) {
             for (int r0 = 0; r0 < nrows; r0 += cap) {
                 const int n = std::min(cap, nrows - r0);
-                if ((rc = pp_channel_noise(c, (const char*)src + (size_t)r0 * rowb, dtype, on_device, n, nbin, norm_method,
-                                           divisor ? divisor + r0 : nullptr, norms + r0, noise + r0)))
+                if ((rc = channel_noise_rows(c, (const char*)src + (size_t)r0 * rowb, dtype, on_device, n, nbin, norm_method,
+                                             divisor ? divisor + r0 : nullptr, norms + r0, noise + r0,
+                                             snrs ? snrs + r0 : nullptr, fudge)))
                     return rc;
             }
             return PP_OK;
@@ -246,7 +258,9 @@ extern "C" int pp_channel_noise(pp_ctx* c, const void* src, int dtype, int on_de
     if ((rc = c->noise.reserve((size_t)nrows * 8))) return rc;
     const cplx* tw = nullptr;
     if ((rc = get_twiddles(c, nbin, &tw))) return rc;
-    ChanNoiseArgs a{dsrc, nullptr, tw, ddiv, c->sdraw.as<double>(), c->noise.as<double>(), nrows, M, norm_method};
+    if (snrs && (rc = c->csum.reserve((size_t)nrows * 8))) return rc;
+    ChanNoiseArgs a{dsrc, nullptr, tw, ddiv, c->sdraw.as<double>(), c->noise.as<double>(), nrows, M, norm_method,
+                    snrs ? c->csum.as<double>() : nullptr, fudge};
     if (anyb) {
         if ((rc = c->X.reserve((size_t)nrows * harmb))) return rc;
         XspecArgs xa;
@@ -271,8 +285,25 @@ extern "C" int pp_channel_noise(pp_ctx* c, const void* src, int dtype, int on_de
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(norms, c->sdraw.p, (size_t)nrows * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(noise, c->noise.p, (size_t)nrows * 8, hipMemcpyDeviceToHost, c->stream));
+    if (snrs) HIP_TRY(hipMemcpyAsync(snrs, c->csum.p, (size_t)nrows * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PP_OK;
+}
+
+extern "C" int pp_channel_noise(pp_ctx* c, const void* src, int dtype, int on_device, int nrows, int nbin,
+                                int norm_method, const double* divisor, double* norms, double* noise) {
+    return channel_noise_rows(c, src, dtype, on_device, nrows, nbin, norm_method, divisor, norms, noise, nullptr, 1.0);
+}
+
+// ---- ppspline: channel S/N ----------------------------------------------------
+// pplib.get_SNR(row, fudge) (pplib.py:2289-2308) of every row: its sum, maximum and get_noise_PS noise from one
+// pass over it
+extern "C" int pp_channel_snrs(pp_ctx* c, const void* src, int dtype, int on_device, int nrows, int nbin, double fudge,
+                               double* snrs) {
+    if (!snrs || nrows < 1) return fail(PP_EINVAL, "pp_channel_snrs: null argument or no rows");
+    std::vector<double> norms((size_t)nrows), noise((size_t)nrows);
+    return channel_noise_rows(c, src, dtype, on_device, nrows, nbin, PP_NORM_NONE, nullptr, norms.data(), noise.data(), snrs,
+                              fudge);
 }
 
 // ---- ppzap: the median / sigma clip ----------------------------------------

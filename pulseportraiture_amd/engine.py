@@ -754,6 +754,93 @@ class Engine(object):
                 self.fit_phase_shift_batch(rows[live], means[sub_of], finish='simplex')[:, 2]
         return div.reshape(-1)
 
+    def _rows_arg(self, ports, what):
+        """(pointer, dtype, on_device, shape, keep-alive) of rows handed over as NumPy or a
+        contiguous device tensor, f64 or f32 (anything else is converted to f64)."""
+        shape = tuple(int(v) for v in ports.shape)
+        if _is_device_array(ports):
+            if not ports.is_contiguous():
+                raise EngineError("%s: device rows must be contiguous" % what)
+            return (C.c_void_p(ports.data_ptr()), PP_F64 if ports.element_size() == 8 else PP_F32, 1,
+                    shape, ports)
+        keep = np.asarray(ports)
+        if keep.dtype != np.float32:
+            keep = keep.astype(np.float64, copy=False)
+        keep = np.ascontiguousarray(keep)
+        return (C.c_void_p(keep.ctypes.data), PP_F64 if keep.dtype == np.float64 else PP_F32, 0,
+                shape, keep)
+
+    def channel_snrs(self, ports, fudge=3.25):
+        """pplib.get_SNR (pplib.py:2289-2308) of every row of ports [..., nbin] (NumPy or a
+        device tensor, f64 or f32): the row's sum, maximum and power-spectrum noise come
+        from one pass over it on the device.  Returns an array shaped like ports without
+        the bin axis."""
+        src, dtype, on_dev, shape, keep = self._rows_arg(ports, "channel_snrs")
+        if len(shape) < 2:
+            raise ValueError("ports must be [..., nbin]")
+        nrows = int(np.prod(shape[:-1]))
+        snrs = np.empty(nrows)
+        _check(self._lib.pp_channel_snrs(self._ctx, src, dtype, on_dev, nrows, shape[-1], float(fudge),
+                                         _dp(snrs)), "pp_channel_snrs")
+        return snrs.reshape(shape[:-1])
+
+    # eigenvectors find_significant_eigvec examines (check_max = 10, pplib.py:1584)
+    PCA_NVEC = 10
+
+    def pca_gram(self, port, weights):
+        """First stage of pplib.pca (pplib.py:1497-1528) for port [nchan,nbin] (NumPy or a
+        device tensor, f64 or f32) and the PCA weights [nchan]: returns (mean_prof [nbin],
+        gram, fact).  gram is np.cov(delta.T, aweights=weights, ddof=1) itself when nchan >=
+        nbin, else its nchan x nchan dual sqrt(w_i w_j) delta_i . delta_j / fact, which has the
+        same non-zero eigenvalues; fact is np.cov's normalisation.  Formed on the f64 MFMA in a
+        fixed order (the same bits on every run).  The centred rows stay on the device for
+        pca_basis and pca_project."""
+        src, dtype, on_dev, shape, keep = self._rows_arg(port, "pca_gram")
+        if len(shape) != 2:
+            raise ValueError("port must be [nchan,nbin]")
+        nchan, nbin = shape
+        w = _f64(weights, (nchan,))
+        sumw = float(np.sum(w))
+        fact = sumw - float(np.sum(w * w)) / sumw
+        n = nchan if nchan < nbin else nbin
+        mean_prof, gram = np.empty(nbin), np.empty((n, n))
+        self._pca_shape = None
+        _check(self._lib.pp_pca_gram(self._ctx, src, dtype, on_dev, nchan, nbin, _dp(w), sumw, fact,
+                                     _dp(mean_prof), _dp(gram)), "pp_pca_gram")
+        self._pca_shape = (nchan, nbin)
+        return mean_prof, gram, fact
+
+    def pca_basis(self, vecs, eigval):
+        """The leading eigenvectors of pca_gram's matrix (vecs [n,nvec], columns, with their
+        eigenvalues, descending) as profiles: returns (eigvec [nbin,nvec], stats [nvec,4]).
+        On the dual side each is mapped back through the resident rows.  stats holds what
+        find_significant_eigvec (pplib.py:1586-1595) measures of every vector without
+        smoothing: sum_{k>=1} |rfft(ev)_k|^2, get_noise(ev), max |ev| and
+        count_crossings(|ev|, 0.1 max |ev|)."""
+        v = np.ascontiguousarray(np.asarray(vecs, dtype=np.float64).T)
+        nvec = v.shape[0]
+        lam = _f64(eigval, (nvec,))
+        if getattr(self, "_pca_shape", None) is None:
+            raise EngineError("pca_basis: no centred portrait is resident (pca_gram first)")
+        basis = np.empty((nvec, self._pca_shape[1]))
+        stats = np.empty((nvec, 4))
+        _check(self._lib.pp_pca_basis(self._ctx, _dp(v), _dp(lam), nvec, _dp(basis), _dp(stats)),
+               "pp_pca_basis")
+        return np.ascontiguousarray(basis.T), stats
+
+    def pca_project(self, ieig):
+        """proj_port [nchan,ncomp] = delta . eigvec[:, ieig] and reconst_port [nchan,nbin] =
+        proj_port . eigvec[:, ieig].T + mean_prof (ppspline.py:126-129) of the resident rows
+        and basis."""
+        if getattr(self, "_pca_shape", None) is None:
+            raise EngineError("pca_project: no centred portrait is resident (pca_gram first)")
+        nchan, nbin = self._pca_shape
+        idx = np.ascontiguousarray(ieig, dtype=np.int32)
+        proj, reconst = np.empty((nchan, len(idx))), np.empty((nchan, nbin))
+        _check(self._lib.pp_pca_project(self._ctx, idx.ctypes.data_as(c_int32_p), len(idx), _dp(proj),
+                                        _dp(reconst)), "pp_pca_project")
+        return proj, reconst
+
     def zap_median(self, noise, good, nstd):
         """get_zap_channels' clip (ppzap.py:18-47) of every subint at once: noise and
         good [nsub,nchan] (good != 0: a channel in ok_ichans).  Returns the uint8

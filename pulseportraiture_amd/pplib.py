@@ -192,6 +192,14 @@ def get_noise(data, method=default_noise_method, frac=4, chans=False):
     return noise if chans else noise[0]
 
 
+def get_SNR(prof, fudge=3.25):
+    """Estimate of a profile's signal-to-noise ratio, baseline removed (pplib.py:2289-2308):
+    sum / (noise sqrt(Weq)) / fudge with Weq = sum / max.  The profile's sum, maximum and
+    power-spectrum noise are taken in one pass on the device (Engine.channel_snrs, which
+    takes whole portraits)."""
+    return default_engine().channel_snrs(np.asarray(prof, dtype=np.float64)[None], fudge=fudge)[0]
+
+
 def fit_phase_shift(data, model, noise=None, bounds=[-0.5, 0.5], Ns=100, finish='simplex'):
     """Fit a phase shift between a data and a model profile on the GPU (pplib.py:2054):
     Ns-point brute grid over `bounds` (both ends included), then -- like the

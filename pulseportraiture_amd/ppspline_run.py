@@ -1,0 +1,114 @@
+"""Command line of ppspline: `python -m pulseportraiture_amd.ppspline_run -d <datafile> [options]`,
+the options of the reference's `ppspline.py` (ppspline.py:288-338).
+
+The input is one aligned, averaged portrait: an .npz archive (the fields of a DataBunch) or a
+metafile naming one.  It is normalised with -N (default 'prof'), modelled with
+DataPortrait.make_spline_model(smooth=False) on the device and written as a .spl pickle
+(default datafile.spl) that pptoas_run, ppzap_run -m and the reference read."""
+import argparse
+import sys
+
+import numpy as np
+
+from .ppzap_run import list_datafiles
+
+MODULE = "pulseportraiture_amd.ppspline_run"
+
+
+def parser():
+    ap = argparse.ArgumentParser(
+        prog="python -m " + MODULE,
+        description="Make a pulse portrait model using PCA & B-spline interpolation (the reference's "
+                    "ppspline.py command line), without smoothing.")
+    ap.add_argument("-d", "--datafile", required=True, metavar="archive",
+                    help="One .npz archive (the fields of a DataBunch) from which to make the model, or a "
+                         "metafile naming one.  The data should be averaged and aligned.")
+    ap.add_argument("-o", "--modelfile", default=None, metavar="modelfile",
+                    help="Name for output model (pickle) file. [default=datafile.spl]")
+    ap.add_argument("-l", "--model_name", default=None, metavar="model_name",
+                    help="Optional name for model [default=datafile.spl].")
+    ap.add_argument("-a", "--archive", default=None, metavar="archive", help="Not available: needs PSRCHIVE.")
+    ap.add_argument("-N", "--norm", default="prof", metavar="normalization",
+                    help="Normalize the input data by channel ('None', 'mean', 'max' (not recommended), 'rms' "
+                         "(off-pulse noise), 'prof' (mean profile flux) [default], or 'abs' (sqrt{vector "
+                         "modulus})).")
+    ap.add_argument("-s", "--smooth", action="store_true",
+                    help="Not available: the wavelet smoothing needs PyWavelets.")
+    ap.add_argument("-n", "--max_ncomp", default=10, metavar="max_ncomp",
+                    help="Maximum number of principal components to use in PCA reconstruction of the data; "
+                         "limited to a maximum of 10 by the B-spline representation.")
+    ap.add_argument("-S", "--snr", dest="snr_cutoff", default=150.0, metavar="snr_cutoff",
+                    help="S/N ratio cutoff for determining 'significant' eigenprofiles. [default=150.0]")
+    ap.add_argument("-T", "--rchi2_tol", default=0.1, metavar="tolerance",
+                    help="Tolerance of the smoothing [default=0.1]; without -s it has no effect.")
+    ap.add_argument("-k", "--degree", dest="k", default=3, metavar="degree",
+                    help="Degree of the spline.  Cubic splines (k=3) are recommended [default]. 1 <= k <= 5.")
+    ap.add_argument("-f", "--sfac", default=1.0, metavar="smooth_factor",
+                    help="To change the smoothness of the B-spline model, tweak this between 0.0 (interpolating "
+                         "spline that passes through all data points) and a large number (guarantees maximum "
+                         "two breakpoints = maximum smoothness).  Alternatively, use -t.")
+    ap.add_argument("-t", "--knots", dest="max_nbreak", default=None, metavar="max_knots",
+                    help="The maximum number of unique knots.")
+    ap.add_argument("--plots", dest="make_plots", action="store_true", help="Not available: no plotting.")
+    ap.add_argument("--quiet", action="store_true", help="Suppresses output.")
+    return ap
+
+
+def refusal(opts, datafiles=None):
+    """The message for a request this command cannot honour, or None."""
+    if opts.smooth:
+        return ("-s/--smooth: the wavelet smoothing needs PyWavelets, which was not available to pin it "
+                "against the reference; models are made without smoothing")
+    if opts.archive is not None:
+        return "-a/--archive needs PSRCHIVE, which this package does not use"
+    if opts.make_plots:
+        return "--plots: plots are not available"
+    if datafiles is not None and len(datafiles) != 1:
+        return ("-d names a metafile of %d archives: joining several bands is not available; give one "
+                "archive" % len(datafiles))
+    return None
+
+
+def load_portrait(datafile):
+    """The DataPortrait of an .npz archive.  An archive without SNRs gets them measured on the
+    device (Engine.channel_snrs), one without noise_stds its power-spectrum noise."""
+    from .engine import default_engine
+    from .ppspline import DataPortrait
+    from .pptoas import _load
+    with np.load(datafile, allow_pickle=True) as z:
+        has_snrs = "SNRs" in z.files
+    data, _ = _load(datafile)
+    eng = default_engine()
+    sub = np.asarray(data.subints)
+    if data.noise_stds is None:
+        data.noise_stds = eng.channel_noise(sub.reshape(-1, sub.shape[-1]))[0].reshape(sub.shape[:-1])
+    if not has_snrs:
+        data.SNRs = eng.channel_snrs(sub.reshape(-1, sub.shape[-1])).reshape(sub.shape[:-1])
+    return DataPortrait(data, quiet=True)
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    opts = parser().parse_args(argv)
+    msg = refusal(opts)
+    if msg is None:
+        datafiles = [f for f in list_datafiles(opts.datafile) if f.strip()]
+        msg = refusal(opts, datafiles)
+    if msg is not None:
+        print("ppspline_run: " + msg, file=sys.stderr)
+        return 2
+    datafile = datafiles[0]
+    max_nbreak = None if opts.max_nbreak is None else int(opts.max_nbreak)
+    dp = load_portrait(datafile)
+    if opts.norm in ("mean", "max", "prof", "rms", "abs"):
+        dp.normalize_portrait(opts.norm)
+    dp.make_spline_model(max_ncomp=int(opts.max_ncomp), smooth=False, snr_cutoff=float(opts.snr_cutoff),
+                         rchi2_tol=float(opts.rchi2_tol), k=int(opts.k), sfac=float(opts.sfac),
+                         max_nbreak=max_nbreak, model_name=opts.model_name, quiet=opts.quiet)
+    modelfile = opts.datafile + ".spl" if opts.modelfile is None else opts.modelfile
+    dp.write_model(modelfile, quiet=opts.quiet)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,378 @@
+"""ppspline on the GPU against the true reference (tests/golden/ppspline_*.npz, from make_golden_ppspline.py).
+
+The bar of every quantity is 10 x the reference's OWN scatter of it -- its worst deviation when the channels
+are handed to it in another order, five orders, stored in the fixture (scat_*) -- floored at 1e-13 of the
+quantity's scale: the device's summation order is one more reordering of that kind.  Eigenvectors have an
+arbitrary sign in both implementations; signs are aligned by the dot product with the reference's column.
+With PP_PPSPLINE_PARITY_OUT set, the measured deviations are written there as JSON (profiles/ppspline_parity.json).
+"""
+import json
+import os
+import pickle
+import signal
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import ppspline_cases as pc
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+P0 = 0.003
+MEASURED = {}
+
+
+def _g(name):
+    return np.load(os.path.join(GOLDEN, "ppspline_%s.npz" % name))
+
+
+def _port(name):
+    if name in pc.REGENERATED:
+        port = pc.make_input(name)[0]
+        assert pc.sha256(port) == str(_g(name)["input_sha256"]), "the regenerated input is not the reference's"
+        return port
+    g = _g(name)
+    return g["port"] if "port" in g.files else _g("64x256")["port"]
+
+
+def _eng():
+    from pulseportraiture_amd.engine import default_engine
+    return default_engine()
+
+
+def _bunch(name, port=None, with_snrs=True):
+    from pulseportraiture_amd.pptoas import data_from_arrays
+    g = _g(name)
+    port = _port(name) if port is None else port
+    return data_from_arrays(port[None, None], g["freqs"], [P0], [55000.0], weights=g["weights"][None],
+                            noise_stds=g["noise_stds"][None, None], SNRs=g["SNRs"][None, None] if with_snrs else None,
+                            bw=float(g["bw"]), source="fake", filename=name + ".npz")
+
+
+def _portrait(name, port=None):
+    from pulseportraiture_amd.ppspline import DataPortrait
+    return DataPortrait(_bunch(name, port), quiet=True)
+
+
+def _bar(g, key, scale, index=None):
+    scat = np.asarray(g["scat_" + key], dtype=np.float64)
+    if index is not None and scat.ndim:
+        scat = scat[index]
+    return np.maximum(10.0 * scat, 1e-13 * scale)
+
+
+def _compare(name, g, mean_prof, eigval, eigvec, stats, ieig, proj_port, tck, fp, ier, modelx, model, tag=""):
+    """Every quantity of a model against the fixture; the failures by name."""
+    name_t = name + tag
+    rec = MEASURED.setdefault(name_t, {})
+    bad = []
+
+    def check(key, got, want, bar):
+        got, want, bar = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64), np.asarray(bar)
+        dev = np.abs(got - want)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            worst = float(np.where(dev == 0.0, 0.0, dev / bar).max()) if dev.size else 0.0
+        rec[key] = dict(deviation=float(dev.max()) if dev.size else 0.0, bar=float(np.min(bar)), of_bar=worst)
+        print("%-20s %-12s dev %.3e  bar %.3e  (%.3f of it)" % (name_t, key, rec[key]["deviation"], rec[key]["bar"], worst))
+        if not np.all(dev <= bar):
+            bad.append(key)
+
+    sg = np.sign(np.sum(eigvec * g["eigvec"], axis=0))
+    sg[sg == 0] = 1.0
+    ie = g["ieig"]
+    check("mean_prof", mean_prof, g["mean_prof"], _bar(g, "mean_prof", np.abs(g["mean_prof"]).max()))
+    check("eigval", eigval[:10] / eigval[0], g["eigval"], _bar(g, "eigval", 1.0))
+    check("lam1", eigval[0] / float(g["lam1"]), 1.0, _bar(g, "eigval", 1.0))
+    st = g["stats"]
+    for col, key in ((0, "ev_power"), (1, "ev_noise"), (2, "ev_maxabs")):
+        check(key, stats[:, col], st[:, col], _bar(g, "stats", np.abs(st[:, col]).max(), col))
+    snr = stats[:, 0] / (stats[:, 1] * np.sqrt(eigvec.shape[0] / 2.0))
+    check("ev_snr", snr, st[:, 4], _bar(g, "stats", np.abs(st[:, 4]).max(), 4))
+    if not np.array_equal(stats[:, 3], st[:, 3]):
+        bad.append("ncross %s != %s" % (stats[:, 3], st[:, 3]))
+    if not np.array_equal(ieig, ie):
+        bad.append("ieig %s != %s" % (ieig, ie))
+        return bad
+    if len(ie):
+        check("eigvec", (eigvec * sg)[:, ie], g["eigvec"][:, ie], _bar(g, "eigvec", 1.0, ie)[None, :])
+        check("proj_port", proj_port * sg[ie], g["proj_port"], _bar(g, "proj_port", np.abs(g["proj_port"]).max(axis=0))[None, :])
+        if not np.array_equal(tck[0], g["t"]):
+            bad.append("knots differ")
+            return bad
+        c = np.array(tck[1]) * sg[ie][:, None]
+        check("coefficients", c, g["c"], _bar(g, "c", np.abs(g["c"]).max(axis=1))[:, None])
+        check("fp", fp, float(g["fp"]), _bar(g, "fp", abs(float(g["fp"]))))
+        if tck[2] != int(g["k"]) or ier != int(g["ier"]):
+            bad.append("k / ier")
+    else:
+        if len(tck[0]) or len(tck[1]) or tck[2] != 0 or fp is not None:
+            bad.append("tck of the mean-profile model")
+    if modelx is not None:
+        if "modelx_rows" in g.files:
+            check("modelx", modelx[g["rows_x"]], g["modelx_rows"], _bar(g, "modelx", np.abs(g["model_rows"]).max()))
+        check("modelx_sums", modelx.sum(axis=1), g["modelx_sums"], _bar(g, "modelx_sums", np.abs(g["model_sums"]).max()))
+    check("model", model[g["rows"]], g["model_rows"], _bar(g, "model", np.abs(g["model_rows"]).max()))
+    check("model_sums", model.sum(axis=1), g["model_sums"], _bar(g, "model_sums", np.abs(g["model_sums"]).max()))
+    return bad
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _write_measured():
+    yield
+    out = os.environ.get("PP_PPSPLINE_PARITY_OUT")
+    if out and MEASURED:
+        with open(out, "w") as f:
+            json.dump(MEASURED, f, indent=1, sort_keys=True)
+
+
+@pytest.mark.parametrize("name", list(pc.CASES))
+def test_make_spline_model_against_the_reference(name):
+    g, kw = _g(name), pc.CASES[name][5]
+    dp = _portrait(name)
+    dp.make_spline_model(smooth=False, quiet=True, **kw)
+    assert dp.eigvec.shape == (pc.CASES[name][1], 10) and dp.ncomp == len(dp.ieig)
+    bad = _compare(name, g, dp.mean_prof, dp.eigval, dp.eigvec, dp.eigvec_stats, dp.ieig, dp.proj_port, dp.tck, dp.fp,
+                   dp.ier, dp.modelx, dp.model)
+    assert not bad, bad
+    ok = g["weights"] > 0
+    np.testing.assert_array_equal(dp.model_masked, dp.model * ok[:, None])
+    assert dp.model_name == name + ".npz.spl"
+    # the reconstruction is the projection's (ppspline.py:126-127)
+    ev = dp.eigvec[:, dp.ieig]
+    want = np.dot(dp.proj_port, ev.T) + dp.mean_prof if dp.ncomp else np.tile(dp.mean_prof, (ok.sum(), 1))
+    np.testing.assert_allclose(dp.reconst_port, want, rtol=0, atol=1e-13 * 10 * np.abs(want).max())
+
+
+@pytest.mark.parametrize("name", ["64x256", "128x512", "48x1000", "300x128"])
+@pytest.mark.parametrize("dtype,rtol", [(np.float64, 1e-12), (np.float32, 2e-5)])
+def test_channel_snrs_against_get_SNR(name, dtype, rtol):
+    from pulseportraiture_amd.pplib import get_SNR
+    g, port = _g(name), _port(name)
+    ok = g["weights"] > 0
+    snrs = _eng().channel_snrs(port[ok].astype(dtype))
+    np.testing.assert_allclose(snrs, g["SNRs"][ok], rtol=rtol, atol=0)
+    if dtype is np.float64:
+        n = int(np.where(ok)[0][3])
+        np.testing.assert_allclose(get_SNR(port[n]), g["SNRs"][n], rtol=rtol, atol=0)
+        np.testing.assert_allclose(get_SNR(port[n], fudge=1.0), 3.25 * g["SNRs"][n], rtol=rtol, atol=0)
+        cube = _eng().channel_snrs(port[None, ok])
+        assert cube.shape == (1, ok.sum()) and np.array_equal(cube[0], snrs)
+    # a profile whose sum is not positive (its maximum is) has no S/N (get_SNR's mask)
+    low = port[ok][:2] - 1.5 * port[ok][:2].mean(axis=1, keepdims=True)
+    assert low.sum(axis=1).max() < 0 < low.max(axis=1).min()
+    assert _eng().channel_snrs(low.astype(dtype)).tolist() == [0.0, 0.0]
+
+
+def test_normalize_portrait_side_effects():
+    g = np.load(os.path.join(GOLDEN, "ppspline_normalize.npz"))
+    name = str(g["case"])
+    dp = _portrait(name)
+    ok = dp.ok_ichans[0]
+    port0, noise0 = dp.port.copy(), np.array(dp.noise_stds[0, 0])
+    dp.normalize_portrait("prof")
+    # (the norms are fit_phase_shift scales and the noise is the device's: ppzap's channel-noise tests hold both to
+    # rtol 1e-12 for 'prof'; a factor ten on it here, where rows are divided by the norms as well)
+    np.testing.assert_allclose(dp.norm_values, g["norm_values"], rtol=1e-11)
+    np.testing.assert_allclose(dp.noise_stds[0, 0], g["noise_stds"], rtol=1e-11, atol=0)
+    np.testing.assert_allclose(dp.noise_stdsxs, g["noise_stdsxs"], rtol=1e-11)
+    np.testing.assert_allclose(dp.flux_prof, g["flux_prof"], rtol=1e-11, atol=1e-14)
+    np.testing.assert_allclose(dp.flux_profx, g["flux_profx"], rtol=1e-11, atol=1e-14)
+    np.testing.assert_allclose(dp.port[g["rows"]], g["port_rows"], rtol=1e-11, atol=1e-14)
+    np.testing.assert_allclose(dp.portx[pc.sample_rows(len(ok))], g["portx_rows"], rtol=1e-11, atol=1e-14)
+    np.testing.assert_array_equal(dp.unnorm_noise_stds[0, 0], noise0)
+    np.testing.assert_array_equal(dp.unnorm_noise_stdsxs, noise0[ok])
+    dp.unnormalize_portrait()
+    assert not hasattr(dp, "unnorm_noise_stds") and not hasattr(dp, "unnorm_noise_stdsxs")
+    np.testing.assert_allclose(dp.port, port0, rtol=1e-14, atol=1e-14)
+    np.testing.assert_allclose(dp.portx, port0[ok], rtol=1e-14, atol=1e-14)
+    np.testing.assert_array_equal(dp.noise_stds[0, 0], noise0)
+    np.testing.assert_array_equal(dp.norm_values, np.ones(len(port0)))
+    # an unknown method changes nothing
+    dp.normalize_portrait("median")
+    assert not hasattr(dp, "unnorm_noise_stds")
+
+
+@pytest.mark.parametrize("nchan,nbin", [(70, 200), (150, 40), (64, 64), (130, 1000)])
+def test_gram_matrix_exact_on_small_integers_and_the_same_bits_twice(nchan, nbin):
+    """Rows come in +/- pairs with unit weights: the mean profile and np.cov's average are exactly zero, every
+    product and sum is a small integer, and the matrix must equal NumPy's to the bit on either side (the dual for
+    nchan < nbin, the covariance otherwise) -- a wrong lane map of the MFMA's operands or result cannot."""
+    rng = np.random.default_rng(nchan * 10000 + nbin)
+    half = rng.integers(-8, 9, size=(nchan // 2, nbin)).astype(np.float64)
+    port = np.concatenate([half, -half])[rng.permutation(nchan)]
+    w = np.ones(nchan)
+    eng = _eng()
+    mean_prof, gram, fact = eng.pca_gram(port, w)
+    assert fact == nchan - 1.0 and not mean_prof.any()
+    want = (np.dot(port, port.T) if nchan < nbin else np.dot(port.T, port)) * (1.0 / fact)
+    assert gram.shape == want.shape
+    np.testing.assert_array_equal(gram, want)
+    np.testing.assert_array_equal(gram, gram.T)
+    again = eng.pca_gram(port, w)[1]
+    assert gram.tobytes() == again.tobytes()
+    # and np.cov itself, to rounding, with unequal weights and a mean to take out
+    w = rng.uniform(0.5, 2.0, nchan)
+    port = port + rng.integers(0, 5, size=nbin)
+    mean_prof, gram, fact = eng.pca_gram(port, w)
+    # (a sum of nchan rounded terms, in another order than NumPy's)
+    np.testing.assert_allclose(mean_prof, (port.T * w).T.sum(axis=0) / w.sum(), rtol=0,
+                               atol=nchan * 2.3e-16 * np.abs(port).max())
+    if nchan >= nbin:
+        cov = np.cov((port - mean_prof).T, aweights=w, ddof=1)
+        np.testing.assert_allclose(gram, cov, rtol=0, atol=1e-13 * np.abs(cov).max())
+    assert eng.pca_gram(port, w)[1].tobytes() == gram.tobytes()
+
+
+@pytest.mark.parametrize("name", ["64x256", "300x128"])
+def test_f32_and_device_tensor_input(name):
+    """An f32 portrait is widened on the device: the same bits as its f64 copy; a device tensor gives the host
+    array's bits; and the f32 model is the f64 model to f32 rounding of the data."""
+    import torch
+    g, port = _g(name), _port(name)
+    ok = g["weights"] > 0
+    x, snrs = port[ok], g["SNRs"][ok]
+    w = snrs / snrs.sum()
+    eng = _eng()
+    m64, g64, _ = eng.pca_gram(x, w)
+    x32 = x.astype(np.float32)
+    m32, g32, _ = eng.pca_gram(x32, w)
+    m32w, g32w, _ = eng.pca_gram(x32.astype(np.float64), w)
+    assert m32.tobytes() == m32w.tobytes() and g32.tobytes() == g32w.tobytes()
+    np.testing.assert_allclose(m32, m64, rtol=0, atol=2e-7 * np.abs(m64).max())
+    for arr in (x, x32):
+        md, gd, _ = eng.pca_gram(torch.as_tensor(arr, device="cuda"), w)
+        mh, gh, _ = eng.pca_gram(arr, w)
+        assert md.tobytes() == mh.tobytes() and gd.tobytes() == gh.tobytes()
+    snr_d = eng.channel_snrs(torch.as_tensor(x, device="cuda"))
+    assert snr_d.tobytes() == eng.channel_snrs(x).tobytes()
+    # the whole model from f32 data
+    dp64, dp32 = _portrait(name), _portrait(name, port.astype(np.float32))
+    assert dp32.portx.dtype == np.float32
+    kw = pc.CASES[name][5]
+    dp64.make_spline_model(smooth=False, quiet=True, **kw)
+    dp32.make_spline_model(smooth=False, quiet=True, **kw)
+    np.testing.assert_array_equal(dp32.ieig, dp64.ieig)
+    np.testing.assert_allclose(dp32.model, dp64.model, rtol=0, atol=1e-5 * np.abs(dp64.model).max())
+
+
+def _run(args, cwd, timeout=300):
+    """`python -m pulseportraiture_amd.ppspline_run args` in a session of its own, under a time limit."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    cmd = [sys.executable, "-m", "pulseportraiture_amd.ppspline_run"] + args
+    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True)
+    try:
+        out, err = p.communicate(timeout=timeout)
+    except subprocess.TimeoutExpired:
+        os.killpg(p.pid, signal.SIGTERM)
+        try:
+            p.communicate(timeout=30)
+        except subprocess.TimeoutExpired:
+            os.killpg(p.pid, signal.SIGKILL)
+            p.communicate()
+        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
+    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
+    return out
+
+
+def _write_archive(path, name, with_snrs=True):
+    g, port = _g(name), _port(name)
+    kw = dict(subints=port[None, None], freqs=g["freqs"][None], Ps=np.array([P0]), epochs=np.array([55000.0]),
+              weights=g["weights"][None], noise_stds=g["noise_stds"][None, None], bw=float(g["bw"]), source="fake")
+    if with_snrs:
+        kw["SNRs"] = g["SNRs"][None, None]
+    np.savez(path, **kw)
+
+
+@pytest.mark.parametrize("name", ["128x512", "48x1000", "64x256_nbreak3"])
+def test_command_line_writes_the_references_model(name, tmp_path):
+    """-N None, as the fixtures' portraits were not normalised, on an archive that carries the reference's SNRs: the
+    same bars.  Then an archive without SNRs (they are measured on the device), a metafile, -o, --quiet and the default
+    normalisation."""
+    from pulseportraiture_amd.splmodel import read_spline_model
+    g, kw = _g(name), pc.CASES[name][5]
+    _write_archive(tmp_path / "avg.npz", name)
+    argv = ["-d", "avg.npz", "-N", "None", "-l", "the model"]
+    for opt, key in (("-n", "max_ncomp"), ("-S", "snr_cutoff"), ("-k", "k"), ("-f", "sfac"), ("-t", "max_nbreak")):
+        if key in kw:
+            argv += [opt, repr(kw[key])]
+    out = _run(argv, tmp_path)
+    assert "Wrote modelfile avg.npz.spl." in out and "B-spline interpolation model the model uses %d basis" % len(g["ieig"]) in out
+    model_name, source, datafile, mean_prof, eigvec, tck = read_spline_model(str(tmp_path / "avg.npz.spl"), quiet=True)
+    assert (model_name, source, datafile) == ("the model", "fake", "avg.npz")
+    ie = g["ieig"]
+    assert eigvec.shape == (pc.CASES[name][1], len(ie))
+    sg = np.sign(np.sum(eigvec * g["eigvec"][:, ie], axis=0))
+    bad = []
+    for key, got, want, bar in (
+            ("mean_prof", mean_prof, g["mean_prof"], _bar(g, "mean_prof", np.abs(g["mean_prof"]).max())),
+            ("eigvec", eigvec * sg, g["eigvec"][:, ie], _bar(g, "eigvec", 1.0, ie)[None, :]),
+            ("coefficients", np.array(tck[1]) * sg[:, None], g["c"], _bar(g, "c", np.abs(g["c"]).max(axis=1))[:, None])):
+        dev = np.abs(got - want)
+        MEASURED.setdefault(name + " (command line)", {})[key] = dict(deviation=float(dev.max()), bar=float(np.min(bar)),
+                                                                      of_bar=float((dev / bar).max()))
+        print(name, "command line", key, "dev %.3e bar %.3e" % (dev.max(), np.min(bar)))
+        if not (dev <= bar).all():
+            bad.append(key)
+    np.testing.assert_array_equal(tck[0], g["t"])
+    assert tck[2] == int(g["k"]) and not bad, bad
+    # without SNRs in the archive: the device's get_SNR (1e-12 of the reference's) weights the same model
+    _write_archive(tmp_path / "bare.npz", name, with_snrs=False)
+    (tmp_path / "meta.txt").write_text("bare.npz\n")
+    assert _run(argv[2:] + ["-d", "meta.txt", "-o", "bare.spl", "--quiet"], tmp_path) == ""
+    bare = read_spline_model(str(tmp_path / "bare.spl"), quiet=True)
+    assert bare[:3] == ("the model", "fake", "bare.npz")
+    np.testing.assert_allclose(bare[3], mean_prof, rtol=0, atol=1e-10 * np.abs(mean_prof).max())
+    np.testing.assert_array_equal(bare[5][0], tck[0])
+    # the default normalisation ('prof') runs through
+    assert _run(["-d", "avg.npz", "-o", "other.spl", "--quiet", "-n", "2"], tmp_path) == ""
+    assert read_spline_model(str(tmp_path / "other.spl"), quiet=True)[4].shape[1] <= 2
+
+
+def test_toas_with_the_device_made_template_are_the_references():
+    """End to end: GetTOAs on 8 synthetic subints with the .spl made here against the same call with a .spl
+    pickled from the reference's outputs; |dphi| <= 1e-9 rot, the standing caller-level bar."""
+    import tempfile
+    from pulseportraiture_amd.gmodel import example_model
+    from pulseportraiture_amd.pplib import rotate_data
+    from pulseportraiture_amd.pptoas import GetTOAs, data_from_arrays
+    name = "64x256"
+    g = _g(name)
+    dp = _portrait(name)
+    dp.make_spline_model(smooth=False, quiet=True)
+    tmp = tempfile.mkdtemp(prefix="ppspline_e2e_")
+    mine, theirs = os.path.join(tmp, "mine.spl"), os.path.join(tmp, "reference.spl")
+    dp.write_model(mine, quiet=True)
+    ie = g["ieig"]
+    with open(theirs, "wb") as f:
+        pickle.dump([dp.model_name, dp.source, dp.datafile, g["mean_prof"], g["eigvec"][:, ie],
+                     [g["t"], list(g["c"]), int(g["k"])]], f, protocol=2)
+    freqs, clean, P = example_model(64, 256)
+    rng = np.random.default_rng(99)
+    nsub = 8
+    subints = np.empty((nsub, 1, 64, 256))
+    for i in range(nsub):
+        subints[i, 0] = rotate_data(clean, -rng.uniform(-0.3, 0.3), -rng.normal(0.0, 3e-4), P, freqs, np.inf) + \
+            0.05 * rng.standard_normal(clean.shape)
+    # (a third template, the reference's with its mean profile moved by one bin: the fit must see the file it is given)
+    moved = os.path.join(tmp, "moved.spl")
+    with open(moved, "wb") as f:
+        pickle.dump([dp.model_name, dp.source, dp.datafile, np.roll(g["mean_prof"], 1), g["eigvec"][:, ie],
+                     [g["t"], list(g["c"]), int(g["k"])]], f, protocol=2)
+    phis = []
+    for modelfile in (mine, theirs, moved):
+        data = data_from_arrays(subints, freqs, np.full(nsub, P), [55000.0 + i for i in range(nsub)], bw=800.0,
+                                filename="synthetic.npz")
+        gt = GetTOAs(data, modelfile, quiet=True)
+        gt.get_TOAs(quiet=True)
+        assert len(gt.ok_isubs[0]) == nsub
+        phis.append(np.array(gt.phis[0]))
+    dphi = np.abs((phis[0] - phis[1] + 0.5) % 1.0 - 0.5)
+    MEASURED["64x256 (TOAs)"] = dict(dphi=dict(deviation=float(dphi.max()), bar=1e-9, of_bar=float(dphi.max() / 1e-9)))
+    print("end to end: max |dphi| = %.3e rot" % dphi.max())
+    assert np.all(dphi <= 1e-9), dphi
+    assert np.all(np.abs((phis[2] - phis[1] + 0.5) % 1.0 - 0.5) > 1e-4)
