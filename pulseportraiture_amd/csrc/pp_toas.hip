@@ -110,14 +110,16 @@ struct pp_ctx {
     std::map<int, AnyPlan> anyplans;  // Bluestein tables of row lengths that are no power of two (pp_anybin.h)
     ModelSlot slots[PP_MAX_SLOTS];
     DevBuf mft_table, msum_table, kt_table, mdc_table, msq_table;   // device arrays of slot base pointers
-    // work buffers
-    DevBuf data, X, sdraw, noise, wts, freqs, errs, mask, P, x0, nufit, nuout, slot, state, csum, partial;
+    // work buffers of the context itself: what only the transform stage touches, and the aux entry points' scratch
+    DevBuf data, X, sdraw, noise, wts, freqs, errs, mask, P, x0, nufit, slot, csum, o_params, misc, seedbuf, seedq, xbase;
     std::map<const void*, int> occ_cache;   // resident workgroups per CU, by kernel
     DevBuf ticket;                          // k_xspec's chunk counter (RowWalk); never reset,
     unsigned ticket_base = 0;               // ... its value before the next launch (wraps)
+    void release_buffers() {
+        for (DevBuf* b : {&mft_table, &msum_table, &kt_table, &mdc_table, &msq_table, &data, &X, &sdraw, &noise, &wts, &freqs, &errs,
+                          &mask, &P, &x0, &nufit, &slot, &csum, &o_params, &misc, &seedbuf, &seedq, &xbase, &ticket}) b->release();
+    }
     int ncu = 0;                            // compute units of the device
-    DevBuf mwords;   // rows in use of a masked batch, one word per chunk (k_mask_words), both row orders
-    DevBuf refbuf;   // reference-seed flow: partial channel sums, spectra, profiles, start points
     // Device work buffers of a batch's SOLVE and POST-FIT stage, two sets: a deferred batch (pp_fit_enqueue) runs those
     // stages on a second stream (`stream2`) while the next batch's transform already runs on `stream` -- the next batch
     // writes the other set.  (inpack: the per-batch small inputs -- freqs, P, x0, nu_fit, nu_out, slot -- one H2D copy.)
@@ -150,7 +152,6 @@ struct pp_ctx {
                                      // retire.  And a wave slot given to the solve is one the transform does not have:
                                      // with registers as the binding resource the two do not co-reside, they alternate.
                                      // Kept as an option: the work-set / two-stream plumbing is what a fused tail would use.
-    DevBuf inpack;   // (aux entry points)
     // ppspline (pp_pca.h): what pp_pca_gram leaves resident for pp_pca_basis and pp_pca_project
     struct Pca {
         DevBuf w, vec, part, D, S, G, U, B, small, idx, proj;   // vec: mean profile, then np.cov's weighted row average
@@ -173,7 +174,6 @@ struct pp_ctx {
         int stage = 0;                   // staging block / work set of the batch it belongs to
         FitArgs fa;                      // arguments of its solve and post-fit stage
         int ns = 0, C = 0, solve_nt = 0, solve_pf0 = 0, fin_nt = 0;
-        size_t solve_lds = 0;
         pp_fit_out out; int s0 = 0; bool chan_dev = false; size_t copy_bytes = 0;
         RefTailArgs rs;                  // reference-seed flow: the guess's finish, fit and start points belong to the tail too
         cplx* rs_dspec = nullptr;        // ... by the stand-alone kernels (flush_tail): the spectrum's array and the fit's
@@ -187,9 +187,6 @@ struct pp_ctx {
     // pp_fit_enqueue / pp_fit_collect: batches queued on the stream and not yet collected (oldest first)
     struct Deferred { pp_fit_in in; pp_fit_out out; int stage; bool queued; int rc; std::string err; size_t span_end = 0; };
     std::deque<Deferred> pending;
-    DevBuf o_pack;   // per-subint scalar outputs, one allocation -> one D2H copy
-    DevBuf o_params, o_errs, o_nu, o_cov, o_chi2, o_rchi2, o_snr, o_nfev, o_rc, o_scales, o_serrs, o_csnr,
-        o_f0, o_g0, o_H0, misc, seedbuf, tay, ph0, act, seedq, xbase, mdl;
     int* nactive_h = nullptr;   // pinned
     // options
     double harm_eps = 8.8817841970012523e-16;  // 2^-50
@@ -297,6 +294,13 @@ static void resolve_spans(pp_ctx* c, size_t upto = (size_t)-1) {
     for (auto& q : c->pending) q.span_end = q.span_end > upto ? q.span_end - upto : 0;
 }
 
+// both streams idle, every span resolved
+static void drain_spans(pp_ctx* c) {
+    (void)hipStreamSynchronize(c->stream);
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+    resolve_spans(c);
+}
+
 // a submitted (pp_fit_submit) or enqueued (pp_fit_enqueue) batch owns the context's work buffers, stream
 // and counters until it has been waited for / collected: every other entry point that uses them refuses
 static int ctx_busy(pp_ctx* c, const char* who) {
@@ -369,9 +373,7 @@ extern "C" int pp_destroy(pp_ctx* c) {
     if (!c) return PP_OK;
     if (c->job_active) { c->job.join(); c->job_active = false; }
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    resolve_spans(c);
+    drain_spans(c);
     for (auto& w : c->work) w.release();
     for (auto& b : c->tailbuf) b.release();
     for (void*& h : c->tail_host) { if (h) (void)hipHostFree(h); h = nullptr; }
@@ -384,16 +386,8 @@ extern "C" int pp_destroy(pp_ctx* c) {
         if (sg.t0) (void)hipEventDestroy(sg.t0);
         if (sg.done) (void)hipEventDestroy(sg.done);
     }
-    c->inpack.release();
     c->pca.release();
-    c->refbuf.release();
-    c->mwords.release();
-    DevBuf* bufs[] = {&c->ticket, &c->o_pack, &c->mft_table, &c->msum_table, &c->kt_table, &c->mdc_table, &c->msq_table, &c->data, &c->X, &c->sdraw, &c->noise, &c->wts, &c->freqs,
-                      &c->errs, &c->mask, &c->P, &c->x0, &c->nufit, &c->nuout, &c->slot, &c->state, &c->csum,
-                      &c->partial, &c->o_params, &c->o_errs, &c->o_nu, &c->o_cov, &c->o_chi2, &c->o_rchi2,
-                      &c->o_snr, &c->o_nfev, &c->o_rc, &c->o_scales, &c->o_serrs, &c->o_csnr, &c->o_f0, &c->o_g0,
-                      &c->o_H0, &c->misc, &c->seedbuf, &c->tay, &c->ph0, &c->act, &c->seedq, &c->xbase};
-    for (DevBuf* b : bufs) b->release();
+    c->release_buffers();
     if (c->nactive_h) (void)hipHostFree(c->nactive_h);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     c->ev_pool.clear();
@@ -469,9 +463,7 @@ extern "C" int pp_get_option(pp_ctx* c, const char* name, double* value) {
 
 extern "C" int pp_kernel_times(pp_ctx* c, int cap, const char** names, double* seconds, int64_t* launches) {
     if (!c) return fail(PP_EINVAL, "null context");
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream2);
-    resolve_spans(c);
+    drain_spans(c);
     int n = std::min(cap, (int)KF_COUNT);
     for (int i = 0; i < n; ++i) {
         if (names) names[i] = kFamilyNames[i];
@@ -483,9 +475,7 @@ extern "C" int pp_kernel_times(pp_ctx* c, int cap, const char** names, double* s
 
 extern "C" int pp_kernel_times_reset(pp_ctx* c) {
     if (!c) return fail(PP_EINVAL, "null context");
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream2);
-    resolve_spans(c);
+    drain_spans(c);
     for (int i = 0; i < KF_COUNT; ++i) { c->fam_sec[i] = 0; c->fam_n[i] = 0; }
     return PP_OK;
 }
@@ -609,6 +599,21 @@ static int fft_grid(int T, long long nrows) {
     return (int)std::max(1LL, std::min(nrows, g));
 }
 
+// f(std::bool_constant<b>) / f(std::integral_constant<int, mode>): a run-time flag or mode (1..MAX, anything else
+// is 0) as the compile-time value a kernel's template parameter wants
+template <typename F>
+static void with_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int MAX, typename F>
+static void with_mode(int mode, F f) {
+    if constexpr (MAX > 0) {
+        if (mode == MAX) f(std::integral_constant<int, MAX>{});
+        else with_mode<MAX - 1>(mode, f);
+    } else f(std::integral_constant<int, 0>{});
+}
+
+template <typename F>
+static void with_dtype(int dtype, F f) { if (dtype == PP_F64) f(double{}); else f(float{}); }
+
 // one launch of the general-length transform (pp_anybin.h): mode -1 = harmonics to hout, 0..3 = k_xspec's modes
 static int launch_any(pp_ctx* c, const XspecArgs& xa, int nbin, int Mp, int dtype, int mode, bool tail, cplx* hout,
                       const unsigned char* mask) {
@@ -621,11 +626,8 @@ static int launch_any(pp_ctx* c, const XspecArgs& xa, int nbin, int Mp, int dtyp
     AnyArgs g{nbin, nbin / 2, Mp, pl->chirp.as<cplx>(), pl->bft.as<cplx>(), twL, twB, mode, tail ? 1 : 0, hout, mask};
     const long long nrows = (long long)xa.nsub * xa.nchan;
     const int grid = (int)std::max(1LL, std::min(nrows, 2048LL));
-#define PP_ANY(LL)                                                                                            \
-    do {                                                                                                      \
-        if (dtype == PP_F64) hipLaunchKernelGGL((k_any<LL, double>), dim3(grid), dim3(FftPlan<LL>::T), 0, c->stream, xa, g); \
-        else hipLaunchKernelGGL((k_any<LL, float>), dim3(grid), dim3(FftPlan<LL>::T), 0, c->stream, xa, g);   \
-    } while (0)
+#define PP_ANY(LL) \
+    with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL((k_any<LL, decltype(t)>), dim3(grid), dim3(FftPlan<LL>::T), 0, c->stream, xa, g); })
     switch (pl->L) {
         case 64: PP_ANY(64); break;
         case 256: PP_ANY(256); break;
@@ -732,8 +734,7 @@ extern "C" int pp_model_set(pp_ctx* c, int slot, const void* portrait, int dtype
         Prof pr(c, KF_MODEL);
         PP_DISPATCH_M(M, {
             const int T = FftPlan<MM>::T;
-            if (dtype == PP_F64) hipLaunchKernelGGL((k_model_fft<MM, double>), dim3(fft_grid(T, nchan)), dim3(T), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_model_fft<MM, float>), dim3(fft_grid(T, nchan)), dim3(T), 0, c->stream, a);
+            with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL((k_model_fft<MM, decltype(t)>), dim3(fft_grid(T, nchan)), dim3(T), 0, c->stream, a); });
         });
     }
     HIP_TRY(hipGetLastError());
@@ -824,27 +825,19 @@ static int resident_grid(pp_ctx* c, K kernel, int T, long long nrows, int fallba
     return (int)std::max(1LL, std::min(nrows, g));
 }
 
-// f(std::bool_constant<b>) / f(std::integral_constant<int, mode>): a run-time flag or mode (1..MAX, anything else
-// is 0) as the compile-time value a kernel's template parameter wants
-template <typename F>
-static void with_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-template <int MAX, typename F>
-static void with_mode(int mode, F f) {
-    if constexpr (MAX > 0) {
-        if (mode == MAX) f(std::integral_constant<int, MAX>{});
-        else with_mode<MAX - 1>(mode, f);
-    } else f(std::integral_constant<int, 0>{});
+// one ticket per chunk of rows is drawn by a launch of a transform that walks its rows by ticket (RowWalk)
+static void draw_tickets(pp_ctx* c, XspecArgs& x, long long nrows, bool advance = true) {
+    x.ticket = c->ticket.as<unsigned>();
+    x.ticket_base = c->ticket_base;
+    if (advance) c->ticket_base += (unsigned)((nrows + PP_ROW_CHUNK - 1) / PP_ROW_CHUNK);
 }
 
 template <int MM, typename TIN>
 static void launch_xspec(pp_ctx* c, const XspecArgs& xa_in, bool tail, int mode) {
     const int T = FftPlan<MM>::T;
     const long long nrows = (long long)xa_in.nsub * xa_in.nchan;
-    // one ticket per chunk of rows is drawn by the launch (RowWalk)
     XspecArgs xa = xa_in;
-    xa.ticket = c->ticket.as<unsigned>();
-    xa.ticket_base = c->ticket_base;
-    if (T == 64) c->ticket_base += (unsigned)((nrows + PP_ROW_CHUNK - 1) / PP_ROW_CHUNK);
+    draw_tickets(c, xa, nrows, T == 64);
     auto launch = [&](auto kernel) {
         const dim3 grid(resident_grid(c, kernel, T, nrows, fft_grid(T, nrows)));
         hipLaunchKernelGGL(kernel, grid, dim3(T), 0, c->stream, xa);
@@ -877,37 +870,65 @@ static void launch_xspec(pp_ctx* c, const XspecArgs& xa_in, bool tail, int mode)
     with_flag(tail, [&](auto TL) { with_mode<3>(mode, [&](auto MD) { launch(k_xspec<MM, TIN, decltype(TL)::value, decltype(MD)::value>); }); });
 }
 
-// the packed per-subint outputs of a batch, from its host staging block to the caller's arrays
+// The packed per-subint outputs of a batch, one allocation -> one D2H copy: blocks of params 5, errs 5, nu 3, cov 25,
+// chi2, red_chi2, snr doubles; nfeval, return_code, npass ints = 340 B / subint, then the count of unfinished subints
+// (as k_finalize saw it), padded to whole 8-byte words (staged_copy).  The reference-seed flow's phase guesses ride in
+// the same pinned block, behind the pack (a copy straight into the caller's pageable array would make the enqueueing
+// call wait for the whole batch).  The one description serves the device block and its host staging copy.
+struct OutBlock {
+    double *params, *errs, *nu, *cov, *chi2, *rchi2, *snr, *seed_phase;
+    int32_t *nfev, *rc, *npass, *unfinished;
+    static size_t bytes(size_t ns) { return (ns * 340 + 8 + 7) & ~(size_t)7; }      // (+ the count of unfinished subints; whole words)
+    static size_t staged_bytes(size_t ns) { return bytes(ns) + ns * 8; }            // (+ the reference-seed flow's phase guesses)
+    OutBlock(const void* base, size_t ns) {
+        double* d = params = reinterpret_cast<double*>(const_cast<void*>(base));
+        errs = d + ns * 5; nu = d + ns * 10; cov = d + ns * 13; chi2 = d + ns * 38; rchi2 = d + ns * 39; snr = d + ns * 40;
+        nfev = reinterpret_cast<int32_t*>(d + ns * 41); rc = nfev + ns; npass = rc + ns; unfinished = npass + ns;
+        seed_phase = reinterpret_cast<double*>(reinterpret_cast<char*>(d) + bytes(ns));
+    }
+};
+// ... from the host staging block to the caller's arrays
 static void unpack_stage(const void* o_host, pp_fit_out* out, int s0, int ns) {
-    const double* h = reinterpret_cast<const double*>(o_host);
-    memcpy(out->params + (size_t)s0 * 5, h, (size_t)ns * 40);
-    memcpy(out->param_errs + (size_t)s0 * 5, h + (size_t)ns * 5, (size_t)ns * 40);
-    memcpy(out->nu_refs + (size_t)s0 * 3, h + (size_t)ns * 10, (size_t)ns * 24);
-    memcpy(out->cov + (size_t)s0 * 25, h + (size_t)ns * 13, (size_t)ns * 200);
-    memcpy(out->chi2 + s0, h + (size_t)ns * 38, (size_t)ns * 8);
-    memcpy(out->red_chi2 + s0, h + (size_t)ns * 39, (size_t)ns * 8);
-    memcpy(out->snr + s0, h + (size_t)ns * 40, (size_t)ns * 8);
-    const int32_t* hi = reinterpret_cast<const int32_t*>(h + (size_t)ns * 41);
-    memcpy(out->nfeval + s0, hi, (size_t)ns * 4);
-    memcpy(out->return_code + s0, hi + ns, (size_t)ns * 4);
-    if (out->npass) memcpy(out->npass + s0, hi + 2 * (size_t)ns, (size_t)ns * 4);
+    const OutBlock h(o_host, ns);
+    const struct { void* dst; const void* src; size_t bytes; } part[] = {      // (bytes per subint)
+        {out->params, h.params, 40}, {out->param_errs, h.errs, 40}, {out->nu_refs, h.nu, 24}, {out->cov, h.cov, 200}, {out->chi2, h.chi2, 8},
+        {out->red_chi2, h.rchi2, 8}, {out->snr, h.snr, 8}, {out->nfeval, h.nfev, 4}, {out->return_code, h.rc, 4}, {out->npass, h.npass, 4}};
+    for (const auto& q : part) if (q.dst) memcpy((char*)q.dst + (size_t)s0 * q.bytes, q.src, (size_t)ns * q.bytes);      // (npass: optional)
 }
-// the reference-seed flow's phase guesses ride in the same pinned block, behind the packed outputs (a copy
-// straight into the caller's pageable array would make the enqueueing call wait for the whole batch)
-static size_t stage_seed_offset(int ns) { return (((size_t)ns * 340 + 8) + 7) & ~(size_t)7; }
 static void unpack_seed_phases(const void* o_host, const pp_fit_in* in, int s0, int ns) {
     if (in->ref_seed && in->ref_seed->seed_phase)
-        memcpy(in->ref_seed->seed_phase + s0, reinterpret_cast<const char*>(o_host) + stage_seed_offset(ns), (size_t)ns * 8);
+        memcpy(in->ref_seed->seed_phase + s0, OutBlock(o_host, ns).seed_phase, (size_t)ns * 8);
 }
 // subints the post-fit stage found unfinished (as k_finalize saw it)
-static int unfinished_in_stage(const void* o_host, int ns) {
-    return reinterpret_cast<const int32_t*>(reinterpret_cast<const double*>(o_host) + (size_t)ns * 41)[3 * (size_t)ns];
-}
+static int unfinished_in_stage(const void* o_host, int ns) { return *OutBlock(o_host, ns).unfinished; }
+
+// The small inputs of a batch travel in ONE copy from a pinned staging block (seven separate pageable copies cost more
+// than the solve of a 512 x 1024 batch): freqs | P | x0 | nu_fit | nu_out | [refseed: the model profile(s), nu_mean and
+// the start points' host-formed part] | slot.  The one description gives the byte count and the pointers into the
+// device block and into its host staging copy.
+struct InBlock { double *freqs, *P, *x0, *nufit, *nuout, *rs_mprof, *rs_numean, *rs_xs; int* slot; };
+struct InLayout {
+    size_t ns, B, nfreq, rs_nprof, rs_on;
+    InLayout(const pp_fit_in* in, int ns_)
+        : ns(ns_), B(in->nbin), nfreq(in->freqs_stride ? (size_t)ns_ * in->nchan : (size_t)in->nchan),
+          rs_nprof(in->ref_seed ? (in->ref_seed->model_prof_stride ? (size_t)ns_ : 1) : 0), rs_on(in->ref_seed ? 1 : 0) {}
+    size_t bytes() const {      // (doubles, then one int per subint; whole 8-byte words: staged_copy)
+        return ((nfreq + ns * (1 + 5 + 3 + 3) + rs_nprof * B + rs_on * ns * (1 + 5)) * 8 + ns * 4 + 7) & ~(size_t)7;
+    }
+    InBlock at(void* base) const {
+        InBlock b;
+        b.freqs = reinterpret_cast<double*>(base);
+        b.P = b.freqs + nfreq; b.x0 = b.P + ns; b.nufit = b.x0 + ns * 5; b.nuout = b.nufit + ns * 3;
+        b.rs_mprof = b.nuout + ns * 3; b.rs_numean = b.rs_mprof + rs_nprof * B; b.rs_xs = b.rs_numean + rs_on * ns;
+        b.slot = reinterpret_cast<int*>(b.rs_xs + rs_on * ns * 5);
+        return b;
+    }
+};
 
 // the solve on the Taylor model: NT threads per subint by band width (or option solve_threads), rows fetched in turn
 // for bands wider than 2048 channels.  `fa.solve_cache` may be lowered (dynamic LDS refused by the runtime).
-static int solve_threads_for(pp_ctx* c, int C) { return c->solve_threads > 0 ? c->solve_threads : (C <= 512 ? 64 : C <= 1024 ? 128 : 256); }
-static bool solve_rows_in_turn(pp_ctx* c, int C, int solve_nt) { return solve_nt == 256 && C > 2048 && c->solve_prefetch <= 0; }
+static int solve_threads_for(const pp_ctx* c, int C) { return c->solve_threads > 0 ? c->solve_threads : (C <= 512 ? 64 : C <= 1024 ? 128 : 256); }
+static bool solve_rows_in_turn(const pp_ctx* c, int C, int solve_nt) { return solve_nt == 256 && C > 2048 && c->solve_prefetch <= 0; }
 static void solve_launch(pp_ctx* c, FitArgs& fa, int ns, int C, int solve_nt, hipStream_t sp) {
     size_t lds = (size_t)fa.solve_cache * 32;
     if (lds > 48 * 1024 && !c->solve_lds_attr) {     // (dynamic LDS beyond the default cap: said once)
@@ -927,49 +948,43 @@ static void solve_launch(pp_ctx* c, FitArgs& fa, int ns, int C, int solve_nt, hi
     }
     if (lds > 48 * 1024 && c->solve_cache == 0) { fa.solve_cache = 0; lds = 0; }
     const bool in_turn = solve_rows_in_turn(c, C, solve_nt);
-    if (c->tail_virtual && solve_nt > 64) {
-        // (experiments: ONE real wave per subint walks the waves of the kernel below in turn -- same bits)
-        if (solve_nt == 128) hipLaunchKernelGGL(k_taylor_solve_v<128>, dim3(ns), dim3(64), lds, sp, fa);
-        else if (solve_nt == 512) hipLaunchKernelGGL(k_taylor_solve_v<512>, dim3(ns), dim3(64), lds, sp, fa);
-        else if (in_turn) hipLaunchKernelGGL((k_taylor_solve_v<256, 0>), dim3(ns), dim3(64), lds, sp, fa);
-        else hipLaunchKernelGGL(k_taylor_solve_v<256>, dim3(ns), dim3(64), lds, sp, fa);
-        return;
-    }
-    if (solve_nt == 64) hipLaunchKernelGGL(k_taylor_solve<64>, dim3(ns), dim3(64), lds, sp, fa);
-    else if (solve_nt == 128) hipLaunchKernelGGL(k_taylor_solve<128>, dim3(ns), dim3(128), lds, sp, fa);
-    else if (solve_nt == 512) hipLaunchKernelGGL(k_taylor_solve<512>, dim3(ns), dim3(512), lds, sp, fa);
-    else if (in_turn) hipLaunchKernelGGL((k_taylor_solve<256, 0>), dim3(ns), dim3(256), lds, sp, fa);
-    else hipLaunchKernelGGL(k_taylor_solve<256>, dim3(ns), dim3(256), lds, sp, fa);
+    // (experiments, option tail_virtual: ONE real wave per subint walks the waves of the kernel in turn -- same bits)
+    const bool virt = c->tail_virtual && solve_nt > 64;
+    void (*kernel)(FitArgs);
+    if (solve_nt == 64) kernel = k_taylor_solve<64>;
+    else if (solve_nt == 128) kernel = virt ? k_taylor_solve_v<128> : k_taylor_solve<128>;
+    else if (solve_nt == 512) kernel = virt ? k_taylor_solve_v<512> : k_taylor_solve<512>;
+    else if (in_turn) kernel = virt ? k_taylor_solve_v<256, 0> : k_taylor_solve<256, 0>;
+    else kernel = virt ? k_taylor_solve_v<256> : k_taylor_solve<256>;
+    const int threads = virt ? 64 : (solve_nt == 64 || solve_nt == 128 || solve_nt == 512) ? solve_nt : 256;
+    hipLaunchKernelGGL(kernel, dim3(ns), dim3(threads), lds, sp, fa);
 }
 // the post-fit stage: phase / DM / GM fits of up to 4096 channels hold a channel's numbers in registers over the
 // passes, as few waves per subint as hold the band at 8 channels per thread; everything else pass by pass.
-// Returns the width taken (64 ... 512; 0 = the pass-by-pass kernel of 256 threads).
-static int finalize_threads_for(pp_ctx* c, const FitArgs& ff, int C) {
+static int finalize_threads_for(const pp_ctx* c, const FitArgs& ff, int C) {
     return (ff.ncs != 3 || C > 4096 || !c->finalize_regs) ? 0
            : c->finalize_regs > 1 ? c->finalize_regs : C <= 512 ? 64 : C <= 1024 ? 128 : C <= 2048 ? 256 : 512;
 }
-static void finalize_launch(pp_ctx* c, const FitArgs& ff, int ns, int C, hipStream_t sp) {
+// The width taken (64 ... 512; 0 = the pass-by-pass kernel of 256 threads): the one table of the stand-alone launch
+// below and of the body tail_work runs for the post-fit stage.
+static int finalize_width_taken(const pp_ctx* c, const FitArgs& ff, int C) {
     const int fnt = finalize_threads_for(c, ff, C);
-    if (c->tail_virtual && fnt > 64 && C <= 8 * fnt) {
-        // (experiments: ONE real wave per subint walks the waves of the kernel below in turn -- same bits)
-        if (fnt == 128) hipLaunchKernelGGL((k_finalize_v<128>), dim3(ns), dim3(64), 0, sp, ff);
-        else if (fnt == 256) hipLaunchKernelGGL((k_finalize_v<256>), dim3(ns), dim3(64), 0, sp, ff);
-        else hipLaunchKernelGGL((k_finalize_v<512>), dim3(ns), dim3(64), 0, sp, ff);
-    } else
-    if (fnt == 64 && C <= 512) hipLaunchKernelGGL((k_finalize<8, 64>), dim3(ns), dim3(64), 0, sp, ff);
-    else if (fnt == 128 && C <= 1024) hipLaunchKernelGGL((k_finalize<8, 128>), dim3(ns), dim3(128), 0, sp, ff);
-    else if (fnt == 256 && C <= 2048) hipLaunchKernelGGL((k_finalize<8, 256>), dim3(ns), dim3(256), 0, sp, ff);
-    else if (fnt == 512) hipLaunchKernelGGL((k_finalize<8, 512>), dim3(ns), dim3(512), 0, sp, ff);
-    else hipLaunchKernelGGL((k_finalize<0, 256>), dim3(ns), dim3(256), 0, sp, ff);
+    return (fnt == 64 && C <= 512) ? 64 : (fnt == 128 && C <= 1024) ? 128 : (fnt == 256 && C <= 2048) ? 256 : fnt == 512 ? 512 : 0;
 }
-// which body tail_work runs for the post-fit stage: the width the stand-alone launch above takes
-static int finalize_width_taken(pp_ctx* c, const FitArgs& ff, int C) {
-    const int fnt = finalize_threads_for(c, ff, C);
-    if (fnt == 64 && C <= 512) return 64;
-    if (fnt == 128 && C <= 1024) return 128;
-    if (fnt == 256 && C <= 2048) return 256;
-    if (fnt == 512) return 512;
-    return 0;
+static void finalize_launch(pp_ctx* c, const FitArgs& ff, int ns, int C, hipStream_t sp) {
+    const int fnt = finalize_threads_for(c, ff, C), w = finalize_width_taken(c, ff, C);
+    // (experiments, option tail_virtual: ONE real wave per subint walks the waves of the kernel in turn -- same bits)
+    const bool virt = c->tail_virtual && fnt > 64 && C <= 8 * fnt;
+    void (*kernel)(FitArgs);
+    if (virt && fnt == 128) kernel = k_finalize_v<128>;
+    else if (virt && fnt == 256) kernel = k_finalize_v<256>;
+    else if (virt) kernel = k_finalize_v<512>;
+    else if (w == 64) kernel = k_finalize<8, 64>;
+    else if (w == 128) kernel = k_finalize<8, 128>;
+    else if (w == 256) kernel = k_finalize<8, 256>;
+    else if (w == 512) kernel = k_finalize<8, 512>;
+    else kernel = k_finalize<0, 256>;
+    hipLaunchKernelGGL(kernel, dim3(ns), dim3(virt ? 64 : w ? w : 256), 0, sp, ff);
 }
 // what follows the post-fit stage of a batch: its packed outputs on their way to the staging block (and the
 // per-channel / objective arrays to the caller's host arrays, when asked for)
@@ -993,23 +1008,32 @@ static int queue_outputs(pp_ctx* c, int stage, const pp_fit_out* out, int s0, in
 #undef PP_D2H
     return PP_OK;
 }
+// the reference's guess from the pass's chunk partials, on stream `st`: k_refseed_finish -> k_fps -> k_refseed_start
+// (`span_to_end`: the profiling span of the flushed tail covers the start points too, the pass's own ends at the fit)
+static int queue_refseed_finish(pp_ctx* c, const RefTailArgs& r, int ns, cplx* dspec, cplx* xwork, hipStream_t st, bool span_to_end) {
+    constexpr int M = 1024;
+    const size_t H = (size_t)M + 1;
+    FpsArgs f = r.fps;
+    f.spec = dspec; f.specm = r.mspec; f.mstride = r.mstride;
+    auto start = [&]() {
+        hipLaunchKernelGGL(k_refseed_start, dim3((ns + 63) / 64), dim3(64), 0, st, (const double*)r.fps.out7, ns, r.xs, r.seed_phase);
+    };
+    {
+        Prof pr(c, KF_FPS, st);
+        hipLaunchKernelGGL(k_refseed_finish, dim3((unsigned)((H + 255) / 256), ns), dim3(256), 0, st, r.part, r.ncc, r.delta, r.wsum,
+                           ns, dspec, r.mws);
+        hipLaunchKernelGGL(k_fps, dim3(ns), dim3(256), 0, st, f, xwork);
+        if (span_to_end) start();
+    }
+    HIP_TRY(hipGetLastError());
+    if (!span_to_end) { start(); HIP_TRY(hipGetLastError()); }
+    return PP_OK;
+}
 // the pending tail by the stand-alone kernels (nobody carried it): solve, post-fit stage, outputs, the batch's event
 static int flush_tail_queue(pp_ctx* c, pp_ctx::PendingTail& t) {
     int rc;
-    if (t.rs.on) {
-        // the reference's guess from the pass's chunk partials: k_refseed_finish -> k_fps -> k_refseed_start
-        constexpr int M = 1024;
-        const size_t H = (size_t)M + 1;
-        Prof pr(c, KF_FPS);
-        hipLaunchKernelGGL(k_refseed_finish, dim3((unsigned)((H + 255) / 256), t.ns), dim3(256), 0, c->stream,
-                           t.rs.part, t.rs.ncc, t.rs.delta, t.rs.wsum, t.ns, t.rs_dspec, t.rs.mws);
-        FpsArgs f = t.rs.fps;
-        f.spec = t.rs_dspec; f.specm = t.rs.mspec; f.mstride = t.rs.mstride;
-        hipLaunchKernelGGL(k_fps, dim3(t.ns), dim3(256), 0, c->stream, f, t.rs_xwork);
-        hipLaunchKernelGGL(k_refseed_start, dim3((t.ns + 63) / 64), dim3(64), 0, c->stream, (const double*)t.rs.fps.out7, t.ns,
-                           t.rs.xs, t.rs.seed_phase);
-        HIP_TRY(hipGetLastError());
-    }
+    HIP_TRY(hipSetDevice(c->device));      // (pp_synchronize comes here without having set it)
+    if (t.rs.on) if ((rc = queue_refseed_finish(c, t.rs, t.ns, t.rs_dspec, t.rs_xwork, c->stream, true))) return rc;
     {
         Prof pr(c, KF_TAYLOR);
         solve_launch(c, t.fa, t.ns, t.C, t.solve_nt, c->stream);
@@ -1026,7 +1050,10 @@ static int flush_tail_queue(pp_ctx* c, pp_ctx::PendingTail& t) {
 }
 // (a tail that could not be queued: the batch it belongs to must not be collected as if it had run -- its `done`
 // event would be a stale one and its staging block another batch's numbers)
-static void fail_pending_stage(pp_ctx* c, int stage, int rc);
+static void fail_pending_stage(pp_ctx* c, int stage, int rc) {
+    for (auto& d : c->pending)
+        if (d.queued && d.stage == stage) { d.queued = false; d.rc = rc; d.err = g_err; }
+}
 static int flush_tail(pp_ctx* c) {
     pp_ctx::PendingTail& t = c->ptail;
     if (!t.valid) return PP_OK;
@@ -1036,122 +1063,41 @@ static int flush_tail(pp_ctx* c) {
     return rc;
 }
 
-static void fail_pending_stage(pp_ctx* c, int stage, int rc) {
-    for (auto& d : c->pending)
-        if (d.queued && d.stage == stage) { d.queued = false; d.rc = rc; d.err = g_err; }
+// Channel chunks of the kernels that sum over channels (evaluators, seed, moments).  The run length is a
+// function of the BAND alone -- never of how many subints share the launch -- so that the partial sums of a
+// subint are formed and added in one order whatever else is in the batch: a subint's answer is a function of
+// that subint alone, as in the reference's loop (pptoas.py:344-489).  (Until round 4 the number of chunks
+// grew as the batch shrank, to fill the chip with a single subint: the rounding of f then depended on the
+// batch, and through SciPy's 1-ulp exit tests so did ~1e-9 rot of some answers.)
+static void chunking(int nch, int& nchunk_, int& cpc_) {
+    cpc_ = nch >= PP_CHUNK_CHANNELS ? PP_CHUNK_CHANNELS : ((nch + 15) / 16) * 16;
+    nchunk_ = (nch + cpc_ - 1) / cpc_;
 }
 
-// `deferred` (pp_fit_enqueue): when non-null and the batch takes the one-pass flow without a host
-// decision in its middle, everything is queued -- outputs on their way to the staging block included --
-// and the call returns WITHOUT waiting (*deferred = true); pp_fit_collect finishes it.
-static int fit_chunk(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, int s0, int ns, int Kt, bool scat,
-                     const std::vector<double>& nufit_h, const std::vector<double>& nuout_h, bool* deferred = nullptr) {
-    pp_ctx::Stage& sg = c->stage[c->cur_stage];
-    pp_ctx::WorkSet& W = c->work[c->cur_stage];
-    const pp_seed_ref* rs = in->ref_seed;        // (applicability was checked by the caller)
-    const bool refseed = (rs != nullptr);
-    const int seed_ns = refseed ? rs->Ns : in->seed_ns;
+// The flow plan: every decision of a batch's flow, made once from the context's options and the batch's description
+// (plan_flow touches no device state).  fit_chunk's stages read it; plan_batch asks it whether a ref_seed batch has a path.
+constexpr int kCoarseStep = 16;
+struct FlowPlan {
+    bool refseed, anyb, noise_tail, taylor, seeded, pilot, seed_full, coarse, fuse_scat, fuse, xmom, xstore, defer_ok, post_stream2,
+        smodel, xf32, want_ph0, can_carry, leaves_tail;
+    int seed_ns, M, cstep, xmode, ncs, nchunk, cpc, solve_nt, ndm, Ks, check_from;
+    size_t Xs;
+};
+static FlowPlan plan_flow(const pp_ctx* c, const pp_fit_in* in, int s0, int Kt, bool scat, bool deferred) {
+    FlowPlan p;
+    const pp_seed_ref* rs = in->ref_seed;        // (applicability is checked by plan_batch)
     const int C = in->nchan, B = in->nbin;
+    p.refseed = (rs != nullptr);
+    p.seed_ns = p.refseed ? rs->Ns : in->seed_ns;
     // row lengths without a tuned plan (pp_anybin.h): the slot's spectrum rows are pitched to Mp
-    const bool anyb = !nbin_ok(B);
-    const int Mp_any = c->slots[in->model_slot ? in->model_slot[s0] : 0].Mp;
-    const int M = anyb ? Mp_any : B / 2;
-    const size_t esz = in->data_dtype == PP_F64 ? 8 : 4;
-    int rc;
-    const cplx* tw = nullptr;
-    if ((rc = get_twiddles(c, B, &tw))) return rc;
-    // ---- inputs ----
-    const void* ddata;
-    const size_t sub_elems = (size_t)C * B;
-    if (in->data_on_device) {
-        ddata = (const char*)in->data + (size_t)s0 * sub_elems * esz;
-    } else {
-        if ((rc = upload(c, c->data, (const char*)in->data + (size_t)s0 * sub_elems * esz, (size_t)ns * sub_elems * esz))) return rc;
-        ddata = c->data.p;
-    }
-    const size_t nc = (size_t)ns * C;
-    // the small inputs travel in ONE copy from a pinned staging block (seven separate pageable
-    // copies cost more than the solve of a 512 x 1024 batch): freqs | P | x0 | nu_fit | nu_out | slot
-    const size_t nfreq = in->freqs_stride ? nc : (size_t)C;
-    // (reference-seed flow: + the model profile(s), nu_mean and the start points' host-formed part)
-    const size_t rs_nprof = refseed ? (rs->model_prof_stride ? (size_t)ns : 1) : 0;
-    const size_t rs_doubles = refseed ? rs_nprof * B + (size_t)ns * (1 + 5) : 0;
-    const size_t in_doubles = nfreq + (size_t)ns * (1 + 5 + 3 + 3) + rs_doubles;
-    const size_t in_bytes = (in_doubles * 8 + (size_t)ns * 4 + 7) & ~(size_t)7;      // (whole 8-byte words: staged_copy)
-    if ((rc = W.inpack.reserve(in_bytes))) return rc;
-    if (sg.in_cap < in_bytes) {
-        if (sg.in_host) (void)hipHostFree(sg.in_host);
-        sg.in_host = nullptr; sg.in_cap = 0;
-        HIP_TRY(hipHostMalloc(&sg.in_host, in_bytes, hipHostMallocDefault));
-        sg.in_cap = in_bytes;
-    }
-    double* const d_freqs = W.inpack.as<double>();
-    double* const d_P = d_freqs + nfreq;
-    double* const d_x0 = d_P + ns;
-    double* const d_nufit = d_x0 + (size_t)ns * 5;
-    double* const d_nuout = d_nufit + (size_t)ns * 3;
-    double* const d_rs_mprof = d_nuout + (size_t)ns * 3;
-    double* const d_rs_numean = d_rs_mprof + rs_nprof * B;
-    double* const d_rs_xs = d_rs_numean + (refseed ? ns : 0);
-    int* const d_slot = reinterpret_cast<int*>(d_nuout + (size_t)ns * 3 + rs_doubles);
-    {
-        double* h = reinterpret_cast<double*>(sg.in_host);
-        memcpy(h, in->freqs + (in->freqs_stride ? (size_t)s0 * C : 0), nfreq * 8); h += nfreq;
-        memcpy(h, in->P + s0, (size_t)ns * 8); h += ns;
-        memcpy(h, in->init_params + (size_t)s0 * 5, (size_t)ns * 40);
-        // (reference seed of a scattering fit: the pass rotates by the DM guess alone -- phase 0 --
-        // and the phases the reference's guess gives are written before the state is set)
-        if (refseed && scat) for (int i = 0; i < ns; ++i) h[(size_t)i * 5] = 0.0;
-        h += (size_t)ns * 5;
-        memcpy(h, nufit_h.data() + (size_t)s0 * 3, (size_t)ns * 24); h += (size_t)ns * 3;
-        memcpy(h, nuout_h.data() + (size_t)s0 * 3, (size_t)ns * 24); h += (size_t)ns * 3;
-        if (refseed) {
-            memcpy(h, rs->model_profs + (rs->model_prof_stride ? (size_t)s0 * B : 0), rs_nprof * B * 8); h += rs_nprof * B;
-            memcpy(h, rs->nu_mean + s0, (size_t)ns * 8); h += ns;
-            // phase_transform(phi, DM, nu_mean, nu_fit, P, mod=True) (pplib.py:2592-2616): the term it adds
-            // depends on the inputs alone -- formed here in NumPy's order of operations with libm's pow, as the
-            // reference forms it -- so the device only adds it to its fit_phase_shift result and wraps: no
-            // host round trip between the pass and the iteration.  The other parameters start as given.
-            for (int i = 0; i < ns; ++i) {
-                const double* x0i = in->init_params + (size_t)(s0 + i) * 5;
-                const double P = in->P[s0 + i], nu1 = rs->nu_mean[s0 + i], nu2 = nufit_h[(size_t)(s0 + i) * 3];
-                h[(size_t)i * 5] = PP_DCONST * x0i[1] * pow(P, -1.0) * (pow(nu2, -2.0) - pow(nu1, -2.0));
-                for (int j = 1; j < 5; ++j) h[(size_t)i * 5 + j] = x0i[j];
-            }
-            h += (size_t)ns * 5;
-        }
-        if (in->model_slot) memcpy(h, in->model_slot + s0, (size_t)ns * 4);
-        if ((rc = staged_copy(c, W.inpack.p, sg.in_host, in_bytes, hipMemcpyHostToDevice))) return fail(rc, "input block copy failed");
-    }
-    const double* d_errs = nullptr;
-    const unsigned char* d_mask = nullptr;
-    if (in->aux_on_device) {
-        if (in->errs) d_errs = in->errs + (size_t)s0 * C;
-        if (in->chan_mask) d_mask = in->chan_mask + (size_t)s0 * C;
-    } else {
-        if (in->errs) { if ((rc = upload(c, c->errs, in->errs + (size_t)s0 * C, nc * 8))) return rc; d_errs = c->errs.as<double>(); }
-        if (in->chan_mask) { if ((rc = upload(c, c->mask, in->chan_mask + (size_t)s0 * C, nc))) return rc; d_mask = c->mask.as<unsigned char>(); }
-    }
-    // rows in use: channels the mask removes from a subint are not transformed at all (RowWalk)
-    const unsigned* mw_main = nullptr;
-    const unsigned* mw_sub = nullptr;
-    if (d_mask && c->skip_masked) {
-        const size_t nw_main = (nc + 31) / 32 + 1, nw_sub = (C % 32 == 0) ? nc / 32 : 0;
-        if ((rc = W.mwords.reserve((nw_main + nw_sub) * sizeof(unsigned)))) return rc;
-        HIP_TRY(hipMemsetAsync(W.mwords.p, 0, (nw_main + nw_sub) * sizeof(unsigned), c->stream));
-        unsigned* wm = W.mwords.as<unsigned>();
-        unsigned* ws = nw_sub ? wm + nw_main : nullptr;
-        hipLaunchKernelGGL(k_mask_words, dim3((unsigned)((C + 255) / 256), (unsigned)((ns + 31) / 32)), dim3(256), 0, c->stream,
-                           d_mask, ns, C, wm, ws);
-        HIP_TRY(hipGetLastError());
-        mw_main = wm; mw_sub = ws;
-    }
-    // ---- work ----
+    p.anyb = !nbin_ok(B);
+    const int M = p.M = p.anyb ? c->slots[in->model_slot ? in->model_slot[s0] : 0].Mp : B / 2;
+    p.noise_tail = (in->errs == nullptr);
     // no scattering: one pass over the data that leaves a Taylor model of every
-    // channel + a solve on it replace the evaluation loop (fallback: the loop below,
+    // channel + a solve on it replace the evaluation loop (fallback: the loop,
     // on the subints that need it); otherwise evaluate as usual
-    const bool taylor = !scat && c->max_iter > 0 && c->use_taylor;
-    const bool seeded = seed_ns > 0;
+    p.taylor = !scat && c->max_iter > 0 && c->use_taylor;
+    p.seeded = p.seed_ns > 0;
     // Phase seed.  The Taylor flow wants the phase BEFORE its single pass, so the seed
     // comes from a pilot pass over every cstep-th channel (1/cstep of the rows and of
     // the bytes), certified by the significance of its correlation peak; subints whose
@@ -1160,632 +1106,658 @@ static int fit_chunk(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, int s0, in
     // (reference-seed flow: the pilot only supplies the expansion point of the Taylor model, which the
     // certificate guards -- wide bands take every 64th channel, a quarter of the pilot's rows)
     const int rstride = c->refseed_stride > 0 ? c->refseed_stride : 64;
-    const int cstep = (refseed && C / rstride >= 32) ? std::max(rstride, c->seed_chan_stride) : std::max(1, c->seed_chan_stride);
-    const bool pilot = seeded && taylor && c->moments_in_xspec && cstep > 1 && C / cstep >= 16;
-    const bool seed_full = seeded && !pilot;
-    // scattering fits of 2048-bin rows (template cut 2 Kt < M): the transform built on the
-    // one-exchange FFT stores the cross-spectrum and takes the first evaluation's nine sums
-    // while X is in registers (k_xspec_qs1024) -- one pass over the stored cross-spectrum fewer
+    // (seed_chan_stride = 1 asks for no pilot at all: a ref_seed batch without scattering then has no single-pass path)
+    p.cstep = (p.refseed && C / rstride >= 32 && c->seed_chan_stride > 1) ? std::max(rstride, c->seed_chan_stride)
+                                                                          : std::max(1, c->seed_chan_stride);
+    p.pilot = p.seeded && p.taylor && c->moments_in_xspec && p.cstep > 1 && C / p.cstep >= 16;
+    p.seed_full = p.seeded && !p.pilot;
     // Newton solver on a scattering fit: the answer does not depend on the path, so the iteration is first
     // run on every 16th channel -- a sixteenth of every evaluation pass over the stored cross-spectrum --
     // and the full-channel iteration starts from there: two or three full passes instead of five or six
-    constexpr int kCoarseStep = 16;
-    const bool coarse = scat && in->method == PP_METHOD_NEWTON && !seeded && !refseed && c->max_iter > 0 &&
-                        c->coarse_newton && C / kCoarseStep >= 32 && !(c->x_f32 > 0);
-    const bool fuse_scat = scat && !seeded && !coarse && c->max_iter > 0 && c->one_exchange && c->fuse_scat && !anyb && B == 2048 &&
-                           2 * Kt < M && !(c->x_f32 > 0) && in->errs != nullptr;
-    const bool fuse = (!scat && !taylor && !seeded) || fuse_scat;   // first evaluation folded into the transform
+    p.coarse = scat && in->method == PP_METHOD_NEWTON && !p.seeded && !p.refseed && c->max_iter > 0 &&
+               c->coarse_newton && C / kCoarseStep >= 32 && !(c->x_f32 > 0);
+    // scattering fits of 2048-bin rows (template cut 2 Kt < M): the transform built on the
+    // one-exchange FFT stores the cross-spectrum and takes the first evaluation's nine sums
+    // while X is in registers (k_xspec_qs1024) -- one pass over the stored cross-spectrum fewer
+    p.fuse_scat = scat && !p.seeded && !p.coarse && c->max_iter > 0 && c->one_exchange && c->fuse_scat && !p.anyb && B == 2048 &&
+                  2 * Kt < M && !(c->x_f32 > 0) && in->errs != nullptr;
+    p.fuse = (!scat && !p.taylor && !p.seeded) || p.fuse_scat;   // first evaluation folded into the transform
     // k_xspec mode: 2/3 = Taylor model only, no cross-spectrum stored;
     // 2 while every thread owns single harmonics (2 Kt < M), else 3 (pairs k, M-k)
-    const bool xmom = taylor && c->moments_in_xspec && !seed_full;
-    const int xmode = xmom ? (2 * Kt < M ? 2 : 3) : (fuse ? 1 : 0);
-    const bool xstore = (xmode < 2);
+    p.xmom = p.taylor && c->moments_in_xspec && !p.seed_full;
+    p.xmode = p.xmom ? (2 * Kt < M ? 2 : 3) : (p.fuse ? 1 : 0);
+    p.xstore = (p.xmode < 2);
     // a batch of the one-pass flow without a host decision in its middle may be left queued (pp_fit_enqueue); its
     // solve and post-fit stage then go to the context's second stream, behind an event of the transform, so that
     // they run BESIDE the next batch's transform (queued on `stream` right behind this one's) instead of in front of
     // it: the solve re-reads the Taylor rows at the HBM roofline with the SIMDs idle, the transform is bound by
     // instruction issue with bandwidth to spare -- and the persistent transform draws its rows by ticket, so its
     // workgroups may start as the solve's retire
-    const bool defer_ok = deferred && taylor && !seed_full && (!pilot || refseed);
-    const hipStream_t sp = (defer_ok && c->overlap_post && c->stream2) ? c->stream2 : c->stream;
-    c->last_post = sp;
-    const int ncs = scat ? PP_NCS : 3;
-    // Channel chunks of the kernels that sum over channels (evaluators, seed, moments).  The run length is a
-    // function of the BAND alone -- never of how many subints share the launch -- so that the partial sums of a
-    // subint are formed and added in one order whatever else is in the batch: a subint's answer is a function of
-    // that subint alone, as in the reference's loop (pptoas.py:344-489).  (Until round 4 the number of chunks
-    // grew as the batch shrank, to fill the chip with a single subint: the rounding of f then depended on the
-    // batch, and through SciPy's 1-ulp exit tests so did ~1e-9 rot of some answers.)
-    auto chunking = [&](int nch, int& nchunk_, int& cpc_) {
-        cpc_ = nch >= PP_CHUNK_CHANNELS ? PP_CHUNK_CHANNELS : ((nch + 15) / 16) * 16;
-        nchunk_ = (nch + cpc_ - 1) / cpc_;
-    };
-    int nchunk, cpc;
-    chunking(C, nchunk, cpc);
+    p.defer_ok = deferred && p.taylor && !p.seed_full && (!p.pilot || p.refseed);
+    p.post_stream2 = p.defer_ok && c->overlap_post && c->stream2;      // (the stream of the post-fit stage: stream2, else stream)
+    p.ncs = scat ? PP_NCS : 3;
+    chunking(C, p.nchunk, p.cpc);
     // pitch of the stored cross-spectrum's rows: Kt harmonics + an optional pad (option x_pad, elements).
     // Kt x 16 B is a multiple of 1 KB and the evaluators stream 32 rows per workgroup at the same
     // pace, which looked like a recipe for memory-channel camping: measured, pads of 8 / 16 / 48
     // elements change nothing (profiles/README.md, round 3) -- the default stays 0
-    const size_t Xs = (size_t)Kt + (size_t)std::max(0, c->x_pad);
-    if (xstore) if ((rc = c->X.reserve(nc * Xs * sizeof(cplx)))) return rc;
-    if ((rc = W.sdraw.reserve(nc * 8))) return rc;
-    if ((rc = W.noise.reserve(nc * 8))) return rc;
-    if ((rc = W.wts.reserve(nc * 8))) return rc;
-    if ((rc = W.state.reserve((size_t)ns * sizeof(SubState)))) return rc;
-    if ((rc = W.csum.reserve(2 * nc * ncs * 8))) return rc;
-    if ((rc = W.partial.reserve((size_t)ns * nchunk * PP_NACC * 8))) return rc;
-    if (taylor) if ((rc = W.tay.reserve(((nc + 63) / 64) * 64 * PP_TSTRIDE * 8))) return rc;   // (whole blocks of 64 rows: tay_idx)
+    p.Xs = (size_t)Kt + (size_t)std::max(0, c->x_pad);
     // (SciPy's trust-ncg spends ~8 of its ~15 evaluations inside the model's range;
     // the Newton iteration only 2-3 of 6, less than the model pass costs)
-    const bool smodel = scat && c->max_iter > 0 && (c->scat_model >= 2 || (c->scat_model == 1 && in->method == PP_METHOD_TRUST_NCG));
-    if (smodel) if ((rc = W.mdl.reserve(nc * PP_MROW * 8))) return rc;
+    p.smodel = scat && c->max_iter > 0 && (c->scat_model >= 2 || (c->scat_model == 1 && in->method == PP_METHOD_TRUST_NCG));
     // Option x_f32 (off by default): the stored cross-spectrum of a scattering fit kept as float
     // pairs, half the bytes of every evaluation pass.  Measured on configs[3] with the Newton
     // solver (profiles/README.md, round 3, with the first evaluator, which was not HBM-bound: the
     // six passes went from 7.92 to 7.28 ms only; k_eval_scat is, so the gain would be larger now)
     // -- but chi2 loses its 1e-10 agreement with the reference (6e-8 of every |X_nk|
     // moves f by ~1e-6 of itself; the optimum by ~1e-11 rot).  Kept for experiments.
-    const bool xf32 = scat && !seeded && !smodel && c->max_iter > 0 && c->x_f32 > 0;
-    const bool want_ph0 = xmode != 0 || fuse_scat || refseed;
-    if (want_ph0) if ((rc = W.ph0.reserve(nc * 8 * (fuse_scat ? 2 : 1)))) return rc;
-    if ((rc = W.misc.reserve(256))) return rc;
-    if ((rc = W.act.reserve((size_t)ns * 4))) return rc;
-    // per-subint scalar outputs: blocks of one allocation (params 5, errs 5, nu 3,
-    // cov 25, chi2, red_chi2, snr doubles; nfeval, return_code, npass ints) = 340 B / subint
-    const size_t o_bytes = ((size_t)ns * 340 + 8 + 7) & ~(size_t)7;       // (+ the count of unfinished subints; whole words)
-    const size_t o_stage = stage_seed_offset(ns) + (size_t)ns * 8;   // (+ the reference-seed flow's phase guesses)
-    if ((rc = W.o_pack.reserve(o_stage))) return rc;      // (the phase guesses of the reference-seed flow behind the pack)
-    if (sg.o_cap < o_stage) {
-        if (sg.o_host) (void)hipHostFree(sg.o_host);
-        sg.o_host = nullptr; sg.o_cap = 0;
-        HIP_TRY(hipHostMalloc(&sg.o_host, o_stage, hipHostMallocDefault));
-        sg.o_cap = o_stage;
-    }
-    double* const o_base = W.o_pack.as<double>();
-    if ((rc = W.o_f0.reserve((size_t)ns * 8))) return rc;
-    if ((rc = W.o_g0.reserve((size_t)ns * 40))) return rc;
-    if ((rc = W.o_H0.reserve((size_t)ns * 200))) return rc;
-    const bool chan_dev = out->chan_on_device != 0;
-    if (!chan_dev) {
-        if (out->scales) if ((rc = W.o_scales.reserve(nc * 8))) return rc;
-        if (out->scale_errs) if ((rc = W.o_serrs.reserve(nc * 8))) return rc;
-        if (out->channel_snrs) if ((rc = W.o_csnr.reserve(nc * 8))) return rc;
-    }
-
-    if (c->debug_poison) {
-        // every buffer a kernel of this batch reads must have been written by one: stale
-        // contents become NaNs that surface as failed certificates / non-finite results
-        // (bit mask: 1 tay, 2 sdraw, 4 noise, 8 wts, 16 csum, 32 ph0, 64 X, 128 mdl)
-        const int pz = c->debug_poison;
-        if ((pz & 1) && taylor) HIP_TRY(hipMemsetAsync(W.tay.p, 0xFF, ((nc + 63) / 64) * 64 * PP_TSTRIDE * 8, c->stream));
-        if (pz & 2) HIP_TRY(hipMemsetAsync(W.sdraw.p, 0xFF, nc * 8, c->stream));
-        if (pz & 4) HIP_TRY(hipMemsetAsync(W.noise.p, 0xFF, nc * 8, c->stream));
-        if (pz & 8) HIP_TRY(hipMemsetAsync(W.wts.p, 0xFF, nc * 8, c->stream));
-        if (pz & 16) HIP_TRY(hipMemsetAsync(W.csum.p, 0xFF, 2 * nc * ncs * 8, c->stream));
-        if ((pz & 32) && want_ph0) HIP_TRY(hipMemsetAsync(W.ph0.p, 0xFF, nc * 8, c->stream));
-        if ((pz & 64) && xstore) HIP_TRY(hipMemsetAsync(c->X.p, 0xFF, nc * Xs * sizeof(cplx), c->stream));
-        if ((pz & 128) && smodel) HIP_TRY(hipMemsetAsync(W.mdl.p, 0xFF, nc * PP_MROW * 8, c->stream));
-    }
-    // ---- argument blocks ----
-    const bool tail = (in->errs == nullptr);
-    XspecArgs xa;
-    memset(&xa, 0, sizeof xa);
-    xa.data = ddata; xa.mft = (const cplx* const*)c->mft_table.p;
-    xa.mft0 = c->slots[0].mft.as<cplx>();
-    xa.ktab = (const int* const*)c->kt_table.p;
-    xa.kt0 = c->slots[0].kt.as<int>();
-    xa.slot = in->model_slot ? d_slot : nullptr;
-    xa.X = c->X.as<cplx>(); xa.sdraw = W.sdraw.as<double>(); xa.noise = W.noise.as<double>();
-    xa.twB = tw; xa.nsub = ns; xa.nchan = C; xa.Kt = Kt; xa.Xs = (int)Xs;
-    xa.x0 = d_x0; xa.P = d_P; xa.nu_fit = d_nufit;
-    xa.freqs = d_freqs; xa.freqs_stride = in->freqs_stride ? C : 0;
-    xa.csum0 = W.csum.as<double>();
-    xa.tay = W.tay.as<double>();
-    xa.ph0 = W.ph0.as<double>();
-    xa.act = nullptr; xa.cstep = 1; xa.coff = 0; xa.nchan_full = C;
-    xa.x_f32 = xf32 ? 1 : 0;
-    FitArgs fa;
-    memset(&fa, 0, sizeof fa);
-    fa.nsub = ns; fa.nchan = C; fa.nbin = B; fa.M = M; fa.Kt = Kt; fa.Xs = (int)Xs;
-    for (int j = 0; j < 5; ++j) fa.flags[j] = in->fit_flags[j] ? 1 : 0;
-    fa.log10_tau = in->log10_tau ? 1 : 0; fa.option = in->option; fa.is_toa = in->is_toa ? 1 : 0;
-    fa.max_iter = c->max_iter; fa.scat = scat ? 1 : 0;
-    fa.method = in->method;
-    fa.X = c->X.as<cplx>();
-    fa.mft = (const cplx* const*)c->mft_table.p;
-    fa.msq = (const double* const*)c->msq_table.p;
-    fa.msum = (const double* const*)c->msum_table.p;
-    fa.ktab = (const int* const*)c->kt_table.p;
-    fa.slot = in->model_slot ? d_slot : nullptr;
-    fa.freqs = d_freqs; fa.freqs_stride = in->freqs_stride ? C : 0;
-    fa.wts = W.wts.as<double>(); fa.sdraw = W.sdraw.as<double>();
-    fa.P = d_P; fa.nu_fit = d_nufit; fa.nu_out = d_nuout;
-    fa.x0 = d_x0; fa.st = W.state.as<SubState>();
-    fa.csum = W.csum.as<double>(); fa.ncs = ncs;
-    fa.tay = W.tay.as<double>();
-    fa.partial = W.partial.as<double>(); fa.nchunk = nchunk; fa.cpc = cpc;
-    fa.nactive = W.misc.as<int>();
-    fa.o_params = o_base; fa.o_errs = o_base + (size_t)ns * 5; fa.o_nu = o_base + (size_t)ns * 10;
-    fa.o_cov = o_base + (size_t)ns * 13; fa.o_chi2 = o_base + (size_t)ns * 38; fa.o_rchi2 = o_base + (size_t)ns * 39;
-    fa.o_snr = o_base + (size_t)ns * 40;
-    fa.o_nfev = reinterpret_cast<int*>(o_base + (size_t)ns * 41); fa.o_rc = fa.o_nfev + ns; fa.o_npass = fa.o_rc + ns;
-    if (chan_dev) {
-        fa.o_scales = out->scales ? out->scales + (size_t)s0 * C : nullptr;
-        fa.o_scale_errs = out->scale_errs ? out->scale_errs + (size_t)s0 * C : nullptr;
-        fa.o_csnr = out->channel_snrs ? out->channel_snrs + (size_t)s0 * C : nullptr;
-    } else {
-        fa.o_scales = out->scales ? W.o_scales.as<double>() : nullptr;
-        fa.o_scale_errs = out->scale_errs ? W.o_serrs.as<double>() : nullptr;
-        fa.o_csnr = out->channel_snrs ? W.o_csnr.as<double>() : nullptr;
-    }
-    fa.o_f0 = W.o_f0.as<double>(); fa.o_g0 = W.o_g0.as<double>(); fa.o_H0 = W.o_H0.as<double>();
-    fa.o_rec = out->records_dev ? out->records_dev + (size_t)s0 * PP_RECORD_WIDTH : nullptr;
-    fa.act = nullptr; fa.nact = ns; fa.nchan_x = C; fa.cstep = 1; fa.coff = 0;
-    fa.mdl = W.mdl.as<double>(); fa.use_model = smodel ? 1 : 0; fa.model_tol = c->scat_model_tol; fa.model_bet = c->scat_model_bet;
-    // (a GM fit walked the SciPy way ends where its path ends: it keeps the exact path; the
-    // Newton solver converges to the optimum from anywhere)
-    fa.recentre = (taylor && xmom && (!in->fit_flags[2] || in->method == PP_METHOD_NEWTON))
-                      ? std::max(0, c->taylor_recentre) : 0;
-    fa.x0w = d_x0;
-    fa.x_f32 = xf32 ? 1 : 0;
-    fa.nfev_shadow = c->nfev_shadow;
+    p.xf32 = scat && !p.seeded && !p.smodel && c->max_iter > 0 && c->x_f32 > 0;
+    p.want_ph0 = p.xmode != 0 || p.fuse_scat || p.refseed;
     // (a band of up to 512 channels: one wave per subint; up to 1024: two; wider: four -- eight measured slower at 4096)
-    const int solve_nt = solve_threads_for(c, C);
-    // (LDS: 32 B per cached channel, 512 channels per wave of the block keep the CU's eight waves within 128 KB)
-    fa.solve_cache = std::min(C, c->solve_cache >= 0 ? c->solve_cache : std::min(PP_SOLVE_CACHE_MAX, solve_nt * 8));
-    {
-        // what the device grants a workgroup (160 KB on gfx950; 64 KB on older parts) less the kernel's static scratch
-        // bounds the cache: a smaller cache only means more channels' invariants formed again per evaluation
-        if (!c->max_lds_bytes) {
-            hipDeviceProp_t prop;
-            c->max_lds_bytes = (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.sharedMemPerBlock > 0)
-                                   ? (int)std::min<size_t>(prop.sharedMemPerBlock, (size_t)1 << 30) : 64 * 1024;
-        }
-        const int room = std::max(0, c->max_lds_bytes - 16 * 1024) / 32;
-        fa.solve_cache = std::min(fa.solve_cache, room);
-    }
-    auto launch_taylor_solve = [&]() { solve_launch(c, fa, ns, C, solve_nt, sp); };
-
-    auto run_xspec = [&](const XspecArgs& x, int mode) -> int {
-        Prof pr(c, KF_XSPEC);
-        if (anyb) return launch_any(c, x, B, M, in->data_dtype, mode, tail, nullptr, c->skip_masked ? d_mask : nullptr);
-        PP_DISPATCH_M(M, {
-            if (in->data_dtype == PP_F64) launch_xspec<MM, double>(c, x, tail, mode);
-            else launch_xspec<MM, float>(c, x, tail, mode);
-        });
-        HIP_TRY(hipGetLastError());
-        return PP_OK;
-    };
-    auto run_prep = [&]() -> int {
-        Prof pr(c, KF_PREP);
-        hipLaunchKernelGGL(k_prep, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, ns, C, B,
-                           d_errs, W.noise.as<double>(), d_mask, W.wts.as<double>());
-        HIP_TRY(hipGetLastError());
-        return PP_OK;
-    };
+    p.solve_nt = solve_threads_for(c, C);
     // the coarse seed uses the lowest 64 * PP_SEED_KPT = 1024 harmonics at most
     // (templates that keep more -- nbin 4096 / 8192 with power out to Nyquist --
     // lose nothing a 100-point grid could resolve)
-    const int Ks = std::min(Kt, 64 * PP_SEED_KPT);
-    // seed the subints f lists (f.act / f.nact, channels f.coff + nn f.cstep) from the
-    // cross-spectrum in f.X; seedq (optional) receives the peak significance
+    p.Ks = std::min(Kt, 64 * PP_SEED_KPT);
     // The coarse grid is (phi, DM): seed_ns phases x seed_ndm trial DMs spaced
     // seed_dm_step about the guess (1 trial = the reference's behaviour, whose seed
     // trusts the header DM, pptoas.py:421-457); the best correlation peak wins.
-    const int ndm = (c->seed_ndm > 1 && c->seed_dm_step > 0.0) ? c->seed_ndm : 1;
-    auto run_seed = [&](const FitArgs& f, double* seedq) -> int {
-        if ((rc = c->seedbuf.reserve(((size_t)f.nact * f.nchunk + f.nact) * Ks * sizeof(cplx)))) return rc;
-        cplx* ypart = c->seedbuf.as<cplx>();
-        cplx* ywork = ypart + (size_t)f.nact * f.nchunk * Ks;
-        Prof pr(c, KF_SEED);
-        const double* xbase = d_x0;
-        if (ndm > 1) {
-            // trial DMs: peak heights only, then the refined DM of every subint, then
-            // the seed proper at that DM
-            if ((rc = c->xbase.reserve((size_t)ns * 80 + (size_t)ns * ndm * 8))) return rc;
-            double* xb = c->xbase.as<double>();          // [ns][5] guesses as given
-            double* xr = xb + (size_t)ns * 5;            // [ns][5] with the chosen DM
-            double* pk = xr + (size_t)ns * 5;            // [ns][ndm]
-            HIP_TRY(hipMemcpyAsync(xb, d_x0, (size_t)ns * 40, hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(xr, d_x0, (size_t)ns * 40, hipMemcpyDeviceToDevice, c->stream));
-            for (int t = 0; t < ndm; ++t) {
-                const double off = (t - (ndm - 1) / 2) * c->seed_dm_step;
-                hipLaunchKernelGGL(k_seed_accum, dim3(f.nact, f.nchunk), dim3(256), 0, c->stream, f, ypart, Ks,
-                                   (const double*)xb, off);
-                hipLaunchKernelGGL(k_seed_fit, dim3(f.nact), dim3(256), 0, c->stream, f, (const cplx*)ypart, ywork,
-                                   d_x0, seed_ns, Ks, (double*)nullptr, (const double*)xb, off,
-                                   pk, t, ndm);
-            }
-            hipLaunchKernelGGL(k_seed_dm_pick, dim3((f.nact + 63) / 64), dim3(64), 0, c->stream, f.act, f.nact,
-                               (const double*)pk, ndm, c->seed_dm_step, (const double*)xb, xr);
-            xbase = xr;
-        }
-        hipLaunchKernelGGL(k_seed_accum, dim3(f.nact, f.nchunk), dim3(256), 0, c->stream, f, ypart, Ks, xbase, 0.0);
-        hipLaunchKernelGGL(k_seed_fit, dim3(f.nact), dim3(256), 0, c->stream, f, (const cplx*)ypart, ywork,
-                           d_x0, seed_ns, Ks, seedq, xbase, 0.0, (double*)nullptr, 0, 1);
-        HIP_TRY(hipGetLastError());
-        return PP_OK;
-    };
-    // list the subints that need more work into W.act; returns their number
-    auto list_active = [&](const double* seedq, double qmin, int* count) -> int {
-        hipLaunchKernelGGL(k_list_active, dim3(1), dim3(256), 0, c->stream, (const SubState*)W.state.p, seedq, qmin,
-                           ns, W.act.as<int>(), W.misc.as<int>() + 1);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->nactive_h + 1, W.misc.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        *count = c->nactive_h[1];
-        return PP_OK;
-    };
-    // transform every channel of the listed subints again with the cross-spectrum
-    // stored (compact in the list index), and point the evaluators at the list
-    auto store_x_for_list = [&](int count) -> int {
-        if ((rc = c->X.reserve((size_t)count * C * Xs * sizeof(cplx)))) return rc;
-        XspecArgs xl = xa;
-        xl.X = c->X.as<cplx>(); xl.act = W.act.as<int>(); xl.nsub = count;
-        if ((rc = run_xspec(xl, 0))) return rc;
-        fa.X = c->X.as<cplx>(); fa.act = W.act.as<int>(); fa.nact = count;
-        chunking(C, fa.nchunk, fa.cpc);
-        if ((rc = W.partial.reserve((size_t)ns * fa.nchunk * PP_NACC * 8))) return rc;
-        fa.partial = W.partial.as<double>();
-        return PP_OK;
-    };
-
-    // (a pending tail of the previous enqueued batch that this batch's transform will not carry -- any flow but the
-    // plain one-pass one -- goes out by the stand-alone kernels now)
-    if (c->ptail.valid && ((refseed && scat) || seed_full || fuse_scat || !xmom || anyb || !c->one_exchange || M != 1024 || !deferred))
-        if ((rc = flush_tail(c))) return rc;
-    // The previous enqueued batch's tail, still unqueued: this batch's transform works it off as tickets if it is one of
-    // the kernels that can (k_xspec_q1024 / k_xspec_qf<1024> / k_xspec_qr1024: 2048-bin rows, Taylor sums only) -- and
-    // if its grid is wide enough for the tickets: a small batch behind a large one would hand each of its few waves
-    // many tickets in a row, ~1 ms each, where the stand-alone kernels take 0.7 ms for all of them.
-    auto carrier_block = [&](XspecArgs& x) -> int {
-        pp_ctx::PendingTail& pt = c->ptail;
-        const int st_i = c->cur_stage;
-        const size_t tb = (sizeof(TailArgs) + 7) & ~(size_t)7;
-        if ((rc = c->tailbuf[st_i].reserve(tb))) return rc;
-        if (!c->tail_host[st_i]) HIP_TRY(hipHostMalloc(&c->tail_host[st_i], tb, hipHostMallocDefault));
-        TailArgs* th = reinterpret_cast<TailArgs*>(c->tail_host[st_i]);
-        memset(th, 0, tb);
-        th->fa = pt.fa; th->ticket = 0; th->done = 0; th->nsub = pt.ns;
-        th->fa.solve_cache = std::min(pt.C, (int)PP_TAIL_CACHE);
-        th->fa.tail_fused = 1;
-        th->solve_nt = pt.solve_nt; th->solve_pf = pt.solve_pf0 ? 0 : PP_SOLVE_PF; th->fin_nt = pt.fin_nt;
-        th->rs = pt.rs;
-        if ((rc = staged_copy(c, c->tailbuf[st_i].p, th, tb, hipMemcpyHostToDevice))) return fail(rc, "tail block copy failed");
-        x.tail = c->tailbuf[st_i].as<TailArgs>();
-        x.tail_nsub = pt.ns;
-        return PP_OK;
-    };
-    // ... and behind the carrying transform: the carried batch's outputs and its event
-    auto carrier_done = [&]() -> int {
-        pp_ctx::PendingTail& pt = c->ptail;
-        int r2 = queue_outputs(c, pt.stage, &pt.out, pt.s0, pt.ns, pt.C, pt.chan_dev, pt.copy_bytes, c->stream);
-        if (!r2 && hipEventRecord(c->stage[pt.stage].done, c->stream) != hipSuccess) r2 = fail(PP_EHIP, "hipEventRecord failed");
-        pt.valid = false;
-        if (r2) fail_pending_stage(c, pt.stage, r2);
-        return r2;
-    };
-    const bool wide_enough = c->ptail.valid && (long long)std::min<long long>((long long)ns * C, 4096) * 2 >= (long long)c->ptail.ns;
-    if (c->ptail.valid && !wide_enough)
-        if ((rc = flush_tail(c))) return rc;
-    // a batch of the one-pass flow whose own tail stays unqueued for the next batch's transform (option fuse_tail)
-    const bool tail_pending = defer_ok && c->fuse_tail && xmom && sp == c->stream && !anyb && M == 1024 && c->one_exchange;
-    // ---- phase seed from a pilot pass ----
-    if (pilot) {
-        const int Cp = (C + cstep - 1) / cstep;
-        if ((rc = c->X.reserve((size_t)ns * Cp * Xs * sizeof(cplx)))) return rc;
-        if ((rc = c->seedq.reserve((size_t)ns * 8))) return rc;
-        XspecArgs xp = xa;
-        xp.X = c->X.as<cplx>(); xp.nchan = Cp; xp.cstep = cstep;
-        if ((rc = run_xspec(xp, 0))) return rc;
-        if ((rc = run_prep())) return rc;      // (rows not transformed yet have no measured noise: unused here)
-        FitArgs fp = fa;
-        fp.X = c->X.as<cplx>(); fp.nchan_x = Cp; fp.cstep = cstep;
-        chunking(Cp, fp.nchunk, fp.cpc);
-        if ((rc = run_seed(fp, c->seedq.as<double>()))) return rc;
-        // (reference-seed flow: the pilot's phase is only the expansion point of the Taylor model, which the
-        // certificate guards -- a weak pilot costs its subint a second expansion, not the batch a host round trip)
-        int nweak = 0;
-        if (!refseed) if ((rc = list_active(c->seedq.as<double>(), c->seed_min_snr, &nweak))) return rc;
-        if (nweak > 0) {
-            // not convincing on a subset: seed these from all their channels
-            if ((rc = store_x_for_list(nweak))) return rc;
-            if ((rc = run_prep())) return rc;
-            if ((rc = run_seed(fa, nullptr))) return rc;
-            fa.act = nullptr; fa.nact = ns; fa.nchunk = nchunk; fa.cpc = cpc;
-        }
-    }
-
-    // ---- rFFT + cross-spectrum (or the Taylor model) of every row ----
-    // one launch in front of it: phi_n at the initial parameters, the weights when the noise is
-    // given, the solver state (a full seed rewrites x0 after the transform: state set then)
-    const bool wts_early = (d_errs != nullptr);
-    {
-        Prof pr(c, KF_PREP);
-        hipLaunchKernelGGL(k_setup, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, fa,
-                           wts_early ? d_errs : (const double*)nullptr, d_mask, W.wts.as<double>(),
-                           want_ph0 ? W.ph0.as<double>() : (double*)nullptr,
-                           fuse_scat ? W.ph0.as<double>() + nc : (double*)nullptr, seed_full ? 0 : 1);
-    }
-    // ---- reference-seed flow: Taylor model about the pilot's phase + the rotated channel sums in
-    // one pass, then the reference's fit_phase_shift on the channel mean, then the start points
-    double* d_seedph = nullptr;      // [ns] the phase guesses the reference-seed flow formed (fetched with the outputs)
-    // hand-over from the transform stage (on `stream`) to the solve / post-fit stage (on `sp`), once per batch
-    bool chained = false;
-    auto chain_post = [&]() -> int {
-        if (sp == c->stream || chained) return PP_OK;
-        HIP_TRY(hipEventRecord(W.xdone, c->stream));
-        HIP_TRY(hipStreamWaitEvent(sp, W.xdone, 0));
-        if (c->eager_flush) (void)hipStreamQuery(c->stream);
-        chained = true;
-        return PP_OK;
-    };
-    RefTailArgs rs_tail;             // this batch's own reference-seed tail, when it stays unqueued (tail_pending)
-    memset(&rs_tail, 0, sizeof rs_tail);
-    cplx* rs_tail_dspec = nullptr;
-    cplx* rs_tail_xwork = nullptr;
-    auto run_refseed_pass = [&]() -> int {
-        const int ncc = C / PP_ROW_CHUNK;
-        const size_t H = (size_t)M + 1;
-        const size_t nprof = rs->model_prof_stride ? (size_t)ns : 1;
-        const bool w_host = (rs->weights && !in->aux_on_device) || d_mask;     // (room for the masked weights)
-        const size_t n_part = (size_t)ns * ncc * RS_NACC * 64;
-        const size_t n_cplx = n_part + (size_t)ns * H + nprof * H + (size_t)ns * M;
-        const size_t n_dbl = (size_t)ns * (1 + 1 + 7) + (w_host ? nc : 0);
-        if ((rc = W.refbuf.reserve(n_cplx * sizeof(cplx) + n_dbl * 8))) return rc;
-        cplx* part = W.refbuf.as<cplx>();
-        cplx* dspec = part + n_part;
-        cplx* mspec = dspec + (size_t)ns * H;
-        cplx* xwork = mspec + nprof * H;
-        // (the model profile(s), nu_mean and the host-formed part of the start points came with the batch's one
-        // input block: no copy command of their own)
-        double* mprof = d_rs_mprof;
-        double* d_numean = d_rs_numean;
-        double* d_xs = d_rs_xs;
-        double* d_delta = reinterpret_cast<double*>(xwork + (size_t)ns * M);
-        double* d_wsum = d_delta + ns;
-        double* d_out7 = d_wsum + ns;
-        double* d_sph = reinterpret_cast<double*>(reinterpret_cast<char*>(W.o_pack.p) + stage_seed_offset(ns));   // (leaves with the outputs)
-        double* d_wh = d_out7 + (size_t)ns * 7;
-        const double* d_w = nullptr;
-        if (rs->weights && !in->aux_on_device) {
-            HIP_TRY(hipMemcpyAsync(d_wh, rs->weights + (size_t)s0 * C, nc * 8, hipMemcpyHostToDevice, c->stream));
-            d_w = d_wh;
-        } else if (rs->weights) d_w = rs->weights + (size_t)s0 * C;
-        if (d_mask) {
-            // the channel mean is taken over the channels the fit uses
-            hipLaunchKernelGGL(k_refseed_weights, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, d_w, d_mask,
-                               (long long)nc, d_wh);
-            d_w = d_wh;
-        }
-        const long long nrows = (long long)ns * C;
-        XspecArgs x = xa;
-        x.ticket = c->ticket.as<unsigned>();
-        x.ticket_base = c->ticket_base;
-        x.mwords = mw_sub;
-        c->ticket_base += (unsigned)((nrows + PP_ROW_CHUNK - 1) / PP_ROW_CHUNK);
-        RefSeedArgs ra{d_w, part, ncc};
-        // what the guess needs beside the pass's channel sums does not depend on the pass: the template profile's
-        // spectrum, Delta_i and the summed weights -- queued in front of it (the expansion points are the pilot's)
-        {
-            Prof pr(c, KF_PREP);
-            hipLaunchKernelGGL((k_rfft_rows<1024, double>), dim3(fft_grid(64, (long long)nprof)), dim3(64), 0, c->stream,
-                               (const void*)mprof, mspec, tw, (int)nprof);
-            hipLaunchKernelGGL(k_refseed_prep, dim3(ns), dim3(256), 0, c->stream, (const double*)d_x0, (const double*)d_P,
-                               (const double*)d_nufit, (const double*)d_numean, d_w, C, d_delta, d_wsum);
-        }
-        HIP_TRY(hipGetLastError());
-        // (the previous batch's tail rides in this pass if it can: see carrier_block)
-        const bool carrier = c->ptail.valid && !scat && deferred != nullptr;
-        if (carrier) { if ((rc = carrier_block(x))) return rc; }
-        else if (c->ptail.valid) { if ((rc = flush_tail(c))) return rc; }
-        {
-            Prof pr(c, KF_XSPEC);
-#define PP_QR(TIN, ST)                                                                                     \
-    do {                                                                                                   \
-        const dim3 grid(resident_grid(c, k_xspec_qr1024<TIN, ST>, 64, nrows, fft_grid(64, nrows)));        \
-        hipLaunchKernelGGL((k_xspec_qr1024<TIN, ST>), grid, dim3(64), 0, c->stream, x, ra);               \
-    } while (0)
-            if (in->data_dtype == PP_F64) { if (scat) PP_QR(double, true); else PP_QR(double, false); }
-            else { if (scat) PP_QR(float, true); else PP_QR(float, false); }
-#undef PP_QR
-        }
-        HIP_TRY(hipGetLastError());
-        if (carrier) if ((rc = carrier_done())) return rc;
-        FpsArgs f{dspec, nullptr, d_out7, rs->lo, rs->hi, rs->Ns, M, ns, rs->finish, mspec,
-                  rs->model_prof_stride ? (int)H : 0};
-        d_seedph = d_sph;
-        if (tail_pending && !scat) {
-            // this batch's own guess -- the spectrum from the chunk partials, the reference's fit_phase_shift, the
-            // start points -- waits with its solve and post-fit stage for the next batch's transform (or flush_tail)
-            memset(&rs_tail, 0, sizeof rs_tail);
-            rs_tail.on = 1; rs_tail.ncc = ncc; rs_tail.part = part; rs_tail.delta = d_delta; rs_tail.wsum = d_wsum;
-            rs_tail.mws = mw_sub; rs_tail.mspec = mspec; rs_tail.mstride = rs->model_prof_stride ? (int)H : 0;
-            rs_tail.fps = f; rs_tail.fps.spec = nullptr; rs_tail.fps.specm = nullptr;
-            rs_tail.xs = d_xs; rs_tail.seed_phase = d_sph;
-            rs_tail_dspec = dspec; rs_tail_xwork = xwork;
-            fa.xstart = d_xs;
-            return PP_OK;
-        }
-        // (what follows the pass -- the channel mean's spectrum, the reference's fit_phase_shift, the start points --
-        // belongs to the solve stage: beside the next batch's transform when the batch is deferred.  The mask words
-        // the finish reads are the transform stage's buffer: a deferred batch has its own copy)
-        if ((rc = chain_post())) return rc;
-        {
-            Prof pr(c, KF_FPS, sp);
-            hipLaunchKernelGGL(k_refseed_finish, dim3((unsigned)((H + 255) / 256), ns), dim3(256), 0, sp,
-                               (const cplx*)part, ncc, (const double*)d_delta, (const double*)d_wsum, ns, dspec, mw_sub);
-            hipLaunchKernelGGL(k_fps, dim3(ns), dim3(256), 0, sp, f, xwork);
-        }
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_refseed_start, dim3((ns + 63) / 64), dim3(64), 0, sp, (const double*)d_out7, ns, d_xs, d_sph);
-        HIP_TRY(hipGetLastError());
-        if (scat) {
-            // stored cross-spectrum: the iteration starts AT the reference's guess
-            HIP_TRY(hipMemcpyAsync(d_x0, d_xs, (size_t)ns * 40, hipMemcpyDeviceToDevice, c->stream));
-            hipLaunchKernelGGL(k_init_state, dim3((ns + 63) / 64), dim3(64), 0, c->stream, fa);
-            HIP_TRY(hipGetLastError());
-        } else fa.xstart = d_xs;       // Taylor model about the pilot's phase: the walk starts off-centre
-        return PP_OK;
-    };
-    if (refseed) {
-        if ((rc = run_refseed_pass())) return rc;
-    } else if (seed_full) {
-        // the seed needs the cross-spectrum at a phase not known yet: store it, seed,
-        // then take the Taylor moments (or iterate) in a second pass over it
-        XspecArgs xm = xa;
-        xm.mwords = mw_main;
-        if ((rc = run_xspec(xm, 0))) return rc;
-        if (!wts_early) if ((rc = run_prep())) return rc;
-        if ((rc = run_seed(fa, nullptr))) return rc;
-        hipLaunchKernelGGL(k_init_state, dim3((ns + 63) / 64), dim3(64), 0, c->stream, fa);
-    } else if (fuse_scat) {
-        const long long nrows = (long long)ns * C;
-        XspecArgs x = xa;
-        x.ticket = c->ticket.as<unsigned>();
-        x.ticket_base = c->ticket_base;
-        x.mwords = mw_main;
-        c->ticket_base += (unsigned)((nrows + PP_ROW_CHUNK - 1) / PP_ROW_CHUNK);
-        {
-            Prof pr(c, KF_XSPEC);
-            if (in->data_dtype == PP_F64) {
-                const dim3 grid(resident_grid(c, k_xspec_qs1024<double>, 64, nrows, fft_grid(64, nrows)));
-                hipLaunchKernelGGL((k_xspec_qs1024<double>), grid, dim3(64), 0, c->stream, x,
-                                   (const double*)(W.ph0.as<double>() + nc), W.csum.as<double>());
-            } else {
-                const dim3 grid(resident_grid(c, k_xspec_qs1024<float>, 64, nrows, fft_grid(64, nrows)));
-                hipLaunchKernelGGL((k_xspec_qs1024<float>), grid, dim3(64), 0, c->stream, x,
-                                   (const double*)(W.ph0.as<double>() + nc), W.csum.as<double>());
-            }
-        }
-        if (!wts_early) if ((rc = run_prep())) return rc;
-    } else {
-        XspecArgs xm = xa;
-        xm.mwords = mw_main;
-        // (the previous enqueued batch's tail rides in this transform if it can: see carrier_block)
-        const bool carrier = c->ptail.valid && xmom && !anyb && c->one_exchange && M == 1024 && deferred != nullptr;
-        if (carrier) { if ((rc = carrier_block(xm))) return rc; }
-        else if (c->ptail.valid) { if ((rc = flush_tail(c))) return rc; }
-        if ((rc = run_xspec(xm, xmode))) return rc;
-        if (carrier) if ((rc = carrier_done())) return rc;
-        if (!wts_early) if ((rc = run_prep())) return rc;
-    }
-    HIP_TRY(hipGetLastError());
-    if (c->eager_flush) (void)hipStreamQuery(c->stream);
-    // ---- post-fit stage + every output in one round trip ----
-    auto finalize_and_fetch = [&](bool wait = true) -> int {
-        FitArgs ff = fa;
-        ff.act = nullptr; ff.nact = ns;
-        {
-            Prof pr(c, KF_FINAL, sp);
-            finalize_launch(c, ff, ns, C, sp);
-        }
-        HIP_TRY(hipGetLastError());
-        if ((rc = queue_outputs(c, c->cur_stage, out, s0, ns, C, chan_dev, d_seedph ? o_stage : o_bytes, sp))) return rc;
-        if (c->eager_flush && sp != c->stream) (void)hipStreamQuery(sp);
-        if (wait) HIP_TRY(hipStreamSynchronize(sp));
-        return PP_OK;
-    };
-    auto unpack_outputs = [&]() { unpack_stage(sg.o_host, out, s0, ns); if (d_seedph) unpack_seed_phases(sg.o_host, in, s0, ns); };
-    auto unfinished = [&]() -> int { return unfinished_in_stage(sg.o_host, ns); };
-    bool all_done = false;
-    if (taylor) {
-        if (xstore) {
-            Prof pr(c, KF_EVAL);
-            hipLaunchKernelGGL(k_eval_moments, dim3(ns, nchunk), dim3(256), 0, c->stream, fa);
-        }
-        if (tail_pending) {
-            // nothing of the tail is queued: the next enqueued batch's transform works it off (or flush_tail does)
-            pp_ctx::PendingTail& pt = c->ptail;
-            pt.valid = true; pt.stage = c->cur_stage;
-            pt.fa = fa; pt.fa.act = nullptr; pt.fa.nact = ns;
-            pt.ns = ns; pt.C = C; pt.solve_nt = solve_nt; pt.solve_pf0 = solve_rows_in_turn(c, C, solve_nt) ? 1 : 0;
-            pt.fin_nt = finalize_width_taken(c, pt.fa, C);
-            pt.out = *out; pt.s0 = s0; pt.chan_dev = chan_dev; pt.copy_bytes = d_seedph ? o_stage : o_bytes;
-            pt.rs = rs_tail; pt.rs_dspec = rs_tail_dspec; pt.rs_xwork = rs_tail_xwork;
-            *deferred = true;
-            return PP_OK;
-        }
-        if ((rc = chain_post())) return rc;
-        {
-            Prof pr(c, KF_TAYLOR, sp);
-            // (rows of the Taylor model in registers where the channel count allows)
-            launch_taylor_solve();
-        }
-        HIP_TRY(hipGetLastError());
-        // The solve certifies nearly every subint of nearly every batch: the post-fit stage is
-        // launched straight behind it and the count of unfinished subints comes back with the
-        // outputs -- one host round trip per batch instead of two.  (When some are left, what
-        // the post-fit stage wrote for them is overwritten below.)
-        if (defer_ok) {
-            // nothing left for the host to decide before the outputs are on their way: pp_fit_collect
-            // looks at the count of unfinished subints (and fits the batch again, synchronously, in the
-            // rare case that some are left -- their guesses were poor)
-            if ((rc = finalize_and_fetch(false))) return rc;
-            *deferred = true;
-            return PP_OK;
-        }
-        if ((rc = finalize_and_fetch())) return rc;
-        all_done = (unfinished() <= 0);
-        if (all_done) { unpack_outputs(); return PP_OK; }
-        // (reference-seed flow: a subint whose walk left the model taken about the pilot's phase is
-        // expanded again about the reference's guess itself -- the ordinary flow from there)
-        const int nrep = std::max(fa.recentre, refseed ? 1 : 0);
-        for (int rep = 0; rep < nrep && !all_done; ++rep) {
-            // some subints failed the certificate (poor guesses): k_taylor_solve moved
-            // their expansion points to its tentative answers -- take the Taylor model of
-            // THOSE again (one more pass over their rows, nothing stored) and solve again
-            int nleft = 0;
-            if ((rc = list_active(nullptr, 0.0, &nleft))) return rc;
-            {
-                Prof pr(c, KF_PREP);
-                hipLaunchKernelGGL(k_phase0, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, ns, C,
-                                   xa.x0, xa.P, xa.nu_fit, xa.freqs, xa.freqs_stride, W.ph0.as<double>());
-            }
-            XspecArgs xl = xa;
-            xl.act = W.act.as<int>(); xl.nsub = nleft;
-            if ((rc = run_xspec(xl, xmode))) return rc;
-            {
-                Prof pr(c, KF_TAYLOR);
-                launch_taylor_solve();
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(c->nactive_h, fa.nactive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            all_done = (c->nactive_h[0] <= 0);
-        }
-        if (!all_done && !xstore) {
-            // still not certified: they need evaluations over the cross-spectrum, which
-            // was not stored -- transform THOSE again, keeping it
-            int nleft = 0;
-            if ((rc = list_active(nullptr, 0.0, &nleft))) return rc;
-            if ((rc = store_x_for_list(nleft))) return rc;
-        }
-    }
-    if (coarse && !all_done) {
-        FitArgs fs = fa;
-        fs.cstep = kCoarseStep; fs.coff = 0; fs.nchan_x = (C + kCoarseStep - 1) / kCoarseStep; fs.x_full = 1;
-        fs.use_model = 0;
-        chunking(fs.nchan_x, fs.nchunk, fs.cpc);
-        // (a fixed number of iterations, no host check: subints that are done cost their kernels nothing)
-        for (int it = 0; it < std::min(12, c->max_iter + 1); ++it) {
-            { Prof pr(c, KF_EVAL);
-              hipLaunchKernelGGL((k_eval_scat<8, false>), dim3(fs.nact, fs.nchunk), dim3(256), 0, c->stream, fs); }
-            { Prof pr(c, KF_STEP);
-              hipLaunchKernelGGL(k_step, dim3(fs.nact), dim3(64), 0, c->stream, fs); }
-        }
-        hipLaunchKernelGGL(k_adopt_coarse, dim3((ns + 63) / 64), dim3(64), 0, c->stream, fa);
-        HIP_TRY(hipGetLastError());
-    }
-    // ---- trust-region iterations: evaluation + step, until every subint is done
-    const int max_evals = all_done ? 0 : std::max(1, c->max_iter + 1);
+    p.ndm = (c->seed_ndm > 1 && c->seed_dm_step > 0.0) ? c->seed_ndm : 1;
     // (the first look at the count of unfinished subints: SciPy's trust-ncg needs ~15 evaluations for a scattering
     // fit and the model takes over after ~6 passes -- no subint is done before iteration 5, and every look before
     // that drains the queue for nothing: +0.8 ... 1.2 % on configs[3], profiles/r05_small_ab.txt)
-    const int check_from = smodel ? std::max(c->check_from, 5) : c->check_from;
+    p.check_from = p.smodel ? std::max(c->check_from, 5) : c->check_from;
+    // The two tail predicates (option fuse_tail).  can_carry: this batch's transform is one of the kernels that work
+    // a pending tail off as tickets (k_xspec_q1024 / k_xspec_qf<1024> / k_xspec_qr1024: 2048-bin rows, Taylor sums
+    // only, enqueued) -- the plain one-pass flow and the reference-seed pass without scattering; whether it DOES carry
+    // the tail pending now also depends on that tail's size (carries_pending_tail).  leaves_tail: a batch of the
+    // one-pass flow whose own tail stays unqueued for the next batch's transform.
+    const bool ticket_kernel = p.xmom && !p.anyb && M == 1024 && c->one_exchange;
+    p.can_carry = deferred && ticket_kernel;      // (xmom: no scattering, no full seed -- the flows that take other transforms)
+    p.leaves_tail = p.defer_ok && c->fuse_tail && ticket_kernel && !p.post_stream2;
+    return p;
+}
+// The previous enqueued batch's tail, still unqueued: this batch's transform works it off as tickets if it is one of the
+// kernels that can (FlowPlan::can_carry) -- and if its grid is wide enough for the tickets: a small batch behind a large
+// one would hand each of its few waves many tickets in a row, ~1 ms each, where the stand-alone kernels take 0.7 ms for
+// all of them.
+static bool carries_pending_tail(const pp_ctx* c, const FlowPlan& p, int ns, int C) {
+    return c->ptail.valid && p.can_carry && std::min<long long>((long long)ns * C, 4096) * 2 >= (long long)c->ptail.ns;
+}
+
+// One sub-batch (chunk) of a fit on its way through the stages below
+struct Chunk {
+    pp_ctx* c; const pp_fit_in* in; pp_fit_out* out; int s0, ns, C, B, Kt; bool scat, chan_dev; bool* deferred;
+    size_t nc;                       // rows: ns * C
+    FlowPlan p; pp_ctx::Stage* sg; pp_ctx::WorkSet* W;
+    hipStream_t sp;                  // the stream of the solve / post-fit stage
+    InBlock d;                       // the small inputs on the device
+    const cplx* tw; const void* ddata; const double* d_errs; const unsigned char* d_mask;
+    const unsigned *mw_main, *mw_sub;    // rows in use of a masked batch (both row orders), or nullptr
+    XspecArgs xa; FitArgs fa;
+    double* d_seedph;                // [ns] the phase guesses the reference-seed flow formed (fetched with the outputs)
+    bool chained;                    // the hand-over from `stream` to `sp` has been queued
+    RefTailArgs rs_tail;             // this batch's own reference-seed tail, when it stays unqueued (leaves_tail)
+    cplx *rs_tail_dspec, *rs_tail_xwork;
+    size_t copy_bytes() const { return d_seedph ? OutBlock::staged_bytes(ns) : OutBlock::bytes(ns); }
+};
+static int pinned_reserve(void** host, size_t* cap, size_t bytes) {
+    if (*cap >= bytes) return PP_OK;
+    if (*host) (void)hipHostFree(*host);
+    *host = nullptr; *cap = 0;
+    HIP_TRY(hipHostMalloc(host, bytes, hipHostMallocDefault));
+    *cap = bytes;
+    return PP_OK;
+}
+// ---- inputs: portraits, the one block of small inputs, noise, mask and the mask's rows-in-use words ----
+static int stage_inputs(Chunk& k, const std::vector<double>& nufit_h, const std::vector<double>& nuout_h) {
+    pp_ctx* c = k.c; const pp_fit_in* in = k.in; pp_ctx::WorkSet& W = *k.W; int rc;
+    const pp_seed_ref* rs = in->ref_seed;
+    const int s0 = k.s0, ns = k.ns, C = k.C, B = k.B;
+    const size_t esz = in->data_dtype == PP_F64 ? 8 : 4, sub_elems = (size_t)C * B, nc = k.nc;
+    if (in->data_on_device) {
+        k.ddata = (const char*)in->data + (size_t)s0 * sub_elems * esz;
+    } else {
+        if ((rc = upload(c, c->data, (const char*)in->data + (size_t)s0 * sub_elems * esz, (size_t)ns * sub_elems * esz))) return rc;
+        k.ddata = c->data.p;
+    }
+    const InLayout il(in, ns);
+    if ((rc = W.inpack.reserve(il.bytes()))) return rc;
+    if ((rc = pinned_reserve(&k.sg->in_host, &k.sg->in_cap, il.bytes()))) return rc;
+    k.d = il.at(W.inpack.p);
+    {
+        const InBlock h = il.at(k.sg->in_host);
+        memcpy(h.freqs, in->freqs + (in->freqs_stride ? (size_t)s0 * C : 0), il.nfreq * 8);
+        memcpy(h.P, in->P + s0, (size_t)ns * 8);
+        memcpy(h.x0, in->init_params + (size_t)s0 * 5, (size_t)ns * 40);
+        // (reference seed of a scattering fit: the pass rotates by the DM guess alone -- phase 0 --
+        // and the phases the reference's guess gives are written before the state is set)
+        if (rs && k.scat) for (int i = 0; i < ns; ++i) h.x0[(size_t)i * 5] = 0.0;
+        memcpy(h.nufit, nufit_h.data() + (size_t)s0 * 3, (size_t)ns * 24);
+        memcpy(h.nuout, nuout_h.data() + (size_t)s0 * 3, (size_t)ns * 24);
+        if (rs) {
+            memcpy(h.rs_mprof, rs->model_profs + (rs->model_prof_stride ? (size_t)s0 * B : 0), il.rs_nprof * B * 8);
+            memcpy(h.rs_numean, rs->nu_mean + s0, (size_t)ns * 8);
+            // phase_transform(phi, DM, nu_mean, nu_fit, P, mod=True) (pplib.py:2592-2616): the term it adds
+            // depends on the inputs alone -- formed here in NumPy's order of operations with libm's pow, as the
+            // reference forms it -- so the device only adds it to its fit_phase_shift result and wraps: no
+            // host round trip between the pass and the iteration.  The other parameters start as given.
+            for (int i = 0; i < ns; ++i) {
+                const double* x0i = in->init_params + (size_t)(s0 + i) * 5;
+                const double P = in->P[s0 + i], nu1 = rs->nu_mean[s0 + i], nu2 = nufit_h[(size_t)(s0 + i) * 3];
+                h.rs_xs[(size_t)i * 5] = PP_DCONST * x0i[1] * pow(P, -1.0) * (pow(nu2, -2.0) - pow(nu1, -2.0));
+                for (int j = 1; j < 5; ++j) h.rs_xs[(size_t)i * 5 + j] = x0i[j];
+            }
+        }
+        if (in->model_slot) memcpy(h.slot, in->model_slot + s0, (size_t)ns * 4);
+        if ((rc = staged_copy(c, W.inpack.p, k.sg->in_host, il.bytes(), hipMemcpyHostToDevice))) return fail(rc, "input block copy failed");
+    }
+    if (in->aux_on_device) {
+        if (in->errs) k.d_errs = in->errs + (size_t)s0 * C;
+        if (in->chan_mask) k.d_mask = in->chan_mask + (size_t)s0 * C;
+    } else {
+        if (in->errs) { if ((rc = upload(c, c->errs, in->errs + (size_t)s0 * C, nc * 8))) return rc; k.d_errs = c->errs.as<double>(); }
+        if (in->chan_mask) { if ((rc = upload(c, c->mask, in->chan_mask + (size_t)s0 * C, nc))) return rc; k.d_mask = c->mask.as<unsigned char>(); }
+    }
+    // rows in use: channels the mask removes from a subint are not transformed at all (RowWalk)
+    if (k.d_mask && c->skip_masked) {
+        const size_t nw_main = (nc + 31) / 32 + 1, nw_sub = (C % 32 == 0) ? nc / 32 : 0;
+        if ((rc = W.mwords.reserve((nw_main + nw_sub) * sizeof(unsigned)))) return rc;
+        HIP_TRY(hipMemsetAsync(W.mwords.p, 0, (nw_main + nw_sub) * sizeof(unsigned), c->stream));
+        unsigned* wm = W.mwords.as<unsigned>();
+        unsigned* ws = nw_sub ? wm + nw_main : nullptr;
+        hipLaunchKernelGGL(k_mask_words, dim3((unsigned)((C + 255) / 256), (unsigned)((ns + 31) / 32)), dim3(256), 0, c->stream,
+                           k.d_mask, ns, C, wm, ws);
+        HIP_TRY(hipGetLastError());
+        k.mw_main = wm; k.mw_sub = ws;
+    }
+    return PP_OK;
+}
+// ---- work buffers of the flow the plan describes, the output block and its pinned staging copy ----
+static int reserve_work(Chunk& k) {
+    pp_ctx* c = k.c; pp_ctx::WorkSet& W = *k.W; const FlowPlan& p = k.p; const pp_fit_out* out = k.out;
+    const size_t nc = k.nc, ns = k.ns; const bool chan_host = !k.chan_dev;
+    // (buffer, bytes, needed by this flow, its bit in option debug_poison: 1 tay, 2 sdraw, 4 noise, 8 wts, 16 csum, 32 ph0,
+    // 64 X, 128 mdl.  In the order they have always been allocated: where a buffer lies relative to its neighbours is
+    // part of a kernel's memory pattern.  tay: whole blocks of 64 rows, tay_idx.  ph0: the fused scattering transform's
+    // phases behind phi_n.  o_pack: the phase guesses of the reference-seed flow behind the pack)
+    const struct { DevBuf* b; size_t bytes; bool on; int poison; } need[] = {
+        {&c->X, nc * p.Xs * sizeof(cplx), p.xstore, 64}, {&W.sdraw, nc * 8, true, 2}, {&W.noise, nc * 8, true, 4},
+        {&W.wts, nc * 8, true, 8}, {&W.state, ns * sizeof(SubState), true, 0}, {&W.csum, 2 * nc * p.ncs * 8, true, 16},
+        {&W.partial, ns * p.nchunk * PP_NACC * 8, true, 0}, {&W.tay, ((nc + 63) / 64) * 64 * PP_TSTRIDE * 8, p.taylor, 1},
+        {&W.mdl, nc * PP_MROW * 8, p.smodel, 128}, {&W.ph0, nc * 8 * (p.fuse_scat ? 2 : 1), p.want_ph0, 32}, {&W.misc, 256, true, 0},
+        {&W.act, ns * 4, true, 0}, {&W.o_pack, OutBlock::staged_bytes(ns), true, 0}, {&W.o_f0, ns * 8, true, 0}, {&W.o_g0, ns * 40, true, 0},
+        {&W.o_H0, ns * 200, true, 0}, {&W.o_scales, nc * 8, chan_host && out->scales, 0},
+        {&W.o_serrs, nc * 8, chan_host && out->scale_errs, 0}, {&W.o_csnr, nc * 8, chan_host && out->channel_snrs, 0}};
+    int rc;
+    for (const auto& n : need) if (n.on) if ((rc = n.b->reserve(n.bytes))) return rc;
+    if ((rc = pinned_reserve(&k.sg->o_host, &k.sg->o_cap, OutBlock::staged_bytes(ns)))) return rc;
+    // option debug_poison: every buffer a kernel of this batch reads must have been written by one: stale
+    // contents become NaNs that surface as failed certificates / non-finite results (bit by bit; of ph0, phi_n)
+    for (int bit = 1; bit <= 128 && c->debug_poison; bit <<= 1)
+        for (const auto& n : need)
+            if (n.on && n.poison == bit && (c->debug_poison & bit)) HIP_TRY(hipMemsetAsync(n.b->p, 0xFF, bit == 32 ? nc * 8 : n.bytes, c->stream));
+    return PP_OK;
+}
+// ---- argument blocks of the transform (xa) and of everything behind it (fa) ----
+static void fill_args(Chunk& k) {
+    pp_ctx* c = k.c; const pp_fit_in* in = k.in; const pp_fit_out* out = k.out; pp_ctx::WorkSet& W = *k.W; const FlowPlan& p = k.p;
+    const int ns = k.ns, C = k.C, s0 = k.s0;
+    XspecArgs& xa = k.xa;
+    memset(&xa, 0, sizeof xa);
+    xa.data = k.ddata; xa.mft = (const cplx* const*)c->mft_table.p; xa.mft0 = c->slots[0].mft.as<cplx>();
+    xa.ktab = (const int* const*)c->kt_table.p; xa.kt0 = c->slots[0].kt.as<int>(); xa.slot = in->model_slot ? k.d.slot : nullptr;
+    xa.X = c->X.as<cplx>(); xa.sdraw = W.sdraw.as<double>(); xa.noise = W.noise.as<double>();
+    xa.twB = k.tw; xa.nsub = ns; xa.nchan = C; xa.Kt = k.Kt; xa.Xs = (int)p.Xs;
+    xa.x0 = k.d.x0; xa.P = k.d.P; xa.nu_fit = k.d.nufit;
+    xa.freqs = k.d.freqs; xa.freqs_stride = in->freqs_stride ? C : 0;
+    xa.csum0 = W.csum.as<double>(); xa.tay = W.tay.as<double>(); xa.ph0 = W.ph0.as<double>();
+    xa.act = nullptr; xa.cstep = 1; xa.coff = 0; xa.nchan_full = C; xa.x_f32 = p.xf32 ? 1 : 0;
+    FitArgs& fa = k.fa;
+    memset(&fa, 0, sizeof fa);
+    fa.nsub = ns; fa.nchan = C; fa.nbin = k.B; fa.M = p.M; fa.Kt = k.Kt; fa.Xs = (int)p.Xs;
+    for (int j = 0; j < 5; ++j) fa.flags[j] = in->fit_flags[j] ? 1 : 0;
+    fa.log10_tau = in->log10_tau ? 1 : 0; fa.option = in->option; fa.is_toa = in->is_toa ? 1 : 0;
+    fa.max_iter = c->max_iter; fa.scat = k.scat ? 1 : 0; fa.method = in->method; fa.X = c->X.as<cplx>();
+    fa.mft = (const cplx* const*)c->mft_table.p; fa.msq = (const double* const*)c->msq_table.p;
+    fa.msum = (const double* const*)c->msum_table.p; fa.ktab = (const int* const*)c->kt_table.p;
+    fa.slot = in->model_slot ? k.d.slot : nullptr;
+    fa.freqs = k.d.freqs; fa.freqs_stride = in->freqs_stride ? C : 0;
+    fa.wts = W.wts.as<double>(); fa.sdraw = W.sdraw.as<double>();
+    fa.P = k.d.P; fa.nu_fit = k.d.nufit; fa.nu_out = k.d.nuout;
+    fa.x0 = k.d.x0; fa.st = W.state.as<SubState>(); fa.csum = W.csum.as<double>(); fa.ncs = p.ncs; fa.tay = W.tay.as<double>();
+    fa.partial = W.partial.as<double>(); fa.nchunk = p.nchunk; fa.cpc = p.cpc; fa.nactive = W.misc.as<int>();
+    const OutBlock o(W.o_pack.p, ns);
+    fa.o_params = o.params; fa.o_errs = o.errs; fa.o_nu = o.nu; fa.o_cov = o.cov; fa.o_chi2 = o.chi2; fa.o_rchi2 = o.rchi2;
+    fa.o_snr = o.snr; fa.o_nfev = o.nfev; fa.o_rc = o.rc; fa.o_npass = o.npass;
+    // (per-channel outputs: straight into the caller's device arrays, or into work buffers that are copied out)
+    auto chan = [&](double* user, const DevBuf& b) { return !user ? nullptr : k.chan_dev ? user + (size_t)s0 * C : b.as<double>(); };
+    fa.o_scales = chan(out->scales, W.o_scales); fa.o_scale_errs = chan(out->scale_errs, W.o_serrs); fa.o_csnr = chan(out->channel_snrs, W.o_csnr);
+    fa.o_f0 = W.o_f0.as<double>(); fa.o_g0 = W.o_g0.as<double>(); fa.o_H0 = W.o_H0.as<double>();
+    fa.o_rec = out->records_dev ? out->records_dev + (size_t)s0 * PP_RECORD_WIDTH : nullptr;
+    fa.act = nullptr; fa.nact = ns; fa.nchan_x = C; fa.cstep = 1; fa.coff = 0;
+    fa.mdl = W.mdl.as<double>(); fa.use_model = p.smodel ? 1 : 0; fa.model_tol = c->scat_model_tol; fa.model_bet = c->scat_model_bet;
+    // (a GM fit walked the SciPy way ends where its path ends: it keeps the exact path; the
+    // Newton solver converges to the optimum from anywhere)
+    fa.recentre = (p.taylor && p.xmom && (!in->fit_flags[2] || in->method == PP_METHOD_NEWTON))
+                      ? std::max(0, c->taylor_recentre) : 0;
+    fa.x0w = k.d.x0; fa.x_f32 = p.xf32 ? 1 : 0; fa.nfev_shadow = c->nfev_shadow;
+    // (LDS: 32 B per cached channel, 512 channels per wave of the block keep the CU's eight waves within 128 KB)
+    fa.solve_cache = std::min(C, c->solve_cache >= 0 ? c->solve_cache : std::min(PP_SOLVE_CACHE_MAX, p.solve_nt * 8));
+    // what the device grants a workgroup (160 KB on gfx950; 64 KB on older parts) less the kernel's static scratch
+    // bounds the cache: a smaller cache only means more channels' invariants formed again per evaluation
+    if (!c->max_lds_bytes) {
+        hipDeviceProp_t prop;
+        c->max_lds_bytes = (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.sharedMemPerBlock > 0)
+                               ? (int)std::min<size_t>(prop.sharedMemPerBlock, (size_t)1 << 30) : 64 * 1024;
+    }
+    fa.solve_cache = std::min(fa.solve_cache, std::max(0, c->max_lds_bytes - 16 * 1024) / 32);
+}
+static int run_xspec(Chunk& k, const XspecArgs& x, int mode) {
+    pp_ctx* c = k.c;
+    Prof pr(c, KF_XSPEC);
+    if (k.p.anyb) return launch_any(c, x, k.B, k.p.M, k.in->data_dtype, mode, k.p.noise_tail, nullptr, c->skip_masked ? k.d_mask : nullptr);
+    PP_DISPATCH_M(k.p.M, { with_dtype(k.in->data_dtype, [&](auto t) { launch_xspec<MM, decltype(t)>(c, x, k.p.noise_tail, mode); }); });
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+static int run_prep(Chunk& k) {
+    pp_ctx* c = k.c;
+    Prof pr(c, KF_PREP);
+    hipLaunchKernelGGL(k_prep, dim3((unsigned)((k.nc + 255) / 256)), dim3(256), 0, c->stream, k.ns, k.C, k.B,
+                       k.d_errs, k.W->noise.as<double>(), k.d_mask, k.W->wts.as<double>());
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+// seed the subints f lists (f.act / f.nact, channels f.coff + nn f.cstep) from the
+// cross-spectrum in f.X; seedq (optional) receives the peak significance
+static int run_seed(Chunk& k, const FitArgs& f, double* seedq) {
+    pp_ctx* c = k.c;
+    const int ns = k.ns, Ks = k.p.Ks, ndm = k.p.ndm, seed_ns = k.p.seed_ns; double* const d_x0 = k.d.x0; int rc;
+    if ((rc = c->seedbuf.reserve(((size_t)f.nact * f.nchunk + f.nact) * Ks * sizeof(cplx)))) return rc;
+    cplx* ypart = c->seedbuf.as<cplx>();
+    cplx* ywork = ypart + (size_t)f.nact * f.nchunk * Ks;
+    Prof pr(c, KF_SEED);
+    const double* xbase = d_x0;
+    if (ndm > 1) {
+        // trial DMs: peak heights only, then the refined DM of every subint, then
+        // the seed proper at that DM
+        if ((rc = c->xbase.reserve((size_t)ns * 80 + (size_t)ns * ndm * 8))) return rc;
+        double* xb = c->xbase.as<double>();          // [ns][5] guesses as given
+        double* xr = xb + (size_t)ns * 5;            // [ns][5] with the chosen DM
+        double* pk = xr + (size_t)ns * 5;            // [ns][ndm]
+        HIP_TRY(hipMemcpyAsync(xb, d_x0, (size_t)ns * 40, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(xr, d_x0, (size_t)ns * 40, hipMemcpyDeviceToDevice, c->stream));
+        for (int t = 0; t < ndm; ++t) {
+            const double off = (t - (ndm - 1) / 2) * c->seed_dm_step;
+            hipLaunchKernelGGL(k_seed_accum, dim3(f.nact, f.nchunk), dim3(256), 0, c->stream, f, ypart, Ks,
+                               (const double*)xb, off);
+            hipLaunchKernelGGL(k_seed_fit, dim3(f.nact), dim3(256), 0, c->stream, f, (const cplx*)ypart, ywork,
+                               d_x0, seed_ns, Ks, (double*)nullptr, (const double*)xb, off,
+                               pk, t, ndm);
+        }
+        hipLaunchKernelGGL(k_seed_dm_pick, dim3((f.nact + 63) / 64), dim3(64), 0, c->stream, f.act, f.nact,
+                           (const double*)pk, ndm, c->seed_dm_step, (const double*)xb, xr);
+        xbase = xr;
+    }
+    hipLaunchKernelGGL(k_seed_accum, dim3(f.nact, f.nchunk), dim3(256), 0, c->stream, f, ypart, Ks, xbase, 0.0);
+    hipLaunchKernelGGL(k_seed_fit, dim3(f.nact), dim3(256), 0, c->stream, f, (const cplx*)ypart, ywork,
+                       d_x0, seed_ns, Ks, seedq, xbase, 0.0, (double*)nullptr, 0, 1);
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+// list the subints that need more work into W.act; returns their number
+static int list_active(Chunk& k, const double* seedq, double qmin, int* count) {
+    pp_ctx* c = k.c; pp_ctx::WorkSet& W = *k.W;
+    hipLaunchKernelGGL(k_list_active, dim3(1), dim3(256), 0, c->stream, (const SubState*)W.state.p, seedq, qmin,
+                       k.ns, W.act.as<int>(), W.misc.as<int>() + 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->nactive_h + 1, W.misc.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *count = c->nactive_h[1];
+    return PP_OK;
+}
+// transform every channel of the listed subints again with the cross-spectrum
+// stored (compact in the list index), and point the evaluators at the list
+static int store_x_for_list(Chunk& k, int count) {
+    pp_ctx* c = k.c; pp_ctx::WorkSet& W = *k.W; FitArgs& fa = k.fa; int rc;
+    if ((rc = c->X.reserve((size_t)count * k.C * k.p.Xs * sizeof(cplx)))) return rc;
+    XspecArgs xl = k.xa;
+    xl.X = c->X.as<cplx>(); xl.act = W.act.as<int>(); xl.nsub = count;
+    if ((rc = run_xspec(k, xl, 0))) return rc;
+    fa.X = c->X.as<cplx>(); fa.act = W.act.as<int>(); fa.nact = count;
+    chunking(k.C, fa.nchunk, fa.cpc);
+    if ((rc = W.partial.reserve((size_t)k.ns * fa.nchunk * PP_NACC * 8))) return rc;
+    fa.partial = W.partial.as<double>();
+    return PP_OK;
+}
+// the pending tail rides in the transform `x` launches: its argument block, by the staging copy of this batch's stage
+static int carrier_block(Chunk& k, XspecArgs& x) {
+    pp_ctx* c = k.c; pp_ctx::PendingTail& pt = c->ptail; int rc;
+    const int st_i = c->cur_stage;
+    const size_t tb = (sizeof(TailArgs) + 7) & ~(size_t)7;
+    if ((rc = c->tailbuf[st_i].reserve(tb))) return rc;
+    if (!c->tail_host[st_i]) HIP_TRY(hipHostMalloc(&c->tail_host[st_i], tb, hipHostMallocDefault));
+    TailArgs* th = reinterpret_cast<TailArgs*>(c->tail_host[st_i]);
+    memset(th, 0, tb);
+    th->fa = pt.fa; th->ticket = 0; th->done = 0; th->nsub = pt.ns;
+    th->fa.solve_cache = std::min(pt.C, (int)PP_TAIL_CACHE);
+    th->fa.tail_fused = 1;
+    th->solve_nt = pt.solve_nt; th->solve_pf = pt.solve_pf0 ? 0 : PP_SOLVE_PF; th->fin_nt = pt.fin_nt;
+    th->rs = pt.rs;
+    if ((rc = staged_copy(c, c->tailbuf[st_i].p, th, tb, hipMemcpyHostToDevice))) return fail(rc, "tail block copy failed");
+    x.tail = c->tailbuf[st_i].as<TailArgs>();
+    x.tail_nsub = pt.ns;
+    return PP_OK;
+}
+// ... and behind the carrying transform: the carried batch's outputs and its event
+static int carrier_done(Chunk& k) {
+    pp_ctx* c = k.c; pp_ctx::PendingTail& pt = c->ptail;
+    int r2 = queue_outputs(c, pt.stage, &pt.out, pt.s0, pt.ns, pt.C, pt.chan_dev, pt.copy_bytes, c->stream);
+    if (!r2 && hipEventRecord(c->stage[pt.stage].done, c->stream) != hipSuccess) r2 = fail(PP_EHIP, "hipEventRecord failed");
+    pt.valid = false;
+    if (r2) fail_pending_stage(c, pt.stage, r2);
+    return r2;
+}
+// hand-over from the transform stage (on `stream`) to the solve / post-fit stage (on `sp`), once per batch
+static int chain_post(Chunk& k) {
+    pp_ctx* c = k.c;
+    if (k.sp == c->stream || k.chained) return PP_OK;
+    HIP_TRY(hipEventRecord(k.W->xdone, c->stream));
+    HIP_TRY(hipStreamWaitEvent(k.sp, k.W->xdone, 0));
+    if (c->eager_flush) (void)hipStreamQuery(c->stream);
+    k.chained = true;
+    return PP_OK;
+}
+// ---- phase seed from a pilot pass ----
+static int run_pilot(Chunk& k) {
+    pp_ctx* c = k.c; const FlowPlan& p = k.p; FitArgs& fa = k.fa;
+    const int ns = k.ns, C = k.C, Cp = (C + p.cstep - 1) / p.cstep; int rc;
+    if ((rc = c->X.reserve((size_t)ns * Cp * p.Xs * sizeof(cplx)))) return rc;
+    if ((rc = c->seedq.reserve((size_t)ns * 8))) return rc;
+    XspecArgs xp = k.xa;
+    xp.X = c->X.as<cplx>(); xp.nchan = Cp; xp.cstep = p.cstep;
+    if ((rc = run_xspec(k, xp, 0))) return rc;
+    if ((rc = run_prep(k))) return rc;      // (rows not transformed yet have no measured noise: unused here)
+    FitArgs fp = fa;
+    fp.X = c->X.as<cplx>(); fp.nchan_x = Cp; fp.cstep = p.cstep;
+    chunking(Cp, fp.nchunk, fp.cpc);
+    if ((rc = run_seed(k, fp, c->seedq.as<double>()))) return rc;
+    // (reference-seed flow: the pilot's phase is only the expansion point of the Taylor model, which the
+    // certificate guards -- a weak pilot costs its subint a second expansion, not the batch a host round trip)
+    int nweak = 0;
+    if (!p.refseed) if ((rc = list_active(k, c->seedq.as<double>(), c->seed_min_snr, &nweak))) return rc;
+    if (nweak > 0) {
+        // not convincing on a subset: seed these from all their channels
+        if ((rc = store_x_for_list(k, nweak))) return rc;
+        if ((rc = run_prep(k))) return rc;
+        if ((rc = run_seed(k, fa, nullptr))) return rc;
+        fa.act = nullptr; fa.nact = ns; fa.nchunk = p.nchunk; fa.cpc = p.cpc;
+    }
+    return PP_OK;
+}
+// ---- reference-seed flow: Taylor model about the pilot's phase + the rotated channel sums in
+// one pass, then the reference's fit_phase_shift on the channel mean, then the start points
+static int run_refseed_pass(Chunk& k) {
+    pp_ctx* c = k.c; const pp_fit_in* in = k.in; const pp_seed_ref* rs = in->ref_seed; pp_ctx::WorkSet& W = *k.W; FitArgs& fa = k.fa;
+    const int ns = k.ns, C = k.C, M = k.p.M; const size_t nc = k.nc; const bool scat = k.scat; int rc;
+    const int ncc = C / PP_ROW_CHUNK;
+    const size_t H = (size_t)M + 1;
+    const size_t nprof = rs->model_prof_stride ? (size_t)ns : 1;
+    const bool w_host = (rs->weights && !in->aux_on_device) || k.d_mask;     // (room for the masked weights)
+    const size_t n_part = (size_t)ns * ncc * RS_NACC * 64;
+    const size_t n_cplx = n_part + (size_t)ns * H + nprof * H + (size_t)ns * M;
+    const size_t n_dbl = (size_t)ns * (1 + 1 + 7) + (w_host ? nc : 0);
+    if ((rc = W.refbuf.reserve(n_cplx * sizeof(cplx) + n_dbl * 8))) return rc;
+    cplx* part = W.refbuf.as<cplx>();
+    cplx* dspec = part + n_part;
+    cplx* mspec = dspec + (size_t)ns * H;
+    cplx* xwork = mspec + nprof * H;
+    // (the model profile(s), nu_mean and the host-formed part of the start points came with the batch's one
+    // input block: no copy command of their own)
+    double* d_delta = reinterpret_cast<double*>(xwork + (size_t)ns * M);
+    double* d_wsum = d_delta + ns;
+    double* d_out7 = d_wsum + ns;
+    double* d_wh = d_out7 + (size_t)ns * 7;
+    const double* d_w = nullptr;
+    if (rs->weights && !in->aux_on_device) {
+        HIP_TRY(hipMemcpyAsync(d_wh, rs->weights + (size_t)k.s0 * C, nc * 8, hipMemcpyHostToDevice, c->stream));
+        d_w = d_wh;
+    } else if (rs->weights) d_w = rs->weights + (size_t)k.s0 * C;
+    if (k.d_mask) {
+        // the channel mean is taken over the channels the fit uses
+        hipLaunchKernelGGL(k_refseed_weights, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, d_w, k.d_mask,
+                           (long long)nc, d_wh);
+        d_w = d_wh;
+    }
+    const long long nrows = (long long)ns * C;
+    XspecArgs x = k.xa;
+    draw_tickets(c, x, nrows);
+    x.mwords = k.mw_sub;
+    RefSeedArgs ra{d_w, part, ncc};
+    // what the guess needs beside the pass's channel sums does not depend on the pass: the template profile's
+    // spectrum, Delta_i and the summed weights -- queued in front of it (the expansion points are the pilot's)
+    {
+        Prof pr(c, KF_PREP);
+        hipLaunchKernelGGL((k_rfft_rows<1024, double>), dim3(fft_grid(64, (long long)nprof)), dim3(64), 0, c->stream,
+                           (const void*)k.d.rs_mprof, mspec, k.tw, (int)nprof);
+        hipLaunchKernelGGL(k_refseed_prep, dim3(ns), dim3(256), 0, c->stream, (const double*)k.d.x0, (const double*)k.d.P,
+                           (const double*)k.d.nufit, (const double*)k.d.rs_numean, d_w, C, d_delta, d_wsum);
+    }
+    HIP_TRY(hipGetLastError());
+    // (the previous batch's tail rides in this pass if it can: fit_chunk has flushed one that cannot)
+    const bool carrier = c->ptail.valid;
+    if (carrier) if ((rc = carrier_block(k, x))) return rc;
+    {
+        Prof pr(c, KF_XSPEC);
+        with_dtype(in->data_dtype, [&](auto t) {
+            with_flag(scat, [&](auto ST) {
+                auto kernel = k_xspec_qr1024<decltype(t), decltype(ST)::value>;
+                const dim3 grid(resident_grid(c, kernel, 64, nrows, fft_grid(64, nrows)));
+                hipLaunchKernelGGL(kernel, grid, dim3(64), 0, c->stream, x, ra);
+            });
+        });
+    }
+    HIP_TRY(hipGetLastError());
+    if (carrier) if ((rc = carrier_done(k))) return rc;
+    // the guess's finish: the spectrum from the chunk partials, the reference's fit_phase_shift, the start points
+    RefTailArgs& r = k.rs_tail;
+    memset(&r, 0, sizeof r);
+    r.on = 1; r.ncc = ncc; r.part = part; r.delta = d_delta; r.wsum = d_wsum;
+    r.mws = k.mw_sub; r.mspec = mspec; r.mstride = rs->model_prof_stride ? (int)H : 0;
+    r.fps = FpsArgs{nullptr, nullptr, d_out7, rs->lo, rs->hi, rs->Ns, M, ns, rs->finish, nullptr, r.mstride};
+    r.xs = k.d.rs_xs;
+    r.seed_phase = k.d_seedph = OutBlock(W.o_pack.p, ns).seed_phase;      // (leaves with the outputs)
+    if (k.p.leaves_tail && !scat) {
+        // this batch's own guess waits with its solve and post-fit stage for the next batch's transform (or flush_tail)
+        k.rs_tail_dspec = dspec; k.rs_tail_xwork = xwork;
+        fa.xstart = r.xs;
+        return PP_OK;
+    }
+    // (what follows the pass -- the channel mean's spectrum, the reference's fit_phase_shift, the start points --
+    // belongs to the solve stage: beside the next batch's transform when the batch is deferred.  The mask words
+    // the finish reads are the transform stage's buffer: a deferred batch has its own copy)
+    if ((rc = chain_post(k))) return rc;
+    if ((rc = queue_refseed_finish(c, r, ns, dspec, xwork, k.sp, false))) return rc;
+    if (scat) {
+        // stored cross-spectrum: the iteration starts AT the reference's guess
+        HIP_TRY(hipMemcpyAsync(k.d.x0, r.xs, (size_t)ns * 40, hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(k_init_state, dim3((ns + 63) / 64), dim3(64), 0, c->stream, fa);
+        HIP_TRY(hipGetLastError());
+    } else fa.xstart = r.xs;       // Taylor model about the pilot's phase: the walk starts off-centre
+    return PP_OK;
+}
+// ---- rFFT + cross-spectrum (or the Taylor model) of every row ----
+// one launch in front of it: phi_n at the initial parameters, the weights when the noise is
+// given, the solver state (a full seed rewrites x0 after the transform: state set then)
+static int run_transform(Chunk& k) {
+    pp_ctx* c = k.c; pp_ctx::WorkSet& W = *k.W; const FlowPlan& p = k.p; FitArgs& fa = k.fa;
+    const int ns = k.ns; const size_t nc = k.nc; const bool wts_early = (k.d_errs != nullptr); int rc;
+    {
+        Prof pr(c, KF_PREP);
+        hipLaunchKernelGGL(k_setup, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, fa,
+                           wts_early ? k.d_errs : (const double*)nullptr, k.d_mask, W.wts.as<double>(),
+                           p.want_ph0 ? W.ph0.as<double>() : (double*)nullptr,
+                           p.fuse_scat ? W.ph0.as<double>() + nc : (double*)nullptr, p.seed_full ? 0 : 1);
+    }
+    XspecArgs x = k.xa;
+    x.mwords = k.mw_main;
+    if (p.refseed) {
+        if ((rc = run_refseed_pass(k))) return rc;
+    } else if (p.seed_full) {
+        // the seed needs the cross-spectrum at a phase not known yet: store it, seed,
+        // then take the Taylor moments (or iterate) in a second pass over it
+        if ((rc = run_xspec(k, x, 0))) return rc;
+        if (!wts_early) if ((rc = run_prep(k))) return rc;
+        if ((rc = run_seed(k, fa, nullptr))) return rc;
+        hipLaunchKernelGGL(k_init_state, dim3((ns + 63) / 64), dim3(64), 0, c->stream, fa);
+    } else if (p.fuse_scat) {
+        const long long nrows = (long long)ns * k.C;
+        draw_tickets(c, x, nrows);
+        {
+            Prof pr(c, KF_XSPEC);
+            with_dtype(k.in->data_dtype, [&](auto t) {
+                auto kernel = k_xspec_qs1024<decltype(t)>;
+                const dim3 grid(resident_grid(c, kernel, 64, nrows, fft_grid(64, nrows)));
+                hipLaunchKernelGGL(kernel, grid, dim3(64), 0, c->stream, x, (const double*)(W.ph0.as<double>() + nc), W.csum.as<double>());
+            });
+        }
+        if (!wts_early) if ((rc = run_prep(k))) return rc;
+    } else {
+        // (the previous enqueued batch's tail rides in this transform if it can: fit_chunk has flushed one that cannot)
+        const bool carrier = c->ptail.valid;
+        if (carrier) if ((rc = carrier_block(k, x))) return rc;
+        if ((rc = run_xspec(k, x, p.xmode))) return rc;
+        if (carrier) if ((rc = carrier_done(k))) return rc;
+        if (!wts_early) if ((rc = run_prep(k))) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    if (c->eager_flush) (void)hipStreamQuery(c->stream);
+    return PP_OK;
+}
+// ---- post-fit stage + every output in one round trip ----
+static int finalize_and_fetch(Chunk& k, bool wait = true) {
+    pp_ctx* c = k.c;
+    FitArgs ff = k.fa; int rc;
+    ff.act = nullptr; ff.nact = k.ns;
+    {
+        Prof pr(c, KF_FINAL, k.sp);
+        finalize_launch(c, ff, k.ns, k.C, k.sp);
+    }
+    HIP_TRY(hipGetLastError());
+    if ((rc = queue_outputs(c, c->cur_stage, k.out, k.s0, k.ns, k.C, k.chan_dev, k.copy_bytes(), k.sp))) return rc;
+    if (c->eager_flush && k.sp != c->stream) (void)hipStreamQuery(k.sp);
+    if (wait) HIP_TRY(hipStreamSynchronize(k.sp));
+    return PP_OK;
+}
+static void unpack_outputs(Chunk& k) {
+    unpack_stage(k.sg->o_host, k.out, k.s0, k.ns);
+    if (k.d_seedph) unpack_seed_phases(k.sg->o_host, k.in, k.s0, k.ns);
+}
+// ---- the one-pass flow: solve on the Taylor model.  *more: -1 = the chunk needs nothing more from fit_chunk (its outputs
+// are unpacked, or it stays queued: *k.deferred), 0 = every subint certified after all, 1 = evaluations are needed
+static int run_taylor(Chunk& k, int* more) {
+    pp_ctx* c = k.c; pp_ctx::WorkSet& W = *k.W; const FlowPlan& p = k.p; FitArgs& fa = k.fa;
+    const int ns = k.ns, C = k.C; int rc;
+    *more = -1;
+    if (p.xstore) {
+        Prof pr(c, KF_EVAL);
+        hipLaunchKernelGGL(k_eval_moments, dim3(ns, p.nchunk), dim3(256), 0, c->stream, fa);
+    }
+    if (p.leaves_tail) {
+        // nothing of the tail is queued: the next enqueued batch's transform works it off (or flush_tail does)
+        pp_ctx::PendingTail& pt = c->ptail;
+        pt.valid = true; pt.stage = c->cur_stage;
+        pt.fa = fa; pt.fa.act = nullptr; pt.fa.nact = ns;
+        pt.ns = ns; pt.C = C; pt.solve_nt = p.solve_nt; pt.solve_pf0 = solve_rows_in_turn(c, C, p.solve_nt) ? 1 : 0;
+        pt.fin_nt = finalize_width_taken(c, pt.fa, C);
+        pt.out = *k.out; pt.s0 = k.s0; pt.chan_dev = k.chan_dev; pt.copy_bytes = k.copy_bytes();
+        pt.rs = k.rs_tail; pt.rs_dspec = k.rs_tail_dspec; pt.rs_xwork = k.rs_tail_xwork;
+        *k.deferred = true;
+        return PP_OK;
+    }
+    if ((rc = chain_post(k))) return rc;
+    {
+        Prof pr(c, KF_TAYLOR, k.sp);
+        // (rows of the Taylor model in registers where the channel count allows)
+        solve_launch(c, fa, ns, C, p.solve_nt, k.sp);
+    }
+    HIP_TRY(hipGetLastError());
+    // The solve certifies nearly every subint of nearly every batch: the post-fit stage is
+    // launched straight behind it and the count of unfinished subints comes back with the
+    // outputs -- one host round trip per batch instead of two.  (When some are left, what
+    // the post-fit stage wrote for them is overwritten below.)
+    if (p.defer_ok) {
+        // nothing left for the host to decide before the outputs are on their way: pp_fit_collect
+        // looks at the count of unfinished subints (and fits the batch again, synchronously, in the
+        // rare case that some are left -- their guesses were poor)
+        if ((rc = finalize_and_fetch(k, false))) return rc;
+        *k.deferred = true;
+        return PP_OK;
+    }
+    if ((rc = finalize_and_fetch(k))) return rc;
+    bool all_done = (unfinished_in_stage(k.sg->o_host, ns) <= 0);
+    if (all_done) { unpack_outputs(k); return PP_OK; }
+    // (reference-seed flow: a subint whose walk left the model taken about the pilot's phase is
+    // expanded again about the reference's guess itself -- the ordinary flow from there)
+    const int nrep = std::max(fa.recentre, p.refseed ? 1 : 0);
+    for (int rep = 0; rep < nrep && !all_done; ++rep) {
+        // some subints failed the certificate (poor guesses): k_taylor_solve moved
+        // their expansion points to its tentative answers -- take the Taylor model of
+        // THOSE again (one more pass over their rows, nothing stored) and solve again
+        int nleft = 0;
+        if ((rc = list_active(k, nullptr, 0.0, &nleft))) return rc;
+        {
+            Prof pr(c, KF_PREP);
+            hipLaunchKernelGGL(k_phase0, dim3((unsigned)((k.nc + 255) / 256)), dim3(256), 0, c->stream, ns, C,
+                               k.xa.x0, k.xa.P, k.xa.nu_fit, k.xa.freqs, k.xa.freqs_stride, W.ph0.as<double>());
+        }
+        XspecArgs xl = k.xa;
+        xl.act = W.act.as<int>(); xl.nsub = nleft;
+        if ((rc = run_xspec(k, xl, p.xmode))) return rc;
+        {
+            Prof pr(c, KF_TAYLOR);
+            solve_launch(c, fa, ns, C, p.solve_nt, k.sp);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->nactive_h, fa.nactive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        all_done = (c->nactive_h[0] <= 0);
+    }
+    if (!all_done && !p.xstore) {
+        // still not certified: they need evaluations over the cross-spectrum, which
+        // was not stored -- transform THOSE again, keeping it
+        int nleft = 0;
+        if ((rc = list_active(k, nullptr, 0.0, &nleft))) return rc;
+        if ((rc = store_x_for_list(k, nleft))) return rc;
+    }
+    *more = all_done ? 0 : 1;
+    return PP_OK;
+}
+// ---- Newton solver on a scattering fit: the iteration on every 16th channel first (FlowPlan::coarse) ----
+static int run_coarse_newton(Chunk& k) {
+    pp_ctx* c = k.c;
+    FitArgs fs = k.fa;
+    fs.cstep = kCoarseStep; fs.coff = 0; fs.nchan_x = (k.C + kCoarseStep - 1) / kCoarseStep; fs.x_full = 1; fs.use_model = 0;
+    chunking(fs.nchan_x, fs.nchunk, fs.cpc);
+    // (a fixed number of iterations, no host check: subints that are done cost their kernels nothing)
+    for (int it = 0; it < std::min(12, c->max_iter + 1); ++it) {
+        { Prof pr(c, KF_EVAL);
+          hipLaunchKernelGGL((k_eval_scat<8, false>), dim3(fs.nact, fs.nchunk), dim3(256), 0, c->stream, fs); }
+        { Prof pr(c, KF_STEP);
+          hipLaunchKernelGGL(k_step, dim3(fs.nact), dim3(64), 0, c->stream, fs); }
+    }
+    hipLaunchKernelGGL(k_adopt_coarse, dim3((k.ns + 63) / 64), dim3(64), 0, c->stream, k.fa);
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+// ---- trust-region iterations: evaluation + step, until every subint is done
+static int run_evaluations(Chunk& k, int max_evals) {
+    pp_ctx* c = k.c; const FlowPlan& p = k.p; const FitArgs& fa = k.fa;
+    const bool scat = k.scat; int rc;
     int pending = -1;           // slot of the lagged check in flight
     for (int it = 0; it < max_evals; ++it) {
-        if (it == 0 && fuse) {
+        if (it == 0 && p.fuse) {
             Prof pr(c, KF_ACCUM);
             hipLaunchKernelGGL(k_accum, dim3(fa.nact, fa.nchunk), dim3(256), 0, c->stream, fa);
         } else {
@@ -1795,7 +1767,7 @@ static int fit_chunk(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, int s0, in
             else if (scat) hipLaunchKernelGGL((k_eval_scat<8, false>), eg, dim3(256), 0, c->stream, fa);
             else hipLaunchKernelGGL(k_eval_fast, dim3(fa.nact, fa.nchunk), dim3(256), 0, c->stream, fa);
         }
-        if (smodel && it >= 2) {
+        if (p.smodel && it >= 2) {
             // subints whose last proposal asked for it: this evaluation is the model
             // pass, and the rest of their iterations run on the model
             Prof pr(c, KF_SCATMODEL);
@@ -1807,7 +1779,8 @@ static int fit_chunk(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, int s0, in
             hipLaunchKernelGGL(k_step, dim3(fa.nact), dim3(64), 0, c->stream, fa);
         }
         HIP_TRY(hipGetLastError());
-        if (c->lagged_check && !smodel) {
+        const bool look = it >= p.check_from && ((it - p.check_from) % c->check_every) == 0;
+        if (c->lagged_check && !p.smodel) {
             // (measured on configs[3]: +5 % with the Newton solver; with the model pass in the loop
             // -0.8 %, so that flow keeps the synchronous check.)  The host looks at the count of unfinished subints ONE iteration behind: the count as
             // it stood after iteration it - 1 arrives while the GPU works on iteration it, so the
@@ -1819,21 +1792,54 @@ static int fit_chunk(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, int s0, in
                 if (c->nactive_h[2 + pending] <= 0) break;
                 pending = -1;
             }
-            if (it >= check_from && ((it - check_from) % c->check_every) == 0) {
+            if (look) {
                 const int slot = it & 1;
                 if ((rc = publish_int(c, c->nactive_h + 2 + slot, fa.nactive))) return fail(rc, "count copy failed");
                 HIP_TRY(hipEventRecord(c->evq[slot], c->stream));
                 pending = slot;
             }
-        } else if (it >= check_from && ((it - check_from) % c->check_every) == 0) {
+        } else if (look) {
             // (a copy command here: followed at once by a wait, it measured faster than the publishing kernel)
             HIP_TRY(hipMemcpyAsync(c->nactive_h, fa.nactive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             if (c->nactive_h[0] <= 0) break;
         }
     }
-    if ((rc = finalize_and_fetch())) return rc;
-    unpack_outputs();
+    return PP_OK;
+}
+
+// One sub-batch through its flow (FlowPlan), stage by stage.
+// `deferred` (pp_fit_enqueue): when non-null and the batch takes the one-pass flow without a host
+// decision in its middle, everything is queued -- outputs on their way to the staging block included --
+// and the call returns WITHOUT waiting (*deferred = true); pp_fit_collect finishes it.
+static int fit_chunk(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, int s0, int ns, int Kt, bool scat,
+                     const std::vector<double>& nufit_h, const std::vector<double>& nuout_h, bool* deferred = nullptr) {
+    Chunk k{};      // (zeros: no seed phases, no hand-over queued, no tail of its own, no mask words yet)
+    k.c = c; k.in = in; k.out = out; k.s0 = s0; k.ns = ns; k.C = in->nchan; k.B = in->nbin; k.Kt = Kt; k.scat = scat;
+    k.deferred = deferred; k.nc = (size_t)ns * in->nchan;
+    k.sg = &c->stage[c->cur_stage]; k.W = &c->work[c->cur_stage];
+    k.p = plan_flow(c, in, s0, Kt, scat, deferred != nullptr);
+    k.sp = k.p.post_stream2 ? c->stream2 : c->stream; k.chan_dev = out->chan_on_device != 0;
+    int rc;
+    if ((rc = get_twiddles(c, k.B, &k.tw))) return rc;
+    if ((rc = stage_inputs(k, nufit_h, nuout_h))) return rc;
+    c->last_post = k.sp;
+    if ((rc = reserve_work(k))) return rc;
+    fill_args(k);
+    // (a pending tail of the previous enqueued batch that this batch's transform will not carry -- any flow but the
+    // plain one-pass one and the reference-seed pass, or too small a batch -- goes out by the stand-alone kernels now;
+    // one that is still pending at the transform is carried by it)
+    if (c->ptail.valid && !carries_pending_tail(c, k.p, ns, k.C))
+        if ((rc = flush_tail(c))) return rc;
+    if (k.p.pilot) if ((rc = run_pilot(k))) return rc;
+    if ((rc = run_transform(k))) return rc;
+    int more = 1;      // (evaluations needed)
+    if (k.p.taylor) if ((rc = run_taylor(k, &more))) return rc;
+    if (more < 0) return PP_OK;
+    if (k.p.coarse && more) if ((rc = run_coarse_newton(k))) return rc;
+    if ((rc = run_evaluations(k, more ? std::max(1, c->max_iter + 1) : 0))) return rc;
+    if ((rc = finalize_and_fetch(k))) return rc;
+    unpack_outputs(k);
     return PP_OK;
 }
 
@@ -1875,9 +1881,9 @@ static int plan_batch(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, BatchPlan
         for (int i = 0; i < N; ++i) if (in->init_params[(size_t)i * 5 + 3] != 0.0) { scat = true; break; }
     if (in->ref_seed) {
         const pp_seed_ref* rs = in->ref_seed;
-        const int cstep = std::max(1, c->seed_chan_stride);
-        // (no scattering: Taylor model about the pilot seed's phase; scattering: cross-spectrum stored)
-        const bool path = scat ? true : (c->use_taylor && c->moments_in_xspec && cstep > 1 && C / cstep >= 16);
+        // (no scattering: Taylor model about the pilot seed's phase -- the flow's own pilot decision --; scattering:
+        // cross-spectrum stored)
+        const bool path = scat || plan_flow(c, in, 0, Kt, scat, false).pilot;
         bool ok = path && c->max_iter > 0 && c->one_exchange &&
                   B == 2048 && 2 * Kt < B / 2 && C % PP_ROW_CHUNK == 0 &&
                   in->errs && in->seed_ns == 0 && rs->model_profs && rs->nu_mean && rs->Ns >= 1 &&
@@ -1886,7 +1892,7 @@ static int plan_batch(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, BatchPlan
         if (!ok)
             return fail(PP_ENOTSUP, "ref_seed: no single-pass path for this batch (needs 2048-bin portraits, "
                                     "a template that keeps < 512 harmonics, nchan a multiple of %d (and >= %d without "
-                                    "scattering), errs given, GM guesses 0)", PP_ROW_CHUNK, 16 * cstep);
+                                    "scattering), errs given, GM guesses 0)", PP_ROW_CHUNK, 16 * std::max(1, c->seed_chan_stride));
     }
     // default reference frequencies: mean of the (unmasked) channel frequencies
     bp->nufit.assign((size_t)N * 3, 0.0);
@@ -1946,6 +1952,12 @@ static int plan_batch(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, BatchPlan
     return PP_OK;
 }
 
+// device time between two events of a finished batch into out->duration, when asked for
+static int set_duration(const pp_fit_out* out, hipEvent_t a, hipEvent_t b) {
+    float ms = 0.f;
+    if (out->duration) { HIP_TRY(hipEventElapsedTime(&ms, a, b)); out->duration[0] = 1e-3 * ms; }
+    return PP_OK;
+}
 // every sub-batch in turn, synchronously; device time of the whole into out->duration
 static int run_batch_sync(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, const BatchPlan& bp) {
     const int N = in->nsub;
@@ -1958,11 +1970,7 @@ static int run_batch_sync(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, const
     c->known_ok[bp.flow_key] = std::max(c->known_ok[bp.flow_key], bp.per_sub * std::min(bp.cap, N));
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
     HIP_TRY(hipEventSynchronize(c->ev1));
-    if (out->duration) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        out->duration[0] = 1e-3 * ms;
-    }
+    if (int rc = set_duration(out, c->ev0, c->ev1)) return rc;
     if (c->profile) resolve_spans(c);
     return PP_OK;
 }
@@ -1970,10 +1978,7 @@ static int run_batch_sync(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out, const
 extern "C" int pp_fit_portrait_batch(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out) {
     if (!c || !in || !out) return fail(PP_EINVAL, "pp_fit_portrait_batch: null argument");
     // a submitted batch owns the context (work buffers, stream, counters) until pp_fit_wait
-    if (c->job_active && t_worker_of != c)
-        return fail(PP_ESTATE, "pp_fit_portrait_batch: a submitted fit is pending on this context (pp_fit_wait first)");
-    if (!c->pending.empty())
-        return fail(PP_ESTATE, "pp_fit_portrait_batch: %zu enqueued batch(es) not collected yet (pp_fit_collect first)", c->pending.size());
+    if (int busy_ = ctx_busy(c, "pp_fit_portrait_batch")) return busy_;
     BatchPlan bp;
     int rc = plan_batch(c, in, out, &bp);
     if (rc) return rc;
@@ -2016,11 +2021,7 @@ extern "C" int pp_fit_enqueue(pp_ctx* c, const pp_fit_in* in, pp_fit_out* out) {
         if (!deferred) {
             // (a flow with host decisions in its middle: it has run to its end)
             HIP_TRY(hipEventSynchronize(sg.done));
-            if (out->duration) {
-                float ms = 0.f;
-                HIP_TRY(hipEventElapsedTime(&ms, sg.t0, sg.done));
-                out->duration[0] = 1e-3 * ms;
-            }
+            if ((rc = set_duration(out, sg.t0, sg.done))) return rc;
             if (c->profile) resolve_spans(c);
             d.span_end = 0;
         }
@@ -2056,11 +2057,7 @@ extern "C" int pp_fit_collect(pp_ctx* c) {
     if (unfinished_in_stage(sg.o_host, ns) <= 0) {
         unpack_stage(sg.o_host, &d.out, 0, ns);
         unpack_seed_phases(sg.o_host, &d.in, 0, ns);
-        if (d.out.duration) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, sg.t0, sg.done));
-            d.out.duration[0] = 1e-3 * ms;
-        }
+        if (int rcd = set_duration(&d.out, sg.t0, sg.done)) return rcd;
         if (c->profile) resolve_spans(c, d.span_end);
         return PP_OK;
     }
