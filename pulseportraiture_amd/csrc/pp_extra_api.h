@@ -10,29 +10,83 @@ static int aux_chunk_cap(pp_ctx* c, double per_sub, int nsub) {
     return (int)std::min<double>(nsub, std::max(1.0, std::floor(budget / std::max(per_sub, 1.0))));
 }
 
-extern "C" int pp_fit_phase_shift_batch(pp_ctx* c, const double* data, const double* model, const double* noise,
-                                        int nprof, int nbin, double lo, double hi, int Ns, double* out7) {
-    if (int busy_ = ctx_busy(c, "pp_fit_phase_shift_batch")) return busy_;
-    if (!c || !data || !model || !out7) return fail(PP_EINVAL, "pp_fit_phase_shift_batch: null argument");
-    if (!nbin_any_ok(nbin)) return nbin_refuse("pp_fit_phase_shift_batch", nbin);
-    const bool anyb = !nbin_ok(nbin);
-    if (nprof < 1) return fail(PP_EINVAL, "pp_fit_phase_shift_batch: bad shape %d x %d", nprof, nbin);
-    if (Ns < 1) return fail(PP_EINVAL, "pp_fit_phase_shift_batch: Ns %d", Ns);
-    HIP_TRY(hipSetDevice(c->device));
+// A run of whole subints (or rows) [s0, s0 + n) of a call's host arrays; at(p, per): where the run starts in an array
+// of `per` elements per subint (a null pointer stays null), so that no entry point offsets its own arguments
+struct Run {
+    int s0, n;
+    template <typename T>
+    T* at(T* p, size_t per) const { return p ? p + (size_t)s0 * per : nullptr; }
+};
+// body(Run) over [0, total) in runs of at most `cap`: the caller's figure, worked out once, before the first run
+template <typename F>
+static int for_runs(int total, int cap, F body) {
+    for (int s0 = 0; s0 < total; s0 += cap)
+        if (int rc = body(Run{s0, std::min(cap, total - s0)})) return rc;
+    return PP_OK;
+}
+
+// Portraits plus per-subint arrays, as four entry points take them (what InLayout is to the fit's input block): one
+// check, one staging, one way to cut a host input into runs
+struct Ports {
+    const void* src;
+    int dtype, on_device, nsub, nchan, nbin;
+    const double* freqs;
+    int64_t freqs_stride;
+    const double *P, *par;      // par: npar doubles per subint (phi, DM, GM or nu_ref; the five fitted parameters)
+    int npar;
+
+    size_t esz() const { return dtype == PP_F64 ? 8 : 4; }
+    size_t sub_bytes() const { return (size_t)nchan * nbin * esz(); }
+    // rest_ok: the entry point's other pointers are there; shape_ok: its other counts are positive
+    int validate(const char* who, bool rest_ok, bool shape_ok = true) const {
+        if (!rest_ok || !src || !freqs || !P || !par) return fail(PP_EINVAL, "%s: null argument", who);
+        if (!nbin_any_ok(nbin)) return nbin_refuse(who, nbin);
+        if (nsub < 1 || nchan < 1 || !shape_ok) return fail(PP_EINVAL, "%s: bad shape", who);
+        if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "%s: dtype %d", who, dtype);
+        if (freqs_stride != 0 && freqs_stride != nchan) return fail(PP_EINVAL, "freqs_stride must be 0 or nchan");
+        return PP_OK;
+    }
+    // how many subints of a host input go through the device at once (extra: device bytes per subint beside the portrait)
+    int cap(pp_ctx* c, double extra) const { return on_device ? nsub : aux_chunk_cap(c, (double)sub_bytes() + extra, nsub); }
+    Ports run(Run r) const {
+        return Ports{r.at((const char*)src, sub_bytes()), dtype, on_device, r.n, nchan, nbin, r.at(freqs, (size_t)freqs_stride),
+                     freqs_stride, r.at(P, 1), r.at(par, npar), npar};
+    }
+    // the portraits on the device (host ones through c->data), freqs -> c->freqs, P -> c->P, par -> c->x0
+    int stage(pp_ctx* c, const void** dsrc) const {
+        int rc;
+        *dsrc = src;
+        if (!on_device) {
+            if ((rc = upload(c, c->data, src, (size_t)nsub * sub_bytes()))) return rc;
+            *dsrc = c->data.p;
+        }
+        if ((rc = upload(c, c->freqs, freqs, (size_t)(freqs_stride ? (size_t)nsub * nchan : nchan) * 8))) return rc;
+        if ((rc = upload(c, c->P, P, (size_t)nsub * 8))) return rc;
+        return upload(c, c->x0, par, (size_t)nsub * npar * 8);
+    }
+};
+
+// 1 / nu^2 and 1 / nu^4 of a reference frequency, 0 for "none" (infinite)
+static double inv_nu2(double nu) { return std::isinf(nu) ? 0.0 : 1.0 / (nu * nu); }
+static double inv_nu4(double nu) { return std::isinf(nu) ? 0.0 : 1.0 / (nu * nu * nu * nu); }
+
+// the end of a call that fits n profiles between c->ev0 and now: seven columns each to the host, the last one the
+// span's time shared out among them
+static int fetch_out7(pp_ctx* c, int n, double* out7) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipMemcpyAsync(out7, c->o_params.p, (size_t)n * 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    for (int i = 0; i < n; ++i) out7[(size_t)i * 7 + 6] = 1e-3 * ms / n;
+    return PP_OK;
+}
+
+static int fit_phase_shift_run(pp_ctx* c, const double* data, const double* model, const double* noise, int nprof,
+                               int nbin, double lo, double hi, int Ns, double* out7) {
     const int M = nbin / 2;
     int rc;
-    {
-        const int cap = aux_chunk_cap(c, 2.0 * nbin * 8 + (2.0 * (M + 1) + M) * 16 + 64, nprof);
-        if (nprof > cap) {
-            for (int p0 = 0; p0 < nprof; p0 += cap) {
-                const int n = std::min(cap, nprof - p0);
-                if ((rc = pp_fit_phase_shift_batch(c, data + (size_t)p0 * nbin, model + (size_t)p0 * nbin,
-                                                   noise ? noise + p0 : nullptr, n, nbin, lo, hi, Ns, out7 + (size_t)p0 * 7)))
-                    return rc;
-            }
-            return PP_OK;
-        }
-    }
     // interleave rows: data_i, model_i
     const size_t rowb = (size_t)nbin * 8;
     if ((rc = c->data.reserve(2 * (size_t)nprof * rowb))) return rc;
@@ -41,25 +95,13 @@ extern "C" int pp_fit_phase_shift_batch(pp_ctx* c, const double* data, const dou
     if ((rc = c->X.reserve((size_t)nprof * (2 * (size_t)(M + 1) + M) * sizeof(cplx)))) return rc;
     if ((rc = c->o_params.reserve((size_t)nprof * 56))) return rc;
     const cplx* tw = nullptr;
-    if ((rc = get_twiddles(c, nbin, &tw))) return rc;
+    if ((rc = get_twiddles(c, nbin, &tw))) return rc;      // (a first use copies the table: not inside the timed span)
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     cplx* spec = c->X.as<cplx>();
     cplx* xwork = spec + 2 * (size_t)nprof * (M + 1);
     {
         Prof pr(c, KF_FPS);
-        if (anyb) {
-            // (row lengths without a tuned plan: the same spectra by the chirp-z path, pp_anybin.h)
-            XspecArgs xa;
-            memset(&xa, 0, sizeof xa);
-            xa.data = c->data.p; xa.nsub = 1; xa.nchan = 2 * nprof; xa.nchan_full = 2 * nprof; xa.cstep = 1;
-            if ((rc = launch_any(c, xa, nbin, ((M + 63) / 64) * 64, PP_F64, -1, false, spec, nullptr))) return rc;
-        } else {
-        PP_DISPATCH_M(M, {
-            const int T = FftPlan<MM>::T;
-            hipLaunchKernelGGL((k_rfft_rows<MM, double>), dim3(fft_grid(T, 2 * nprof)), dim3(T), 0, c->stream,
-                               (const void*)c->data.p, spec, tw, 2 * nprof);
-        });
-        }
+        if ((rc = rows_harmonics(c, c->data.p, PP_F64, 2 * nprof, nbin, spec))) return rc;
         const double* dnoise = nullptr;
         if (noise) {
             if ((rc = upload(c, c->errs, noise, (size_t)nprof * 8))) return rc;
@@ -68,67 +110,40 @@ extern "C" int pp_fit_phase_shift_batch(pp_ctx* c, const double* data, const dou
         FpsArgs fa{spec, dnoise, c->o_params.as<double>(), lo, hi, Ns, M, nprof, c->fps_finish, nullptr, M + 1};
         hipLaunchKernelGGL(k_fps, dim3(nprof), dim3(256), 0, c->stream, fa, xwork);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipMemcpyAsync(out7, c->o_params.p, (size_t)nprof * 56, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    for (int i = 0; i < nprof; ++i) out7[(size_t)i * 7 + 6] = 1e-3 * ms / nprof;
-    return PP_OK;
+    return fetch_out7(c, nprof, out7);
+}
+
+extern "C" int pp_fit_phase_shift_batch(pp_ctx* c, const double* data, const double* model, const double* noise,
+                                        int nprof, int nbin, double lo, double hi, int Ns, double* out7) {
+    if (int busy_ = ctx_busy(c, "pp_fit_phase_shift_batch")) return busy_;
+    if (!c || !data || !model || !out7) return fail(PP_EINVAL, "pp_fit_phase_shift_batch: null argument");
+    if (!nbin_any_ok(nbin)) return nbin_refuse("pp_fit_phase_shift_batch", nbin);
+    if (nprof < 1) return fail(PP_EINVAL, "pp_fit_phase_shift_batch: bad shape %d x %d", nprof, nbin);
+    if (Ns < 1) return fail(PP_EINVAL, "pp_fit_phase_shift_batch: Ns %d", Ns);
+    HIP_TRY(hipSetDevice(c->device));
+    const int M = nbin / 2;
+    return for_runs(nprof, aux_chunk_cap(c, 2.0 * nbin * 8 + (2.0 * (M + 1) + M) * 16 + 64, nprof), [&](Run r) {
+        return fit_phase_shift_run(c, r.at(data, nbin), r.at(model, nbin), r.at(noise, 1), r.n, nbin, lo, hi, Ns, r.at(out7, 7));
+    });
 }
 
 // ---- the reference's initial phase guess, data side fused --------------------
-extern "C" int pp_reference_phase_seed(pp_ctx* c, const void* src, int dtype, int on_device, int nsub, int nchan,
-                                       int nbin, const double* freqs, int64_t freqs_stride, const double* P,
-                                       const double* par3, double nu_DM, double nu_GM, const double* weights,
-                                       const double* model_profs, double lo, double hi, int Ns, double* out7) {
-    if (int busy_ = ctx_busy(c, "pp_reference_phase_seed")) return busy_;
-    if (!c || !src || !freqs || !P || !par3 || !weights || !model_profs || !out7)
-        return fail(PP_EINVAL, "pp_reference_phase_seed: null argument");
-    if (!nbin_any_ok(nbin)) return nbin_refuse("pp_reference_phase_seed", nbin);
+static int reference_phase_seed_run(pp_ctx* c, const Ports& in, double nu_DM, double nu_GM, const double* weights,
+                                    const double* model_profs, double lo, double hi, int Ns, double* out7) {
+    const int nsub = in.nsub, nchan = in.nchan, nbin = in.nbin, M = nbin / 2;
     const bool anyb = !nbin_ok(nbin);
-    if (nsub < 1 || nchan < 1 || Ns < 1) return fail(PP_EINVAL, "pp_reference_phase_seed: bad shape");
-    if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "pp_reference_phase_seed: dtype %d", dtype);
-    if (freqs_stride != 0 && freqs_stride != nchan) return fail(PP_EINVAL, "freqs_stride must be 0 or nchan");
-    HIP_TRY(hipSetDevice(c->device));
-    const int M = nbin / 2;
-    const size_t esz = dtype == PP_F64 ? 8 : 4;
-    const size_t sub_b = (size_t)nchan * nbin * esz;
+    const void* dsrc = nullptr;
     int rc;
-    if (!on_device) {
-        const int cap = aux_chunk_cap(c, (double)sub_b + 64.0 * nchan + 64.0 * nbin, nsub);
-        if (nsub > cap) {
-            for (int s0 = 0; s0 < nsub; s0 += cap) {
-                const int n = std::min(cap, nsub - s0);
-                if ((rc = pp_reference_phase_seed(c, (const char*)src + s0 * sub_b, dtype, 0, n, nchan, nbin,
-                                                  freqs + (freqs_stride ? (size_t)s0 * nchan : 0), freqs_stride, P + s0,
-                                                  par3 + (size_t)s0 * 3, nu_DM, nu_GM, weights + (size_t)s0 * nchan,
-                                                  model_profs + (size_t)s0 * nbin, lo, hi, Ns, out7 + (size_t)s0 * 7)))
-                    return rc;
-            }
-            return PP_OK;
-        }
-    }
-    const void* dsrc = src;
-    if (!on_device) {
-        if ((rc = c->data.reserve((size_t)nsub * sub_b))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->data.p, src, (size_t)nsub * sub_b, hipMemcpyHostToDevice, c->stream));
-        dsrc = c->data.p;
-    }
-    if ((rc = upload(c, c->freqs, freqs, (size_t)(freqs_stride ? (size_t)nsub * nchan : nchan) * 8))) return rc;
-    if ((rc = upload(c, c->P, P, (size_t)nsub * 8))) return rc;
-    if ((rc = upload(c, c->x0, par3, (size_t)nsub * 24))) return rc;
+    if ((rc = in.stage(c, &dsrc))) return rc;
     if ((rc = upload(c, c->wts, weights, (size_t)nsub * nchan * 8))) return rc;
     if ((rc = upload(c, c->errs, model_profs, (size_t)nsub * nbin * 8))) return rc;
     // runs of channels per subint: one partial spectrum per run, the runs added in a fixed order.  The run
     // length is a function of the band alone (an eighth of it, 16 ... 256 channels), never of the number of
     // subints in the call: the reference's guess for a subint does not depend on its neighbours (pptoas.py:421-457)
     const int cpr = std::max(16, std::min(256, (((nchan + 7) / 8) + 15) / 16 * 16));
-    int nrun = (nchan + cpr - 1) / cpr;
-    const size_t H = (size_t)M + 1;
     // (general row lengths: the harmonics of every row are written out first -- nrun = nchan slots of H)
-    if (anyb) nrun = nchan;
+    const int nrun = anyb ? nchan : (nchan + cpr - 1) / cpr;
+    const size_t H = (size_t)M + 1;
     // X: [nsub][nrun][H] partial spectra | [nsub][H] data spectra | [nsub][H] model spectra | [nsub][M] k_fps work
     if ((rc = c->X.reserve(((size_t)nsub * nrun * H + 2 * (size_t)nsub * H + (size_t)nsub * M) * sizeof(cplx)))) return rc;
     if ((rc = c->sdraw.reserve((size_t)nsub * nrun * 8))) return rc;
@@ -139,90 +154,60 @@ extern "C" int pp_reference_phase_seed(pp_ctx* c, const void* src, int dtype, in
     cplx* dspec = part + (size_t)nsub * nrun * H;
     cplx* mspec = dspec + (size_t)nsub * H;
     cplx* xwork = mspec + (size_t)nsub * H;
-    RotMeanArgs ra{dsrc, c->freqs.as<double>(), (long long)freqs_stride, c->P.as<double>(), c->x0.as<double>(),
-                   c->wts.as<double>(), tw, std::isinf(nu_DM) ? 0.0 : 1.0 / (nu_DM * nu_DM),
-                   std::isinf(nu_GM) ? 0.0 : 1.0 / (nu_GM * nu_GM * nu_GM * nu_GM), part, c->sdraw.as<double>(),
-                   nsub, nchan, nrun, cpr};
+    RotMeanArgs ra{dsrc, c->freqs.as<double>(), (long long)in.freqs_stride, c->P.as<double>(), c->x0.as<double>(),
+                   c->wts.as<double>(), tw, inv_nu2(nu_DM), inv_nu4(nu_GM), part, c->sdraw.as<double>(), nsub, nchan, nrun, cpr};
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    if (anyb) {
-        // row lengths without a tuned plan (pp_anybin.h): every row's harmonics by the chirp-z path, then
-        // the weighted, rotated channel sum per harmonic, and the template profiles' spectra the same way
+    {
         Prof pr(c, KF_FPS);
-        XspecArgs xa;
-        memset(&xa, 0, sizeof xa);
-        xa.data = dsrc; xa.nsub = nsub; xa.nchan = nchan; xa.nchan_full = nchan; xa.cstep = 1;
-        const int Mp = ((M + 63) / 64) * 64;
-        if ((rc = launch_any(c, xa, nbin, Mp, dtype, -1, false, part, nullptr))) return rc;
-        hipLaunchKernelGGL(k_rot_mean_harm, dim3((unsigned)((M + 1 + 255) / 256), nsub), dim3(256), 0, c->stream,
-                           (const cplx*)part, ra, M, dspec);
-        memset(&xa, 0, sizeof xa);
-        xa.data = c->errs.p; xa.nsub = 1; xa.nchan = nsub; xa.nchan_full = nsub; xa.cstep = 1;
-        if ((rc = launch_any(c, xa, nbin, Mp, PP_F64, -1, false, mspec, nullptr))) return rc;
-        FpsArgs fa{dspec, nullptr, c->o_params.as<double>(), lo, hi, Ns, M, nsub, c->fps_finish, mspec, M + 1};
-        hipLaunchKernelGGL(k_fps, dim3(nsub), dim3(256), 0, c->stream, fa, xwork);
-    } else {
-        Prof pr(c, KF_FPS);
-        PP_DISPATCH_M(M, {
-            const int T = FftPlan<MM>::T;
-            if (MM == 1024 && c->one_exchange) {
-                // 2048-bin rows: the one-exchange transform (k_rot_mean_q1024)
-                if (dtype == PP_F64) hipLaunchKernelGGL((k_rot_mean_q1024<double>), dim3(nsub * nrun), dim3(64), 0, c->stream, ra);
-                else hipLaunchKernelGGL((k_rot_mean_q1024<float>), dim3(nsub * nrun), dim3(64), 0, c->stream, ra);
-            } else if (dtype == PP_F64) hipLaunchKernelGGL((k_rot_mean<MM, double>), dim3(nsub * nrun), dim3(T), 0, c->stream, ra);
-            else hipLaunchKernelGGL((k_rot_mean<MM, float>), dim3(nsub * nrun), dim3(T), 0, c->stream, ra);
-            hipLaunchKernelGGL(k_rot_mean_finish, dim3((M + 1 + 255) / 256, nsub), dim3(256), 0, c->stream,
-                               (const cplx*)part, (const double*)c->sdraw.as<double>(), nsub, nrun, M, dspec);
-            hipLaunchKernelGGL((k_rfft_rows<MM, double>), dim3(fft_grid(T, nsub)), dim3(T), 0, c->stream,
-                               (const void*)c->errs.p, mspec, tw, nsub);
-        });
+        if (anyb) {
+            // row lengths without a tuned plan (pp_anybin.h): every row's harmonics by the chirp-z path, then
+            // the weighted, rotated channel sum per harmonic
+            if ((rc = harmonics_any(c, dsrc, in.dtype, nsub, nchan, nbin, part))) return rc;
+            hipLaunchKernelGGL(k_rot_mean_harm, dim3((unsigned)((M + 1 + 255) / 256), nsub), dim3(256), 0, c->stream,
+                               (const cplx*)part, ra, M, dspec);
+        } else {
+            PP_DISPATCH_M(M, {
+                const int T = FftPlan<MM>::T;
+                with_dtype(in.dtype, [&](auto t) {
+                    // 2048-bin rows: the one-exchange transform (k_rot_mean_q1024)
+                    if (MM == 1024 && c->one_exchange) hipLaunchKernelGGL((k_rot_mean_q1024<decltype(t)>), dim3(nsub * nrun), dim3(64), 0, c->stream, ra);
+                    else hipLaunchKernelGGL((k_rot_mean<MM, decltype(t)>), dim3(nsub * nrun), dim3(T), 0, c->stream, ra);
+                });
+                hipLaunchKernelGGL(k_rot_mean_finish, dim3((M + 1 + 255) / 256, nsub), dim3(256), 0, c->stream,
+                                   (const cplx*)part, (const double*)c->sdraw.as<double>(), nsub, nrun, M, dspec);
+            });
+        }
+        // the template profiles' spectra
+        if ((rc = rows_harmonics(c, c->errs.p, PP_F64, nsub, nbin, mspec))) return rc;
         FpsArgs fa{dspec, nullptr, c->o_params.as<double>(), lo, hi, Ns, M, nsub, c->fps_finish, mspec, M + 1};
         hipLaunchKernelGGL(k_fps, dim3(nsub), dim3(256), 0, c->stream, fa, xwork);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipMemcpyAsync(out7, c->o_params.p, (size_t)nsub * 56, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    for (int i = 0; i < nsub; ++i) out7[(size_t)i * 7 + 6] = 1e-3 * ms / nsub;
-    return PP_OK;
+    return fetch_out7(c, nsub, out7);
 }
 
-// ---- general row lengths (pp_anybin.h): harmonics out, harmonics back ---------------------
-// the Bluestein tables of a row length as the kernels take them
-static int any_args(pp_ctx* c, int nbin, AnyArgs* g, int* L) {
-    pp_ctx::AnyPlan* pl = nullptr;
-    int rc;
-    if ((rc = get_any_plan(c, nbin, &pl))) return rc;
-    const cplx *twL = nullptr, *twB = nullptr;
-    if ((rc = get_twiddles(c, 2 * pl->L, &twL))) return rc;
-    if ((rc = get_twiddles(c, nbin, &twB))) return rc;
-    const int M = nbin / 2;
-    *g = AnyArgs{nbin, M, ((M + 63) / 64) * 64, pl->chirp.as<cplx>(), pl->bft.as<cplx>(), twL, twB, 0, 0, nullptr, nullptr};
-    *L = pl->L;
-    return PP_OK;
+extern "C" int pp_reference_phase_seed(pp_ctx* c, const void* src, int dtype, int on_device, int nsub, int nchan,
+                                       int nbin, const double* freqs, int64_t freqs_stride, const double* P,
+                                       const double* par3, double nu_DM, double nu_GM, const double* weights,
+                                       const double* model_profs, double lo, double hi, int Ns, double* out7) {
+    if (int busy_ = ctx_busy(c, "pp_reference_phase_seed")) return busy_;
+    const Ports in{src, dtype, on_device, nsub, nchan, nbin, freqs, freqs_stride, P, par3, 3};
+    if (int rc = in.validate("pp_reference_phase_seed", c && weights && model_profs && out7, Ns >= 1)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return for_runs(nsub, in.cap(c, 64.0 * nchan + 64.0 * nbin), [&](Run r) {
+        return reference_phase_seed_run(c, in.run(r), nu_DM, nu_GM, r.at(weights, nchan), r.at(model_profs, nbin), lo, hi, Ns, r.at(out7, 7));
+    });
 }
-// harmonics 0..M of nrows_sub x nrows_chan rows of `rows` (row-major [nsub][nchan][nbin]) into hout, CHANNEL-major
-// (hout row = n nsub + i), by k_any
-static int harmonics_any(pp_ctx* c, const void* rows, int dtype, int nsub, int nchan, int nbin, cplx* hout) {
-    XspecArgs xa;
-    memset(&xa, 0, sizeof xa);
-    xa.data = rows; xa.nsub = nsub; xa.nchan = nchan; xa.nchan_full = nchan; xa.cstep = 1;
-    return launch_any(c, xa, nbin, ((nbin / 2 + 63) / 64) * 64, dtype, -1, false, hout, nullptr);
-}
+
+// ---- general row lengths (pp_anybin.h): harmonics back ---------------------
 // numpy.fft.irfft of nrows rows of M + 1 harmonics -> out[nrows][nbin] (device pointers)
 static int irfft_any(pp_ctx* c, int nbin, const cplx* harm, long long nrows, double* out) {
     AnyArgs g;
     int L = 0, rc;
     if ((rc = any_args(c, nbin, &g, &L))) return rc;
-    const int grid = (int)std::max(1LL, std::min(nrows, 2048LL));
-    switch (L) {
-        case 64: hipLaunchKernelGGL((k_irfft_any<64>), dim3(grid), dim3(FftPlan<64>::T), 0, c->stream, harm, g, nrows, out); break;
-        case 256: hipLaunchKernelGGL((k_irfft_any<256>), dim3(grid), dim3(FftPlan<256>::T), 0, c->stream, harm, g, nrows, out); break;
-        case 1024: hipLaunchKernelGGL((k_irfft_any<1024>), dim3(grid), dim3(FftPlan<1024>::T), 0, c->stream, harm, g, nrows, out); break;
-        case 4096: hipLaunchKernelGGL((k_irfft_any<4096>), dim3(grid), dim3(FftPlan<4096>::T), 0, c->stream, harm, g, nrows, out); break;
-        default: return fail(PP_EINVAL, "no transform of %d points", L);
-    }
+    if ((rc = with_any_len(L, [&](auto LL) {
+            hipLaunchKernelGGL((k_irfft_any<decltype(LL)::value>), dim3(any_grid(nrows)), dim3(FftPlan<decltype(LL)::value>::T), 0, c->stream, harm, g, nrows, out);
+        })))
+        return rc;
     HIP_TRY(hipGetLastError());
     return PP_OK;
 }
@@ -248,36 +233,62 @@ extern "C" int pp_synth_portraits(pp_ctx* c, int slot, void* dst, int dtype, int
     SynthArgs a{s.mft.as<cplx>(), s.mdc.as<double>(), dst, c->freqs.as<double>(), c->P.as<double>(),
                 c->x0.as<double>(), tw, sigma, seed, first_subint, nsub, C,
                 gains ? c->errs.as<double>() : (const double*)nullptr};
-    if (!nbin_ok(B)) {
-        // a row length without a tuned plan: the rotated template's harmonics back by the chirp-z route
+    const long long nrows = (long long)nsub * C;
+    {
         Prof pr(c, KF_SYNTH);
-        AnyArgs g;
-        int L = 0;
-        if ((rc = any_args(c, B, &g, &L))) return rc;
-        const int grid = (int)std::max(1LL, std::min((long long)nsub * C, 2048LL));
-#define PP_SYN_ANY(LL)                                                                                          \
-    do {                                                                                                        \
-        if (dtype == PP_F64) hipLaunchKernelGGL((k_synth_any<LL, double>), dim3(grid), dim3(FftPlan<LL>::T), 0, c->stream, a, g); \
-        else hipLaunchKernelGGL((k_synth_any<LL, float>), dim3(grid), dim3(FftPlan<LL>::T), 0, c->stream, a, g); \
-    } while (0)
-        switch (L) {
-            case 64: PP_SYN_ANY(64); break;
-            case 256: PP_SYN_ANY(256); break;
-            case 1024: PP_SYN_ANY(1024); break;
-            case 4096: PP_SYN_ANY(4096); break;
-            default: return fail(PP_EINVAL, "no transform of %d points", L);
+        if (!nbin_ok(B)) {
+            // a row length without a tuned plan: the rotated template's harmonics back by the chirp-z route
+            AnyArgs g;
+            int L = 0;
+            if ((rc = any_args(c, B, &g, &L))) return rc;
+            if ((rc = with_any_len(L, [&](auto LL) {
+                    with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL((k_synth_any<decltype(LL)::value, decltype(t)>), dim3(any_grid(nrows)), dim3(FftPlan<decltype(LL)::value>::T), 0, c->stream, a, g); });
+                })))
+                return rc;
+        } else {
+            PP_DISPATCH_M(M, {
+                const int T = FftPlan<MM>::T;
+                with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL((k_synth<MM, decltype(t)>), dim3(fft_grid(T, nrows)), dim3(T), 0, c->stream, a); });
+            });
         }
-#undef PP_SYN_ANY
-    } else {
-        Prof pr(c, KF_SYNTH);
-        PP_DISPATCH_M(M, {
-            const int T = FftPlan<MM>::T;
-            const int grid = fft_grid(T, (long long)nsub * C);
-            if (dtype == PP_F64) hipLaunchKernelGGL((k_synth<MM, double>), dim3(grid), dim3(T), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_synth<MM, float>), dim3(grid), dim3(T), 0, c->stream, a);
-        });
     }
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PP_OK;
+}
+
+// (dst: where the run's rotated portraits go; host portraits are rotated in place in c->data)
+static int rotate_portraits_run(pp_ctx* c, const Ports& in, void* dst, double nu_DM, double nu_GM) {
+    const int nsub = in.nsub, nchan = in.nchan, nbin = in.nbin, M = nbin / 2;
+    const size_t bytes = (size_t)nsub * in.sub_bytes();
+    const long long nrows = (long long)nsub * nchan;
+    const void* dsrc = nullptr;
+    int rc;
+    if ((rc = in.stage(c, &dsrc))) return rc;
+    const cplx* tw = nullptr;
+    if ((rc = get_twiddles(c, nbin, &tw))) return rc;
+    RotateArgs a{dsrc, in.on_device ? dst : c->data.p, c->freqs.as<double>(), (long long)in.freqs_stride, c->P.as<double>(),
+                 c->x0.as<double>(), tw, inv_nu2(nu_DM), inv_nu4(nu_GM), nsub, nchan};
+    {
+        Prof pr(c, KF_SYNTH);
+        if (!nbin_ok(nbin)) {
+            // a row length without a tuned plan: the chirp-z route, forward and back (pp_anybin.h)
+            AnyArgs g;
+            int L = 0;
+            if ((rc = any_args(c, nbin, &g, &L))) return rc;
+            if ((rc = with_any_len(L, [&](auto LL) {
+                    with_dtype(in.dtype, [&](auto t) { hipLaunchKernelGGL((k_rotate_any<decltype(LL)::value, decltype(t)>), dim3(any_grid(nrows)), dim3(FftPlan<decltype(LL)::value>::T), 0, c->stream, a, g); });
+                })))
+                return rc;
+        } else {
+            PP_DISPATCH_M(M, {
+                const int T = FftPlan<MM>::T;
+                with_dtype(in.dtype, [&](auto t) { hipLaunchKernelGGL((k_rotate<MM, decltype(t)>), dim3(fft_grid(T, nrows)), dim3(T), 0, c->stream, a); });
+            });
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    if (!in.on_device) HIP_TRY(hipMemcpyAsync(dst, c->data.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PP_OK;
 }
@@ -286,160 +297,58 @@ extern "C" int pp_rotate_portraits(pp_ctx* c, const void* src, void* dst, int dt
                                    int nchan, int nbin, const double* freqs, int64_t freqs_stride,
                                    const double* P, const double* par3, double nu_DM, double nu_GM) {
     if (int busy_ = ctx_busy(c, "pp_rotate_portraits")) return busy_;
-    if (!c || !src || !dst || !freqs || !P || !par3) return fail(PP_EINVAL, "pp_rotate_portraits: null argument");
-    if (!nbin_any_ok(nbin)) return nbin_refuse("pp_rotate_portraits", nbin);
-    if (nsub < 1 || nchan < 1) return fail(PP_EINVAL, "pp_rotate_portraits: bad shape");
-    if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "pp_rotate_portraits: dtype %d", dtype);
-    if (freqs_stride != 0 && freqs_stride != nchan) return fail(PP_EINVAL, "freqs_stride must be 0 or nchan");
+    const Ports in{src, dtype, on_device, nsub, nchan, nbin, freqs, freqs_stride, P, par3, 3};
+    if (int rc = in.validate("pp_rotate_portraits", c && dst)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const int M = nbin / 2;
-    const size_t esz = dtype == PP_F64 ? 8 : 4;
-    const size_t bytes = (size_t)nsub * nchan * nbin * esz;
-    int rc;
-    if (!on_device) {
-        const size_t sub_b = (size_t)nchan * nbin * esz;
-        const int cap = aux_chunk_cap(c, (double)sub_b + 64.0 * nchan, nsub);
-        if (nsub > cap) {
-            for (int s0 = 0; s0 < nsub; s0 += cap) {
-                const int n = std::min(cap, nsub - s0);
-                if ((rc = pp_rotate_portraits(c, (const char*)src + s0 * sub_b, (char*)dst + s0 * sub_b, dtype, 0, n, nchan, nbin,
-                                              freqs + (freqs_stride ? (size_t)s0 * nchan : 0), freqs_stride, P + s0,
-                                              par3 + (size_t)s0 * 3, nu_DM, nu_GM)))
-                    return rc;
-            }
-            return PP_OK;
-        }
-    }
-    const void* dsrc = src;
-    void* ddst = dst;
-    if (!on_device) {
-        if ((rc = c->data.reserve(bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->data.p, src, bytes, hipMemcpyHostToDevice, c->stream));
-        dsrc = c->data.p; ddst = c->data.p;
-    }
-    if ((rc = upload(c, c->freqs, freqs, (size_t)(freqs_stride ? (size_t)nsub * nchan : nchan) * 8))) return rc;
-    if ((rc = upload(c, c->P, P, (size_t)nsub * 8))) return rc;
-    if ((rc = upload(c, c->x0, par3, (size_t)nsub * 24))) return rc;
-    const cplx* tw = nullptr;
-    if ((rc = get_twiddles(c, nbin, &tw))) return rc;
-    RotateArgs a{dsrc, ddst, c->freqs.as<double>(), (long long)freqs_stride, c->P.as<double>(), c->x0.as<double>(), tw,
-                 std::isinf(nu_DM) ? 0.0 : 1.0 / (nu_DM * nu_DM),
-                 std::isinf(nu_GM) ? 0.0 : 1.0 / (nu_GM * nu_GM * nu_GM * nu_GM), nsub, nchan};
-    if (!nbin_ok(nbin)) {
-        // a row length without a tuned plan: the chirp-z route, forward and back (pp_anybin.h)
-        Prof pr(c, KF_SYNTH);
-        pp_ctx::AnyPlan* pl = nullptr;
-        if ((rc = get_any_plan(c, nbin, &pl))) return rc;
-        const cplx* twL = nullptr;
-        if ((rc = get_twiddles(c, 2 * pl->L, &twL))) return rc;
-        AnyArgs g{nbin, M, ((M + 63) / 64) * 64, pl->chirp.as<cplx>(), pl->bft.as<cplx>(), twL, tw, 0, 0, nullptr, nullptr};
-        const int grid = (int)std::max(1LL, std::min((long long)nsub * nchan, 2048LL));
-#define PP_ROT_ANY(LL)                                                                                          \
-    do {                                                                                                        \
-        if (dtype == PP_F64) hipLaunchKernelGGL((k_rotate_any<LL, double>), dim3(grid), dim3(FftPlan<LL>::T), 0, c->stream, a, g); \
-        else hipLaunchKernelGGL((k_rotate_any<LL, float>), dim3(grid), dim3(FftPlan<LL>::T), 0, c->stream, a, g); \
-    } while (0)
-        switch (pl->L) {
-            case 64: PP_ROT_ANY(64); break;
-            case 256: PP_ROT_ANY(256); break;
-            case 1024: PP_ROT_ANY(1024); break;
-            case 4096: PP_ROT_ANY(4096); break;
-            default: return fail(PP_EINVAL, "no transform of %d points", pl->L);
-        }
-#undef PP_ROT_ANY
-    } else {
-        Prof pr(c, KF_SYNTH);
-        PP_DISPATCH_M(M, {
-            const int T = FftPlan<MM>::T;
-            const int grid = fft_grid(T, (long long)nsub * nchan);
-            if (dtype == PP_F64) hipLaunchKernelGGL((k_rotate<MM, double>), dim3(grid), dim3(T), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_rotate<MM, float>), dim3(grid), dim3(T), 0, c->stream, a);
-        });
-    }
-    HIP_TRY(hipGetLastError());
-    if (!on_device) HIP_TRY(hipMemcpyAsync(dst, c->data.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return PP_OK;
+    return for_runs(nsub, in.cap(c, 64.0 * nchan), [&](Run r) {
+        return rotate_portraits_run(c, in.run(r), r.at((char*)dst, in.sub_bytes()), nu_DM, nu_GM);
+    });
 }
 
 // ---- ppalign accumulation -------------------------------------------------
-extern "C" int pp_align_accumulate(pp_ctx* c, const void* src, int dtype, int on_device, int nsub, int nchan,
-                                   int nbin, const double* freqs, int64_t freqs_stride, const double* P,
-                                   const double* par3, const double* weights, double* aligned,
-                                   double* total_weights) {
-    if (int busy_ = ctx_busy(c, "pp_align_accumulate")) return busy_;
-    if (!c || !src || !freqs || !P || !par3 || !weights || !aligned || !total_weights)
-        return fail(PP_EINVAL, "pp_align_accumulate: null argument");
-    if (!nbin_any_ok(nbin)) return nbin_refuse("pp_align_accumulate", nbin);
-    if (nsub < 1 || nchan < 1) return fail(PP_EINVAL, "pp_align_accumulate: bad shape");
-    if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "pp_align_accumulate: dtype %d", dtype);
-    if (freqs_stride != 0 && freqs_stride != nchan) return fail(PP_EINVAL, "freqs_stride must be 0 or nchan");
-    HIP_TRY(hipSetDevice(c->device));
-    const int M = nbin / 2;
-    const size_t esz = dtype == PP_F64 ? 8 : 4;
-    const size_t bytes = (size_t)nsub * nchan * nbin * esz;
+// how many subints' harmonics (general row lengths: M + 1 per row) fit a 2 GB scratch buffer
+static int harm_chunk(int nsub, int nchan, size_t H) {
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)nsub, ((size_t)2 << 30) / ((size_t)nchan * H * sizeof(cplx))));
+}
+
+static int align_accumulate_run(pp_ctx* c, const Ports& in, const double* weights, double* aligned, double* total_weights) {
+    const int nsub = in.nsub, nchan = in.nchan, nbin = in.nbin, M = nbin / 2;
+    const void* dsrc = nullptr;
     int rc;
-    if (!on_device) {
-        const size_t sub_b = (size_t)nchan * nbin * esz;
-        const int cap = aux_chunk_cap(c, (double)sub_b + 64.0 * nchan, nsub);
-        if (nsub > cap) {
-            // the sums of the runs are added on the host
-            std::vector<double> part((size_t)nchan * nbin), wpart((size_t)nchan);
-            std::fill(aligned, aligned + (size_t)nchan * nbin, 0.0);
-            std::fill(total_weights, total_weights + nchan, 0.0);
-            for (int s0 = 0; s0 < nsub; s0 += cap) {
-                const int n = std::min(cap, nsub - s0);
-                if ((rc = pp_align_accumulate(c, (const char*)src + s0 * sub_b, dtype, 0, n, nchan, nbin,
-                                              freqs + (freqs_stride ? (size_t)s0 * nchan : 0), freqs_stride, P + s0,
-                                              par3 + (size_t)s0 * 3, weights + (size_t)s0 * nchan, part.data(), wpart.data())))
-                    return rc;
-                for (size_t j = 0; j < part.size(); ++j) aligned[j] += part[j];
-                for (int j = 0; j < nchan; ++j) total_weights[j] += wpart[j];
-            }
-            return PP_OK;
-        }
-    }
-    const void* dsrc = src;
-    if (!on_device) {
-        if ((rc = c->data.reserve(bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->data.p, src, bytes, hipMemcpyHostToDevice, c->stream));
-        dsrc = c->data.p;
-    }
-    if ((rc = upload(c, c->freqs, freqs, (size_t)(freqs_stride ? (size_t)nsub * nchan : nchan) * 8))) return rc;
-    if ((rc = upload(c, c->P, P, (size_t)nsub * 8))) return rc;
-    if ((rc = upload(c, c->x0, par3, (size_t)nsub * 24))) return rc;
+    if ((rc = in.stage(c, &dsrc))) return rc;
     if ((rc = upload(c, c->wts, weights, (size_t)nsub * nchan * 8))) return rc;
     if ((rc = c->X.reserve((size_t)nchan * nbin * 8))) return rc;          // aligned portrait
     if ((rc = c->sdraw.reserve((size_t)nchan * 8))) return rc;             // total weights
     const cplx* tw = nullptr;
     if ((rc = get_twiddles(c, nbin, &tw))) return rc;
-    AlignArgs a{dsrc, c->freqs.as<double>(), (long long)freqs_stride, c->P.as<double>(), c->x0.as<double>(),
+    AlignArgs a{dsrc, c->freqs.as<double>(), (long long)in.freqs_stride, c->P.as<double>(), c->x0.as<double>(),
                 c->wts.as<double>(), tw, c->X.as<double>(), c->sdraw.as<double>(), nsub, nchan};
-    if (!nbin_ok(nbin)) {
-        // a row length without a tuned plan (pp_anybin.h): harmonics of every row by the chirp-z route, the weighted,
-        // rotated sum per (channel, harmonic) over the subints in index order, ONE inverse transform per channel.
-        // Subints go through in chunks whose harmonics fit a 2 GB scratch buffer.
+    {
         Prof pr(c, KF_SYNTH);
-        const size_t H = (size_t)M + 1;
-        const int cs = (int)std::max<size_t>(1, std::min<size_t>((size_t)nsub, ((size_t)2 << 30) / ((size_t)nchan * H * sizeof(cplx))));
-        if ((rc = c->seedbuf.reserve(((size_t)cs * nchan * H + (size_t)nchan * H) * sizeof(cplx)))) return rc;
-        cplx* hout = c->seedbuf.as<cplx>();
-        cplx* spec = hout + (size_t)cs * nchan * H;
-        for (int s0 = 0; s0 < nsub; s0 += cs) {
-            const int ns = std::min(cs, nsub - s0);
-            if ((rc = harmonics_any(c, (const char*)dsrc + (size_t)s0 * nchan * nbin * esz, dtype, ns, nchan, nbin, hout))) return rc;
-            hipLaunchKernelGGL(k_align_harm, dim3((unsigned)((H + 255) / 256), nchan), dim3(256), 0, c->stream,
-                               (const cplx*)hout, a, s0, ns, M, spec, c->sdraw.as<double>(), s0 == 0 ? 1 : 0);
-            HIP_TRY(hipGetLastError());
+        if (!nbin_ok(nbin)) {
+            // a row length without a tuned plan (pp_anybin.h): harmonics of every row by the chirp-z route, the weighted,
+            // rotated sum per (channel, harmonic) over the subints in index order, ONE inverse transform per channel.
+            // Subints go through in chunks whose harmonics fit the scratch buffer.
+            const size_t H = (size_t)M + 1;
+            const int cs = harm_chunk(nsub, nchan, H);
+            if ((rc = c->seedbuf.reserve(((size_t)cs * nchan * H + (size_t)nchan * H) * sizeof(cplx)))) return rc;
+            cplx* hout = c->seedbuf.as<cplx>();
+            cplx* spec = hout + (size_t)cs * nchan * H;
+            if ((rc = for_runs(nsub, cs, [&](Run r) {
+                    if (int rc = harmonics_any(c, r.at((const char*)dsrc, in.sub_bytes()), in.dtype, r.n, nchan, nbin, hout)) return rc;
+                    hipLaunchKernelGGL(k_align_harm, dim3((unsigned)((H + 255) / 256), nchan), dim3(256), 0, c->stream,
+                                       (const cplx*)hout, a, r.s0, r.n, M, spec, c->sdraw.as<double>(), r.s0 == 0 ? 1 : 0);
+                    HIP_TRY(hipGetLastError());
+                    return (int)PP_OK;
+                })))
+                return rc;
+            if ((rc = irfft_any(c, nbin, spec, nchan, c->X.as<double>()))) return rc;
+        } else {
+            PP_DISPATCH_M(M, {
+                const int T = FftPlan<MM>::T;
+                with_dtype(in.dtype, [&](auto t) { hipLaunchKernelGGL((k_align_accum<MM, decltype(t)>), dim3(nchan), dim3(T), 0, c->stream, a); });
+            });
         }
-        if ((rc = irfft_any(c, nbin, spec, nchan, c->X.as<double>()))) return rc;
-    } else {
-        Prof pr(c, KF_SYNTH);
-        PP_DISPATCH_M(M, {
-            const int T = FftPlan<MM>::T;
-            if (dtype == PP_F64) hipLaunchKernelGGL((k_align_accum<MM, double>), dim3(nchan), dim3(T), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_align_accum<MM, float>), dim3(nchan), dim3(T), 0, c->stream, a);
-        });
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(aligned, c->X.p, (size_t)nchan * nbin * 8, hipMemcpyDeviceToHost, c->stream));
@@ -448,56 +357,36 @@ extern "C" int pp_align_accumulate(pp_ctx* c, const void* src, int dtype, int on
     return PP_OK;
 }
 
-// ---- per-channel reduced chi^2 of fitted subints ---------------------------
-extern "C" int pp_channel_red_chi2(pp_ctx* c, const void* src, int dtype, int on_device, int nsub, int nchan,
-                                   int nbin, const int32_t* model_slot, const double* freqs,
-                                   int64_t freqs_stride, const double* P, const double* params5,
-                                   const double* nu_refs3, const double* scales, const double* errs,
-                                   double* red_chi2) {
-    if (int busy_ = ctx_busy(c, "pp_channel_red_chi2")) return busy_;
-    if (!c || !src || !freqs || !P || !params5 || !nu_refs3 || !scales || !errs || !red_chi2)
-        return fail(PP_EINVAL, "pp_channel_red_chi2: null argument");
-    if (!nbin_any_ok(nbin)) return nbin_refuse("pp_channel_red_chi2", nbin);
-    if (nsub < 1 || nchan < 1) return fail(PP_EINVAL, "pp_channel_red_chi2: bad shape");
-    if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "pp_channel_red_chi2: dtype %d", dtype);
-    if (freqs_stride != 0 && freqs_stride != nchan) return fail(PP_EINVAL, "freqs_stride must be 0 or nchan");
+extern "C" int pp_align_accumulate(pp_ctx* c, const void* src, int dtype, int on_device, int nsub, int nchan,
+                                   int nbin, const double* freqs, int64_t freqs_stride, const double* P,
+                                   const double* par3, const double* weights, double* aligned,
+                                   double* total_weights) {
+    if (int busy_ = ctx_busy(c, "pp_align_accumulate")) return busy_;
+    const Ports in{src, dtype, on_device, nsub, nchan, nbin, freqs, freqs_stride, P, par3, 3};
+    if (int rc = in.validate("pp_align_accumulate", c && weights && aligned && total_weights)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    for (int i = 0; i < nsub; ++i) {
-        const int sl = model_slot ? model_slot[i] : 0;
-        if (sl < 0 || sl >= PP_MAX_SLOTS || !c->slots[sl].set || c->slots[sl].nchan != nchan ||
-            c->slots[sl].nbin != nbin)
-            return fail(PP_EINVAL, "pp_channel_red_chi2: model slot %d is not a %d x %d template", sl, nchan, nbin);
-    }
-    const int M = nbin / 2;
-    const size_t esz = dtype == PP_F64 ? 8 : 4;
-    const size_t bytes = (size_t)nsub * nchan * nbin * esz;
+    const int cap = in.cap(c, 64.0 * nchan);
+    if (nsub <= cap) return align_accumulate_run(c, in, weights, aligned, total_weights);
+    // the sums of the runs are added on the host
+    std::vector<double> part((size_t)nchan * nbin), wpart((size_t)nchan);
+    std::fill(aligned, aligned + (size_t)nchan * nbin, 0.0);
+    std::fill(total_weights, total_weights + nchan, 0.0);
+    return for_runs(nsub, cap, [&](Run r) {
+        if (int rc = align_accumulate_run(c, in.run(r), r.at(weights, nchan), part.data(), wpart.data())) return rc;
+        for (size_t j = 0; j < part.size(); ++j) aligned[j] += part[j];
+        for (int j = 0; j < nchan; ++j) total_weights[j] += wpart[j];
+        return (int)PP_OK;
+    });
+}
+
+// ---- per-channel reduced chi^2 of fitted subints ---------------------------
+static int channel_red_chi2_run(pp_ctx* c, const Ports& in, const int32_t* model_slot, const double* nu_refs3,
+                                const double* scales, const double* errs, double* red_chi2) {
+    const int nsub = in.nsub, nchan = in.nchan, nbin = in.nbin, M = nbin / 2;
     const size_t nc = (size_t)nsub * nchan;
+    const void* dsrc = nullptr;
     int rc;
-    if (!on_device) {
-        const size_t sub_b = (size_t)nchan * nbin * esz;
-        const int cap = aux_chunk_cap(c, (double)sub_b + 64.0 * nchan, nsub);
-        if (nsub > cap) {
-            for (int s0 = 0; s0 < nsub; s0 += cap) {
-                const int n = std::min(cap, nsub - s0);
-                const size_t o = (size_t)s0 * nchan;
-                if ((rc = pp_channel_red_chi2(c, (const char*)src + s0 * sub_b, dtype, 0, n, nchan, nbin,
-                                              model_slot ? model_slot + s0 : nullptr, freqs + (freqs_stride ? o : 0),
-                                              freqs_stride, P + s0, params5 + (size_t)s0 * 5, nu_refs3 + (size_t)s0 * 3,
-                                              scales + o, errs + o, red_chi2 + o)))
-                    return rc;
-            }
-            return PP_OK;
-        }
-    }
-    const void* dsrc = src;
-    if (!on_device) {
-        if ((rc = c->data.reserve(bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->data.p, src, bytes, hipMemcpyHostToDevice, c->stream));
-        dsrc = c->data.p;
-    }
-    if ((rc = upload(c, c->freqs, freqs, (size_t)(freqs_stride ? nc : (size_t)nchan) * 8))) return rc;
-    if ((rc = upload(c, c->P, P, (size_t)nsub * 8))) return rc;
-    if ((rc = upload(c, c->x0, params5, (size_t)nsub * 40))) return rc;
+    if ((rc = in.stage(c, &dsrc))) return rc;
     if ((rc = upload(c, c->nufit, nu_refs3, (size_t)nsub * 24))) return rc;
     if ((rc = upload(c, c->wts, scales, nc * 8))) return rc;
     if ((rc = upload(c, c->errs, errs, nc * 8))) return rc;
@@ -506,36 +395,79 @@ extern "C" int pp_channel_red_chi2(pp_ctx* c, const void* src, int dtype, int on
     const cplx* tw = nullptr;
     if ((rc = get_twiddles(c, nbin, &tw))) return rc;
     ChanChi2Args a{dsrc, (const cplx* const*)c->mft_table.p, (const double* const*)c->mdc_table.p,
-                   model_slot ? c->slot.as<int>() : nullptr, c->freqs.as<double>(), (long long)freqs_stride,
+                   model_slot ? c->slot.as<int>() : nullptr, c->freqs.as<double>(), (long long)in.freqs_stride,
                    c->P.as<double>(), c->x0.as<double>(), c->nufit.as<double>(), c->wts.as<double>(),
                    c->errs.as<double>(), tw, c->sdraw.as<double>(), nsub, nchan};
-    if (!nbin_ok(nbin)) {
-        // a row length without a tuned plan: the data rows' harmonics by the chirp-z route, then Parseval on the
-        // residual spectrum exactly as k_chan_chi2 forms it (the slot's spectrum rows are pitched to Mp)
+    {
         Prof pr(c, KF_FINAL);
-        const size_t H = (size_t)M + 1;
-        const int Mp = c->slots[model_slot ? model_slot[0] : 0].Mp;
-        const int cs = (int)std::max<size_t>(1, std::min<size_t>((size_t)nsub, ((size_t)2 << 30) / ((size_t)nchan * H * sizeof(cplx))));
-        if ((rc = c->seedbuf.reserve((size_t)cs * nchan * H * sizeof(cplx)))) return rc;
-        cplx* hout = c->seedbuf.as<cplx>();
-        for (int s0 = 0; s0 < nsub; s0 += cs) {
-            const int ns = std::min(cs, nsub - s0);
-            if ((rc = harmonics_any(c, (const char*)dsrc + (size_t)s0 * nchan * nbin * esz, dtype, ns, nchan, nbin, hout))) return rc;
-            const int grid = (int)std::max(1LL, std::min((long long)ns * nchan, 4096LL));
-            hipLaunchKernelGGL(k_chan_chi2_harm, dim3(grid), dim3(256), 0, c->stream, (const cplx*)hout, a, s0, ns, M, Mp);
-            HIP_TRY(hipGetLastError());
+        if (!nbin_ok(nbin)) {
+            // a row length without a tuned plan: the data rows' harmonics by the chirp-z route, then Parseval on the
+            // residual spectrum exactly as k_chan_chi2 forms it (the slot's spectrum rows are pitched to Mp)
+            const size_t H = (size_t)M + 1;
+            const int Mp = c->slots[model_slot ? model_slot[0] : 0].Mp;
+            const int cs = harm_chunk(nsub, nchan, H);
+            if ((rc = c->seedbuf.reserve((size_t)cs * nchan * H * sizeof(cplx)))) return rc;
+            cplx* hout = c->seedbuf.as<cplx>();
+            if ((rc = for_runs(nsub, cs, [&](Run r) {
+                    if (int rc = harmonics_any(c, r.at((const char*)dsrc, in.sub_bytes()), in.dtype, r.n, nchan, nbin, hout)) return rc;
+                    const int grid = (int)std::max(1LL, std::min((long long)r.n * nchan, 4096LL));
+                    hipLaunchKernelGGL(k_chan_chi2_harm, dim3(grid), dim3(256), 0, c->stream, (const cplx*)hout, a, r.s0, r.n, M, Mp);
+                    HIP_TRY(hipGetLastError());
+                    return (int)PP_OK;
+                })))
+                return rc;
+        } else {
+            PP_DISPATCH_M(M, {
+                const int T = FftPlan<MM>::T;
+                with_dtype(in.dtype, [&](auto t) { hipLaunchKernelGGL((k_chan_chi2<MM, decltype(t)>), dim3(fft_grid(T, (long long)nc)), dim3(T), 0, c->stream, a); });
+            });
         }
-    } else {
-        Prof pr(c, KF_FINAL);
-        PP_DISPATCH_M(M, {
-            const int T = FftPlan<MM>::T;
-            const int grid = fft_grid(T, (long long)nc);
-            if (dtype == PP_F64) hipLaunchKernelGGL((k_chan_chi2<MM, double>), dim3(grid), dim3(T), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_chan_chi2<MM, float>), dim3(grid), dim3(T), 0, c->stream, a);
-        });
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(red_chi2, c->sdraw.p, nc * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PP_OK;
+}
+
+extern "C" int pp_channel_red_chi2(pp_ctx* c, const void* src, int dtype, int on_device, int nsub, int nchan,
+                                   int nbin, const int32_t* model_slot, const double* freqs,
+                                   int64_t freqs_stride, const double* P, const double* params5,
+                                   const double* nu_refs3, const double* scales, const double* errs,
+                                   double* red_chi2) {
+    if (int busy_ = ctx_busy(c, "pp_channel_red_chi2")) return busy_;
+    const Ports in{src, dtype, on_device, nsub, nchan, nbin, freqs, freqs_stride, P, params5, 5};
+    if (int rc = in.validate("pp_channel_red_chi2", c && nu_refs3 && scales && errs && red_chi2)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    for (int i = 0; i < nsub; ++i) {
+        const int sl = model_slot ? model_slot[i] : 0;
+        if (sl < 0 || sl >= PP_MAX_SLOTS || !c->slots[sl].set || c->slots[sl].nchan != nchan ||
+            c->slots[sl].nbin != nbin)
+            return fail(PP_EINVAL, "pp_channel_red_chi2: model slot %d is not a %d x %d template", sl, nchan, nbin);
+    }
+    return for_runs(nsub, in.cap(c, 64.0 * nchan), [&](Run r) {
+        return channel_red_chi2_run(c, in.run(r), r.at(model_slot, 1), r.at(nu_refs3, 3), r.at(scales, nchan), r.at(errs, nchan),
+                                    r.at(red_chi2, nchan));
+    });
+}
+
+// A template generated on the device -- gen(dev_out) checks the generator's arguments and queues it -- into the
+// caller's device buffer, to the host (portrait, !out_on_device), or, with portrait == nullptr, into model slot
+// `slot` without a host copy
+template <typename G>
+static int generated_template(pp_ctx* c, int nchan, int nbin, G gen, double* portrait, int out_on_device, int slot) {
+    const size_t bytes = (size_t)nchan * nbin * 8;
+    int rc;
+    double* dout = portrait;
+    if (!portrait || !out_on_device) {
+        // scratch for the portrait.  On its way into a slot it is c->X, except for general row lengths: there
+        // pp_model_set leaves the rows' harmonics in c->X
+        DevBuf& scratch = !portrait && nbin_ok(nbin) ? c->X : c->data;
+        if ((rc = scratch.reserve(bytes))) return rc;
+        dout = scratch.as<double>();
+    }
+    if ((rc = gen(dout))) return rc;
+    if (!portrait) return pp_model_set(c, slot, dout, PP_F64, 1, nchan, nbin);
+    if (!out_on_device) HIP_TRY(hipMemcpyAsync(portrait, dout, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PP_OK;
 }
@@ -593,17 +525,9 @@ extern "C" int pp_gaussian_portrait(pp_ctx* c, int nchan, int nbin, const double
     if (int busy_ = ctx_busy(c, "pp_gaussian_portrait")) return busy_;
     if (!c || !portrait) return fail(PP_EINVAL, "pp_gaussian_portrait: null argument");
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    double* dout = portrait;
-    if (!out_on_device) {
-        if ((rc = c->data.reserve((size_t)nchan * nbin * 8))) return rc;
-        dout = c->data.as<double>();
-    }
-    if ((rc = gauss_generate(c, nchan, nbin, freqs, code, nu_ref, dc, tau_rot, alpha, ngauss, comps, dout))) return rc;
-    if (!out_on_device)
-        HIP_TRY(hipMemcpyAsync(portrait, dout, (size_t)nchan * nbin * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return PP_OK;
+    return generated_template(c, nchan, nbin, [&](double* dout) {
+        return gauss_generate(c, nchan, nbin, freqs, code, nu_ref, dc, tau_rot, alpha, ngauss, comps, dout);
+    }, portrait, out_on_device, -1);
 }
 
 extern "C" int pp_model_set_gaussian(pp_ctx* c, int slot, int nchan, int nbin, const double* freqs,
@@ -612,14 +536,9 @@ extern "C" int pp_model_set_gaussian(pp_ctx* c, int slot, int nchan, int nbin, c
     if (int busy_ = ctx_busy(c, "pp_model_set_gaussian")) return busy_;
     if (!c) return fail(PP_EINVAL, "pp_model_set_gaussian: null context");
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    // scratch for the portrait (general row lengths: pp_model_set leaves the rows' harmonics in c->X)
-    DevBuf& scratch = nbin_ok(nbin) ? c->X : c->data;
-    if ((rc = scratch.reserve((size_t)nchan * nbin * 8))) return rc;
-    if ((rc = gauss_generate(c, nchan, nbin, freqs, code, nu_ref, dc, tau_rot, alpha, ngauss, comps,
-                             scratch.as<double>())))
-        return rc;
-    return pp_model_set(c, slot, scratch.p, PP_F64, 1, nchan, nbin);
+    return generated_template(c, nchan, nbin, [&](double* dout) {
+        return gauss_generate(c, nchan, nbin, freqs, code, nu_ref, dc, tau_rot, alpha, ngauss, comps, dout);
+    }, nullptr, 0, slot);
 }
 
 // ---- spline (PCA + B-spline) templates on the device --------------------------
@@ -657,17 +576,9 @@ extern "C" int pp_spline_portrait(pp_ctx* c, int nchan, int nbin, const double* 
     if (int busy_ = ctx_busy(c, "pp_spline_portrait")) return busy_;
     if (!c || !portrait) return fail(PP_EINVAL, "pp_spline_portrait: null argument");
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    double* dout = portrait;
-    if (!out_on_device) {
-        if ((rc = c->data.reserve((size_t)nchan * nbin * 8))) return rc;
-        dout = c->data.as<double>();
-    }
-    if ((rc = spline_generate(c, nchan, nbin, freqs, ncomp, basis, nknots, t, coefs, degree, dout))) return rc;
-    if (!out_on_device)
-        HIP_TRY(hipMemcpyAsync(portrait, dout, (size_t)nchan * nbin * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return PP_OK;
+    return generated_template(c, nchan, nbin, [&](double* dout) {
+        return spline_generate(c, nchan, nbin, freqs, ncomp, basis, nknots, t, coefs, degree, dout);
+    }, portrait, out_on_device, -1);
 }
 
 extern "C" int pp_model_set_spline(pp_ctx* c, int slot, int nchan, int nbin, const double* freqs, int ncomp,
@@ -677,12 +588,9 @@ extern "C" int pp_model_set_spline(pp_ctx* c, int slot, int nchan, int nbin, con
     if (!c) return fail(PP_EINVAL, "pp_model_set_spline: null context");
     if (!nbin_any_ok(nbin)) return nbin_refuse("pp_model_set_spline", nbin);
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    DevBuf& scratch = nbin_ok(nbin) ? c->X : c->data;      // (as pp_model_set_gaussian)
-    if ((rc = scratch.reserve((size_t)nchan * nbin * 8))) return rc;
-    if ((rc = spline_generate(c, nchan, nbin, freqs, ncomp, basis, nknots, t, coefs, degree, scratch.as<double>())))
-        return rc;
-    return pp_model_set(c, slot, scratch.p, PP_F64, 1, nchan, nbin);
+    return generated_template(c, nchan, nbin, [&](double* dout) {
+        return spline_generate(c, nchan, nbin, freqs, ncomp, basis, nknots, t, coefs, degree, dout);
+    }, nullptr, 0, slot);
 }
 
 // ---- instrumental response applied to a resident template ---------------------

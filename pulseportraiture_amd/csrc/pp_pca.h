@@ -261,18 +261,16 @@ extern "C" int pp_pca_gram(pp_ctx* c, const void* src, int dtype, int on_device,
     double *mean = p.vec.as<double>(), *avg = mean + nbin;
     HIP_TRY(hipMemsetAsync(p.S.p, 0, (size_t)npad * mpad * 8, c->stream));
     const dim3 grid((nbin + 63) / 64, nchunk);
-#define PP_PCA_T(KERNEL, ...)                                                                             \
-    do {                                                                                                  \
-        if (dtype == PP_F64) hipLaunchKernelGGL(KERNEL<double>, grid, dim3(64), 0, c->stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<float>, grid, dim3(64), 0, c->stream, __VA_ARGS__);                \
-    } while (0)
-    PP_PCA_T(k_pca_colsum, dsrc, p.w.as<double>(), (const double*)nullptr, nchan, nbin, p.part.as<double>());
-    hipLaunchKernelGGL(k_pca_colfinish, dim3(grid.x), dim3(64), 0, c->stream, p.part.as<double>(), nchunk, nbin, sumw, mean);
-    PP_PCA_T(k_pca_colsum, dsrc, p.w.as<double>(), (const double*)mean, nchan, nbin, p.part.as<double>());
-    hipLaunchKernelGGL(k_pca_colfinish, dim3(grid.x), dim3(64), 0, c->stream, p.part.as<double>(), nchunk, nbin, sumw, avg);
-    PP_PCA_T(k_pca_centre, dsrc, p.w.as<double>(), (const double*)mean, (const double*)avg, nchan, nbin, dual, mpad,
-             p.D.as<double>(), p.S.as<double>());
-#undef PP_PCA_T
+    const double* dw = p.w.as<double>();
+    with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_pca_colsum<T>, grid, dim3(64), 0, c->stream, dsrc, dw, (const double*)nullptr, nchan, nbin, p.part.as<double>());
+        hipLaunchKernelGGL(k_pca_colfinish, dim3(grid.x), dim3(64), 0, c->stream, p.part.as<double>(), nchunk, nbin, sumw, mean);
+        hipLaunchKernelGGL(k_pca_colsum<T>, grid, dim3(64), 0, c->stream, dsrc, dw, (const double*)mean, nchan, nbin, p.part.as<double>());
+        hipLaunchKernelGGL(k_pca_colfinish, dim3(grid.x), dim3(64), 0, c->stream, p.part.as<double>(), nchunk, nbin, sumw, avg);
+        hipLaunchKernelGGL(k_pca_centre<T>, grid, dim3(64), 0, c->stream, dsrc, dw, (const double*)mean, (const double*)avg, nchan, nbin, dual, mpad,
+                           p.D.as<double>(), p.S.as<double>());
+    });
     const int nb = npad / PCA_TB;
     {
         Prof pf(c, KF_PCA);
@@ -314,20 +312,7 @@ extern "C" int pp_pca_basis(pp_ctx* c, const double* vecs, const double* lam, in
     }
     // the vectors' harmonics, by the row transform of the fit
     if ((rc = c->X.reserve((size_t)nvec * (M + 1) * sizeof(cplx)))) return rc;
-    if (!nbin_ok(nbin)) {
-        XspecArgs xa;
-        memset(&xa, 0, sizeof xa);
-        xa.data = p.B.p; xa.nsub = 1; xa.nchan = nvec; xa.nchan_full = nvec; xa.cstep = 1;
-        if ((rc = launch_any(c, xa, nbin, ((M + 63) / 64) * 64, PP_F64, -1, false, c->X.as<cplx>(), nullptr))) return rc;
-    } else {
-        const cplx* tw = nullptr;
-        if ((rc = get_twiddles(c, nbin, &tw))) return rc;
-        PP_DISPATCH_M(M, {
-            const int T = FftPlan<MM>::T;
-            hipLaunchKernelGGL((k_rfft_rows<MM, double>), dim3(fft_grid(T, nvec)), dim3(T), 0, c->stream, (const void*)p.B.p,
-                               c->X.as<cplx>(), tw, nvec);
-        });
-    }
+    if ((rc = rows_harmonics(c, p.B.p, PP_F64, nvec, nbin, c->X.as<cplx>()))) return rc;
     hipLaunchKernelGGL(k_pca_stats, dim3(nvec), dim3(PCA_ST), 0, c->stream, p.B.as<double>(), c->X.as<cplx>(), nbin, dstats);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(basis, p.B.p, (size_t)nvec * nbin * 8, hipMemcpyDeviceToHost, c->stream));

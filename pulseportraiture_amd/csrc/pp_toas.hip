@@ -614,30 +614,58 @@ static void with_mode(int mode, F f) {
 template <typename F>
 static void with_dtype(int dtype, F f) { if (dtype == PP_F64) f(double{}); else f(float{}); }
 
-// one launch of the general-length transform (pp_anybin.h): mode -1 = harmonics to hout, 0..3 = k_xspec's modes
-static int launch_any(pp_ctx* c, const XspecArgs& xa, int nbin, int Mp, int dtype, int mode, bool tail, cplx* hout,
-                      const unsigned char* mask) {
+// f(std::integral_constant<int, L>): the transform size of a Bluestein plan as the compile-time value the general-length
+// kernels want; get_any_plan picks one of these four, anything else is refused here.  (The return type is deduced, so the
+// body is instantiated at the call like the switch it replaces; tools/kernel_resources.py --compare shows no kernel moved.)
+template <typename F>
+static auto with_any_len(int L, F f) {
+    switch (L) {
+        case 64: f(std::integral_constant<int, 64>{}); return (int)PP_OK;
+        case 256: f(std::integral_constant<int, 256>{}); return (int)PP_OK;
+        case 1024: f(std::integral_constant<int, 1024>{}); return (int)PP_OK;
+        case 4096: f(std::integral_constant<int, 4096>{}); return (int)PP_OK;
+        default: return fail(PP_EINVAL, "no transform of %d points", L);
+    }
+}
+
+// the Bluestein tables of a row length as the kernels take them, and the plan's transform size
+static int any_args(pp_ctx* c, int nbin, AnyArgs* g, int* L, int mode = 0, bool tail = false, cplx* hout = nullptr,
+                    const unsigned char* mask = nullptr) {
     pp_ctx::AnyPlan* pl = nullptr;
     int rc;
     if ((rc = get_any_plan(c, nbin, &pl))) return rc;
     const cplx *twL = nullptr, *twB = nullptr;
     if ((rc = get_twiddles(c, 2 * pl->L, &twL))) return rc;
     if ((rc = get_twiddles(c, nbin, &twB))) return rc;
-    AnyArgs g{nbin, nbin / 2, Mp, pl->chirp.as<cplx>(), pl->bft.as<cplx>(), twL, twB, mode, tail ? 1 : 0, hout, mask};
-    const long long nrows = (long long)xa.nsub * xa.nchan;
-    const int grid = (int)std::max(1LL, std::min(nrows, 2048LL));
-#define PP_ANY(LL) \
-    with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL((k_any<LL, decltype(t)>), dim3(grid), dim3(FftPlan<LL>::T), 0, c->stream, xa, g); })
-    switch (pl->L) {
-        case 64: PP_ANY(64); break;
-        case 256: PP_ANY(256); break;
-        case 1024: PP_ANY(1024); break;
-        case 4096: PP_ANY(4096); break;
-        default: return fail(PP_EINVAL, "no transform of %d points", pl->L);
-    }
-#undef PP_ANY
+    const int M = nbin / 2;
+    *g = AnyArgs{nbin, M, ((M + 63) / 64) * 64, pl->chirp.as<cplx>(), pl->bft.as<cplx>(), twL, twB, mode, tail ? 1 : 0, hout, mask};
+    *L = pl->L;
+    return PP_OK;
+}
+// what the general-length kernels launch with: at most 2048 workgroups walk the rows
+static int any_grid(long long nrows) { return (int)std::max(1LL, std::min(nrows, 2048LL)); }
+
+// one launch of the general-length transform (pp_anybin.h): mode -1 = harmonics to hout, 0..3 = k_xspec's modes
+static int launch_any(pp_ctx* c, const XspecArgs& xa, int nbin, int dtype, int mode, bool tail, cplx* hout,
+                      const unsigned char* mask) {
+    AnyArgs g;
+    int L = 0, rc;
+    if ((rc = any_args(c, nbin, &g, &L, mode, tail, hout, mask))) return rc;
+    const int grid = any_grid((long long)xa.nsub * xa.nchan);
+    if ((rc = with_any_len(L, [&](auto LL) {
+            with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL((k_any<decltype(LL)::value, decltype(t)>), dim3(grid), dim3(FftPlan<decltype(LL)::value>::T), 0, c->stream, xa, g); });
+        })))
+        return rc;
     HIP_TRY(hipGetLastError());
     return PP_OK;
+}
+// harmonics 0..M of nsub x nchan rows of `rows` (row-major [nsub][nchan][nbin]) into hout, CHANNEL-major (hout row =
+// n nsub + i; plain rows: nsub = 1), by k_any
+static int harmonics_any(pp_ctx* c, const void* rows, int dtype, int nsub, int nchan, int nbin, cplx* hout) {
+    XspecArgs xa;
+    memset(&xa, 0, sizeof xa);
+    xa.data = rows; xa.nsub = nsub; xa.nchan = nchan; xa.nchan_full = nchan; xa.cstep = 1;
+    return launch_any(c, xa, nbin, dtype, -1, false, hout, nullptr);
 }
 
 // dispatch a templated kernel on (M, dtype)
@@ -715,11 +743,8 @@ extern "C" int pp_model_set(pp_ctx* c, int slot, const void* portrait, int dtype
     if (anyb) {
         // general row length: harmonics by the Bluestein path, then the slot's padded rows
         if ((rc = c->X.reserve((size_t)nchan * (M + 1) * sizeof(cplx)))) return rc;
-        XspecArgs xa;
-        memset(&xa, 0, sizeof xa);
-        xa.data = dport; xa.nsub = 1; xa.nchan = nchan; xa.nchan_full = nchan; xa.cstep = 1;
         Prof pr(c, KF_MODEL);
-        if ((rc = launch_any(c, xa, nbin, Mp, dtype, -1, false, c->X.as<cplx>(), nullptr))) return rc;
+        if ((rc = harmonics_any(c, dport, dtype, 1, nchan, nbin, c->X.as<cplx>()))) return rc;
         hipLaunchKernelGGL(k_model_from_harm, dim3(nchan), dim3(64), 0, c->stream, (const cplx*)c->X.p, M, Mp,
                            s.mft.as<cplx>(), s.msq.as<double>(), s.msum.as<double>(), s.mmax.as<double>(), s.mdc.as<double>());
         HIP_TRY(hipGetLastError());
@@ -757,35 +782,38 @@ extern "C" int pp_model_nharm(pp_ctx* c, int slot) {
 }
 
 // --------------------------------------------------------------------------
-// rFFT parity hook
+// rows -> harmonics, and the rFFT parity hook
 // --------------------------------------------------------------------------
+// harmonics 0..M of nrows plain rows (device, of dtype) into hout[nrows][M + 1]: the tuned transform of the row length
+// where there is one, the general-length route (pp_anybin.h) where not
+// (the element type is branched on, not handed to with_dtype: a generic lambda around k_rfft_rows moves its
+// instantiations within the code object, and with them the pc-relative call of the transforms that carry a tail)
+static int rows_harmonics(pp_ctx* c, const void* rows, int dtype, int nrows, int nbin, cplx* hout) {
+    if (!nbin_ok(nbin)) return harmonics_any(c, rows, dtype, 1, nrows, nbin, hout);
+    const cplx* tw = nullptr;
+    int rc;
+    if ((rc = get_twiddles(c, nbin, &tw))) return rc;
+    PP_DISPATCH_M(nbin / 2, {
+        const int T = FftPlan<MM>::T;
+        if (dtype == PP_F64) hipLaunchKernelGGL((k_rfft_rows<MM, double>), dim3(fft_grid(T, nrows)), dim3(T), 0, c->stream, rows, hout, tw, nrows);
+        else hipLaunchKernelGGL((k_rfft_rows<MM, float>), dim3(fft_grid(T, nrows)), dim3(T), 0, c->stream, rows, hout, tw, nrows);
+    });
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+
 extern "C" int pp_rfft_rows(pp_ctx* c, const void* rows, int dtype, int nrows, int nbin, double* out) {
     if (int busy_ = ctx_busy(c, "pp_rfft_rows")) return busy_;
     if (!c || !rows || !out) return fail(PP_EINVAL, "pp_rfft_rows: null argument");
     if (!nbin_any_ok(nbin) || nrows < 1) return fail(PP_EINVAL, "pp_rfft_rows: bad shape %d x %d", nrows, nbin);
     HIP_TRY(hipSetDevice(c->device));
-    const int M = nbin / 2;
-    const size_t esz = dtype == PP_F64 ? 8 : 4;
+    const size_t in_b = (size_t)nrows * nbin * (dtype == PP_F64 ? 8 : 4), out_b = (size_t)nrows * (nbin / 2 + 1) * sizeof(cplx);
     int rc;
-    if ((rc = c->data.reserve((size_t)nrows * nbin * esz))) return rc;
-    if ((rc = c->X.reserve((size_t)nrows * (M + 1) * sizeof(cplx)))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->data.p, rows, (size_t)nrows * nbin * esz, hipMemcpyHostToDevice, c->stream));
-    if (!nbin_ok(nbin)) {
-        XspecArgs xa;
-        memset(&xa, 0, sizeof xa);
-        xa.data = c->data.p; xa.nsub = 1; xa.nchan = nrows; xa.nchan_full = nrows; xa.cstep = 1;
-        if ((rc = launch_any(c, xa, nbin, ((M + 63) / 64) * 64, dtype, -1, false, c->X.as<cplx>(), nullptr))) return rc;
-    } else {
-        const cplx* tw = nullptr;
-        if ((rc = get_twiddles(c, nbin, &tw))) return rc;
-        PP_DISPATCH_M(M, {
-            const int T = FftPlan<MM>::T;
-            if (dtype == PP_F64) hipLaunchKernelGGL((k_rfft_rows<MM, double>), dim3(fft_grid(T, nrows)), dim3(T), 0, c->stream, (const void*)c->data.p, c->X.as<cplx>(), tw, nrows);
-            else hipLaunchKernelGGL((k_rfft_rows<MM, float>), dim3(fft_grid(T, nrows)), dim3(T), 0, c->stream, (const void*)c->data.p, c->X.as<cplx>(), tw, nrows);
-        });
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(out, c->X.p, (size_t)nrows * (M + 1) * sizeof(cplx), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = c->data.reserve(in_b))) return rc;
+    if ((rc = c->X.reserve(out_b))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->data.p, rows, in_b, hipMemcpyHostToDevice, c->stream));
+    if ((rc = rows_harmonics(c, c->data.p, dtype, nrows, nbin, c->X.as<cplx>()))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->X.p, out_b, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PP_OK;
 }
@@ -1356,7 +1384,7 @@ static void fill_args(Chunk& k) {
 static int run_xspec(Chunk& k, const XspecArgs& x, int mode) {
     pp_ctx* c = k.c;
     Prof pr(c, KF_XSPEC);
-    if (k.p.anyb) return launch_any(c, x, k.B, k.p.M, k.in->data_dtype, mode, k.p.noise_tail, nullptr, c->skip_masked ? k.d_mask : nullptr);
+    if (k.p.anyb) return launch_any(c, x, k.B, k.in->data_dtype, mode, k.p.noise_tail, nullptr, c->skip_masked ? k.d_mask : nullptr);
     PP_DISPATCH_M(k.p.M, { with_dtype(k.in->data_dtype, [&](auto t) { launch_xspec<MM, decltype(t)>(c, x, k.p.noise_tail, mode); }); });
     HIP_TRY(hipGetLastError());
     return PP_OK;

@@ -213,40 +213,14 @@ __global__ __launch_bounds__(PP_ZAP_T) void k_zap_median(const double* noise, co
 // pplib.get_noise_PS(row, frac=4) (pplib.py:2227-2253) of every row, with the norm of
 // normalize_portrait (pplib.py:2462-2507) that ppzap applies before it (ppzap.py:222-230)
 // (snrs: pp_channel_snrs' output of the same pass, or nullptr)
-static int channel_noise_rows(pp_ctx* c, const void* src, int dtype, int on_device, int nrows, int nbin, int norm_method,
-                              const double* divisor, double* norms, double* noise, double* snrs, double fudge) {
-    if (int busy_ = ctx_busy(c, "pp_channel_noise")) return busy_;
-    if (!c || !src || !norms || !noise) return fail(PP_EINVAL, "pp_channel_noise: null argument");
-    if (!nbin_any_ok(nbin) || nbin > 4096) return fail(PP_EINVAL, "pp_channel_noise: nbin %d must be even and in [8, 4096]", nbin);
-    if (nrows < 1) return fail(PP_EINVAL, "pp_channel_noise: bad shape %d x %d", nrows, nbin);
-    if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "pp_channel_noise: dtype %d", dtype);
-    if (norm_method < PP_NORM_NONE || norm_method > PP_NORM_ABS) return fail(PP_EINVAL, "pp_channel_noise: norm method %d", norm_method);
-    if (norm_method == PP_NORM_PROF && !divisor) return fail(PP_EINVAL, "pp_channel_noise: norm 'prof' needs the divisors");
-    HIP_TRY(hipSetDevice(c->device));
+static int channel_noise_run(pp_ctx* c, const void* src, int dtype, int on_device, int nrows, int nbin, int norm_method,
+                             const double* divisor, double* norms, double* noise, double* snrs, double fudge) {
     const int M = nbin / 2;
     const bool anyb = !nbin_ok(nbin);
-    const size_t esz = dtype == PP_F64 ? 8 : 4;
-    const size_t rowb = (size_t)nbin * esz, harmb = anyb ? (size_t)(M + 1) * sizeof(cplx) : 0;
     int rc;
-    {
-        // runs of rows: host rows through the work memory, and k_any's harmonics of at most 256 MiB at a time
-        int cap = on_device ? nrows : aux_chunk_cap(c, (double)(rowb + harmb) + 24.0, nrows);
-        if (anyb) cap = std::min<long long>(cap, std::max<long long>(1, ((long long)256 << 20) / (long long)harmb));
-        if (nrows > cap) {
-            for (int r0 = 0; r0 < nrows; r0 += cap) {
-                const int n = std::min(cap, nrows - r0);
-                if ((rc = channel_noise_rows(c, (const char*)src + (size_t)r0 * rowb, dtype, on_device, n, nbin, norm_method,
-                                             divisor ? divisor + r0 : nullptr, norms + r0, noise + r0,
-                                             snrs ? snrs + r0 : nullptr, fudge)))
-                    return rc;
-            }
-            return PP_OK;
-        }
-    }
     const void* dsrc = src;
     if (!on_device) {
-        if ((rc = c->data.reserve((size_t)nrows * rowb))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->data.p, src, (size_t)nrows * rowb, hipMemcpyHostToDevice, c->stream));
+        if ((rc = upload(c, c->data, src, (size_t)nrows * nbin * (dtype == PP_F64 ? 8 : 4)))) return rc;
         dsrc = c->data.p;
     }
     const double* ddiv = nullptr;
@@ -262,24 +236,18 @@ static int channel_noise_rows(pp_ctx* c, const void* src, int dtype, int on_devi
     ChanNoiseArgs a{dsrc, nullptr, tw, ddiv, c->sdraw.as<double>(), c->noise.as<double>(), nrows, M, norm_method,
                     snrs ? c->csum.as<double>() : nullptr, fudge};
     if (anyb) {
-        if ((rc = c->X.reserve((size_t)nrows * harmb))) return rc;
-        XspecArgs xa;
-        memset(&xa, 0, sizeof xa);
-        xa.data = dsrc; xa.nsub = 1; xa.nchan = nrows; xa.nchan_full = nrows; xa.cstep = 1;
-        if ((rc = launch_any(c, xa, nbin, ((M + 63) / 64) * 64, dtype, -1, false, c->X.as<cplx>(), nullptr))) return rc;
+        if ((rc = c->X.reserve((size_t)nrows * (M + 1) * sizeof(cplx)))) return rc;
+        if ((rc = harmonics_any(c, dsrc, dtype, 1, nrows, nbin, c->X.as<cplx>()))) return rc;
         a.harm = c->X.as<cplx>();
-        if (dtype == PP_F64) hipLaunchKernelGGL(k_chan_noise_harm<double>, dim3(nrows), dim3(64), 0, c->stream, a);
-        else hipLaunchKernelGGL(k_chan_noise_harm<float>, dim3(nrows), dim3(64), 0, c->stream, a);
+        with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(k_chan_noise_harm<decltype(t)>, dim3(nrows), dim3(64), 0, c->stream, a); });
     } else {
         PP_DISPATCH_M(M, {
             const int T = FftPlan<MM>::T;
             // (a persistent grid of the kernel's residency: registers, not LDS, bound it at M = 1024)
-            if (dtype == PP_F64)
-                hipLaunchKernelGGL((k_chan_noise<MM, double>), dim3(resident_grid(c, k_chan_noise<MM, double>, T, nrows, fft_grid(T, nrows))),
+            with_dtype(dtype, [&](auto t) {
+                hipLaunchKernelGGL((k_chan_noise<MM, decltype(t)>), dim3(resident_grid(c, k_chan_noise<MM, decltype(t)>, T, nrows, fft_grid(T, nrows))),
                                    dim3(T), 0, c->stream, a);
-            else
-                hipLaunchKernelGGL((k_chan_noise<MM, float>), dim3(resident_grid(c, k_chan_noise<MM, float>, T, nrows, fft_grid(T, nrows))),
-                                   dim3(T), 0, c->stream, a);
+            });
         });
     }
     HIP_TRY(hipGetLastError());
@@ -288,6 +256,26 @@ static int channel_noise_rows(pp_ctx* c, const void* src, int dtype, int on_devi
     if (snrs) HIP_TRY(hipMemcpyAsync(snrs, c->csum.p, (size_t)nrows * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PP_OK;
+}
+
+static int channel_noise_rows(pp_ctx* c, const void* src, int dtype, int on_device, int nrows, int nbin, int norm_method,
+                              const double* divisor, double* norms, double* noise, double* snrs, double fudge) {
+    if (int busy_ = ctx_busy(c, "pp_channel_noise")) return busy_;
+    if (!c || !src || !norms || !noise) return fail(PP_EINVAL, "pp_channel_noise: null argument");
+    if (!nbin_any_ok(nbin) || nbin > 4096) return fail(PP_EINVAL, "pp_channel_noise: nbin %d must be even and in [8, 4096]", nbin);
+    if (nrows < 1) return fail(PP_EINVAL, "pp_channel_noise: bad shape %d x %d", nrows, nbin);
+    if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "pp_channel_noise: dtype %d", dtype);
+    if (norm_method < PP_NORM_NONE || norm_method > PP_NORM_ABS) return fail(PP_EINVAL, "pp_channel_noise: norm method %d", norm_method);
+    if (norm_method == PP_NORM_PROF && !divisor) return fail(PP_EINVAL, "pp_channel_noise: norm 'prof' needs the divisors");
+    HIP_TRY(hipSetDevice(c->device));
+    // runs of rows: host rows through the work memory, and k_any's harmonics of at most 256 MiB at a time (device rows too)
+    const size_t rowb = (size_t)nbin * (dtype == PP_F64 ? 8 : 4), harmb = nbin_ok(nbin) ? 0 : (size_t)(nbin / 2 + 1) * sizeof(cplx);
+    int cap = on_device ? nrows : aux_chunk_cap(c, (double)(rowb + harmb) + 24.0, nrows);
+    if (harmb) cap = std::min<long long>(cap, std::max<long long>(1, ((long long)256 << 20) / (long long)harmb));
+    return for_runs(nrows, cap, [&](Run r) {
+        return channel_noise_run(c, r.at((const char*)src, rowb), dtype, on_device, r.n, nbin, norm_method, r.at(divisor, 1),
+                                 r.at(norms, 1), r.at(noise, 1), r.at(snrs, 1), fudge);
+    });
 }
 
 extern "C" int pp_channel_noise(pp_ctx* c, const void* src, int dtype, int on_device, int nrows, int nbin,

@@ -493,11 +493,7 @@ class Engine(object):
         and the channel mean fused into one read of the portraits (pptoas.py:421-457).
         Returns [nsub, 7] like fit_phase_shift_batch."""
         src, dtype, on_dev, (nsub, nchan, nbin), keep = self._ports_arg(ports)
-        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-        fstride = 0 if freqs.ndim == 1 else nchan
-        P = _f64(np.broadcast_to(np.asarray(P, dtype=np.float64), (nsub,)))
-        par = np.ascontiguousarray(np.stack([
-            np.broadcast_to(np.asarray(v, dtype=np.float64), (nsub,)) for v in (phi, DM, GM)], axis=1))
+        freqs, fstride, P, par = self._subint_args(freqs, P, (phi, DM, GM), nsub, nchan)
         w = _f64(weights, (nsub, nchan))
         mp = _f64(np.broadcast_to(np.asarray(model_profs, dtype=np.float64), (nsub, nbin)))
         out = np.empty((nsub, 7))
@@ -515,26 +511,12 @@ class Engine(object):
                          nu_GM=np.inf):
         """Fourier-rotate ports[nsub,nchan,nbin] (numpy -> new numpy array; CUDA
         tensor -> rotated in place) by per-subint (phi, DM, GM)."""
-        if _is_device_array(ports):
-            nsub, nchan, nbin = (int(v) for v in ports.shape)
-            dtype = PP_F64 if ports.element_size() == 8 else PP_F32
-            src = dst = C.c_void_p(ports.data_ptr())
-            on_dev, out = 1, ports
-        else:
-            a = np.asarray(ports)
-            if a.dtype != np.float32:
-                a = a.astype(np.float64, copy=False)
-            a = np.ascontiguousarray(a)
-            nsub, nchan, nbin = a.shape
-            dtype = PP_F64 if a.dtype == np.float64 else PP_F32
-            out = np.empty_like(a)
-            src, dst, on_dev = C.c_void_p(a.ctypes.data), C.c_void_p(out.ctypes.data), 0
-        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-        fstride = 0 if freqs.ndim == 1 else nchan
-        P = _f64(P, (nsub,))
-        par = np.ascontiguousarray(np.stack([
-            np.broadcast_to(np.asarray(v, dtype=np.float64), (nsub,)) for v in (phi, DM, GM)],
-            axis=1))
+        src, dtype, on_dev, (nsub, nchan, nbin), keep = self._ports_arg(ports)
+        out, dst = keep, src
+        if not on_dev:
+            out = np.empty_like(keep)
+            dst = C.c_void_p(out.ctypes.data)
+        freqs, fstride, P, par = self._subint_args(freqs, P, (phi, DM, GM), nsub, nchan)
         _check(self._lib.pp_rotate_portraits(self._ctx, src, dst, dtype, on_dev, nsub, nchan,
                                              nbin, _dp(freqs), fstride, _dp(P), _dp(par),
                                              float(nu_DM), float(nu_GM)),
@@ -642,17 +624,23 @@ class Engine(object):
         return (C.c_void_p(a.ctypes.data), PP_F64 if a.dtype == np.float64 else PP_F32, 0,
                 a.shape, a)
 
+    @staticmethod
+    def _subint_args(freqs, P, triple, nsub, nchan):
+        """(freqs, freqs_stride, P, par3) as the entry points that take portraits plus
+        per-subint arrays want them: freqs[nchan] shared (stride 0) or [nsub,nchan];
+        `triple`: three scalars or per-subint arrays stacked into par3[nsub,3] (None:
+        the call has no such triple)."""
+        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
+        par = None if triple is None else np.ascontiguousarray(np.stack([
+            np.broadcast_to(np.asarray(v, dtype=np.float64), (nsub,)) for v in triple], axis=1))
+        return freqs, 0 if freqs.ndim == 1 else nchan, _f64(P, (nsub,)), par
+
     def align_accumulate(self, ports, freqs, P, phase, DM, nu_ref, weights):
         """ppalign's accumulation (ppalign.py:199-206): returns
         (sum_i w[i,n] * rotate_data(ports[i,n], phase_i, DM_i, P_i, freqs, nu_ref_i)
         as [nchan,nbin], sum_i w[i,n] as [nchan]); rows with w = 0 are skipped."""
         src, dtype, on_dev, (nsub, nchan, nbin), keep = self._ports_arg(ports)
-        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-        fstride = 0 if freqs.ndim == 1 else nchan
-        P = _f64(P, (nsub,))
-        par = np.ascontiguousarray(np.stack([
-            np.broadcast_to(np.asarray(v, dtype=np.float64), (nsub,))
-            for v in (phase, DM, nu_ref)], axis=1))
+        freqs, fstride, P, par = self._subint_args(freqs, P, (phase, DM, nu_ref), nsub, nchan)
         w = _f64(weights, (nsub, nchan))
         aligned = np.empty((nchan, nbin))
         totw = np.empty(nchan)
@@ -667,9 +655,7 @@ class Engine(object):
         tau [rot, linear], alpha at nu_refs[nsub,3]; the template is the resident
         model slot of each subint."""
         src, dtype, on_dev, (nsub, nchan, nbin), keep = self._ports_arg(ports)
-        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-        fstride = 0 if freqs.ndim == 1 else nchan
-        P = _f64(P, (nsub,))
+        freqs, fstride, P, _ = self._subint_args(freqs, P, None, nsub, nchan)
         params = _f64(params, (nsub, 5))
         nu_refs = _f64(nu_refs, (nsub, 3))
         scales = _f64(scales, (nsub, nchan))

@@ -2582,34 +2582,52 @@ def test_scattering_model_evaluations_that_fail_their_certificate_are_made_over_
     np.testing.assert_allclose(refn["params"][:, 3:], rn["params"][:, 3:], rtol=1e-10)
 
 
-@pytest.mark.gpu
-def test_auxiliary_entry_points_split_host_inputs_that_exceed_the_work_budget(eng):
-    """fit_phase_shift_batch, rotate_portraits, align_accumulate and channel_red_chi2
-    take host arrays of any size: beyond `max_work_bytes` they pass through the device
-    in runs of whole subints, with the same results."""
+def _aux_split_inputs(B, dtype, freqs_per_subint, slots, nsub=11, C=24):
+    """The inputs of the split test and of tools/compare_builds.py's auxiliary calls: 11 subints x 24 channels x B
+    bins, seeded; per-subint frequencies that really differ from subint to subint; two templates when `slots`."""
     from tests.synth_host import model_portrait
     rng = np.random.default_rng(4242)
-    nsub, C, B = 11, 24, 256
     freqs, model = model_portrait(C, B)
-    eng.set_model(model)
-    ports = model[None] * rng.uniform(0.5, 2.0, (nsub, C, 1)) + 0.02 * rng.standard_normal((nsub, C, B))
-    P = np.full(nsub, 0.004)
-    phi, DM = rng.uniform(-0.3, 0.3, nsub), rng.normal(0, 1e-3, nsub)
-    w = rng.uniform(0.5, 1.5, (nsub, C))
-    prof, mprof = ports.reshape(-1, B)[:40], np.tile(model, (nsub, 1))[:40]
-    params = np.zeros((nsub, 5)); params[:, 0] = phi; params[:, 1] = DM
-    nus = np.full((nsub, 3), freqs.mean())
-    scales = rng.uniform(0.5, 2.0, (nsub, C)); errs = np.full((nsub, C), 0.02)
+    ports = (model[None] * rng.uniform(0.5, 2.0, (nsub, C, 1)) + 0.02 * rng.standard_normal((nsub, C, B))).astype(dtype)
+    d = dict(nsub=nsub, C=C, B=B, model=model, model2=0.5 * np.roll(model, 3, axis=1), ports=ports, freqs1=freqs,
+             freqs=freqs[None] + 1.5 * np.arange(nsub)[:, None] if freqs_per_subint else freqs,
+             P=np.full(nsub, 0.004), phi=rng.uniform(-0.3, 0.3, nsub), DM=rng.normal(0, 1e-3, nsub),
+             w=rng.uniform(0.5, 1.5, (nsub, C)), slots=np.arange(nsub, dtype=np.int32) % 2 if slots else None,
+             nus=np.full((nsub, 3), freqs.mean()), scales=rng.uniform(0.5, 2.0, (nsub, C)), errs=np.full((nsub, C), 0.02))
+    d["params"] = np.zeros((nsub, 5)); d["params"][:, 0] = d["phi"]; d["params"][:, 1] = d["DM"]
+    d["prof"], d["mprof"] = ports.reshape(-1, B)[:40].astype(np.float64), np.tile(model, (nsub, 1))[:40]
+    return d
 
-    def run():
-        return (eng.fit_phase_shift_batch(prof, mprof, noise=np.full(40, 0.02)),
-                eng.rotate_portraits(ports.copy(), freqs, P, phi=phi, DM=DM, nu_DM=freqs.mean()),
-                eng.align_accumulate(ports, freqs, P, phi, DM, freqs.mean(), w),
-                eng.channel_red_chi2(ports, freqs, P, params, nus, scales, errs))
-    whole = run()
-    eng.set_option("max_work_bytes", 3.4 * C * B * 8)      # three subints (or ~50 profiles) at a time
+
+def _aux_split_calls(eng, d):
+    """fit_phase_shift_batch, rotate_portraits, align_accumulate, channel_red_chi2, reference_phase_seed on those."""
+    eng.set_model(d["model"])
+    eng.set_model(d["model2"], slot=1)
+    nu = d["freqs1"].mean()
+    return (eng.fit_phase_shift_batch(d["prof"], d["mprof"], noise=np.full(40, 0.02)),
+            eng.rotate_portraits(d["ports"].copy(), d["freqs"], d["P"], phi=d["phi"], DM=d["DM"], nu_DM=nu),
+            eng.align_accumulate(d["ports"], d["freqs"], d["P"], d["phi"], d["DM"], nu, d["w"]),
+            eng.channel_red_chi2(d["ports"], d["freqs"], d["P"], d["params"], d["nus"], d["scales"], d["errs"], slots=d["slots"]),
+            eng.reference_phase_seed(d["ports"], d["freqs"], d["P"], d["w"], d["model"].mean(axis=0), phi=d["phi"], DM=d["DM"],
+                                     nu_DM=nu))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [256, 100])
+@pytest.mark.parametrize("dtype,freqs_per_subint,slots", [(np.float64, False, False), (np.float64, True, True),
+                                                          (np.float32, True, True)])
+def test_auxiliary_entry_points_split_host_inputs_that_exceed_the_work_budget(eng, B, dtype, freqs_per_subint, slots):
+    """fit_phase_shift_batch, rotate_portraits, align_accumulate, channel_red_chi2 and
+    reference_phase_seed take host arrays of any size: beyond `max_work_bytes` they pass
+    through the device in runs of whole subints, with the same results -- with shared and
+    with per-subint frequencies, one template or one per subint, float64 and float32
+    portraits, a tuned row length (256) and a general one (100)."""
+    d = _aux_split_inputs(B, dtype, freqs_per_subint, slots)
+    whole = _aux_split_calls(eng, d)
+    # three subints (or a few profiles) at a time
+    eng.set_option("max_work_bytes", 3.4 * d["C"] * B * np.dtype(dtype).itemsize)
     try:
-        split = run()
+        split = _aux_split_calls(eng, d)
     finally:
         eng.set_option("max_work_bytes", 96e9)
     np.testing.assert_array_equal(whole[0][:, :6], split[0][:, :6])     # (column 6 is the duration)
@@ -2617,6 +2635,7 @@ def test_auxiliary_entry_points_split_host_inputs_that_exceed_the_work_budget(en
     np.testing.assert_allclose(whole[2][0], split[2][0], rtol=1e-13, atol=1e-13)
     np.testing.assert_allclose(whole[2][1], split[2][1], rtol=1e-14)
     np.testing.assert_array_equal(whole[3], split[3])
+    np.testing.assert_array_equal(whole[4][:, :6], split[4][:, :6])
 
 
 @pytest.mark.gpu

@@ -11,7 +11,9 @@ build agrees with itself.  Exit status 1 when some array differs.
     python tools/compare_builds.py --run out.npz        (the child: the list of fits with the library in use)
 
 The synthetic batches come from tests/test_gpu_parity.py's helper _full_shape_case (the bench's recipe), so the tool
-follows that helper's signature.
+follows that helper's signature.  After the fits come the auxiliary entry points -- every export that is no fit -- on
+the inputs of that module's split test (_aux_split_inputs: 11 subints x 24 channels, 256 and 100 bins, f64 and f32,
+shared and per-subint frequencies, one and two templates), whole and with a work budget of three subints.
 """
 import os
 import subprocess
@@ -100,6 +102,74 @@ def fits():
     e.close()
 
 
+def aux_calls():
+    """Yields (case name, {output name: array}) for the auxiliary entry points."""
+    import torch
+    from tests.test_gpu_parity import _aux_split_inputs, _aux_split_calls
+    from pulseportraiture_amd import gmodel
+    from pulseportraiture_amd.engine import Engine
+    e = Engine(0)
+    gm = gmodel.parse_gmodel(gmodel.EXAMPLE_GMODEL)
+    for B in (256, 100):
+        for dtype, per_subint, slots in ((np.float64, False, False), (np.float64, True, True), (np.float32, True, True)):
+            d = _aux_split_inputs(B, dtype, per_subint, slots)
+            tag = "aux %d %s freqs%s slots=%d" % (B, np.dtype(dtype).name, "[nsub,nchan]" if per_subint else "[nchan]", slots)
+            ports, C, nsub = d["ports"], d["C"], d["nsub"]
+            dev = torch.from_numpy(ports).to("cuda:0")
+            for budget in (96e9, 3.4 * C * B * np.dtype(dtype).itemsize):
+                e.set_option("max_work_bytes", budget)
+                r = _aux_split_calls(e, d)
+                out = {"fit_phase_shift_batch": r[0][:, :6], "rotate_portraits": r[1], "align_accumulate": r[2][0],
+                       "align_accumulate weights": r[2][1], "channel_red_chi2": r[3], "reference_phase_seed": r[4][:, :6]}
+                # the same from device-resident portraits (rotate_portraits works in place: on a copy)
+                nu = d["freqs1"].mean()
+                out["rotate_portraits device"] = e.rotate_portraits(dev.clone(), d["freqs"], d["P"], phi=d["phi"], DM=d["DM"], nu_DM=nu)
+                out["align_accumulate device"] = e.align_accumulate(dev, d["freqs"], d["P"], d["phi"], d["DM"], nu, d["w"])[0]
+                out["channel_red_chi2 device"] = e.channel_red_chi2(dev, d["freqs"], d["P"], d["params"], d["nus"], d["scales"],
+                                                                  d["errs"], slots=d["slots"])
+                out["reference_phase_seed device"] = e.reference_phase_seed(dev, d["freqs"], d["P"], d["w"], d["model"].mean(axis=0),
+                                                                          phi=d["phi"], DM=d["DM"], nu_DM=nu)[:, :6]
+                out["rfft_rows"] = e.rfft_rows(ports.reshape(-1, B)).view(np.float64)
+                for norm in (None, "max", "prof"):
+                    out["channel_noise %s" % norm], out["channel_noise %s norms" % norm] = e.channel_noise(ports, norm=norm, weights=d["w"])
+                out["channel_noise device"] = e.channel_noise(dev, norm="rms")[0]
+                out["channel_snrs"] = e.channel_snrs(ports)
+                out["channel_snrs device"] = e.channel_snrs(dev)
+                out["zap_median"] = e.zap_median(out["channel_noise None"], np.ones((nsub, C)), 1.5)
+                # pca: 24 channels (the dual side), then all the rows as one tall portrait (nchan >= nbin)
+                for name, port, w in (("pca", ports[0], d["w"][0]), ("pca tall", ports.reshape(-1, B), d["w"].reshape(-1))):
+                    mean_prof, gram, fact = e.pca_gram(port, w)
+                    lam, vec = np.linalg.eigh(gram)
+                    eigvec, stats = e.pca_basis(vec[:, ::-1][:, :4], lam[::-1][:4])
+                    proj, reconst = e.pca_project([2, 0])
+                    out.update({name + " mean": mean_prof, name + " gram": gram, name + " basis": eigvec, name + " stats": stats,
+                                name + " proj": proj, name + " reconst": reconst})
+                # generated templates: to the host, to the device, into a slot; the response on that slot
+                out["gaussian_portrait"] = e.gaussian_portrait(gm, d["freqs1"], B, 0.004)
+                gdev = torch.empty((C, B), dtype=torch.float64, device="cuda:0")
+                e.gaussian_portrait(gm, d["freqs1"], B, 0.004, out=gdev)
+                out["gaussian_portrait device"] = gdev
+                tck = (np.r_[[d["freqs1"][0]] * 4, [d["freqs1"][-1]] * 4], [np.linspace(-1, 1, 8), np.linspace(2, 0, 8)], 3)
+                spl = (d["model"].mean(axis=0), np.stack([np.roll(d["model"][0], 1), np.roll(d["model"][-1], 2)], axis=1), tck)
+                out["spline_portrait"] = e.spline_portrait(spl[0], spl[1], spl[2], d["freqs1"])
+                out["set_model_gaussian nharm"] = np.array(e.set_model_gaussian(gm, d["freqs1"], B, 0.004, slot=2))
+                out["set_model_spline nharm"] = np.array(e.set_model_spline(spl[0], spl[1], spl[2], d["freqs1"], slot=3))
+                out["apply_response nharm"] = np.array(e.apply_response(3, rconst=np.exp(-0.01 * np.arange(B // 2 + 1)) + 0j,
+                                                                       smear_wid=np.full(C, 1e-3)))
+                # what the slots hold, seen through their own calls: the templates' means and noiseless synthetic subints
+                for slot in (2, 3):
+                    out["model_means slot %d" % slot] = e.model_means(slot, C, B)
+                    syn = torch.empty((3, C, B), dtype=torch.float64 if dtype == np.float64 else torch.float32, device="cuda:0")
+                    e.synth_portraits(syn, d["freqs1"], d["P"][:3], np.c_[d["phi"][:3], d["DM"][:3], np.zeros(3)], 0.05, 11, 2,
+                                      slot=slot, gains=d["scales"][:3])
+                    out["synth_portraits slot %d" % slot] = syn
+                    out["channel_red_chi2 slot %d" % slot] = e.channel_red_chi2(
+                        dev, d["freqs"], d["P"], d["params"], d["nus"], d["scales"], d["errs"], slots=np.full(nsub, slot, dtype=np.int32))
+                yield tag + (" split" if budget < 96e9 else ""), out
+            e.set_option("max_work_bytes", 96e9)
+    e.close()
+
+
 def run(path):
     out = {}
     for name, r in fits():
@@ -107,6 +177,10 @@ def run(path):
             if key in r and r[key] is not None:
                 v = r[key]
                 out[name + "|" + key] = v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+        print("ran", name, flush=True)
+    for name, r in aux_calls():
+        for key, v in r.items():
+            out[name + "|" + key] = v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
         print("ran", name, flush=True)
     np.savez(path, **out)
 

@@ -5,10 +5,12 @@
 // only: the same source builds against any commit's library.  Kernels do not run and the stub's device memory is all
 // zeros, so every host decision that reads a device count sees "all done": the weak-pilot re-seed, the recentre loop,
 // the re-transform of listed subints and the re-fit on collect are NOT reached here (the GPU suite asserts those).
+// aux_cases() walks the auxiliary entry points the same way, and checks where their outputs land.
 #include <dlfcn.h>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <vector>
 #include "../../include/pp_toas.h"
@@ -230,6 +232,401 @@ static void option_cases() {
     }
 }
 
+// ---- the auxiliary entry points (everything in the C ABI that is no fit) ----------------------------------------
+// Host arrays are sized exactly (a write past one is AddressSanitizer's to catch: make asan-run) and every output is
+// all 0xFF bytes -- NaN for floating point -- before the call.  The stub really copies and its device memory is
+// zeros, so after a successful call a D2H that landed where it should has left no such element: that pins the output
+// offsets of the runs a large host input is split into.  A refused call marks its code AND its message.
+struct Outs {
+    struct A { unsigned char* p; size_t n, elem; };
+    std::vector<A> v;
+    void* raw(size_t n, size_t elem) {
+        unsigned char* p = new unsigned char[n * elem];
+        memset(p, 0xFF, n * elem);
+        v.push_back({p, n, elem});
+        return p;
+    }
+    double* d(size_t n) { return (double*)raw(n, 8); }
+    ~Outs() { for (A& a : v) delete[] a.p; }
+    void require_filled(const char* what) const {
+        for (size_t k = 0; k < v.size(); ++k)
+            for (size_t i = 0; i < v[k].n; ++i) {
+                size_t ff = 0;
+                for (size_t b = 0; b < v[k].elem; ++b) ff += v[k].p[i * v[k].elem + b] == 0xFF;
+                if (ff == v[k].elem) { fprintf(stderr, "%s: output %zu, element %zu of %zu was not written\n", what, k, i, v[k].n); exit(1); }
+            }
+    }
+};
+static int g_ncase = 0;
+// the end of one call: its code, its message when refused, its outputs when not
+static void done(const char* what, int rc, const Outs& o) {
+    mark("rc %d", rc);
+    if (rc != PP_OK) mark("err %s", pp_last_error());
+    else o.require_filled(what);
+}
+#define AUX(o, what, call) do { mark("case aux %s", what); ++g_ncase; done(what, (call), o); } while (0)
+
+// "device" memory of the stub is host memory: a copy of a host array as an on_device input
+static void* dev_copy(const void* h, size_t bytes) {
+    static auto mal = (int (*)(void**, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
+    void* p = nullptr;
+    if (!mal || mal(&p, bytes) != 0) { fprintf(stderr, "trace_driver: no hipMalloc (the stub is not loaded)\n"); exit(1); }
+    if (h) memcpy(p, h, bytes);
+    return p;
+}
+static void dev_free(void* p) {
+    static auto fr = (int (*)(void*))dlsym(RTLD_DEFAULT, "hipFree");
+    if (fr) fr(p);
+}
+
+struct AuxCfg { int B, C, ns, f32, dev, fstride, slot, small; };
+// the inputs of one configuration, every array exactly as long as the entry points read
+struct AuxIn {
+    AuxCfg k;
+    size_t esz, nrow;
+    std::vector<unsigned char> ports;      // [ns][C][B] of the dtype
+    void* dports = nullptr;
+    std::vector<double> freqs, P, par3, params5, nus3, w, mprof, scales, errs;
+    std::vector<int32_t> slots;
+    explicit AuxIn(const AuxCfg& kk) : k(kk), esz(kk.f32 ? 4 : 8), nrow((size_t)kk.ns * kk.C) {
+        const int ns = k.ns, C = k.C, B = k.B;
+        ports.resize(nrow * B * esz);
+        for (size_t j = 0; j < nrow * B; ++j) {
+            const double v = 0.5 + (j % 13) * 0.01;
+            if (k.f32) ((float*)ports.data())[j] = (float)v; else ((double*)ports.data())[j] = v;
+        }
+        if (k.dev) dports = dev_copy(ports.data(), ports.size());
+        freqs.resize(k.fstride ? nrow : (size_t)C);
+        for (size_t j = 0; j < freqs.size(); ++j) freqs[j] = 1100.0 + 800.0 * ((j % C) + 0.5) / C + (j / C);
+        P.assign(ns, 0.003); par3.assign((size_t)ns * 3, 0.0); params5.assign((size_t)ns * 5, 0.0); nus3.assign((size_t)ns * 3, 1500.0);
+        for (int i = 0; i < ns; ++i) { par3[(size_t)i * 3] = 0.01 * i; par3[(size_t)i * 3 + 2] = 1500.0; params5[(size_t)i * 5] = 0.01 * i; }
+        w.assign(nrow, 1.0); mprof.assign((size_t)ns * B, 1.0); scales.assign(nrow, 1.0); errs.assign(nrow, 0.05);
+        if (k.slot) { slots.resize(ns); for (int i = 0; i < ns; ++i) slots[i] = i % 2; }
+    }
+    ~AuxIn() { if (dports) dev_free(dports); }
+    const void* src() const { return k.dev ? dports : (const void*)ports.data(); }
+    int dtype() const { return k.f32 ? PP_F32 : PP_F64; }
+    int64_t fstride() const { return k.fstride ? k.C : 0; }
+    const int32_t* slot() const { return k.slot ? slots.data() : nullptr; }
+};
+
+// the four entry points that take portraits plus per-subint arrays: every configuration
+static void aux_ports_calls(pp_ctx* c, const AuxCfg& k, const char* tag) {
+    AuxIn in(k);
+    const int ns = k.ns, C = k.C, B = k.B;
+    char nm[200];
+    auto name = [&](const char* fn) {
+        snprintf(nm, sizeof nm, "%s %s %dx%dx%d %s %s fstride=%d slot=%d", fn, tag, ns, C, B, k.f32 ? "f32" : "f64", k.dev ? "device" : "host",
+                 (int)in.fstride(), k.slot);
+        return nm;
+    };
+    { Outs o; double* out7 = o.d((size_t)ns * 7);
+      AUX(o, name("pp_reference_phase_seed"), pp_reference_phase_seed(c, in.src(), in.dtype(), k.dev, ns, C, B, in.freqs.data(), in.fstride(), in.P.data(),
+          in.par3.data(), k.slot ? 1500.0 : INFINITY, k.slot ? 1400.0 : INFINITY, in.w.data(), in.mprof.data(), -0.5, 0.5, 20, out7)); }
+    { Outs o; void* dst = k.dev ? in.dports : o.raw(in.nrow * B, in.esz);
+      AUX(o, name("pp_rotate_portraits"), pp_rotate_portraits(c, in.src(), dst, in.dtype(), k.dev, ns, C, B, in.freqs.data(), in.fstride(), in.P.data(),
+          in.par3.data(), k.slot ? 1500.0 : INFINITY, INFINITY)); }
+    { Outs o; double* al = o.d((size_t)C * B); double* tw = o.d(C);
+      AUX(o, name("pp_align_accumulate"), pp_align_accumulate(c, in.src(), in.dtype(), k.dev, ns, C, B, in.freqs.data(), in.fstride(), in.P.data(),
+          in.par3.data(), in.w.data(), al, tw)); }
+    { Outs o; double* rc2 = o.d(in.nrow);
+      AUX(o, name("pp_channel_red_chi2"), pp_channel_red_chi2(c, in.src(), in.dtype(), k.dev, ns, C, B, in.slot(), in.freqs.data(), in.fstride(), in.P.data(),
+          in.params5.data(), in.nus3.data(), in.scales.data(), in.errs.data(), rc2)); }
+}
+
+// the entry points that take rows: dtype and where the rows are
+static void aux_rows_calls(pp_ctx* c, const AuxCfg& k, const char* tag) {
+    AuxIn in(k);
+    const int ns = k.ns, C = k.C, B = k.B, nrows = ns * C;
+    char nm[200];
+    auto name = [&](const char* fn) {
+        snprintf(nm, sizeof nm, "%s %s %dx%d %s %s", fn, tag, nrows, B, k.f32 ? "f32" : "f64", k.dev ? "device" : "host");
+        return nm;
+    };
+    for (int method : {PP_NORM_NONE, PP_NORM_PROF}) {
+        Outs o; double* norms = o.d(nrows); double* noise = o.d(nrows);
+        AUX(o, name(method == PP_NORM_PROF ? "pp_channel_noise prof" : "pp_channel_noise"),
+            pp_channel_noise(c, in.src(), in.dtype(), k.dev, nrows, B, method, method == PP_NORM_PROF ? in.scales.data() : nullptr, norms, noise));
+    }
+    { Outs o; double* snrs = o.d(nrows);
+      AUX(o, name("pp_channel_snrs"), pp_channel_snrs(c, in.src(), in.dtype(), k.dev, nrows, B, 3.25, snrs)); }
+    // pca: the first C rows as a portrait (C < B: the dual side), then, for the shortest rows, 80 of them (nchan >= nbin)
+    for (int nchan : {C, 80}) {
+        if (nchan > nrows || (nchan == 80 && B != 64)) continue;
+        const int n = nchan < B ? nchan : B, nvec = 3;
+        snprintf(nm, sizeof nm, "pca %s %dx%d %s %s", tag, nchan, B, k.f32 ? "f32" : "f64", k.dev ? "device" : "host");
+        std::vector<double> vecs((size_t)nvec * n, 0.1), lam(nvec, 2.0);
+        const int32_t ieig[2] = {2, 0};
+        { Outs o; double* mean = o.d(B); double* gram = o.d((size_t)n * n);
+          AUX(o, nm, pp_pca_gram(c, in.src(), in.dtype(), k.dev, nchan, B, in.w.data(), (double)nchan, nchan - 1.0, mean, gram)); }
+        { Outs o; double* basis = o.d((size_t)nvec * B); double* stats = o.d((size_t)nvec * 4);
+          AUX(o, "pp_pca_basis", pp_pca_basis(c, vecs.data(), lam.data(), nvec, basis, stats)); }
+        { Outs o; double* proj = o.d((size_t)nchan * 2); double* rec = o.d((size_t)nchan * B);
+          AUX(o, "pp_pca_project", pp_pca_project(c, ieig, 2, proj, rec)); }
+    }
+    if (!k.dev) {
+        Outs o; double* out = o.d((size_t)nrows * (B / 2 + 1) * 2);
+        AUX(o, name("pp_rfft_rows"), pp_rfft_rows(c, in.ports.data(), in.dtype(), nrows, B, out));
+    }
+    { Outs o; void* dst = dev_copy(nullptr, in.nrow * B * in.esz);
+      std::vector<double> inj((size_t)ns * 3, 0.0);
+      AUX(o, name("pp_synth_portraits"), pp_synth_portraits(c, k.dev, dst, in.dtype(), ns, in.freqs.data(), in.P.data(), inj.data(),
+          k.dev ? in.scales.data() : nullptr, 0.05, 7, 3));
+      dev_free(dst); }
+}
+
+// the entry points whose inputs are all double precision on the host
+static void aux_host_calls(pp_ctx* c, int ns, int C, int B, const char* tag) {
+    char nm[200];
+    auto name = [&](const char* fn) { snprintf(nm, sizeof nm, "%s %s %dx%dx%d", fn, tag, ns, C, B); return nm; };
+    std::vector<double> freqs(C);
+    for (int j = 0; j < C; ++j) freqs[j] = 1100.0 + 800.0 * (j + 0.5) / C;
+    for (int with_noise : {0, 1}) {
+        const int nprof = 2 * ns + 1 + 17 * with_noise;
+        std::vector<double> data((size_t)nprof * B, 0.5), model((size_t)nprof * B, 1.0), noise(nprof, 0.05);
+        Outs o; double* out7 = o.d((size_t)nprof * 7);
+        AUX(o, name(with_noise ? "pp_fit_phase_shift_batch noise" : "pp_fit_phase_shift_batch"),
+            pp_fit_phase_shift_batch(c, data.data(), model.data(), with_noise ? noise.data() : nullptr, nprof, B, -0.5, 0.5, 20, out7));
+    }
+    // templates generated on the device: to the host, to a device buffer, into a slot; then the response on that slot
+    const double comps[12] = {0.3, 0.0, 0.02, 0.0, 1.0, 0.0, 0.6, 0.0, 0.05, 0.0, 0.5, -1.0};
+    for (double tau : {0.0, 1e-3}) {
+        snprintf(nm, sizeof nm, "pp_gaussian_portrait %s %dx%d tau=%g", tag, C, B, tau);
+        { Outs o; double* port = o.d((size_t)C * B);
+          AUX(o, nm, pp_gaussian_portrait(c, C, B, freqs.data(), "000", 1500.0, 0.1, tau, -4.0, 2, comps, port, 0)); }
+        { Outs o; double* dport = (double*)dev_copy(nullptr, (size_t)C * B * 8);
+          AUX(o, "pp_gaussian_portrait to the device", pp_gaussian_portrait(c, C, B, freqs.data(), "101", 1500.0, 0.1, tau, -4.0, 2, comps, dport, 1));
+          dev_free(dport); }
+        { Outs o; AUX(o, "pp_model_set_gaussian", pp_model_set_gaussian(c, 2, C, B, freqs.data(), "000", 1500.0, 0.1, tau, -4.0, 2, comps)); }
+    }
+    for (int ncomp : {0, 2}) {
+        const int deg = 3, nknots = 8;
+        std::vector<double> basis((size_t)(ncomp + 1) * B, 0.25), t(nknots), coefs((size_t)(ncomp ? ncomp : 1) * nknots, 0.5);
+        for (int j = 0; j < nknots; ++j) t[j] = j < 4 ? 1100.0 : 1900.0;
+        snprintf(nm, sizeof nm, "pp_spline_portrait %s %dx%d ncomp=%d", tag, C, B, ncomp);
+        { Outs o; double* port = o.d((size_t)C * B);
+          AUX(o, nm, pp_spline_portrait(c, C, B, freqs.data(), ncomp, basis.data(), nknots, ncomp ? t.data() : nullptr, ncomp ? coefs.data() : nullptr, deg, port, 0)); }
+        { Outs o; double* dport = (double*)dev_copy(nullptr, (size_t)C * B * 8);
+          AUX(o, "pp_spline_portrait to the device", pp_spline_portrait(c, C, B, freqs.data(), ncomp, basis.data(), nknots, t.data(), coefs.data(), deg, dport, 1));
+          dev_free(dport); }
+        { Outs o; AUX(o, "pp_model_set_spline", pp_model_set_spline(c, 3, C, B, freqs.data(), ncomp, basis.data(), nknots, t.data(), coefs.data(), deg)); }
+    }
+    {
+        std::vector<double> rconst((size_t)(B / 2 + 1) * 2, 1.0), wid(C, 1e-3);
+        Outs o;
+        AUX(o, name("pp_model_apply_response both"), pp_model_apply_response(c, 2, rconst.data(), wid.data()));
+        AUX(o, "pp_model_apply_response rconst", pp_model_apply_response(c, 3, rconst.data(), nullptr));
+        AUX(o, "pp_model_apply_response smear", pp_model_apply_response(c, 3, nullptr, wid.data()));
+        AUX(o, "pp_model_apply_response neither", pp_model_apply_response(c, 3, nullptr, nullptr));
+    }
+    {
+        std::vector<double> noise((size_t)ns * C, 1.0);
+        std::vector<unsigned char> good((size_t)ns * C, 1);
+        Outs o; unsigned char* zap = (unsigned char*)o.raw((size_t)ns * C, 1);
+        AUX(o, name("pp_zap_median"), pp_zap_median(c, noise.data(), good.data(), ns, C, 5.0, zap));
+    }
+}
+
+// every refusal the preambles can give, on one context with C x B templates in slots 0 and 1
+static void aux_refusals(int C, int B) {
+    mark("case aux context %dx%d for the refusals", C, B);
+    pp_ctx* c = make_ctx(C, B);
+    const int ns = 3;
+    AuxCfg k{B, C, ns, 0, 0, 0, 0, 0};
+    AuxIn in(k);
+    // (no output is checked here: a refused call writes nothing, and in the null-pointer loop the calls that do not
+    // take the pointer in turn succeed, into `out`, which is large enough for each of them)
+    const Outs o;
+    std::vector<double> outv((size_t)ns * C * B);
+    double* out = outv.data();
+    std::vector<int32_t> badslot(ns, 9);
+    const void* src = in.src();
+    const double *f = in.freqs.data(), *P = in.P.data(), *p3 = in.par3.data(), *w = in.w.data(), *mp = in.mprof.data();
+    const double *p5 = in.params5.data(), *n3 = in.nus3.data(), *sc = in.scales.data(), *er = in.errs.data();
+#define REF(what, call) AUX(o, "refused: " what, call)
+    // the shared preamble, entry point by entry point: null, nbin, shape, dtype, freqs_stride
+    for (int B2 : {B + 1, 6, 4098}) {
+        REF("pp_reference_phase_seed nbin", pp_reference_phase_seed(c, src, PP_F64, 0, ns, C, B2, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 20, out));
+        REF("pp_rotate_portraits nbin", pp_rotate_portraits(c, src, out, PP_F64, 0, ns, C, B2, f, 0, P, p3, INFINITY, INFINITY));
+        REF("pp_align_accumulate nbin", pp_align_accumulate(c, src, PP_F64, 0, ns, C, B2, f, 0, P, p3, w, out, out));
+        REF("pp_channel_red_chi2 nbin", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B2, nullptr, f, 0, P, p5, n3, sc, er, out));
+        REF("pp_fit_phase_shift_batch nbin", pp_fit_phase_shift_batch(c, mp, mp, nullptr, ns, B2, -0.5, 0.5, 20, out));
+        REF("pp_rfft_rows nbin", pp_rfft_rows(c, src, PP_F64, ns, B2, out));
+        REF("pp_channel_noise nbin", pp_channel_noise(c, src, PP_F64, 0, ns, B2, PP_NORM_NONE, nullptr, out, out));
+        REF("pp_channel_snrs nbin", pp_channel_snrs(c, src, PP_F64, 0, ns, B2, 3.25, out));
+        REF("pp_pca_gram nbin", pp_pca_gram(c, src, PP_F64, 0, C, B2, w, (double)C, C - 1.0, out, out));
+        REF("pp_gaussian_portrait nbin", pp_gaussian_portrait(c, C, B2, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5, out, 0));
+        REF("pp_model_set_gaussian nbin", pp_model_set_gaussian(c, 2, C, B2, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5));
+        REF("pp_model_set_spline nbin", pp_model_set_spline(c, 2, C, B2, f, 0, mp, 0, nullptr, nullptr, 3));
+        REF("pp_model_set nbin", pp_model_set(c, 2, src, PP_F64, 0, C, B2));
+    }
+    for (int which = 0; which < 2; ++which) {        // 0: nsub 0, 1: nchan 0
+        const int s = which == 0 ? 0 : ns, ch = which == 1 ? 0 : C;
+        REF("pp_reference_phase_seed shape", pp_reference_phase_seed(c, src, PP_F64, 0, s, ch, B, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 20, out));
+        REF("pp_rotate_portraits shape", pp_rotate_portraits(c, src, out, PP_F64, 0, s, ch, B, f, 0, P, p3, INFINITY, INFINITY));
+        REF("pp_align_accumulate shape", pp_align_accumulate(c, src, PP_F64, 0, s, ch, B, f, 0, P, p3, w, out, out));
+        REF("pp_channel_red_chi2 shape", pp_channel_red_chi2(c, src, PP_F64, 0, s, ch, B, nullptr, f, 0, P, p5, n3, sc, er, out));
+    }
+    REF("pp_reference_phase_seed Ns", pp_reference_phase_seed(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 0, out));
+    REF("pp_fit_phase_shift_batch nprof", pp_fit_phase_shift_batch(c, mp, mp, nullptr, 0, B, -0.5, 0.5, 20, out));
+    REF("pp_fit_phase_shift_batch Ns", pp_fit_phase_shift_batch(c, mp, mp, nullptr, ns, B, -0.5, 0.5, 0, out));
+    REF("pp_rfft_rows nrows", pp_rfft_rows(c, src, PP_F64, 0, B, out));
+    REF("pp_synth_portraits nsub", pp_synth_portraits(c, 0, out, PP_F64, 0, f, P, p3, nullptr, 0.05, 7, 0));
+    REF("pp_channel_noise nrows", pp_channel_noise(c, src, PP_F64, 0, 0, B, PP_NORM_NONE, nullptr, out, out));
+    REF("pp_channel_noise method", pp_channel_noise(c, src, PP_F64, 0, ns, B, 9, nullptr, out, out));
+    REF("pp_channel_noise prof without divisors", pp_channel_noise(c, src, PP_F64, 0, ns, B, PP_NORM_PROF, nullptr, out, out));
+    REF("pp_channel_snrs nrows", pp_channel_snrs(c, src, PP_F64, 0, 0, B, 3.25, out));
+    REF("pp_channel_snrs null", pp_channel_snrs(c, src, PP_F64, 0, ns, B, 3.25, nullptr));
+    REF("pp_zap_median shape", pp_zap_median(c, sc, (const unsigned char*)src, 0, C, 5.0, (unsigned char*)out));
+    REF("pp_zap_median channels", pp_zap_median(c, sc, (const unsigned char*)src, ns, 5000, 5.0, (unsigned char*)out));
+    REF("pp_pca_gram nchan", pp_pca_gram(c, src, PP_F64, 0, 1, B, w, 1.0, 1.0, out, out));
+    REF("pp_pca_gram weights", pp_pca_gram(c, src, PP_F64, 0, C, B, w, 0.0, 1.0, out, out));
+    for (int dt : {7, -1}) {
+        REF("pp_reference_phase_seed dtype", pp_reference_phase_seed(c, src, dt, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 20, out));
+        REF("pp_rotate_portraits dtype", pp_rotate_portraits(c, src, out, dt, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY));
+        REF("pp_align_accumulate dtype", pp_align_accumulate(c, src, dt, 0, ns, C, B, f, 0, P, p3, w, out, out));
+        REF("pp_channel_red_chi2 dtype", pp_channel_red_chi2(c, src, dt, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, out));
+        REF("pp_synth_portraits dtype", pp_synth_portraits(c, 0, out, dt, ns, f, P, p3, nullptr, 0.05, 7, 0));
+        REF("pp_channel_noise dtype", pp_channel_noise(c, src, dt, 0, ns, B, PP_NORM_NONE, nullptr, out, out));
+        REF("pp_channel_snrs dtype", pp_channel_snrs(c, src, dt, 0, ns, B, 3.25, out));
+        REF("pp_pca_gram dtype", pp_pca_gram(c, src, dt, 0, C, B, w, (double)C, C - 1.0, out, out));
+        REF("pp_model_set dtype", pp_model_set(c, 2, src, dt, 0, C, B));
+    }
+    for (int64_t fs : {(int64_t)5, (int64_t)-1, (int64_t)C + 1}) {
+        REF("pp_reference_phase_seed freqs_stride", pp_reference_phase_seed(c, src, PP_F64, 0, ns, C, B, f, fs, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 20, out));
+        REF("pp_rotate_portraits freqs_stride", pp_rotate_portraits(c, src, out, PP_F64, 0, ns, C, B, f, fs, P, p3, INFINITY, INFINITY));
+        REF("pp_align_accumulate freqs_stride", pp_align_accumulate(c, src, PP_F64, 0, ns, C, B, f, fs, P, p3, w, out, out));
+        REF("pp_channel_red_chi2 freqs_stride", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B, nullptr, f, fs, P, p5, n3, sc, er, out));
+    }
+    // one null pointer at a time
+    for (int z = 0; z < 9; ++z) {
+#define NZ(i, p) (z == (i) ? nullptr : (p))
+        REF("pp_reference_phase_seed null", pp_reference_phase_seed(NZ(8, c), NZ(0, src), PP_F64, 0, ns, C, B, NZ(1, f), 0, NZ(2, P), NZ(3, p3), INFINITY, INFINITY,
+                                                                   NZ(4, w), NZ(5, mp), -0.5, 0.5, 20, NZ(6, out)));
+        REF("pp_rotate_portraits null", pp_rotate_portraits(NZ(8, c), NZ(0, src), NZ(6, out), PP_F64, 0, ns, C, B, NZ(1, f), 0, NZ(2, P), NZ(3, p3), INFINITY, INFINITY));
+        REF("pp_align_accumulate null", pp_align_accumulate(NZ(8, c), NZ(0, src), PP_F64, 0, ns, C, B, NZ(1, f), 0, NZ(2, P), NZ(3, p3), NZ(4, w), NZ(6, out), NZ(7, out)));
+        REF("pp_channel_red_chi2 null", pp_channel_red_chi2(NZ(8, c), NZ(0, src), PP_F64, 0, ns, C, B, nullptr, NZ(1, f), 0, NZ(2, P), NZ(3, p5), NZ(4, n3), NZ(5, sc),
+                                                           NZ(7, er), NZ(6, out)));
+        REF("pp_fit_phase_shift_batch null", pp_fit_phase_shift_batch(NZ(8, c), NZ(0, mp), NZ(1, mp), nullptr, ns, B, -0.5, 0.5, 20, NZ(6, out)));
+        REF("pp_rfft_rows null", pp_rfft_rows(NZ(8, c), NZ(0, src), PP_F64, ns, B, NZ(6, out)));
+        REF("pp_synth_portraits null", pp_synth_portraits(NZ(8, c), 0, NZ(6, out), PP_F64, ns, NZ(1, f), NZ(2, P), NZ(3, p3), nullptr, 0.05, 7, 0));
+        REF("pp_channel_noise null", pp_channel_noise(NZ(8, c), NZ(0, src), PP_F64, 0, ns, B, PP_NORM_NONE, nullptr, NZ(6, out), NZ(7, out)));
+        REF("pp_zap_median null", pp_zap_median(NZ(8, c), NZ(0, sc), NZ(1, (const unsigned char*)src), ns, C, 5.0, NZ(6, (unsigned char*)out)));
+        REF("pp_pca_gram null", pp_pca_gram(NZ(8, c), NZ(0, src), PP_F64, 0, C, B, NZ(4, w), (double)C, C - 1.0, NZ(6, out), NZ(7, out)));
+        REF("pp_gaussian_portrait null", pp_gaussian_portrait(NZ(8, c), C, B, NZ(1, f), NZ(0, "000"), 1500.0, 0.0, 0.0, -4.0, 1, NZ(3, p5), NZ(6, out), 0));
+        REF("pp_model_set_gaussian null", pp_model_set_gaussian(NZ(8, c), 2, C, B, NZ(1, f), NZ(0, "000"), 1500.0, 0.0, 0.0, -4.0, 1, NZ(3, p5)));
+        REF("pp_spline_portrait null", pp_spline_portrait(NZ(8, c), C, B, NZ(1, f), 1, NZ(0, mp), 8, NZ(2, sc), NZ(3, sc), 3, NZ(6, out), 0));
+        REF("pp_model_set_spline null", pp_model_set_spline(NZ(8, c), 2, C, B, NZ(1, f), 1, NZ(0, mp), 8, NZ(2, sc), NZ(3, sc), 3));
+        REF("pp_model_set null", pp_model_set(NZ(8, c), 2, NZ(0, src), PP_F64, 0, C, B));
+        REF("pp_model_apply_response null", pp_model_apply_response(NZ(8, c), 0, NZ(0, mp), NZ(1, sc)));
+#undef NZ
+    }
+    // slots
+    REF("pp_synth_portraits unset slot", pp_synth_portraits(c, 9, out, PP_F64, ns, f, P, p3, nullptr, 0.05, 7, 0));
+    REF("pp_synth_portraits slot out of range", pp_synth_portraits(c, PP_MAX_SLOTS, out, PP_F64, ns, f, P, p3, nullptr, 0.05, 7, 0));
+    REF("pp_channel_red_chi2 unset slot", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B, badslot.data(), f, 0, P, p5, n3, sc, er, out));
+    REF("pp_channel_red_chi2 slot of another shape", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C / 2, B, nullptr, f, 0, P, p5, n3, sc, er, out));
+    REF("pp_model_apply_response unset slot", pp_model_apply_response(c, 9, mp, nullptr));
+    REF("pp_model_apply_response slot out of range", pp_model_apply_response(c, -1, mp, nullptr));
+    REF("pp_model_set slot", pp_model_set(c, PP_MAX_SLOTS, src, PP_F64, 0, C, B));
+    REF("pp_model_set nchan", pp_model_set(c, 2, src, PP_F64, 0, 0, B));
+    // generators
+    REF("pp_gaussian_portrait shape", pp_gaussian_portrait(c, 0, B, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5, out, 0));
+    REF("pp_gaussian_portrait components", pp_gaussian_portrait(c, C, B, f, "000", 1500.0, 0.0, 0.0, -4.0, 65, p5, out, 0));
+    REF("pp_gaussian_portrait code", pp_gaussian_portrait(c, C, B, f, "0x0", 1500.0, 0.0, 0.0, -4.0, 1, p5, out, 0));
+    REF("pp_model_set_gaussian code", pp_model_set_gaussian(c, 2, C, B, f, "002", 1500.0, 0.0, 0.0, -4.0, 1, p5));
+    REF("pp_model_set_gaussian slot", pp_model_set_gaussian(c, -1, C, B, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5));
+    REF("pp_spline_portrait shape", pp_spline_portrait(c, 0, B, f, 0, mp, 0, nullptr, nullptr, 3, out, 0));
+    REF("pp_spline_portrait components", pp_spline_portrait(c, C, B, f, 33, mp, 8, sc, sc, 3, out, 0));
+    REF("pp_spline_portrait degree", pp_spline_portrait(c, C, B, f, 1, mp, 8, sc, sc, 6, out, 0));
+    REF("pp_model_set_spline knots", pp_model_set_spline(c, 2, C, B, f, 1, mp, 7, sc, sc, 3));
+    // the pca calls out of order, then their own argument checks
+    std::vector<double> vecs((size_t)3 * C, 0.1), lam(3, 2.0);
+    const int32_t ieig[2] = {2, 0}, ieig_bad[2] = {0, 5};
+    REF("pp_pca_basis before pp_pca_gram", pp_pca_basis(c, vecs.data(), lam.data(), 3, out, out));
+    REF("pp_pca_project before pp_pca_gram", pp_pca_project(c, ieig, 2, out, out));
+    { Outs g; double* mean = g.d(B); double* gram = g.d((size_t)C * C);
+      AUX(g, "pp_pca_gram for the refusals", pp_pca_gram(c, src, PP_F64, 0, C, B, w, (double)C, C - 1.0, mean, gram)); }
+    REF("pp_pca_project before pp_pca_basis", pp_pca_project(c, ieig, 2, out, out));
+    REF("pp_pca_basis nvec", pp_pca_basis(c, vecs.data(), lam.data(), 17, out, out));
+    REF("pp_pca_basis null", pp_pca_basis(c, vecs.data(), nullptr, 3, out, out));
+    { Outs g; double* basis = g.d((size_t)3 * B); double* stats = g.d(12);
+      AUX(g, "pp_pca_basis for the refusals", pp_pca_basis(c, vecs.data(), lam.data(), 3, basis, stats)); }
+    REF("pp_pca_project ncomp", pp_pca_project(c, ieig, 4, out, out));
+    REF("pp_pca_project index", pp_pca_project(c, ieig_bad, 2, out, out));
+    REF("pp_pca_project null", pp_pca_project(c, nullptr, 2, out, out));
+    REF("pp_pca_gram refused drops the resident rows", pp_pca_gram(c, src, PP_F64, 0, C, B, w, (double)C, -1.0, out, out));
+    REF("pp_pca_basis after a refused pp_pca_gram", pp_pca_basis(c, vecs.data(), lam.data(), 3, out, out));
+    // an enqueued batch owns the context: every auxiliary call refuses until it is collected
+    {
+        Spec s; s.C = C; s.B = B;
+        Batch b(s);
+        mark("case aux refused: a batch is pending");
+        ++g_ncase;
+        mark("enqueue rc %d", pp_fit_enqueue(c, &b.in, &b.out));
+        REF("pending pp_fit_phase_shift_batch", pp_fit_phase_shift_batch(c, mp, mp, nullptr, ns, B, -0.5, 0.5, 20, out));
+        REF("pending pp_reference_phase_seed", pp_reference_phase_seed(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 20, out));
+        REF("pending pp_synth_portraits", pp_synth_portraits(c, 0, out, PP_F64, ns, f, P, p3, nullptr, 0.05, 7, 0));
+        REF("pending pp_rotate_portraits", pp_rotate_portraits(c, src, out, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY));
+        REF("pending pp_align_accumulate", pp_align_accumulate(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, w, out, out));
+        REF("pending pp_channel_red_chi2", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, out));
+        REF("pending pp_gaussian_portrait", pp_gaussian_portrait(c, C, B, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5, out, 0));
+        REF("pending pp_model_set_gaussian", pp_model_set_gaussian(c, 2, C, B, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5));
+        REF("pending pp_spline_portrait", pp_spline_portrait(c, C, B, f, 0, mp, 0, nullptr, nullptr, 3, out, 0));
+        REF("pending pp_model_set_spline", pp_model_set_spline(c, 2, C, B, f, 0, mp, 0, nullptr, nullptr, 3));
+        REF("pending pp_model_apply_response", pp_model_apply_response(c, 0, mp, nullptr));
+        REF("pending pp_rfft_rows", pp_rfft_rows(c, src, PP_F64, ns, B, out));
+        REF("pending pp_channel_noise", pp_channel_noise(c, src, PP_F64, 0, ns, B, PP_NORM_NONE, nullptr, out, out));
+        REF("pending pp_channel_snrs", pp_channel_snrs(c, src, PP_F64, 0, ns, B, 3.25, out));
+        REF("pending pp_zap_median", pp_zap_median(c, sc, (const unsigned char*)src, ns, C, 5.0, (unsigned char*)out));
+        REF("pending pp_pca_gram", pp_pca_gram(c, src, PP_F64, 0, C, B, w, (double)C, C - 1.0, out, out));
+        REF("pending pp_pca_basis", pp_pca_basis(c, vecs.data(), lam.data(), 3, out, out));
+        REF("pending pp_pca_project", pp_pca_project(c, ieig, 2, out, out));
+        REF("pending pp_model_set", pp_model_set(c, 2, src, PP_F64, 0, C, B));
+        mark("collect rc %d", pp_fit_collect(c));
+    }
+#undef REF
+    MUST(pp_destroy(c));
+}
+
+// row lengths 64, 2048 (with option one_exchange 0 and 1) and 1000; option profile 0 and 1; the work budget large, and
+// small enough that a host input goes through in three or more runs with a short last one; inside each: f64 / f32,
+// host / device rows, freqs_stride 0 / nchan, model_slot null / set
+static void aux_cases() {
+    struct Len { int B, one_exchange; };
+    const Len lens[] = {{64, -1}, {2048, 0}, {2048, 1}, {1000, -1}};
+    const int chans[3] = {8, 24, 48};
+    int q = 0;
+    char tag[96];
+    for (const Len& L : lens)
+        for (int profile : {0, 1})
+            for (int small : {0, 1}) {
+                const int C = chans[q % 3];
+                const int ns_of[2][3] = {{3, 5, 11}, {7, 10, 11}};
+                mark("case aux context %dx%d one_exchange=%d profile=%d budget=%s", C, L.B, L.one_exchange, profile, small ? "small" : "large");
+                pp_ctx* c = make_ctx(C, L.B);
+                if (L.one_exchange >= 0) MUST(pp_set_option(c, "one_exchange", L.one_exchange));
+                MUST(pp_set_option(c, "profile", profile));
+                snprintf(tag, sizeof tag, "one_exchange=%d profile=%d budget=%s", L.one_exchange, profile, small ? "small" : "large");
+                int j = q;
+                for (int f32 : {0, 1})
+                    for (int dev : {0, 1}) {
+                        // the budget: 3.4 subints' portraits of this element size
+                        if (small) MUST(pp_set_option(c, "max_work_bytes", 3.4 * C * L.B * (f32 ? 4 : 8)));
+                        for (int fstride : {0, 1})
+                            for (int slot : {0, 1})
+                                aux_ports_calls(c, AuxCfg{L.B, C, ns_of[small][j++ % 3], f32, dev, fstride, slot, small}, tag);
+                        aux_rows_calls(c, AuxCfg{L.B, C, ns_of[small][j++ % 3], f32, dev, 0, 0, small}, tag);
+                    }
+                if (small) MUST(pp_set_option(c, "max_work_bytes", 3.4 * C * L.B * 8));
+                aux_host_calls(c, ns_of[small][j % 3], C, L.B, tag);
+                MUST(pp_destroy(c));
+                ++q;
+            }
+    aux_refusals(24, 64);
+    aux_refusals(8, 1000);
+}
+
 int main() {
     g_mark = (void (*)(const char*))dlsym(RTLD_DEFAULT, "hip_stub_mark");
     if (!g_mark) fprintf(stderr, "trace_driver: no hip_stub_mark (LD_PRELOAD libhip_stub.so): cases go unnamed\n");
@@ -238,6 +635,7 @@ int main() {
     entry_cases();
     chain("chain");
     option_cases();
+    aux_cases();
     printf("trace_driver: done\n");
     return 0;
 }
