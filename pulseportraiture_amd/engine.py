@@ -4,6 +4,7 @@ The batch entry point `Engine.fit_batch` is what reaches 10^4 fits/s; the
 reference-shaped single-subint functions in pptoaslib.py / pplib.py marshal
 into it.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -76,6 +77,23 @@ def _wait_for_producer(x):
     waited.add(key)
 
 
+def _array_arg(x, what):
+    """(pointer, dtype code, on_device, shape, keep-alive) of an array argument: NumPy (anything
+    that is not f32 is converted to f64, and made contiguous) or a device tensor, f64 or f32.  A
+    device tensor must be contiguous -- the library reads (rotate_portraits: writes) it as dense
+    memory, so a strided view is refused: "<what> must be contiguous"."""
+    if _is_device_array(x):
+        if not x.is_contiguous():
+            raise EngineError("%s must be contiguous" % what)
+        return (C.c_void_p(x.data_ptr()), PP_F64 if x.element_size() == 8 else PP_F32, 1,
+                tuple(int(v) for v in x.shape), x)
+    a = np.asarray(x)
+    if a.dtype != np.float32:
+        a = a.astype(np.float64, copy=False)
+    a = np.ascontiguousarray(a)
+    return C.c_void_p(a.ctypes.data), PP_F64 if a.dtype == np.float64 else PP_F32, 0, a.shape, a
+
+
 def _dp(a):
     return None if a is None else a.ctypes.data_as(c_double_p)
 
@@ -101,10 +119,29 @@ def _nu_array(nus, nsub):
                                                 (nsub, 3)))
 
 
+class _Batch(object):
+    """One prepared fit: the result dict, the two argument blocks, and everything those point
+    to.  Whoever holds it keeps all of that alive -- until the synchronous call returns, or
+    until collect() / wait() has returned for an enqueued / submitted batch."""
+
+    def __init__(self, res, fin, fout, keep):
+        self.res, self.fin, self.fout, self.keep = res, fin, fout, keep
+
+    def finish(self):
+        """The result dict of the completed batch (`duration` becomes a Python float)."""
+        self.res["duration"] = float(self.res["duration"][0])
+        return self.res
+
+
 class Engine(object):
     """Device context + scratch; not thread-safe (one per host thread and GPU)."""
 
     def __init__(self, device=0):
+        self._ctx = None
+        self._digests = {}      # slot -> content digest of the resident template
+        self._queue = []        # enqueued batches (_Batch), oldest first, until collect()
+        self._pending = None    # the submitted batch (_Batch) until wait()
+        self._pca_shape = None  # (nchan, nbin) of the centred portrait pca_gram left on the device
         self._lib = _lib.load()
         ctx = C.c_void_p()
         _check(self._lib.pp_create(int(device), C.byref(ctx)), "pp_create")
@@ -119,10 +156,9 @@ class Engine(object):
             # (run the GPU suite once with the solve / post-fit stage of enqueued batches on the context's second
             # stream: PP_OVERLAP_POST=1)
             self.set_option("overlap_post", int(os.environ["PP_OVERLAP_POST"]))
-        self._digests = {}      # slot -> content digest of the resident template
 
     def close(self):
-        if getattr(self, "_ctx", None):
+        if self._ctx:
             self._lib.pp_destroy(self._ctx)
             self._ctx = None
 
@@ -153,20 +189,10 @@ class Engine(object):
         """Upload an nchan x nbin template (numpy array or CUDA tensor).
         `digest` (optional) tags the slot's content for set_model_cached."""
         self._digests[int(slot)] = digest
-        if _is_device_array(model):
-            nchan, nbin = int(model.shape[-2]), int(model.shape[-1])
-            dtype = PP_F64 if model.element_size() == 8 else PP_F32
-            ptr, on_dev, keep = model.data_ptr(), 1, model
-        else:
-            m = np.asarray(model)
-            if m.dtype != np.float32:
-                m = m.astype(np.float64, copy=False)
-            m = np.ascontiguousarray(m)
-            nchan, nbin = m.shape
-            dtype = PP_F64 if m.dtype == np.float64 else PP_F32
-            ptr, on_dev, keep = m.ctypes.data, 0, m
-        _check(self._lib.pp_model_set(self._ctx, int(slot), C.c_void_p(ptr), dtype,
-                                      on_dev, nchan, nbin), "pp_model_set")
+        ptr, dtype, on_dev, shape, keep = _array_arg(model, "set_model: the device template")
+        nchan, nbin = shape[-2:] if on_dev else shape
+        _check(self._lib.pp_model_set(self._ctx, int(slot), ptr, dtype, on_dev, nchan, nbin),
+               "pp_model_set")
         del keep
         return self._lib.pp_model_nharm(self._ctx, int(slot))
 
@@ -188,12 +214,18 @@ class Engine(object):
     def model_nharm(self, slot=0):
         return self._lib.pp_model_nharm(self._ctx, int(slot))
 
+    def _slot_changed(self, slot):
+        """The library rewrote the slot's template: forget what set_model_cached knew of it;
+        returns the number of harmonics kept."""
+        self._digests.pop(int(slot), None)
+        return int(self._lib.pp_model_nharm(self._ctx, int(slot)))
+
     # -- the fit ------------------------------------------------------------
     def fit_batch(self, data, freqs, P, init_params, errs=None, nu_fits=None,
                   nu_outs=None, fit_flags=(1, 1, 0, 0, 0), log10_tau=False,
                   option=0, is_toa=True, model_slot=None, chan_mask=None,
                   per_channel=True, objective=False, seed_ns=0, method='trust-ncg',
-                  records=None, ref_seed=None, _submit=False):
+                  records=None, ref_seed=None):
         """Fit nsub subints.  data: [nsub,nchan,nbin] numpy array (f64/f32) or
         CUDA tensor.  freqs: [nchan] or [nsub,nchan].  Returns a dict of arrays
         (see include/pp_toas.h pp_fit_out).  errs / chan_mask may be CUDA
@@ -211,6 +243,19 @@ class Engine(object):
         single pass over the portraits, and replaces init_params[:, 0]; the result gains
         "seed_phase".  Raises EngineNotSupported when the batch has no single-pass path
         (include/pp_toas.h pp_seed_ref): form the guess with reference_phase_seed then."""
+        b = self._prepare(data, freqs, P, init_params, errs, nu_fits, nu_outs, fit_flags, log10_tau, option,
+                          is_toa, model_slot, chan_mask, per_channel, objective, seed_ns, method, records,
+                          ref_seed)
+        _check(self._lib.pp_fit_portrait_batch(self._ctx, C.byref(b.fin), C.byref(b.fout)),
+               "pp_fit_portrait_batch")
+        return b.finish()
+
+    def _prepare(self, data, freqs, P, init_params, errs=None, nu_fits=None, nu_outs=None,
+                 fit_flags=(1, 1, 0, 0, 0), log10_tau=False, option=0, is_toa=True, model_slot=None,
+                 chan_mask=None, per_channel=True, objective=False, seed_ns=0, method='trust-ncg',
+                 records=None, ref_seed=None):
+        """fit_batch's arguments (and defaults: submit and enqueue hand theirs straight through)
+        as a _Batch ready for one of the three C calls."""
         if method not in METHODS:
             raise EngineError("unknown method %r" % (method,))
         if records is not None and not (
@@ -218,22 +263,22 @@ class Engine(object):
                 records.element_size() == 8 and tuple(records.shape)[-1] == _lib.PP_RECORD_WIDTH):
             raise EngineError("records must be a contiguous float64 CUDA tensor [nsub, %d]"
                               % _lib.PP_RECORD_WIDTH)
-        if _is_device_array(data):
-            nsub, nchan, nbin = (int(s) for s in data.shape)
-            if not data.is_contiguous():
-                raise EngineError("device data must be contiguous")
-            dtype = PP_F64 if data.element_size() == 8 else PP_F32
-            dptr, on_dev, keep = data.data_ptr(), 1, data
-        else:
-            d = np.asarray(data)
-            if d.dtype != np.float32:
-                d = d.astype(np.float64, copy=False)
-            d = np.ascontiguousarray(d)
-            if d.ndim == 2:
-                d = d[None]
-            nsub, nchan, nbin = d.shape
-            dtype = PP_F64 if d.dtype == np.float64 else PP_F32
-            dptr, on_dev, keep = d.ctypes.data, 0, d
+        fin, in_keep, aux_given = self._fit_in(data, freqs, P, init_params, errs, nu_fits, nu_outs, fit_flags,
+                                               log10_tau, option, is_toa, model_slot, chan_mask, seed_ns, method)
+        seed_keep = None if ref_seed is None else self._seed_ref(fin, ref_seed, aux_given)
+        fout, res = self._fit_out(fin, data.device if fin.data_on_device else None, per_channel, objective,
+                                  records, fit_flags)
+        if seed_keep is not None:
+            res["seed_phase"] = seed_keep[-1]
+        return _Batch(res, fin, fout, (in_keep, seed_keep, records))
+
+    def _fit_in(self, data, freqs, P, init_params, errs, nu_fits, nu_outs, fit_flags, log10_tau, option,
+                is_toa, model_slot, chan_mask, seed_ns, method):
+        """The inputs as a FitIn: (fin, what it points to, whether errs / chan_mask were given)."""
+        dptr, dtype, on_dev, shape, keep = _array_arg(data, "device data")
+        if not on_dev and len(shape) == 2:      # (one host portrait: a batch of one subint)
+            shape = (1,) + shape
+        nsub, nchan, nbin = shape
         freqs = np.ascontiguousarray(freqs, dtype=np.float64)
         if freqs.ndim == 1:
             if freqs.shape[0] != nchan:
@@ -271,7 +316,7 @@ class Engine(object):
 
         fin = FitIn()
         fin.nsub, fin.nchan, fin.nbin = nsub, nchan, nbin
-        fin.data = C.c_void_p(dptr)
+        fin.data = dptr
         fin.data_dtype, fin.data_on_device = dtype, on_dev
         fin.model_slot = None if slot is None else slot.ctypes.data_as(c_int32_p)
         fin.freqs, fin.freqs_stride = _dp(freqs), fstride
@@ -291,43 +336,53 @@ class Engine(object):
         fin.option, fin.is_toa = int(option), int(bool(is_toa))
         fin.seed_ns = int(seed_ns)
         fin.method = METHODS[method]
-        seed_keep = None
-        if ref_seed is not None:
-            sr = SeedRef()
-            w = ref_seed.get("weights")
-            if w is not None and _is_device_array(w):
-                if not aux_dev and (errs is not None or chan_mask is not None):
-                    raise EngineError("ref_seed weights on the device need errs / chan_mask there too")
-                if not (w.is_contiguous() and w.element_size() == 8 and tuple(w.shape) == (nsub, nchan)):
-                    raise EngineError("device ref_seed weights must be a contiguous float64 tensor [nsub,nchan]")
-                fin.aux_on_device = 1
-                sr.weights = C.cast(w.data_ptr(), c_double_p)
-            elif w is not None:
-                if aux_dev:
-                    raise EngineError("ref_seed weights must be a CUDA tensor when errs / chan_mask are")
-                w = _f64(w, (nsub, nchan))
-                sr.weights = _dp(w)
-            mp = np.ascontiguousarray(ref_seed["model_profs"], dtype=np.float64)
-            if mp.ndim == 1:
-                sr.model_prof_stride = 0
-            elif mp.shape == (nsub, nbin):
-                sr.model_prof_stride = nbin
-            else:
-                raise EngineError("ref_seed model_profs must be [nbin] or [nsub,nbin]")
-            if mp.shape[-1] != nbin:
-                raise EngineError("ref_seed model_profs has %d bins, the data %d" % (mp.shape[-1], nbin))
-            sr.model_profs = _dp(mp)
-            numean = _f64(ref_seed["nu_mean"], (nsub,))
-            sr.nu_mean = _dp(numean)
-            lo_hi = ref_seed.get("bounds", (-0.5, 0.5))
-            sr.lo, sr.hi = float(lo_hi[0]), float(lo_hi[1])
-            sr.Ns = int(ref_seed.get("Ns", 100))
-            sr.finish = 1 if ref_seed.get("finish", "simplex") == "simplex" else 0
-            sphase = np.empty(nsub)
-            sr.seed_phase = _dp(sphase)
-            fin.ref_seed = C.pointer(sr)
-            seed_keep = (sr, w, mp, numean, sphase)
+        return fin, (keep, freqs, P, x0, errs, nu_fits, nu_outs, slot, mask, chan_mask), \
+            errs is not None or chan_mask is not None
 
+    def _seed_ref(self, fin, ref_seed, aux_given):
+        """fit_batch's ref_seed dict as a SeedRef hung into `fin`; returns what must stay alive:
+        (the SeedRef, what it points to ..., the seed_phase output array)."""
+        nsub, nchan, nbin = fin.nsub, fin.nchan, fin.nbin
+        aux_dev = bool(fin.aux_on_device)
+        sr = SeedRef()
+        w = ref_seed.get("weights")
+        if w is not None and _is_device_array(w):
+            if not aux_dev and aux_given:
+                raise EngineError("ref_seed weights on the device need errs / chan_mask there too")
+            if not (w.is_contiguous() and w.element_size() == 8 and tuple(w.shape) == (nsub, nchan)):
+                raise EngineError("device ref_seed weights must be a contiguous float64 tensor [nsub,nchan]")
+            fin.aux_on_device = 1
+            sr.weights = C.cast(w.data_ptr(), c_double_p)
+        elif w is not None:
+            if aux_dev:
+                raise EngineError("ref_seed weights must be a CUDA tensor when errs / chan_mask are")
+            w = _f64(w, (nsub, nchan))
+            sr.weights = _dp(w)
+        mp = np.ascontiguousarray(ref_seed["model_profs"], dtype=np.float64)
+        if mp.ndim == 1:
+            sr.model_prof_stride = 0
+        elif mp.shape == (nsub, nbin):
+            sr.model_prof_stride = nbin
+        else:
+            raise EngineError("ref_seed model_profs must be [nbin] or [nsub,nbin]")
+        if mp.shape[-1] != nbin:
+            raise EngineError("ref_seed model_profs has %d bins, the data %d" % (mp.shape[-1], nbin))
+        sr.model_profs = _dp(mp)
+        numean = _f64(ref_seed["nu_mean"], (nsub,))
+        sr.nu_mean = _dp(numean)
+        lo_hi = ref_seed.get("bounds", (-0.5, 0.5))
+        sr.lo, sr.hi = float(lo_hi[0]), float(lo_hi[1])
+        sr.Ns = int(ref_seed.get("Ns", 100))
+        sr.finish = 1 if ref_seed.get("finish", "simplex") == "simplex" else 0
+        sphase = np.empty(nsub)
+        sr.seed_phase = _dp(sphase)
+        fin.ref_seed = C.pointer(sr)
+        return sr, w, mp, numean, sphase
+
+    def _fit_out(self, fin, data_device, per_channel, objective, records, fit_flags):
+        """The result dict (arrays the library fills in place) and the FitOut that points into
+        it.  `data_device`: the device of device-resident portraits, None for host portraits."""
+        nsub, nchan = fin.nsub, fin.nchan
         res = dict(params=np.empty((nsub, 5)), param_errs=np.empty((nsub, 5)),
                    nu_refs=np.empty((nsub, 3)), cov=np.empty((nsub, 5, 5)),
                    chi2=np.empty(nsub), red_chi2=np.empty(nsub), snr=np.empty(nsub),
@@ -338,7 +393,7 @@ class Engine(object):
         chan_dev = (per_channel == "device")
         if chan_dev:
             import torch
-            dev = data.device if on_dev else torch.device("cuda", self.device)
+            dev = data_device if data_device is not None else torch.device("cuda", self.device)
             res.update({k: torch.empty((nsub, nchan), dtype=torch.float64, device=dev)
                         for k in ("scales", "scale_errs", "channel_snrs")})
         elif per_channel:
@@ -367,52 +422,33 @@ class Engine(object):
             else:
                 setattr(fout, name, arr.ctypes.data_as(c_double_p))
         res["fit_flags"] = [1 if f else 0 for f in fit_flags]
-        if seed_keep is not None:
-            res["seed_phase"] = seed_keep[4]
-        if _submit == "enqueue":
-            _check(self._lib.pp_fit_enqueue(self._ctx, C.byref(fin), C.byref(fout)), "pp_fit_enqueue")
-            # every array the argument blocks point to stays alive until collect()
-            if not hasattr(self, "_queue"):
-                self._queue = []
-            self._queue.append((res, (keep, freqs, P, x0, errs, nu_fits, nu_outs, slot, mask, chan_mask,
-                                      records, fin, fout, seed_keep)))
-            return None
-        if _submit:
-            _check(self._lib.pp_fit_submit(self._ctx, C.byref(fin), C.byref(fout)), "pp_fit_submit")
-            # every array the argument blocks point to stays alive until wait()
-            self._pending = (res, (keep, freqs, P, x0, errs, nu_fits, nu_outs, slot, mask, chan_mask,
-                                   records, fin, fout, seed_keep))
-            return None
-        _check(self._lib.pp_fit_portrait_batch(self._ctx, C.byref(fin),
-                                               C.byref(fout)),
-               "pp_fit_portrait_batch")
-        del keep, seed_keep
-        res["duration"] = float(res["duration"][0])
-        return res
+        return fout, res
 
     def submit(self, *args, **kwargs):
         """fit_batch started on a worker thread of the context (pp_fit_submit): returns at
         once; wait() returns the result dict.  The caller's arrays must not be modified
         until then.  Two engines on one GPU overlap their copies and kernels."""
-        kwargs["_submit"] = True
-        self.fit_batch(*args, **kwargs)
+        b = self._prepare(*args, **kwargs)
+        _check(self._lib.pp_fit_submit(self._ctx, C.byref(b.fin), C.byref(b.fout)), "pp_fit_submit")
+        self._pending = b       # (everything the argument blocks point to stays alive until wait())
 
     def enqueue(self, *args, **kwargs):
         """fit_batch queued on the engine's stream (pp_fit_enqueue): returns without waiting for the
         GPU; collect() returns the result dict of the OLDEST enqueued batch.  Up to three batches may be
         pending: enqueue batch k + 1, then collect batch k, and the GPU never waits for the host
         between batches.  The caller's arrays must not be modified until the batch is collected."""
-        kwargs["_submit"] = "enqueue"
-        self.fit_batch(*args, **kwargs)
+        b = self._prepare(*args, **kwargs)
+        _check(self._lib.pp_fit_enqueue(self._ctx, C.byref(b.fin), C.byref(b.fout)), "pp_fit_enqueue")
+        self._queue.append(b)   # (everything the argument blocks point to stays alive until collect())
 
     def collect(self):
         """Complete the oldest enqueued batch; returns what fit_batch returns."""
-        if not getattr(self, "_queue", None):
+        if not self._queue:
             raise EngineError("nothing enqueued")
-        # the entry (result arrays + keep-alive references of everything the argument blocks point to) leaves the
-        # queue only once the C call is through with it; if that call fails, the Python queue is brought back in
-        # step with the library's (pp_fit_pending): the failed batch is gone there, younger ones may still be queued
-        res, keep = self._queue[0]
+        # the batch (result arrays + everything the argument blocks point to) leaves the queue only once the C
+        # call is through with it; if that call fails, the Python queue is brought back in step with the
+        # library's (pp_fit_pending): the failed batch is gone there, younger ones may still be queued
+        b = self._queue[0]
         try:
             _check(self._lib.pp_fit_collect(self._ctx), "pp_fit_collect")
         finally:
@@ -420,9 +456,7 @@ class Engine(object):
             left = left if left >= 0 else 0
             while len(self._queue) > left:
                 self._queue.pop(0)
-        del keep
-        res["duration"] = float(res["duration"][0])
-        return res
+        return b.finish()
 
     def poll(self):
         """True once the submitted batch is complete."""
@@ -433,29 +467,31 @@ class Engine(object):
 
     def wait(self):
         """Block until the submitted batch is complete; returns what fit_batch returns."""
-        if getattr(self, "_pending", None) is None:
+        if self._pending is None:
             raise EngineError("nothing submitted")
-        res, keep = self._pending
-        self._pending = None
+        b, self._pending = self._pending, None
         _check(self._lib.pp_fit_wait(self._ctx), "pp_fit_wait")
-        del keep
-        res["duration"] = float(res["duration"][0])
-        return res
+        return b.finish()
 
     # -- parity hooks / measurement ---------------------------------------
     def rfft_rows(self, rows):
-        r = np.asarray(rows)
-        if r.dtype != np.float32:
-            r = r.astype(np.float64, copy=False)
-        r = np.ascontiguousarray(r)
-        nrows, nbin = r.shape
+        src, dtype, on_dev, (nrows, nbin), keep = _array_arg(rows, "rfft_rows: rows")
+        if on_dev:
+            raise EngineError("rfft_rows takes host rows")
         out = np.empty((nrows, nbin // 2 + 1), dtype=np.complex128)
-        _check(self._lib.pp_rfft_rows(self._ctx, C.c_void_p(r.ctypes.data),
-                                      PP_F64 if r.dtype == np.float64 else PP_F32,
-                                      nrows, nbin,
-                                      out.ctypes.data_as(c_double_p)),
+        _check(self._lib.pp_rfft_rows(self._ctx, src, dtype, nrows, nbin, out.ctypes.data_as(c_double_p)),
                "pp_rfft_rows")
         return out
+
+    @contextlib.contextmanager
+    def _fps_finish(self, finish):
+        """The `fps_finish` option (how fit_phase_shift ends: SciPy's simplex, or Newton) set for
+        the calls made inside, and back to its default after them."""
+        self.set_option("fps_finish", 1 if finish == 'simplex' else 0)
+        try:
+            yield
+        finally:
+            self.set_option("fps_finish", 0)
 
     def fit_phase_shift_batch(self, data, model, noise=None, bounds=(-0.5, 0.5),
                               Ns=100, finish='newton'):
@@ -477,13 +513,10 @@ class Engine(object):
             nz = _f64([np.nan if v is None else v for v in
                        np.broadcast_to(np.asarray(noise, dtype=object), (nprof,))])
         out = np.empty((nprof, 7))
-        self.set_option("fps_finish", 1 if finish == 'simplex' else 0)
-        try:
+        with self._fps_finish(finish):
             _check(self._lib.pp_fit_phase_shift_batch(
                 self._ctx, _dp(d), _dp(m), _dp(nz), nprof, nbin, float(bounds[0]),
                 float(bounds[1]), int(Ns), _dp(out)), "pp_fit_phase_shift_batch")
-        finally:
-            self.set_option("fps_finish", 0)
         return out
 
     def reference_phase_seed(self, ports, freqs, P, weights, model_profs, phi=0.0, DM=0.0, GM=0.0,
@@ -492,26 +525,23 @@ class Engine(object):
         axis=0, weights=weights_i), model_profs_i, Ns) for every subint, the rotation
         and the channel mean fused into one read of the portraits (pptoas.py:421-457).
         Returns [nsub, 7] like fit_phase_shift_batch."""
-        src, dtype, on_dev, (nsub, nchan, nbin), keep = self._ports_arg(ports)
+        src, dtype, on_dev, (nsub, nchan, nbin), keep = _array_arg(ports, "reference_phase_seed: device ports")
         freqs, fstride, P, par = self._subint_args(freqs, P, (phi, DM, GM), nsub, nchan)
         w = _f64(weights, (nsub, nchan))
         mp = _f64(np.broadcast_to(np.asarray(model_profs, dtype=np.float64), (nsub, nbin)))
         out = np.empty((nsub, 7))
-        self.set_option("fps_finish", 1 if finish == 'simplex' else 0)
-        try:
+        with self._fps_finish(finish):
             _check(self._lib.pp_reference_phase_seed(
                 self._ctx, src, dtype, on_dev, nsub, nchan, nbin, _dp(freqs), fstride, _dp(P), _dp(par),
                 float(nu_DM), float(nu_GM), _dp(w), _dp(mp), float(bounds[0]), float(bounds[1]), int(Ns),
                 _dp(out)), "pp_reference_phase_seed")
-        finally:
-            self.set_option("fps_finish", 0)
         return out
 
     def rotate_portraits(self, ports, freqs, P, phi=0.0, DM=0.0, GM=0.0, nu_DM=np.inf,
                          nu_GM=np.inf):
         """Fourier-rotate ports[nsub,nchan,nbin] (numpy -> new numpy array; CUDA
         tensor -> rotated in place) by per-subint (phi, DM, GM)."""
-        src, dtype, on_dev, (nsub, nchan, nbin), keep = self._ports_arg(ports)
+        src, dtype, on_dev, (nsub, nchan, nbin), keep = _array_arg(ports, "rotate_portraits: device ports")
         out, dst = keep, src
         if not on_dev:
             out = np.empty_like(keep)
@@ -561,8 +591,7 @@ class Engine(object):
         _check(self._lib.pp_model_set_gaussian(self._ctx, int(slot), len(freqs), int(nbin),
                                                _dp(freqs), code, nu_ref, dc, tau_rot, alpha, ng,
                                                _dp(comps)), "pp_model_set_gaussian")
-        self._digests.pop(int(slot), None)
-        return int(self._lib.pp_model_nharm(self._ctx, int(slot)))
+        return self._slot_changed(slot)
 
     def _spline_args(self, mean_prof, eigvec, tck, nbin):
         from .splmodel import spline_device_args
@@ -589,8 +618,7 @@ class Engine(object):
         _check(self._lib.pp_model_set_spline(self._ctx, int(slot), len(freqs), basis.shape[1], _dp(freqs),
                                              ncomp, _dp(basis), len(t), _dp(t), _dp(coefs), k),
                "pp_model_set_spline")
-        self._digests.pop(int(slot), None)
-        return int(self._lib.pp_model_nharm(self._ctx, int(slot)))
+        return self._slot_changed(slot)
 
     def apply_response(self, slot, rconst=None, smear_wid=None):
         """Multiply the template resident in `slot` by an instrumental response in the
@@ -602,8 +630,7 @@ class Engine(object):
         wd = None if smear_wid is None else _f64(smear_wid)
         _check(self._lib.pp_model_apply_response(self._ctx, int(slot), _dp(rc), _dp(wd)),
                "pp_model_apply_response")
-        self._digests.pop(int(slot), None)
-        return int(self._lib.pp_model_nharm(self._ctx, int(slot)))
+        return self._slot_changed(slot)
 
     def model_means(self, slot, nchan, nbin):
         """Mean over phase of every channel of the template in `slot` (its DC
@@ -611,18 +638,6 @@ class Engine(object):
         dc = np.empty(int(nchan))
         _check(self._lib.pp_model_dc(self._ctx, int(slot), _dp(dc)), "pp_model_dc")
         return dc / float(nbin)
-
-    def _ports_arg(self, ports):
-        if _is_device_array(ports):
-            nsub, nchan, nbin = (int(v) for v in ports.shape)
-            dtype = PP_F64 if ports.element_size() == 8 else PP_F32
-            return C.c_void_p(ports.data_ptr()), dtype, 1, (nsub, nchan, nbin), ports
-        a = np.asarray(ports)
-        if a.dtype != np.float32:
-            a = a.astype(np.float64, copy=False)
-        a = np.ascontiguousarray(a)
-        return (C.c_void_p(a.ctypes.data), PP_F64 if a.dtype == np.float64 else PP_F32, 0,
-                a.shape, a)
 
     @staticmethod
     def _subint_args(freqs, P, triple, nsub, nchan):
@@ -639,7 +654,7 @@ class Engine(object):
         """ppalign's accumulation (ppalign.py:199-206): returns
         (sum_i w[i,n] * rotate_data(ports[i,n], phase_i, DM_i, P_i, freqs, nu_ref_i)
         as [nchan,nbin], sum_i w[i,n] as [nchan]); rows with w = 0 are skipped."""
-        src, dtype, on_dev, (nsub, nchan, nbin), keep = self._ports_arg(ports)
+        src, dtype, on_dev, (nsub, nchan, nbin), keep = _array_arg(ports, "align_accumulate: device ports")
         freqs, fstride, P, par = self._subint_args(freqs, P, (phase, DM, nu_ref), nsub, nchan)
         w = _f64(weights, (nsub, nchan))
         aligned = np.empty((nchan, nbin))
@@ -654,7 +669,7 @@ class Engine(object):
         (get_channels_to_zap, pptoas.py:1239-1245).  params[nsub,5] = phi, DM, GM,
         tau [rot, linear], alpha at nu_refs[nsub,3]; the template is the resident
         model slot of each subint."""
-        src, dtype, on_dev, (nsub, nchan, nbin), keep = self._ports_arg(ports)
+        src, dtype, on_dev, (nsub, nchan, nbin), keep = _array_arg(ports, "channel_red_chi2: device ports")
         freqs, fstride, P, _ = self._subint_args(freqs, P, None, nsub, nchan)
         params = _f64(params, (nsub, 5))
         nu_refs = _f64(nu_refs, (nsub, 3))
@@ -684,18 +699,7 @@ class Engine(object):
             raise ValueError("ports must be [nsub,nchan,nbin] or [nrows,nbin]")
         nbin = shape[-1]
         nrows = int(np.prod(shape[:-1]))
-        if _is_device_array(ports):
-            if not ports.is_contiguous():
-                raise EngineError("channel_noise: device ports must be contiguous")
-            src, on_dev = C.c_void_p(ports.data_ptr()), 1
-            dtype = PP_F64 if ports.element_size() == 8 else PP_F32
-        else:
-            keep = np.asarray(ports)
-            if keep.dtype != np.float32:
-                keep = keep.astype(np.float64, copy=False)
-            keep = np.ascontiguousarray(keep)
-            src, on_dev = C.c_void_p(keep.ctypes.data), 0
-            dtype = PP_F64 if keep.dtype == np.float64 else PP_F32
+        src, dtype, on_dev, _, keep = _array_arg(ports, "channel_noise: device ports")
         div = None
         if norm == 'prof':
             div = self._prof_norms(ports, weights)
@@ -740,28 +744,12 @@ class Engine(object):
                 self.fit_phase_shift_batch(rows[live], means[sub_of], finish='simplex')[:, 2]
         return div.reshape(-1)
 
-    def _rows_arg(self, ports, what):
-        """(pointer, dtype, on_device, shape, keep-alive) of rows handed over as NumPy or a
-        contiguous device tensor, f64 or f32 (anything else is converted to f64)."""
-        shape = tuple(int(v) for v in ports.shape)
-        if _is_device_array(ports):
-            if not ports.is_contiguous():
-                raise EngineError("%s: device rows must be contiguous" % what)
-            return (C.c_void_p(ports.data_ptr()), PP_F64 if ports.element_size() == 8 else PP_F32, 1,
-                    shape, ports)
-        keep = np.asarray(ports)
-        if keep.dtype != np.float32:
-            keep = keep.astype(np.float64, copy=False)
-        keep = np.ascontiguousarray(keep)
-        return (C.c_void_p(keep.ctypes.data), PP_F64 if keep.dtype == np.float64 else PP_F32, 0,
-                shape, keep)
-
     def channel_snrs(self, ports, fudge=3.25):
         """pplib.get_SNR (pplib.py:2289-2308) of every row of ports [..., nbin] (NumPy or a
         device tensor, f64 or f32): the row's sum, maximum and power-spectrum noise come
         from one pass over it on the device.  Returns an array shaped like ports without
         the bin axis."""
-        src, dtype, on_dev, shape, keep = self._rows_arg(ports, "channel_snrs")
+        src, dtype, on_dev, shape, keep = _array_arg(ports, "channel_snrs: device rows")
         if len(shape) < 2:
             raise ValueError("ports must be [..., nbin]")
         nrows = int(np.prod(shape[:-1]))
@@ -781,7 +769,7 @@ class Engine(object):
         same non-zero eigenvalues; fact is np.cov's normalisation.  Formed on the f64 MFMA in a
         fixed order (the same bits on every run).  The centred rows stay on the device for
         pca_basis and pca_project."""
-        src, dtype, on_dev, shape, keep = self._rows_arg(port, "pca_gram")
+        src, dtype, on_dev, shape, keep = _array_arg(port, "pca_gram: device rows")
         if len(shape) != 2:
             raise ValueError("port must be [nchan,nbin]")
         nchan, nbin = shape
@@ -806,7 +794,7 @@ class Engine(object):
         v = np.ascontiguousarray(np.asarray(vecs, dtype=np.float64).T)
         nvec = v.shape[0]
         lam = _f64(eigval, (nvec,))
-        if getattr(self, "_pca_shape", None) is None:
+        if self._pca_shape is None:
             raise EngineError("pca_basis: no centred portrait is resident (pca_gram first)")
         basis = np.empty((nvec, self._pca_shape[1]))
         stats = np.empty((nvec, 4))
@@ -818,7 +806,7 @@ class Engine(object):
         """proj_port [nchan,ncomp] = delta . eigvec[:, ieig] and reconst_port [nchan,nbin] =
         proj_port . eigvec[:, ieig].T + mean_prof (ppspline.py:126-129) of the resident rows
         and basis."""
-        if getattr(self, "_pca_shape", None) is None:
+        if self._pca_shape is None:
             raise EngineError("pca_project: no centred portrait is resident (pca_gram first)")
         nchan, nbin = self._pca_shape
         idx = np.ascontiguousarray(ieig, dtype=np.int32)
@@ -890,9 +878,9 @@ def _fresh_waits(fn):
     def call(self, *args, **kwargs):
         # a submitted batch owns the context (its buffers, stream and counters) until wait():
         # include/pp_toas.h forbids every other call meanwhile -- enforce it here
-        if getattr(self, "_pending", None) is not None and fn.__name__ not in _WHILE_PENDING:
+        if self._pending is not None and fn.__name__ not in _WHILE_PENDING:
             raise EngineError("a submitted batch is pending on this engine: wait() before %s()" % fn.__name__)
-        if getattr(self, "_queue", None) and fn.__name__ not in _WHILE_QUEUED:
+        if self._queue and fn.__name__ not in _WHILE_QUEUED:
             raise EngineError("enqueued batches are pending on this engine: collect() before %s()" % fn.__name__)
         _new_call()
         return fn(self, *args, **kwargs)

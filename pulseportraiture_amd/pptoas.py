@@ -175,6 +175,14 @@ def data_from_arrays(subints, freqs, Ps, epochs, weights=None, noise_stds=None,
         source=source, filename=filename, masks=(weights > 0)[:, None, :, None])
 
 
+def _unscattered(mdl):
+    """A copy of a parsed .gmodel with its scattering time set to zero."""
+    mdl = dict(mdl)
+    mdl["params"] = mdl["params"].copy()
+    mdl["params"][1] = 0.0
+    return mdl
+
+
 def _load(datafile):
     if isinstance(datafile, dict):
         return datafile, datafile.get("filename", "arrays")
@@ -364,6 +372,14 @@ _ARCHIVE_ARRAYS = ("nu_fits", "nu_refs", "phis", "phi_errs", "TOAs", "TOA_errs",
                    "covariances", "red_chi2s", "nfevals", "rcs")
 
 
+# the result lists that take the field of _archive_meta of the same name, wideband and narrowband alike, and
+# those get_narrowband_TOAs fills with one [nsub, nchan] array per archive
+_ARCHIVE_META = ("obs", "doppler_fs", "ok_isubs", "epochs", "MJDs", "Ps")
+_NARROWBAND_ARRAYS = ("phis", "phi_errs", "TOAs", "TOA_errs", "taus", "tau_errs", "scales", "scale_errs",
+                      "channel_snrs", "profile_fluxes", "profile_flux_errs", "covariances", "channel_red_chi2s",
+                      "nfevals", "rcs")
+
+
 def merge_blocks(blocks):
     """One archive rebuilt from the blocks of the ranks that fitted its subints (in rank
     order, i.e. subint order): each block carries its subints' rows of the per-subint
@@ -383,6 +399,62 @@ def merge_blocks(blocks):
         arrays[name] = full
     toas = [t for b in blocks for t in b["toas"]]
     return arrays, toas, sum(b["fit_duration"] for b in blocks), meta
+
+
+def toa_flags(d, isub, fl, p, e, cov, GM_out, df, nu_ref_tau, snr, gof, tmplt, opt, flux=None):
+    """The flags of one wideband TOA (pptoas.py:607-657) of subint `isub` of the DataBunch `d`, fitted
+    under the flags `fl`: p, e = its parameters and their errors, cov = the covariance of the fitted
+    ones, GM_out = the GM as reported, df = the Doppler factor applied, nu_ref_tau = the scattering
+    reference frequency, flux = (flux, flux_err, flux_ref_freq) under opt.print_flux.
+
+    The statements stand in the reference's order ON PURPOSE: a dict lists its keys in the order
+    they were first set, and that is the order toa_string writes the flags of a .tim line in."""
+    nchan, nbin, P = d.nchan, d.nbin, d.Ps[isub]
+    freqsx = d.freqs[isub, np.asarray(d.ok_ichans[isub], dtype=int)]
+    flags = {}
+    if fl[2]:
+        flags['gm'] = GM_out
+        flags['gm_err'] = e[2]
+    if fl[3]:
+        if opt.log10_tau:
+            flags['scat_time'] = 10 ** p[3] * P / df * 1e6
+            flags['log10_scat_time'] = p[3] + np.log10(P / df)
+            flags['log10_scat_time_err'] = e[3]
+        else:
+            flags['scat_time'] = p[3] * P / df * 1e6
+            flags['scat_time_err'] = e[3] * P / df * 1e6
+        flags['scat_ref_freq'] = nu_ref_tau * df
+        flags['scat_ind'] = p[4]
+    if fl[4]:
+        flags['scat_ind_err'] = e[4]
+    flags['be'] = d.backend
+    flags['fe'] = d.frontend
+    flags['f'] = d.frontend + "_" + d.backend
+    flags['nbin'] = int(nbin)
+    flags['nch'] = int(nchan)
+    flags['nchx'] = int(len(freqsx))
+    flags['bw'] = freqsx.max() - freqsx.min()
+    flags['chbw'] = abs(d.bw) / nchan
+    flags['subint'] = int(isub)
+    flags['tobs'] = d.subtimes[isub]
+    flags['fratio'] = freqsx.max() / freqsx.min()
+    flags['tmplt'] = tmplt
+    flags['snr'] = snr
+    if opt.nu_refs is not None and fl[0] and fl[1]:
+        flags['phi_DM_cov'] = cov[0, 1]
+    flags['gof'] = gof
+    if opt.print_phase:
+        flags['phs'] = p[0]
+        flags['phs_err'] = e[0]
+    if opt.print_flux:
+        flags['flux'] = flux[0]
+        flags['flux_err'] = flux[1]
+        flags['flux_ref_freq'] = flux[2]
+    if opt.print_parangle:
+        flags['par_angle'] = d.parallactic_angles[isub]
+    for k, v in opt.addtnl_toa_flags.items():
+        flags[k] = v
+    return flags
 
 
 class GetTOAs(object):
@@ -413,19 +485,24 @@ class GetTOAs(object):
         self.instrumental_response_dict = self.ird = \
             {'DM': 0.0, 'wids': [], 'irf_types': []}
         self.quiet = quiet
+        self._gmodels = {}      # model file -> its parsed .gmodel (None: not a .gmodel)
 
     # -- template ----------------------------------------------------------
     def _gmodel(self):
         """The parsed .gmodel, or None if the model file is not one (then it is
         tried as a spline model: the reference's fallback order, pptoas.py:352-379)."""
-        mdl = self.modelfile if isinstance(self.modelfile, dict) else None
-        if mdl is None:
-            try:
-                mdl = gmodel.read_gmodel(self.modelfile)
-                if mdl["nu_ref"] is None or not mdl["ngauss"]:
+        if isinstance(self.modelfile, dict):
+            mdl = self.modelfile
+        else:
+            if self.modelfile not in self._gmodels:         # (parsed once per distinct model file)
+                try:
+                    mdl = gmodel.read_gmodel(self.modelfile)
+                    if mdl["nu_ref"] is None or not mdl["ngauss"]:
+                        mdl = None
+                except (UnicodeDecodeError, ValueError, IndexError):
                     mdl = None
-            except (UnicodeDecodeError, ValueError, IndexError):
-                mdl = None
+                self._gmodels[self.modelfile] = mdl
+            mdl = self._gmodels[self.modelfile]
         if mdl is not None:
             self.model_name, self.ngauss = mdl["name"], mdl["ngauss"]
             self.model_code, self.model_nu_ref = mdl["code"], mdl["nu_ref"]
@@ -440,11 +517,7 @@ class GetTOAs(object):
             self.model_name, port = read_spline_model(self.modelfile, freqs_row, nbin,
                                                       quiet=True)
             return port
-        if unscattered:
-            mdl = dict(mdl)
-            mdl["params"] = mdl["params"].copy()
-            mdl["params"][1] = 0.0
-        return gmodel.gaussian_portrait(mdl, freqs_row, nbin, P)
+        return gmodel.gaussian_portrait(_unscattered(mdl) if unscattered else mdl, freqs_row, nbin, P)
 
     def _load_template(self, eng, slot, freqs_row, nbin, P, unscattered=False):
         """Put the template for these frequencies into a model slot of the engine:
@@ -464,11 +537,27 @@ class GetTOAs(object):
         if mdl is None or mdl["ngauss"] > 64:
             eng.set_model(self._model_for(freqs_row, nbin, P, unscattered), slot=slot)
             return
-        if unscattered:
-            mdl = dict(mdl)
-            mdl["params"] = mdl["params"].copy()
-            mdl["params"][1] = 0.0
-        eng.set_model_gaussian(mdl, freqs_row, nbin, P, slot=slot)
+        eng.set_model_gaussian(_unscattered(mdl) if unscattered else mdl, freqs_row, nbin, P, slot=slot)
+
+    def _template_slot(self, eng, slots, key, d, isub, P, unscattered, use_ird, ichans=None):
+        """The engine's model slot of the template `key` among an archive's `slots` (key -> slot),
+        loaded on first sight from subint isub's frequencies at period P; with use_ird it is
+        multiplied there by the instrumental response formed over the channels `ichans` (None:
+        all of them) -- in the Fourier domain on the device: constant responses x per-channel
+        dispersive smearing."""
+        if key not in slots:
+            if len(slots) >= 64:
+                raise NotImplementedError("more than 64 distinct templates in one archive")
+            slots[key] = len(slots)
+            self._load_template(eng, slots[key], d.freqs[isub], d.nbin, P, unscattered=unscattered)
+            if use_ird:
+                from .pptoaslib import instrumental_response_device_args
+                freqs = d.freqs[isub] if ichans is None else d.freqs[isub, ichans]
+                rconst, smear = instrumental_response_device_args(
+                    d.nbin, freqs, self.ird['DM'], d.Ps[isub], self.ird['wids'], self.ird['irf_types'],
+                    nchan=d.nchan, ichans=ichans)
+                eng.apply_response(slots[key], rconst, smear)
+        return slots[key]
 
     def _reference_seed_inputs(self, port, d, ok_isubs, mask, tau_lin, nu_fit_tau, fit_scat, use_ird):
         """What the reference's phase guess is formed from (pptoas.py:421-457), per good
@@ -591,143 +680,10 @@ class GetTOAs(object):
                         log10_tau=log10_tau, use_ird=use_ird, seed=seed, method=method,
                         print_phase=print_phase, print_flux=print_flux,
                         print_parangle=print_parangle, addtnl_toa_flags=addtnl_toa_flags)
-        # (stage 3 lives in this body: its flags are set in the reference's statement order)
-        def archive_entries(d, fname, a, res, slot_means):
-            """Stage 3 of an archive: the TOA bookkeeping on the host (pptoas.py:528-721) for
-            the subints a.isubs -- their rows of the archive's per-subint result arrays
-            (nsub long; the rows of other subints stay zero) and their TOA objects, in subint
-            order.  Returns (arrays, toas); `arrays` is keyed by the result list's name."""
-            nu_refs, log10_tau = opt.nu_refs, opt.log10_tau
-            print_phase, print_flux, print_parangle = opt.print_phase, opt.print_flux, opt.print_parangle
-            nsub, nchan, nbin = d.nsub, d.nchan, d.nbin
-            flags_per, slot_of, nu_fit_arr = a.flags_per, a.slot_of, a.nu_fit_arr
-            phis = np.zeros(nsub); phi_errs = np.zeros(nsub)
-            TOAs = np.zeros(nsub, dtype="object"); TOA_errs = np.zeros(nsub, dtype="object")
-            DMs = np.zeros(nsub); DM_errs = np.zeros(nsub)
-            GMs = np.zeros(nsub); GM_errs = np.zeros(nsub)
-            taus = np.zeros(nsub); tau_errs = np.zeros(nsub)
-            alphas = np.zeros(nsub); alpha_errs = np.zeros(nsub)
-            scales = np.zeros([nsub, nchan]); scale_errs = np.zeros([nsub, nchan])
-            snrs = np.zeros(nsub); channel_snrs = np.zeros([nsub, nchan])
-            red_chi2s = np.zeros(nsub)
-            profile_fluxes = np.zeros([nsub, nchan]); profile_flux_errs = np.zeros([nsub, nchan])
-            fluxes = np.zeros(nsub); flux_errs = np.zeros(nsub); flux_freqs = np.zeros(nsub)
-            covariances = np.zeros([nsub, self.nfit, self.nfit])
-            nfevals = np.zeros(nsub, dtype="int"); rcs = np.zeros(nsub, dtype="int")
-            nu_fits_out = list(np.zeros([nsub, 3])); nu_refs_out = list(np.zeros([nsub, 3]))
-            toas = []
-            for j, isub in enumerate(a.isubs):
-                fl = flags_per[j]
-                P = d.Ps[isub]
-                p, e = res["params"][j].copy(), res["param_errs"][j]
-                ifit = np.where(fl)[0]
-                cov = res["cov"][j][np.ix_(ifit, ifit)]
-                TOA_MJD = d.epochs[isub] + MJD(0, (p[0] * P + d.backend_delay) / (3600 * 24.))
-                TOA_err = e[0] * P * 1e6   # [us]
-                df = d.doppler_factors[isub] if self.bary else 1.0
-                DM_out, GM_out = p[1], p[2]
-                if self.bary:
-                    if fl[1]:
-                        DM_out *= df
-                    if fl[2]:
-                        GM_out *= df ** 3
-                nu_fits_out[isub] = list(nu_fit_arr[j])
-                nu_refs_out[isub] = list(res["nu_refs"][j])
-                phis[isub], phi_errs[isub] = p[0], e[0]
-                TOAs[isub], TOA_errs[isub] = TOA_MJD, TOA_err
-                DMs[isub], DM_errs[isub] = DM_out, e[1]
-                GMs[isub], GM_errs[isub] = GM_out, e[2]
-                taus[isub], tau_errs[isub] = p[3], e[3]
-                alphas[isub], alpha_errs[isub] = p[4], e[4]
-                nfevals[isub], rcs[isub] = res["nfeval"][j], res["return_code"][j]
-                ich = np.asarray(d.ok_ichans[isub], dtype=int)
-                scales[isub, ich] = res["scales"][j, ich]
-                scale_errs[isub, ich] = res["scale_errs"][j, ich]
-                snrs[isub] = res["snr"][j]
-                channel_snrs[isub, ich] = res["channel_snrs"][j, ich]
-                if cov.shape == covariances[isub].shape:
-                    covariances[isub] = cov
-                elif cov.shape == (1, 1):
-                    # (`covariances[isub] = results.covariance_matrix`, pptoas.py:598: NumPy broadcasts a 1 x 1 matrix
-                    # over the whole nfit x nfit slot instead of raising -- a phase-only fit fills every entry with
-                    # var(phi); reproduced)
-                    covariances[isub] = cov
-                else:
-                    for ii, a_ in enumerate(ifit):
-                        for jj, b_ in enumerate(ifit):
-                            if a_ < self.nfit and b_ < self.nfit:
-                                covariances[isub][a_, b_] = cov[ii, jj]
-                red_chi2s[isub] = res["red_chi2"][j]
-                freqsx = d.freqs[isub, ich]
-                if print_flux:       # pptoas.py:554-575
-                    means = slot_means[slot_of[j]][ich]
-                    profile_fluxes[isub, ich] = means * res["scales"][j, ich]
-                    profile_flux_errs[isub, ich] = np.abs(means) * res["scale_errs"][j, ich]
-                    fluxes[isub], flux_errs[isub] = weighted_mean(
-                        profile_fluxes[isub, ich], profile_flux_errs[isub, ich])
-                    flux_freqs[isub], _ = weighted_mean(freqsx, profile_flux_errs[isub, ich])
-                toa_flags = {}
-                DM_flag, DM_err_flag = (DM_out, e[1]) if fl[1] else (None, None)
-                if fl[2]:
-                    toa_flags['gm'] = GM_out
-                    toa_flags['gm_err'] = e[2]
-                if fl[3]:
-                    if log10_tau:
-                        toa_flags['scat_time'] = 10 ** p[3] * P / df * 1e6
-                        toa_flags['log10_scat_time'] = p[3] + np.log10(P / df)
-                        toa_flags['log10_scat_time_err'] = e[3]
-                    else:
-                        toa_flags['scat_time'] = p[3] * P / df * 1e6
-                        toa_flags['scat_time_err'] = e[3] * P / df * 1e6
-                    toa_flags['scat_ref_freq'] = res["nu_refs"][j, 2] * df
-                    toa_flags['scat_ind'] = p[4]
-                if fl[4]:
-                    toa_flags['scat_ind_err'] = e[4]
-                toa_flags['be'] = d.backend
-                toa_flags['fe'] = d.frontend
-                toa_flags['f'] = d.frontend + "_" + d.backend
-                toa_flags['nbin'] = int(nbin)
-                toa_flags['nch'] = int(nchan)
-                toa_flags['nchx'] = int(len(freqsx))
-                toa_flags['bw'] = freqsx.max() - freqsx.min()
-                toa_flags['chbw'] = abs(d.bw) / nchan
-                toa_flags['subint'] = int(isub)
-                toa_flags['tobs'] = d.subtimes[isub]
-                toa_flags['fratio'] = freqsx.max() / freqsx.min()
-                toa_flags['tmplt'] = self.modelfile if isinstance(self.modelfile, str) \
-                    else self.model_name
-                toa_flags['snr'] = res["snr"][j]
-                if nu_refs is not None and fl[0] and fl[1]:
-                    toa_flags['phi_DM_cov'] = cov[0, 1]
-                toa_flags['gof'] = res["red_chi2"][j]
-                if print_phase:
-                    toa_flags['phs'] = p[0]
-                    toa_flags['phs_err'] = e[0]
-                if print_flux:
-                    toa_flags['flux'] = fluxes[isub]
-                    toa_flags['flux_err'] = flux_errs[isub]
-                    toa_flags['flux_ref_freq'] = flux_freqs[isub]
-                if print_parangle:
-                    toa_flags['par_angle'] = d.parallactic_angles[isub]
-                for k, v in opt.addtnl_toa_flags.items():
-                    toa_flags[k] = v
-                toas.append(TOA(fname, res["nu_refs"][j, 0], TOA_MJD, TOA_err,
-                                d.telescope, d.telescope_code, DM_flag,
-                                DM_err_flag, toa_flags))
-            arrays = dict(nu_fits=nu_fits_out, nu_refs=nu_refs_out, phis=phis, phi_errs=phi_errs,
-                          TOAs=TOAs, TOA_errs=TOA_errs, DMs=DMs, DM_errs=DM_errs, GMs=GMs,
-                          GM_errs=GM_errs, taus=taus, tau_errs=tau_errs, alphas=alphas,
-                          alpha_errs=alpha_errs, scales=scales, scale_errs=scale_errs, snrs=snrs,
-                          channel_snrs=channel_snrs, profile_fluxes=profile_fluxes,
-                          profile_flux_errs=profile_flux_errs, fluxes=fluxes, flux_errs=flux_errs,
-                          flux_freqs=flux_freqs, covariances=covariances, red_chi2s=red_chi2s,
-                          nfevals=nfevals, rcs=rcs)
-            return arrays, toas
-
         start = time.time()
         datafiles = self.datafiles if datafile is None else [datafile]
         if world > 1:
-            self._get_TOAs_sharded(datafiles, opt, rank, world, quiet, archive_entries)
+            self._get_TOAs_sharded(datafiles, opt, rank, world, quiet)
             self._print_total(start, quiet or rank != 0)
             return
         eng = self._engine(False)
@@ -738,11 +694,8 @@ class GetTOAs(object):
                 continue
             d, fname = loaded
             self.ok_idatafiles.append(iarch)
-            ok_isubs = np.asarray(d.ok_isubs, dtype=int)
-            a = self._archive_inputs(eng, d, ok_isubs, last_fl, opt)
+            a, arrays, toas, fit_duration = self._fit_archive(eng, d, fname, d.ok_isubs, last_fl, opt)
             last_fl = a.carry
-            res, fit_duration, slot_means = self._archive_fit(eng, d, a, opt)
-            arrays, toas = archive_entries(d, fname, a, res, slot_means)
             self.TOA_list.extend(toas)
             self._append_archive(_archive_meta(d, fname, self.DM0), arrays, fit_duration, quiet)
         self._print_total(start, quiet)
@@ -764,6 +717,15 @@ class GetTOAs(object):
         if tdist.get_backend() == "nccl":
             torch.cuda.set_device(dev)
         return default_engine(dev)
+
+    def _fit_archive(self, eng, d, fname, isubs, carry, opt):
+        """The three stages of an archive for the run `isubs` of its good subints (all of them, or a
+        rank's slice) with the fit flags carried in: inputs, fit, TOA bookkeeping.  Returns
+        (the inputs -- their .carry goes into the next run --, arrays, toas, fit_duration)."""
+        a = self._archive_inputs(eng, d, isubs, carry, opt)
+        res, fit_duration, slot_means = self._archive_fit(eng, d, a, opt)
+        arrays, toas = self._archive_entries(d, fname, a, res, slot_means, opt)
+        return a, arrays, toas, fit_duration
 
     def _archive_inputs(self, eng, d, isubs, carry, opt):
         """Stage 1 of an archive: everything the device calls need for the good subints
@@ -795,22 +757,8 @@ class GetTOAs(object):
                 if (fit_scat or use_ird) else d.freqs[isub].tobytes()
             if use_ird:
                 key += ich.tobytes()    # the smearing width uses the good channels' spacing
-            if key not in slots:
-                if len(slots) >= 64:
-                    raise NotImplementedError("more than 64 distinct templates in one archive")
-                slots[key] = len(slots)
-                self._load_template(eng, slots[key], d.freqs[isub], nbin, d.Ps[isub],
-                                    unscattered=fit_scat)
-                if use_ird:
-                    # template x instrumental response of the good channels
-                    # (pptoas.py:388-394), multiplied in the Fourier domain on the
-                    # device: constant responses x per-channel dispersive smearing
-                    from .pptoaslib import instrumental_response_device_args
-                    rconst, smear = instrumental_response_device_args(
-                        nbin, freqsx, self.ird['DM'], d.Ps[isub], self.ird['wids'],
-                        self.ird['irf_types'], nchan=nchan, ichans=ich)
-                    eng.apply_response(slots[key], rconst, smear)
-            slot_of[j] = slots[key]
+            # (the response of the good channels, pptoas.py:388-394)
+            slot_of[j] = self._template_slot(eng, slots, key, d, isub, d.Ps[isub], fit_scat, use_ird, ichans=ich)
             if nu_fits is None:
                 nu_fit = guess_fit_freq(freqsx, d.SNRs[isub, 0, ich])
                 nu_fit_arr[j] = nu_fit
@@ -913,6 +861,97 @@ class GetTOAs(object):
                 slot_means[sl] = eng.model_means(sl, d.nchan, d.nbin)
         return res, fit_duration, slot_means
 
+    def _archive_entries(self, d, fname, a, res, slot_means, opt):
+        """Stage 3 of an archive: the TOA bookkeeping on the host (pptoas.py:528-721) for
+        the subints a.isubs -- their rows of the archive's per-subint result arrays
+        (nsub long; the rows of other subints stay zero) and their TOA objects, in subint
+        order.  Returns (arrays, toas); `arrays` is keyed by the result list's name."""
+        print_flux = opt.print_flux
+        tmplt = self.modelfile if isinstance(self.modelfile, str) else self.model_name
+        nsub, nchan = d.nsub, d.nchan
+        flags_per, slot_of, nu_fit_arr = a.flags_per, a.slot_of, a.nu_fit_arr
+        phis = np.zeros(nsub); phi_errs = np.zeros(nsub)
+        TOAs = np.zeros(nsub, dtype="object"); TOA_errs = np.zeros(nsub, dtype="object")
+        DMs = np.zeros(nsub); DM_errs = np.zeros(nsub)
+        GMs = np.zeros(nsub); GM_errs = np.zeros(nsub)
+        taus = np.zeros(nsub); tau_errs = np.zeros(nsub)
+        alphas = np.zeros(nsub); alpha_errs = np.zeros(nsub)
+        scales = np.zeros([nsub, nchan]); scale_errs = np.zeros([nsub, nchan])
+        snrs = np.zeros(nsub); channel_snrs = np.zeros([nsub, nchan])
+        red_chi2s = np.zeros(nsub)
+        profile_fluxes = np.zeros([nsub, nchan]); profile_flux_errs = np.zeros([nsub, nchan])
+        fluxes = np.zeros(nsub); flux_errs = np.zeros(nsub); flux_freqs = np.zeros(nsub)
+        covariances = np.zeros([nsub, self.nfit, self.nfit])
+        nfevals = np.zeros(nsub, dtype="int"); rcs = np.zeros(nsub, dtype="int")
+        nu_fits_out = list(np.zeros([nsub, 3])); nu_refs_out = list(np.zeros([nsub, 3]))
+        toas = []
+        for j, isub in enumerate(a.isubs):
+            fl = flags_per[j]
+            P = d.Ps[isub]
+            p, e = res["params"][j].copy(), res["param_errs"][j]
+            ifit = np.where(fl)[0]
+            cov = res["cov"][j][np.ix_(ifit, ifit)]
+            TOA_MJD = d.epochs[isub] + MJD(0, (p[0] * P + d.backend_delay) / (3600 * 24.))
+            TOA_err = e[0] * P * 1e6   # [us]
+            df = d.doppler_factors[isub] if self.bary else 1.0
+            DM_out, GM_out = p[1], p[2]
+            if self.bary:
+                if fl[1]:
+                    DM_out *= df
+                if fl[2]:
+                    GM_out *= df ** 3
+            nu_fits_out[isub] = list(nu_fit_arr[j])
+            nu_refs_out[isub] = list(res["nu_refs"][j])
+            phis[isub], phi_errs[isub] = p[0], e[0]
+            TOAs[isub], TOA_errs[isub] = TOA_MJD, TOA_err
+            DMs[isub], DM_errs[isub] = DM_out, e[1]
+            GMs[isub], GM_errs[isub] = GM_out, e[2]
+            taus[isub], tau_errs[isub] = p[3], e[3]
+            alphas[isub], alpha_errs[isub] = p[4], e[4]
+            nfevals[isub], rcs[isub] = res["nfeval"][j], res["return_code"][j]
+            ich = np.asarray(d.ok_ichans[isub], dtype=int)
+            scales[isub, ich] = res["scales"][j, ich]
+            scale_errs[isub, ich] = res["scale_errs"][j, ich]
+            snrs[isub] = res["snr"][j]
+            channel_snrs[isub, ich] = res["channel_snrs"][j, ich]
+            if cov.shape == covariances[isub].shape:
+                covariances[isub] = cov
+            elif cov.shape == (1, 1):
+                # (`covariances[isub] = results.covariance_matrix`, pptoas.py:598: NumPy broadcasts a 1 x 1 matrix
+                # over the whole nfit x nfit slot instead of raising -- a phase-only fit fills every entry with
+                # var(phi); reproduced)
+                covariances[isub] = cov
+            else:
+                for ii, a_ in enumerate(ifit):
+                    for jj, b_ in enumerate(ifit):
+                        if a_ < self.nfit and b_ < self.nfit:
+                            covariances[isub][a_, b_] = cov[ii, jj]
+            red_chi2s[isub] = res["red_chi2"][j]
+            freqsx = d.freqs[isub, ich]
+            if print_flux:       # pptoas.py:554-575
+                means = slot_means[slot_of[j]][ich]
+                profile_fluxes[isub, ich] = means * res["scales"][j, ich]
+                profile_flux_errs[isub, ich] = np.abs(means) * res["scale_errs"][j, ich]
+                fluxes[isub], flux_errs[isub] = weighted_mean(
+                    profile_fluxes[isub, ich], profile_flux_errs[isub, ich])
+                flux_freqs[isub], _ = weighted_mean(freqsx, profile_flux_errs[isub, ich])
+            DM_flag, DM_err_flag = (DM_out, e[1]) if fl[1] else (None, None)
+            flags = toa_flags(d, isub, fl, p, e, cov, GM_out, df, res["nu_refs"][j, 2], res["snr"][j],
+                              res["red_chi2"][j], tmplt, opt,
+                              flux=(fluxes[isub], flux_errs[isub], flux_freqs[isub]))
+            toas.append(TOA(fname, res["nu_refs"][j, 0], TOA_MJD, TOA_err,
+                            d.telescope, d.telescope_code, DM_flag,
+                            DM_err_flag, flags))
+        arrays = dict(nu_fits=nu_fits_out, nu_refs=nu_refs_out, phis=phis, phi_errs=phi_errs,
+                      TOAs=TOAs, TOA_errs=TOA_errs, DMs=DMs, DM_errs=DM_errs, GMs=GMs,
+                      GM_errs=GM_errs, taus=taus, tau_errs=tau_errs, alphas=alphas,
+                      alpha_errs=alpha_errs, scales=scales, scale_errs=scale_errs, snrs=snrs,
+                      channel_snrs=channel_snrs, profile_fluxes=profile_fluxes,
+                      profile_flux_errs=profile_flux_errs, fluxes=fluxes, flux_errs=flux_errs,
+                      flux_freqs=flux_freqs, covariances=covariances, red_chi2s=red_chi2s,
+                      nfevals=nfevals, rcs=rcs)
+        return arrays, toas
+
     def _append_archive(self, meta, arrays, fit_duration, quiet):
         """One archive's entries of the result lists; its mean DM offset is formed here
         from the (merged) per-subint DMs (deltadm_mean)."""
@@ -920,13 +959,9 @@ class GetTOAs(object):
         DeltaDM_mean, DeltaDM_err = deltadm_mean(arrays["DMs"], arrays["DM_errs"], meta["DM0"],
                                                  ok_isubs)
         self.order.append(meta["fname"])
-        self.obs.append(meta["obs"])
-        self.doppler_fs.append(meta["doppler_fs"])
+        for name in _ARCHIVE_META:
+            getattr(self, name).append(meta[name])
         self.nu0s.append(meta["nu0"])
-        self.ok_isubs.append(ok_isubs)
-        self.epochs.append(meta["epochs"])
-        self.MJDs.append(meta["MJDs"])
-        self.Ps.append(meta["Ps"])
         self.DM0s.append(meta["DM0"])
         self.DeltaDM_means.append(DeltaDM_mean)
         self.DeltaDM_errs.append(DeltaDM_err)
@@ -947,7 +982,7 @@ class GetTOAs(object):
             print("Total time: %.2f sec, ~%.4f sec/TOA" %
                   (tot_duration, tot_duration / sum(len(o) for o in self.ok_isubs)))
 
-    def _get_TOAs_sharded(self, datafiles, opt, rank, world, quiet, archive_entries):
+    def _get_TOAs_sharded(self, datafiles, opt, rank, world, quiet):
         """get_TOAs over the ranks of a process group (see its docstring): this rank's
         blocks, ONE gather_object to rank 0, and rank 0's merge."""
         import torch.distributed as tdist
@@ -973,9 +1008,7 @@ class GetTOAs(object):
                 carry = subint_fit_flags(nchx, self.fit_flags, carry)[1]
                 if j0 == j1:
                     continue            # (an empty slice of this archive: nothing to send)
-                a = self._archive_inputs(eng, d, ok_isubs[j0:j1], carry_in, opt)
-                res, fit_duration, slot_means = self._archive_fit(eng, d, a, opt)
-                arrays, toas = archive_entries(d, fname, a, res, slot_means)
+                a, arrays, toas, fit_duration = self._fit_archive(eng, d, fname, ok_isubs[j0:j1], carry_in, opt)
                 rows = a.isubs
                 blocks.append(dict(
                     iarch=iarch, meta=_archive_meta(d, fname, self.DM0), nsub=int(d.nsub), rows=rows,
@@ -1050,8 +1083,8 @@ class GetTOAs(object):
                 continue
             self.ok_idatafiles.append(iarch)
             nsub, nchan, nbin = d.nsub, d.nchan, d.nbin
-            ok_isubs = np.asarray(d.ok_isubs, dtype=int)
-            obs = DataBunch(telescope=d.telescope, backend=d.backend, frontend=d.frontend)
+            meta = _archive_meta(d, fname, None)
+            ok_isubs = meta["ok_isubs"]
             z2 = lambda dt=np.float64: np.zeros([nsub, nchan], dtype=dt)  # noqa: E731
             phis, phi_errs, taus, tau_errs = z2(), z2(), z2(), z2()
             TOAs, TOA_errs = z2("object"), z2("object")
@@ -1059,7 +1092,6 @@ class GetTOAs(object):
             profile_fluxes, profile_flux_errs, channel_red_chi2s = z2(), z2(), z2()
             covariances = np.zeros([nsub, nchan, self.nfit, self.nfit])
             nfevals, rcs = z2("int"), z2("int")
-            MJDs = np.array([e.in_days() for e in d.epochs], dtype=np.double)
             # ---- gather every (subint, good channel) profile pair ----
             profs, mprofs, noises, where = [], [], [], []
             sub_all = np.asarray(d.subints)
@@ -1110,27 +1142,14 @@ class GetTOAs(object):
                 self.TOA_list.append(TOA(fname, d.freqs[isub, ichan], TOA_MJD, TOA_err,
                                          d.telescope, d.telescope_code, None, None, toa_flags))
             self.order.append(fname)
-            self.obs.append(obs)
-            self.doppler_fs.append(d.doppler_factors)
-            self.ok_isubs.append(ok_isubs)
-            self.epochs.append(d.epochs)
-            self.MJDs.append(MJDs)
-            self.Ps.append(d.Ps)
-            self.phis.append(phis)
-            self.phi_errs.append(phi_errs)
-            self.TOAs.append(TOAs)
-            self.TOA_errs.append(TOA_errs)
-            self.taus.append(taus)
-            self.tau_errs.append(tau_errs)
-            self.scales.append(scales)
-            self.scale_errs.append(scale_errs)
-            self.channel_snrs.append(channel_snrs)
-            self.profile_fluxes.append(profile_fluxes)
-            self.profile_flux_errs.append(profile_flux_errs)
-            self.covariances.append(covariances)
-            self.channel_red_chi2s.append(channel_red_chi2s)
-            self.nfevals.append(nfevals)
-            self.rcs.append(rcs)
+            for name in _ARCHIVE_META:
+                getattr(self, name).append(meta[name])
+            arrays = dict(phis=phis, phi_errs=phi_errs, TOAs=TOAs, TOA_errs=TOA_errs, taus=taus, tau_errs=tau_errs,
+                          scales=scales, scale_errs=scale_errs, channel_snrs=channel_snrs,
+                          profile_fluxes=profile_fluxes, profile_flux_errs=profile_flux_errs,
+                          covariances=covariances, channel_red_chi2s=channel_red_chi2s, nfevals=nfevals, rcs=rcs)
+            for name in _NARROWBAND_ARRAYS:
+                getattr(self, name).append(arrays[name])
             self.fit_durations.append(fit_duration)
             if not quiet:
                 print("--------------------------")
@@ -1159,7 +1178,6 @@ class GetTOAs(object):
         for iarch, ok_idatafile in enumerate(self.ok_idatafiles):
             data, fname = _load(self.datafiles[ok_idatafile])
             d = data
-            nbin = d.nbin
             ok_isubs = np.asarray(self.ok_isubs[iarch], dtype=int)
             nok = len(ok_isubs)
             params = np.zeros((nok, 5))
@@ -1177,19 +1195,8 @@ class GetTOAs(object):
                                (self.ird['DM'] or len(self.ird['wids'])))
                 key = (d.freqs[isub].tobytes(), scat,
                        np.float64(d.Ps[isub]).tobytes() if use_ird else b"")
-                if key not in slots:
-                    if len(slots) >= 64:
-                        raise NotImplementedError("more than 64 distinct templates in one archive")
-                    slots[key] = len(slots)
-                    self._load_template(eng, slots[key], d.freqs[isub], nbin, d.Ps.mean(),
-                                        unscattered=scat)
-                    if use_ird:     # show_fit applies it over all channels (pptoas.py:1389-1395)
-                        from .pptoaslib import instrumental_response_device_args
-                        rconst, smear = instrumental_response_device_args(
-                            nbin, d.freqs[isub], self.ird['DM'], d.Ps[isub], self.ird['wids'],
-                            self.ird['irf_types'])
-                        eng.apply_response(slots[key], rconst, smear)
-                slot_of[j] = slots[key]
+                # (show_fit applies the response over all channels, pptoas.py:1389-1395)
+                slot_of[j] = self._template_slot(eng, slots, key, d, isub, d.Ps.mean(), scat, use_ird)
                 scales[j] = self.scales[iarch][isub]
             port = _dededisperse(eng, _take_subints(d.subints, ok_isubs), d, ok_isubs)
             noise = _noise_rows(d, ok_isubs)

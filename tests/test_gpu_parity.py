@@ -2746,6 +2746,49 @@ def test_engine_waits_for_the_callers_stream(eng):
 
 
 @pytest.mark.gpu
+def test_strided_device_views_are_refused_before_anything_is_launched(eng):
+    """The library reads (rotate_portraits: writes) a device tensor as dense memory, so every entry
+    point that takes portraits or a template refuses a strided view on the host -- EngineError naming
+    "contiguous", the tensor untouched -- and the engine fits afterwards exactly as before."""
+    import torch
+    from pulseportraiture_amd.engine import EngineError
+    from tests.synth_host import model_portrait
+    C, B, nsub = 8, 64, 2
+    freqs, model = model_portrait(C, B)
+    rng = np.random.default_rng(31)
+    data = model[None] * rng.uniform(0.5, 2.0, (nsub, C, 1)) + 0.02 * rng.standard_normal((nsub, C, B))
+    P, x0 = np.full(nsub, 0.004), np.zeros((nsub, 5))
+    slot = 7        # (a slot of this test's own: the template other tests left in slot 0 stays)
+    kw = dict(errs=np.full((nsub, C), 0.02), nu_fits=np.full((nsub, 3), freqs.mean()), fit_flags=[1, 1, 0, 0, 0],
+              model_slot=np.full(nsub, slot, dtype=np.int32))
+    eng.set_model(model, slot=slot)
+    before = eng.fit_batch(data, freqs, P, x0, **kw)
+
+    big = torch.randn(3, 16, 64, dtype=torch.float64, device="cuda:0")
+    big_before = big.clone()
+    view = big[:, ::2]
+    assert tuple(view.shape) == (3, C, B) and not view.is_contiguous()
+    P3, w = np.full(3, 0.004), np.ones((3, C))
+    calls = [lambda: eng.rotate_portraits(view, freqs, P3, phi=0.1, DM=1e-3),
+             lambda: eng.reference_phase_seed(view, freqs, P3, w, model.mean(axis=0)),
+             lambda: eng.align_accumulate(view, freqs, P3, np.zeros(3), np.zeros(3), freqs.mean(), w),
+             lambda: eng.channel_red_chi2(view, freqs, P3, np.zeros((3, 5)), np.full((3, 3), freqs.mean()),
+                                          np.ones((3, C)), np.full((3, C), 0.02), slots=np.full(3, slot, dtype=np.int32)),
+             lambda: eng.set_model(big[0, ::2].T.T[:, ::2], slot=slot)]
+    for call in calls:
+        with pytest.raises(EngineError, match="contiguous"):
+            call()
+        torch.cuda.synchronize()
+        assert torch.equal(big, big_before)
+
+    after = eng.fit_batch(data, freqs, P, x0, **kw)
+    assert set(after) == set(before)
+    for k in before:
+        if k != "duration":
+            np.testing.assert_array_equal(after[k], before[k], err_msg=k)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("dtype,on_device", [(np.float64, False), (np.float32, False), (np.float64, True)])
 def test_fused_reference_seed_equals_rotation_mean_and_fit(eng, dtype, on_device):
     """pp_reference_phase_seed = rotate_data + np.average over the channels +

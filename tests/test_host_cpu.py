@@ -162,16 +162,28 @@ def test_tim_lines_match_the_hand_derived_fixture(tmp_path):
 
 def test_get_TOAs_flag_order_is_the_reference_insertion_order():
     """The flag dictionary get_TOAs builds follows the statement order of the reference
-    (pptoas.py:607-657), which is the order the .tim line lists them in."""
-    import inspect
+    (pptoas.py:607-657), which is the order the .tim line lists them in: every optional flag
+    switched on, a two-subint archive through get_TOAs' own bookkeeping over a fabricated fit
+    (no device), once with log10_tau and once without."""
     from pulseportraiture_amd import pptoas
-    src = inspect.getsource(pptoas.GetTOAs.get_TOAs)
-    order = ["'gm'", "'gm_err'", "'scat_time'", "'scat_ref_freq'", "'scat_ind'", "'scat_ind_err'", "'be'",
-             "'fe'", "'f'", "'nbin'", "'nch'", "'nchx'", "'bw'", "'chbw'", "'subint'", "'tobs'", "'fratio'",
-             "'tmplt'", "'snr'", "'phi_DM_cov'", "'gof'", "'phs'", "'phs_err'", "'flux'", "'flux_err'",
-             "'flux_ref_freq'", "'par_angle'"]
-    pos = [src.index("toa_flags[%s]" % k) for k in order]
-    assert pos == sorted(pos), [k for k, a, b in zip(order[1:], pos, pos[1:]) if b < a]
+    from tests.test_pptoas_run_cpu import MODEL, _StubGetTOAs, _archives
+    order = ["gm", "gm_err", "scat_time", "scat_ref_freq", "scat_ind", "scat_ind_err", "be",
+             "fe", "f", "nbin", "nch", "nchx", "bw", "chbw", "subint", "tobs", "fratio",
+             "tmplt", "snr", "phi_DM_cov", "gof", "phs", "phs_err", "flux", "flux_err",
+             "flux_ref_freq", "par_angle"]
+    extra = {"pta": "X", "ver": "0.1", "be": "overridden"}      # (a key set before keeps its place)
+    at = order.index("scat_time") + 1
+    for log10_tau, scat in ((True, ["log10_scat_time", "log10_scat_time_err"]), (False, ["scat_time_err"])):
+        gt = _StubGetTOAs(_archives([[32, 32]]), MODEL, quiet=True)
+        gt.get_TOAs(quiet=True, seed="device", fit_GM=True, fit_scat=True, log10_tau=log10_tau, print_phase=True,
+                    print_flux=True, print_parangle=True, nu_refs=(1500.0, 1400.0), addtnl_toa_flags=extra)
+        assert len(gt.TOA_list) == 2
+        for toa in gt.TOA_list:
+            assert list(toa.flags) == order[:at] + scat + order[at:] + ["pta", "ver"]
+            assert toa.flags["be"] == "overridden" and toa.flags["pta"] == "X"
+            line = pptoas.toa_string(toa)
+            pos = [line.index(" -%s " % k) for k in toa.flags]
+            assert pos == sorted(pos)
 
 
 def test_scale_run_checker(tmp_path):
