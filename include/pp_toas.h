@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 7
+#define PP_ABI_VERSION 8
 
 /* status codes */
 #define PP_OK 0
@@ -472,6 +472,46 @@ int pp_align_accumulate(pp_ctx* ctx, const void* src, int dtype, int on_device,
                         int nsub, int nchan, int nbin, const double* freqs,
                         int64_t freqs_stride, const double* P, const double* par3,
                         const double* weights, double* aligned, double* total_weights);
+
+/* ---- ppalign: an accumulator that stays on the device between calls --------- */
+/* align_archives' sum over archives and subints (ppalign.py:116-117, :202-212): the context keeps
+ * aligned_port as packed half-spectra [npol][nchan_model][nbin/2] and total_weights [nchan_model].
+ * pp_align_begin allocates (or reuses) and zeroes them; a second begin starts over. */
+int pp_align_begin(pp_ctx* ctx, int npol, int nchan_model, int nbin);
+
+/* ppalign.py:202-208 for every subint of src[nsub][npol][nchan][nbin] (`dtype`, host or device):
+ *   aligned_port[ipol, chan_map[i][n]] += weights[i][n] * rotate_data(src[i][ipol][n], phase_i,
+ *                                          DM_i, P_i, freqs, nu_ref_i)       for every ipol
+ *   total_weights[chan_map[i][n]]      += weights[i][n]                      once
+ * par3[i] = {phase, DM, nu_ref} (nu_ref may be INFINITY).  weights [nsub][nchan] (host): 0 or NaN
+ * skips the row, a negative weight counts.  chan_map [nsub][nchan] (host) names the accumulator row
+ * of every data channel -- the reference's model_ichans (:161-172); several channels may share a row
+ * and a row may get nothing; NULL is the identity and needs nchan == nchan_model.  A row's
+ * contributions are added in the order (subint, data channel) by the one workgroup that owns the
+ * row: the accumulator's bits depend on the sequence of rows only, not on how the subints are cut
+ * into calls.  PP_EINVAL before pp_align_begin, for npol / nbin other than begin's, and for a
+ * chan_map entry outside [0, nchan_model) -- checked on the host before anything is launched. */
+int pp_align_add(pp_ctx* ctx, const void* src, int dtype, int on_device, int nsub, int npol,
+                 int nchan, int nbin, const double* freqs, int64_t freqs_stride,
+                 const double* P, const double* par3, const double* weights,
+                 const int32_t* chan_map);
+
+/* The contribution lists pp_align_add builds from weights and chan_map, for inspection (host only, no context):
+ * off[nchan_model + 1] and pairs[2 x live rows] = (subint, data channel) of accumulator row m at off[m] .. off[m+1],
+ * by subint, then data channel; rows of weight 0 or NaN are left out.  pairs must hold 2 nsub nchan ints.  Returns
+ * the number of pairs, or PP_EINVAL (a chan_map entry outside [0, nchan_model), or no map with nchan != nchan_model). */
+int pp_align_lists(int nsub, int nchan, int nchan_model, const double* weights,
+                   const int32_t* chan_map, int32_t* off, int32_t* pairs);
+
+/* ppalign.py:210-212 and :220-226: rows of positive total weight divided by it, the overall
+ * rotation rotate_data(aligned_port, rot_phase) applied in the spectrum (0: the rows are not
+ * touched), ONE inverse transform per row; aligned [npol][nchan_model][nbin] and total_weights
+ * [nchan_model] are host arrays, overwritten.  to_slot >= 0 also installs polarisation 0 as the
+ * template of that model slot from the device copy (the next iteration's model_port, :213) --
+ * the same bits as pp_model_set of `aligned`.  The accumulator stays valid: finish may be called
+ * again with another rot_phase, and pp_align_add may go on. */
+int pp_align_finish(pp_ctx* ctx, double rot_phase, double* aligned, double* total_weights,
+                    int to_slot);
 
 /* Per-channel reduced chi^2 of fitted subints in the time domain, as
  * get_channels_to_zap forms it (pptoas.py:1239-1245 via show_fit :1394-1404 and

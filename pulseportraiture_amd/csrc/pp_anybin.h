@@ -416,6 +416,123 @@ __global__ __launch_bounds__(256) void k_align_harm(const cplx* hout, AlignArgs 
     if (k == 0) totw[n] = wsum;
 }
 
+// k_align_add for general row lengths (a list-walking twin of k_align_harm): from k_any's harmonics of the run's rows
+// -- channel-major, ns * npol rows per data channel, row (i, ipol) of channel n at n ns npol + i npol + ipol -- one
+// thread per slot k of the packed row adds the row's contributions in list order
+__global__ __launch_bounds__(256) void k_align_harm_list(const cplx* hout, AlignListArgs a, int ns, int M) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ipol = blockIdx.y / a.nchan_model, m = blockIdx.y % a.nchan_model;
+    const int q0 = a.off[m], q1 = a.off[m + 1];
+    if (k >= M || q0 == q1) return;
+    const size_t H = (size_t)M + 1;
+    cplx* arow = a.acc + ((size_t)ipol * a.nchan_model + m) * M;
+    cplx acc = arow[k];
+    for (int q = q0; q < q1; ++q) {
+        const int i = a.pairs[q].x, n = a.pairs[q].y;
+        const double w = a.w[(size_t)i * a.nchan + n];
+        const double phin = align_phase(a.par[i * 3], a.par[i * 3 + 1], a.par[i * 3 + 2],
+                                        a.freqs[(size_t)i * a.freqs_stride + n], a.P[i]);
+        const cplx* h = hout + (((size_t)n * ns + i) * a.npol + ipol) * H;
+        cplx yk, ym;
+        if (k == 0) { yk = make_double2(h[0].x, 0.0); ym = make_double2(h[M].x * unit_phasor((double)M, phin).x, 0.0); }
+        else {
+            yk = cmul(h[k], unit_phasor((double)k, phin));
+            ym = cmul(h[M - k], unit_phasor((double)(M - k), phin));
+        }
+        const cplx p = irfft_pack(yk, ym, a.twB[k]);
+        acc.x = fma(w, p.x, acc.x);
+        acc.y = fma(w, p.y, acc.y);
+    }
+    arow[k] = acc;
+    if (ipol == 0 && k == 0) align_add_totw(a, m);
+}
+
+// One accumulator row back to the time domain (ppalign.py:210-212, :220-226): the packed row unpacked into its
+// harmonics, those turned by rot_phase (rotate_data(aligned, rot_phase): phase only; the Nyquist harmonic keeps its
+// real part) and packed again -- rot_phase = 0 copies the row, bit for bit.  Slot k of `dst` from slots k and M - k
+// of `arow`: with Z = conj(packed), ev = (Z_k + conj Z_{M-k}) / 2 and od W^-k = (Z_k - conj Z_{M-k}) / 2i.
+__device__ __forceinline__ cplx align_turn_slot(const cplx* arow, const cplx* twB, int M, int k, double rot) {
+    const cplx zk = arow[k];
+    if (rot == 0.0) return zk;
+    cplx yk, ym;
+    if (k == 0) {
+        yk = make_double2(zk.x - zk.y, 0.0);                                  // DC, unchanged
+        ym = make_double2((zk.x + zk.y) * unit_phasor((double)M, rot).x, 0.0);    // Nyquist
+    } else {
+        const cplx zm = arow[M - k];
+        // Z_k = (zk.x, -zk.y), conj Z_{M-k} = (zm.x, zm.y)
+        const cplx ev = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zm.y - zk.y));
+        const cplx dq = make_double2(0.5 * (zk.x - zm.x), 0.5 * (-zk.y - zm.y));   // (Z_k - conj Z_{M-k}) / 2
+        const cplx od = cmul(make_double2(dq.y, -dq.x), twB[k]);                      // / i, times W^k
+        yk = cmul(make_double2(ev.x + od.x, ev.y + od.y), unit_phasor((double)k, rot));
+        ym = cmul(make_double2(ev.x - od.x, -(ev.y - od.y)), unit_phasor((double)(M - k), rot));
+    }
+    return irfft_pack(yk, ym, twB[k]);
+}
+
+struct AlignFinishArgs {
+    const cplx* acc;      // [npol][nchan_model][M]
+    const double* totw;   // [nchan_model]
+    const cplx* twB;
+    double* out;          // [npol][nchan_model][B]
+    double rot;
+    int npol, nchan_model;
+};
+
+template <int M>
+__global__ __launch_bounds__(FftPlan<M>::T) void k_align_finish(AlignFinishArgs a) {
+    constexpr int T = FftPlan<M>::T;
+    constexpr int PL = FftPlan<M>::PADLOG;
+    __shared__ cplx lds[FftPlan<M>::LDS_ELEMS];
+    __shared__ cplx zin[M];
+    const int tid = threadIdx.x;
+    const int nrows = a.npol * a.nchan_model;
+    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const cplx* arow = a.acc + (size_t)row * M;
+        for (int k = tid; k < M; k += T) zin[k] = align_turn_slot(arow, a.twB, M, k, a.rot);
+        __syncthreads();
+        fft_row<M, cplx>(lds, zin, a.twB, tid);
+        double* out = a.out + (size_t)row * (2 * M);
+        const double tw = a.totw[row % a.nchan_model];
+        const double inv = 1.0 / (double)M;
+        for (int j = tid; j < M; j += T) {
+            const cplx r = lds[lds_pad<PL>(j)];
+            double x0 = r.x * inv, x1 = -r.y * inv;
+            if (tw > 0.0) { x0 /= tw; x1 /= tw; }
+            reinterpret_cast<double2*>(out)[j] = make_double2(x0, x1);
+        }
+        __syncthreads();
+    }
+}
+
+// k_align_finish for general row lengths: the packed row through the chirp-z transform (as k_irfft_any's)
+template <int L>
+__global__ __launch_bounds__(FftPlan<L>::T) void k_align_finish_any(AlignFinishArgs a, AnyArgs g) {
+    constexpr int T = FftPlan<L>::T;
+    __shared__ cplx lds[FftPlan<L>::LDS_ELEMS];
+    __shared__ cplx buf[L];
+    const int tid = threadIdx.x;
+    const int M = g.M;
+    const int nrows = a.npol * a.nchan_model;
+    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const cplx* arow = a.acc + (size_t)row * M;
+        for (int k = tid; k < M; k += T) buf[k] = align_turn_slot(arow, g.twB, M, k, a.rot);
+        __syncthreads();
+        czt_any<L>(buf, lds, g, tid);
+        double* o = a.out + (size_t)row * g.nbin;
+        const double tw = a.totw[row % a.nchan_model];
+        const double inv = 1.0 / (double)M;
+        for (int j = tid; j < M; j += T) {
+            const cplx r = buf[j];
+            double x0 = r.x * inv, x1 = -r.y * inv;
+            if (tw > 0.0) { x0 /= tw; x1 /= tw; }
+            o[2 * j] = x0;
+            o[2 * j + 1] = x1;
+        }
+        __syncthreads();
+    }
+}
+
 // per-channel reduced chi^2 (k_chan_chi2 for general row lengths) from k_any's harmonics of the data rows,
 // channel-major (row = n ns + i); the slot's spectrum rows are pitched to Mp
 __global__ __launch_bounds__(256) void k_chan_chi2_harm(const cplx* hout, ChanChi2Args a, int s0, int ns, int M, int Mp) {

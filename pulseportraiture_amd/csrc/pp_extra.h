@@ -654,6 +654,43 @@ struct AlignArgs {
     int nsub, nchan;
 };
 
+// the turn rotate_data gives channel nu of a subint, in the reference's order of operations (pplib.py:2419-2424)
+__device__ __forceinline__ double align_phase(double phase, double DM, double nuref, double nu, double P) {
+    const double D = PP_DCONST * DM / P;
+    const double iref = (nuref == INFINITY) ? 0.0 : 1.0 / (nuref * nuref);
+    return (DM == 0.0) ? phase : phase + D * (1.0 / (nu * nu) - iref);
+}
+
+// zin += w x (the packed half-spectrum of the inverse transform of `row` turned by phin): one forward transform, the
+// harmonics rotated and packed pairwise, every thread adding into its own slots of zin
+template <int M, typename Tio>
+__device__ __forceinline__ void align_add_row(cplx* lds, cplx* zin, const Tio* row, const cplx* twB, double w,
+                                              double phin, int tid) {
+    constexpr int T = FftPlan<M>::T;
+    fft_row<M, Tio>(lds, row, twB, tid);
+    const cplx z0 = lds[0];
+    const double y0 = z0.x + z0.y;                                    // DC, unchanged
+    const double yM = (z0.x - z0.y) * unit_phasor((double)M, phin).x; // Nyquist: real part kept
+    for (int k = tid; k < M; k += T) {
+        cplx yk, ym;
+        if (k == 0) { yk = make_double2(y0, 0.0); ym = make_double2(yM, 0.0); }
+        else {
+            yk = cmul(rfft_harmonic<M>(lds, twB, k), unit_phasor((double)k, phin));
+            ym = cmul(rfft_harmonic<M>(lds, twB, M - k), unit_phasor((double)(M - k), phin));
+        }
+        ym.y = -ym.y;
+        const cplx ev = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y + ym.y));
+        cplx od = make_double2(0.5 * (yk.x - ym.x), 0.5 * (yk.y - ym.y));
+        cplx tw = twB[k];
+        tw.y = -tw.y;
+        od = cmul(od, tw);
+        cplx acc = zin[k];      // this thread's own slot
+        acc.x = fma(w, ev.x - od.y, acc.x);
+        acc.y = fma(w, -(ev.y + od.x), acc.y);    // conj(ev + i od)
+        zin[k] = acc;
+    }
+}
+
 template <int M, typename Tio>
 __global__ __launch_bounds__(FftPlan<M>::T) void k_align_accum(AlignArgs a) {
     constexpr int T = FftPlan<M>::T;
@@ -668,35 +705,10 @@ __global__ __launch_bounds__(FftPlan<M>::T) void k_align_accum(AlignArgs a) {
             const double w = a.w[(size_t)i * a.nchan + n];
             if (w == 0.0 || w != w) continue;  // (uniform over the workgroup; negative fitted
                                                // amplitudes weigh negatively, as in the reference)
-            const double nu = a.freqs[(size_t)i * a.freqs_stride + n], P = a.P[i];
-            const double phase = a.par[i * 3], DM = a.par[i * 3 + 1], nuref = a.par[i * 3 + 2];
-            // reference order of operations (pplib.py:2419-2424)
-            const double D = PP_DCONST * DM / P;
-            const double iref = (nuref == INFINITY) ? 0.0 : 1.0 / (nuref * nuref);
-            const double phin = (DM == 0.0) ? phase : phase + D * (1.0 / (nu * nu) - iref);
-            fft_row<M, Tio>(lds, reinterpret_cast<const Tio*>(a.src) + ((size_t)i * a.nchan + n) * (2 * M), a.twB,
-                            tid);
-            const cplx z0 = lds[0];
-            const double y0 = z0.x + z0.y;                                    // DC, unchanged
-            const double yM = (z0.x - z0.y) * unit_phasor((double)M, phin).x; // Nyquist: real part kept
-            for (int k = tid; k < M; k += T) {
-                cplx yk, ym;
-                if (k == 0) { yk = make_double2(y0, 0.0); ym = make_double2(yM, 0.0); }
-                else {
-                    yk = cmul(rfft_harmonic<M>(lds, a.twB, k), unit_phasor((double)k, phin));
-                    ym = cmul(rfft_harmonic<M>(lds, a.twB, M - k), unit_phasor((double)(M - k), phin));
-                }
-                ym.y = -ym.y;
-                const cplx ev = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y + ym.y));
-                cplx od = make_double2(0.5 * (yk.x - ym.x), 0.5 * (yk.y - ym.y));
-                cplx tw = a.twB[k];
-                tw.y = -tw.y;
-                od = cmul(od, tw);
-                cplx acc = zin[k];      // this thread's own slot
-                acc.x = fma(w, ev.x - od.y, acc.x);
-                acc.y = fma(w, -(ev.y + od.x), acc.y);    // conj(ev + i od)
-                zin[k] = acc;
-            }
+            const double phin = align_phase(a.par[i * 3], a.par[i * 3 + 1], a.par[i * 3 + 2],
+                                            a.freqs[(size_t)i * a.freqs_stride + n], a.P[i]);
+            align_add_row<M, Tio>(lds, zin, reinterpret_cast<const Tio*>(a.src) + ((size_t)i * a.nchan + n) * (2 * M),
+                                  a.twB, w, phin, tid);
             wsum += w;
             __syncthreads();            // the image is overwritten by the next row
         }
@@ -711,6 +723,59 @@ __global__ __launch_bounds__(FftPlan<M>::T) void k_align_accum(AlignArgs a) {
         if (tid == 0) a.totw[n] = wsum;
         __syncthreads();
     }
+}
+
+// --------------------------------------------------------------------------
+// The resident accumulator of align_archives (ppalign.py:202-212): packed half-spectra
+// acc[npol][nchan_model][M] (the packing of k_align_accum's zin) and totw[nchan_model] stay in
+// device memory between calls.  No atomics: one workgroup owns one accumulator row (ipol, model
+// channel) for the whole launch and walks that row's contributions -- (subint, data channel) pairs
+// listed by the host in a fixed order (CSR: off, pairs) -- so the bits of a row depend only on the
+// sequence of rows added to it, never on how the subints were cut into calls.
+// --------------------------------------------------------------------------
+struct AlignListArgs {
+    const void* src;      // [nsub][npol][nchan][B]
+    const double* freqs; long long freqs_stride;
+    const double* P;      // [nsub]
+    const double* par;    // [nsub][3] phase, DM, nu_ref
+    const double* w;      // [nsub][nchan] weights, one for all polarisations
+    const cplx* twB;
+    cplx* acc;            // [npol][nchan_model][M]
+    double* totw;         // [nchan_model]
+    const int* off;       // [nchan_model + 1] where model row m's pairs start
+    const int2* pairs;    // (subint, data channel), by subint, then channel
+    int npol, nchan, nchan_model;
+};
+
+// totw[m] += the row's weights in list order (one thread; the polarisation-0 workgroup of the row)
+__device__ __forceinline__ void align_add_totw(const AlignListArgs& a, int m) {
+    double t = a.totw[m];
+    for (int q = a.off[m]; q < a.off[m + 1]; ++q) t += a.w[(size_t)a.pairs[q].x * a.nchan + a.pairs[q].y];
+    a.totw[m] = t;
+}
+
+template <int M, typename Tio>
+__global__ __launch_bounds__(FftPlan<M>::T) void k_align_add(AlignListArgs a) {
+    constexpr int T = FftPlan<M>::T;
+    __shared__ cplx lds[FftPlan<M>::LDS_ELEMS];
+    __shared__ cplx zin[M];
+    const int tid = threadIdx.x;
+    const int ipol = blockIdx.x / a.nchan_model, m = blockIdx.x % a.nchan_model;
+    const int q0 = a.off[m], q1 = a.off[m + 1];
+    if (q0 == q1) return;               // (uniform over the workgroup) nothing lands on this row
+    cplx* arow = a.acc + ((size_t)ipol * a.nchan_model + m) * M;
+    for (int k = tid; k < M; k += T) zin[k] = arow[k];     // every thread its own slots, here and below
+    for (int q = q0; q < q1; ++q) {
+        const int i = a.pairs[q].x, n = a.pairs[q].y;
+        const double w = a.w[(size_t)i * a.nchan + n];
+        const double phin = align_phase(a.par[i * 3], a.par[i * 3 + 1], a.par[i * 3 + 2],
+                                        a.freqs[(size_t)i * a.freqs_stride + n], a.P[i]);
+        align_add_row<M, Tio>(lds, zin, reinterpret_cast<const Tio*>(a.src) + (((size_t)i * a.npol + ipol) * a.nchan + n) * (2 * M),
+                              a.twB, w, phin, tid);
+        __syncthreads();                // the image is overwritten by the next row
+    }
+    for (int k = tid; k < M; k += T) arow[k] = zin[k];
+    if (ipol == 0 && tid == 0) align_add_totw(a, m);
 }
 
 // --------------------------------------------------------------------------

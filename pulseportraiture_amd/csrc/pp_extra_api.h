@@ -34,9 +34,10 @@ struct Ports {
     int64_t freqs_stride;
     const double *P, *par;      // par: npar doubles per subint (phi, DM, GM or nu_ref; the five fitted parameters)
     int npar;
+    int npol = 1;               // portraits per subint (pp_align_add: src[nsub][npol][nchan][nbin])
 
     size_t esz() const { return dtype == PP_F64 ? 8 : 4; }
-    size_t sub_bytes() const { return (size_t)nchan * nbin * esz(); }
+    size_t sub_bytes() const { return (size_t)npol * nchan * nbin * esz(); }
     // rest_ok: the entry point's other pointers are there; shape_ok: its other counts are positive
     int validate(const char* who, bool rest_ok, bool shape_ok = true) const {
         if (!rest_ok || !src || !freqs || !P || !par) return fail(PP_EINVAL, "%s: null argument", who);
@@ -50,7 +51,7 @@ struct Ports {
     int cap(pp_ctx* c, double extra) const { return on_device ? nsub : aux_chunk_cap(c, (double)sub_bytes() + extra, nsub); }
     Ports run(Run r) const {
         return Ports{r.at((const char*)src, sub_bytes()), dtype, on_device, r.n, nchan, nbin, r.at(freqs, (size_t)freqs_stride),
-                     freqs_stride, r.at(P, 1), r.at(par, npar), npar};
+                     freqs_stride, r.at(P, 1), r.at(par, npar), npar, npol};
     }
     // the portraits on the device (host ones through c->data), freqs -> c->freqs, P -> c->P, par -> c->x0
     int stage(pp_ctx* c, const void** dsrc) const {
@@ -377,6 +378,175 @@ extern "C" int pp_align_accumulate(pp_ctx* c, const void* src, int dtype, int on
         for (int j = 0; j < nchan; ++j) total_weights[j] += wpart[j];
         return (int)PP_OK;
     });
+}
+
+// ---- ppalign: the resident accumulator ------------------------------------
+extern "C" int pp_align_begin(pp_ctx* c, int npol, int nchan_model, int nbin) {
+    if (int busy_ = ctx_busy(c, "pp_align_begin")) return busy_;
+    if (!c) return fail(PP_EINVAL, "pp_align_begin: null context");
+    c->align.open = false;      // (a refused begin leaves no accumulator either)
+    if (!nbin_any_ok(nbin)) return nbin_refuse("pp_align_begin", nbin);
+    if (npol < 1 || npol > 4 || nchan_model < 1) return fail(PP_EINVAL, "pp_align_begin: bad shape %d x %d", npol, nchan_model);
+    HIP_TRY(hipSetDevice(c->device));
+    pp_ctx::Align& A = c->align;
+    const size_t accb = (size_t)npol * nchan_model * (nbin / 2) * sizeof(cplx);
+    int rc;
+    if ((rc = A.acc.reserve(accb))) return rc;
+    if ((rc = A.totw.reserve((size_t)nchan_model * 8))) return rc;
+    if ((rc = A.out.reserve((size_t)npol * nchan_model * nbin * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(A.acc.p, 0, accb, c->stream));
+    HIP_TRY(hipMemsetAsync(A.totw.p, 0, (size_t)nchan_model * 8, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    A.npol = npol; A.nchan = nchan_model; A.nbin = nbin; A.open = true;
+    return PP_OK;
+}
+
+// the contribution lists of a run (CSR): off[m] .. off[m + 1] are model row m's (subint, data channel) pairs, by subint,
+// then data channel; rows of weight 0 or NaN are left out.  chan_map: [nsub][nchan] or null (identity)
+static void align_lists(int nsub, int nchan, int nchan_model, const double* weights, const int32_t* chan_map,
+                        std::vector<int>& off, std::vector<int>& pairs) {
+    off.assign((size_t)nchan_model + 1, 0);
+    auto live = [&](size_t j) { return !(weights[j] == 0.0 || weights[j] != weights[j]); };
+    auto row_of = [&](size_t j, int n) { return chan_map ? (int)chan_map[j] : n; };
+    for (int i = 0; i < nsub; ++i)
+        for (int n = 0; n < nchan; ++n) {
+            const size_t j = (size_t)i * nchan + n;
+            if (live(j)) ++off[(size_t)row_of(j, n) + 1];
+        }
+    for (int m = 0; m < nchan_model; ++m) off[(size_t)m + 1] += off[m];
+    pairs.assign(2 * (size_t)off[nchan_model], 0);
+    std::vector<int> at(off.begin(), off.end() - 1);
+    for (int i = 0; i < nsub; ++i)
+        for (int n = 0; n < nchan; ++n) {
+            const size_t j = (size_t)i * nchan + n;
+            if (!live(j)) continue;
+            const int q = at[row_of(j, n)]++;
+            pairs[2 * (size_t)q] = i;
+            pairs[2 * (size_t)q + 1] = n;
+        }
+}
+
+// the lists pp_align_add builds for one run, for callers and tests that want to see them (no device is touched):
+// off[nchan_model + 1], pairs[2 x (number of live rows)] as (subint, data channel); returns the number of pairs
+extern "C" int pp_align_lists(int nsub, int nchan, int nchan_model, const double* weights, const int32_t* chan_map,
+                              int32_t* off, int32_t* pairs) {
+    if (!weights || !off || !pairs) return fail(PP_EINVAL, "pp_align_lists: null argument");
+    if (nsub < 1 || nchan < 1 || nchan_model < 1) return fail(PP_EINVAL, "pp_align_lists: bad shape");
+    if (!chan_map && nchan != nchan_model)
+        return fail(PP_EINVAL, "pp_align_lists: %d channels without a channel map onto %d rows", nchan, nchan_model);
+    if (chan_map)
+        for (size_t j = 0; j < (size_t)nsub * nchan; ++j)
+            if (chan_map[j] < 0 || chan_map[j] >= nchan_model)
+                return fail(PP_EINVAL, "pp_align_lists: chan_map[%zu][%zu] = %d is no row of %d", j / nchan, j % nchan, (int)chan_map[j], nchan_model);
+    std::vector<int> o, p;
+    align_lists(nsub, nchan, nchan_model, weights, chan_map, o, p);
+    std::copy(o.begin(), o.end(), off);
+    std::copy(p.begin(), p.end(), pairs);
+    return (int)(p.size() / 2);
+}
+
+static int align_add_run(pp_ctx* c, const Ports& in, const double* weights, const int32_t* chan_map) {
+    pp_ctx::Align& A = c->align;
+    const int nsub = in.nsub, nchan = in.nchan, nbin = in.nbin, M = nbin / 2;
+    std::vector<int> off, pairs;
+    align_lists(nsub, nchan, A.nchan, weights, chan_map, off, pairs);
+    if (pairs.empty()) return PP_OK;          // every row of the run is skipped
+    const void* dsrc = nullptr;
+    int rc;
+    if ((rc = in.stage(c, &dsrc))) return rc;
+    if ((rc = upload(c, c->wts, weights, (size_t)nsub * nchan * 8))) return rc;
+    if ((rc = upload(c, A.off, off.data(), off.size() * sizeof(int)))) return rc;
+    if ((rc = upload(c, A.pairs, pairs.data(), pairs.size() * sizeof(int)))) return rc;
+    const cplx* tw = nullptr;
+    if ((rc = get_twiddles(c, nbin, &tw))) return rc;
+    AlignListArgs a{dsrc, c->freqs.as<double>(), (long long)in.freqs_stride, c->P.as<double>(), c->x0.as<double>(),
+                    c->wts.as<double>(), tw, A.acc.as<cplx>(), A.totw.as<double>(), A.off.as<int>(), A.pairs.as<int2>(),
+                    A.npol, nchan, A.nchan};
+    const unsigned nrows = (unsigned)(A.npol * A.nchan);
+    {
+        Prof pr(c, KF_SYNTH);
+        if (!nbin_ok(nbin)) {
+            // a row length without a tuned plan (pp_anybin.h): the harmonics of the run's rows by the chirp-z route, then
+            // the list walk per slot of the packed row
+            const size_t H = (size_t)M + 1;
+            if ((rc = A.harm.reserve((size_t)nsub * A.npol * nchan * H * sizeof(cplx)))) return rc;
+            if ((rc = harmonics_any(c, dsrc, in.dtype, nsub * A.npol, nchan, nbin, A.harm.as<cplx>()))) return rc;
+            hipLaunchKernelGGL(k_align_harm_list, dim3((unsigned)((M + 255) / 256), nrows), dim3(256), 0, c->stream,
+                               (const cplx*)A.harm.as<cplx>(), a, nsub, M);
+        } else {
+            PP_DISPATCH_M(M, {
+                const int T = FftPlan<MM>::T;
+                with_dtype(in.dtype, [&](auto t) { hipLaunchKernelGGL((k_align_add<MM, decltype(t)>), dim3(nrows), dim3(T), 0, c->stream, a); });
+            });
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (the lists and the caller's arrays are free again)
+    return PP_OK;
+}
+
+extern "C" int pp_align_add(pp_ctx* c, const void* src, int dtype, int on_device, int nsub, int npol, int nchan,
+                            int nbin, const double* freqs, int64_t freqs_stride, const double* P, const double* par3,
+                            const double* weights, const int32_t* chan_map) {
+    if (int busy_ = ctx_busy(c, "pp_align_add")) return busy_;
+    const Ports in{src, dtype, on_device, nsub, nchan, nbin, freqs, freqs_stride, P, par3, 3, npol};
+    if (int rc = in.validate("pp_align_add", c && weights, npol >= 1)) return rc;
+    const pp_ctx::Align& A = c->align;
+    if (!A.open) return fail(PP_EINVAL, "pp_align_add: no accumulator (pp_align_begin first)");
+    if (npol != A.npol || nbin != A.nbin)
+        return fail(PP_EINVAL, "pp_align_add: %d x %d-bin rows, the accumulator holds %d x %d-bin rows", npol, nbin, A.npol, A.nbin);
+    if (!chan_map && nchan != A.nchan)
+        return fail(PP_EINVAL, "pp_align_add: %d channels without a channel map, the accumulator holds %d", nchan, A.nchan);
+    if (chan_map)
+        for (size_t j = 0; j < (size_t)nsub * nchan; ++j)
+            if (chan_map[j] < 0 || chan_map[j] >= A.nchan)
+                return fail(PP_EINVAL, "pp_align_add: chan_map[%zu][%zu] = %d is no row of the %d-channel accumulator", j / nchan,
+                            j % nchan, (int)chan_map[j], A.nchan);
+    HIP_TRY(hipSetDevice(c->device));
+    // (general row lengths: a run's harmonics, 16 (nbin / 2 + 1) bytes per sample row, are device work memory too)
+    const double harm = nbin_ok(nbin) ? 0.0 : 16.0 * (nbin / 2 + 1) * npol * nchan;
+    int cap = in.cap(c, 64.0 * nchan + harm);
+    if (harm > 0.0) cap = std::min(cap, harm_chunk(nsub, npol * nchan, (size_t)nbin / 2 + 1));
+    return for_runs(nsub, cap, [&](Run r) { return align_add_run(c, in.run(r), r.at(weights, nchan), r.at(chan_map, nchan)); });
+}
+
+extern "C" int pp_align_finish(pp_ctx* c, double rot_phase, double* aligned, double* total_weights, int to_slot) {
+    if (int busy_ = ctx_busy(c, "pp_align_finish")) return busy_;
+    if (!c || !aligned || !total_weights) return fail(PP_EINVAL, "pp_align_finish: null argument");
+    pp_ctx::Align& A = c->align;
+    if (!A.open) return fail(PP_EINVAL, "pp_align_finish: no accumulator (pp_align_begin first)");
+    if (to_slot >= PP_MAX_SLOTS) return fail(PP_EINVAL, "pp_align_finish: slot %d", to_slot);
+    if (rot_phase != rot_phase) return fail(PP_EINVAL, "pp_align_finish: rot_phase is NaN");
+    HIP_TRY(hipSetDevice(c->device));
+    const int nbin = A.nbin, M = nbin / 2, nrows = A.npol * A.nchan;
+    const cplx* tw = nullptr;
+    int rc;
+    if ((rc = get_twiddles(c, nbin, &tw))) return rc;
+    AlignFinishArgs a{A.acc.as<cplx>(), A.totw.as<double>(), tw, A.out.as<double>(), rot_phase, A.npol, A.nchan};
+    {
+        Prof pr(c, KF_SYNTH);
+        if (!nbin_ok(nbin)) {
+            AnyArgs g;
+            int L = 0;
+            if ((rc = any_args(c, nbin, &g, &L))) return rc;
+            if ((rc = with_any_len(L, [&](auto LL) {
+                    hipLaunchKernelGGL((k_align_finish_any<decltype(LL)::value>), dim3(any_grid(nrows)), dim3(FftPlan<decltype(LL)::value>::T), 0, c->stream, a, g);
+                })))
+                return rc;
+        } else {
+            PP_DISPATCH_M(M, {
+                const int T = FftPlan<MM>::T;
+                hipLaunchKernelGGL((k_align_finish<MM>), dim3(fft_grid(T, nrows)), dim3(T), 0, c->stream, a);
+            });
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(aligned, A.out.p, (size_t)nrows * nbin * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(total_weights, A.totw.p, (size_t)A.nchan * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // polarisation 0 into a template slot from the device copy: the bytes pp_model_set of `aligned` would transform
+    if (to_slot >= 0) return pp_model_set(c, to_slot, A.out.p, PP_F64, 1, A.nchan, nbin);
+    return PP_OK;
 }
 
 // ---- per-channel reduced chi^2 of fitted subints ---------------------------

@@ -159,6 +159,15 @@ struct pp_ctx {
         double fact = 0.0;
         void release() { for (DevBuf* b : {&w, &vec, &part, &D, &S, &G, &U, &B, &small, &idx, &proj}) b->release(); }
     } pca;
+    // ppalign (pp_align_begin / _add / _finish): the accumulator that outlives a call -- packed half-spectra
+    // acc[npol][nchan][nbin / 2], totw[nchan] -- the contribution lists of the run being added, and the portrait of the
+    // last finish
+    struct Align {
+        DevBuf acc, totw, off, pairs, harm, out;
+        int npol = 0, nchan = 0, nbin = 0;
+        bool open = false;
+        void release() { for (DevBuf* b : {&acc, &totw, &off, &pairs, &harm, &out}) b->release(); open = false; }
+    } align;
     // pinned host staging of the small inputs / the packed outputs of a batch: two sets, so that a
     // deferred batch (pp_fit_enqueue) keeps its own while the next one is being queued
     struct Stage { void* in_host = nullptr; size_t in_cap = 0; void* o_host = nullptr; size_t o_cap = 0;
@@ -387,6 +396,7 @@ extern "C" int pp_destroy(pp_ctx* c) {
         if (sg.done) (void)hipEventDestroy(sg.done);
     }
     c->pca.release();
+    c->align.release();
     c->release_buffers();
     if (c->nactive_h) (void)hipHostFree(c->nactive_h);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);

@@ -142,6 +142,7 @@ class Engine(object):
         self._queue = []        # enqueued batches (_Batch), oldest first, until collect()
         self._pending = None    # the submitted batch (_Batch) until wait()
         self._pca_shape = None  # (nchan, nbin) of the centred portrait pca_gram left on the device
+        self._align_shape = None  # (npol, nchan_model, nbin) of the resident accumulator (align_begin)
         self._lib = _lib.load()
         ctx = C.c_void_p()
         _check(self._lib.pp_create(int(device), C.byref(ctx)), "pp_create")
@@ -662,6 +663,51 @@ class Engine(object):
         _check(self._lib.pp_align_accumulate(self._ctx, src, dtype, on_dev, nsub, nchan, nbin,
                                              _dp(freqs), fstride, _dp(P), _dp(par), _dp(w),
                                              _dp(aligned), _dp(totw)), "pp_align_accumulate")
+        return aligned, totw
+
+    def align_begin(self, npol, nchan_model, nbin):
+        """Start (or start over) the device-resident accumulator of align_archives
+        (ppalign.py:116-117): aligned_port[npol,nchan_model,nbin] and total_weights, zeroed."""
+        self._align_shape = None
+        _check(self._lib.pp_align_begin(self._ctx, int(npol), int(nchan_model), int(nbin)), "pp_align_begin")
+        self._align_shape = (int(npol), int(nchan_model), int(nbin))
+
+    def align_add(self, ports, freqs, P, phase, DM, nu_ref, weights, chan_map=None):
+        """ppalign.py:202-208 for every subint of ports[nsub,npol,nchan,nbin] (or
+        [nsub,nchan,nbin]: one polarisation; NumPy or a device tensor): row (i, ipol, n),
+        rotated by (phase_i, DM_i, nu_ref_i) and weighted by weights[i,n] -- 0 or NaN skips
+        it --, is added to accumulator row (ipol, chan_map[i,n]); chan_map None is the
+        identity.  The accumulator's bits do not depend on how the subints are cut into calls."""
+        src, dtype, on_dev, shape, keep = _array_arg(ports, "align_add: device ports")
+        if len(shape) == 3:
+            shape = (shape[0], 1) + tuple(shape[1:])
+        if len(shape) != 4:
+            raise ValueError("ports must be [nsub,npol,nchan,nbin] or [nsub,nchan,nbin]")
+        nsub, npol, nchan, nbin = shape
+        freqs, fstride, P, par = self._subint_args(freqs, P, (phase, DM, nu_ref), nsub, nchan)
+        w = _f64(weights, (nsub, nchan))
+        cm = None
+        if chan_map is not None:
+            cm = np.ascontiguousarray(np.broadcast_to(np.asarray(chan_map, dtype=np.int32), (nsub, nchan)))
+        _check(self._lib.pp_align_add(self._ctx, src, dtype, on_dev, nsub, npol, nchan, nbin, _dp(freqs),
+                                      fstride, _dp(P), _dp(par), _dp(w),
+                                      None if cm is None else cm.ctypes.data_as(c_int32_p)), "pp_align_add")
+        del keep
+
+    def align_finish(self, rot_phase=0.0, to_slot=-1):
+        """ppalign.py:210-212 (and the overall rotation of :220-226) of the resident
+        accumulator: returns (aligned_port[npol,nchan_model,nbin], total_weights[nchan_model]);
+        rows of positive total weight are divided by it.  to_slot >= 0 also makes polarisation
+        0 the template of that model slot, from the device copy (the bits set_model of the
+        returned array would give).  May be called again, e.g. with another rot_phase."""
+        if self._align_shape is None:
+            raise EngineError("align_finish: no accumulator (align_begin first)")
+        npol, nchan, nbin = self._align_shape
+        aligned, totw = np.empty((npol, nchan, nbin)), np.empty(nchan)
+        _check(self._lib.pp_align_finish(self._ctx, float(rot_phase), _dp(aligned), _dp(totw), int(to_slot)),
+               "pp_align_finish")
+        if int(to_slot) >= 0:
+            self._slot_changed(to_slot)
         return aligned, totw
 
     def channel_red_chi2(self, ports, freqs, P, params, nu_refs, scales, errs, slots=None):

@@ -192,6 +192,26 @@ def get_noise(data, method=default_noise_method, frac=4, chans=False):
     return noise if chans else noise[0]
 
 
+def gaussian_profile(nbin, loc, wid):
+    """A Gaussian pulse of FWHM wid [rot] centred on phase loc, sampled at the nbin bin
+    centres nearest to loc (wrapped), scaled so that the underlying curve peaks at 1
+    (pplib.py:770-825); zeros for wid <= 0 and beyond 20 sigma."""
+    out = np.zeros(int(nbin))
+    if not wid > 0.0:
+        return out
+    sigma = wid / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+    mean = loc % 1.0
+    x = get_bin_centers(nbin)
+    x = np.where(x > mean + 0.5, x - 1.0, x) if mean < 0.5 else np.where(x < mean - 0.5, x + 1.0, x)
+    z = (x - mean) / sigma
+    near = np.fabs(z) < 20.0
+    out[near] = np.exp(-0.5 * z[near] ** 2.0) / (sigma * np.sqrt(2.0 * np.pi))
+    if not out.any():
+        return out
+    ipk = out.argmax()
+    return np.exp(-0.5 * ((x[ipk] - loc) / sigma) ** 2.0) / out[ipk] * out
+
+
 def get_SNR(prof, fudge=3.25):
     """Estimate of a profile's signal-to-noise ratio, baseline removed (pplib.py:2289-2308):
     sum / (noise sqrt(Weq)) / fudge with Weq = sum / max.  The profile's sum, maximum and

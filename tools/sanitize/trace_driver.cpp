@@ -627,6 +627,130 @@ static void aux_cases() {
     aux_refusals(8, 1000);
 }
 
+// ---- the resident alignment accumulator: pp_align_begin / pp_align_add / pp_align_finish ------------------------
+// (after aux_cases(), so that everything in front keeps its place in the trace)  Every array exactly as long as the
+// entry points read or write; rows of f64 / f32, host / device, one polarisation / four, identity / many-to-one map
+// with a row nothing lands on, weights with a zero and a NaN, adds of a host input in one run and in several, a second
+// add into the same accumulator, finish into a slot and with a rotation
+static void aux_align_calls(pp_ctx* c, int B, int Cm, int ns, int f32, int dev, int npol, int mapped, const char* tag) {
+    const int C = mapped ? Cm + 4 : Cm;
+    const size_t esz = f32 ? 4 : 8, nrow = (size_t)ns * npol * C;
+    std::vector<unsigned char> ports(nrow * B * esz);
+    for (size_t j = 0; j < nrow * B; ++j) {
+        const double v = 0.5 + (j % 13) * 0.01;
+        if (f32) ((float*)ports.data())[j] = (float)v; else ((double*)ports.data())[j] = v;
+    }
+    void* dports = dev ? dev_copy(ports.data(), ports.size()) : nullptr;
+    const void* src = dev ? dports : (const void*)ports.data();
+    std::vector<double> freqs(C), P(ns, 0.003), par3((size_t)ns * 3, 0.0), w((size_t)ns * C, 1.5);
+    for (int j = 0; j < C; ++j) freqs[j] = 1100.0 + 800.0 * (j + 0.5) / C;
+    for (int i = 0; i < ns; ++i) { par3[(size_t)i * 3] = 0.01 * i; par3[(size_t)i * 3 + 1] = i % 2 ? 1e-3 : 0.0; par3[(size_t)i * 3 + 2] = i % 3 ? 1500.0 : INFINITY; }
+    w[1] = 0.0; w[w.size() - 1] = NAN; w[C] = -0.5;
+    std::vector<int32_t> cmap((size_t)ns * C);
+    for (int i = 0; i < ns; ++i)
+        for (int n = 0; n < C; ++n) cmap[(size_t)i * C + n] = (n * (Cm - 1)) / C;        // the last row gets nothing
+    const int32_t* cm = mapped ? cmap.data() : nullptr;
+    char nm[200];
+    auto name = [&](const char* fn) {
+        snprintf(nm, sizeof nm, "%s %s %dx%dx%dx%d -> %d %s %s %s", fn, tag, ns, npol, C, B, Cm, f32 ? "f32" : "f64", dev ? "device" : "host", mapped ? "mapped" : "identity");
+        return nm;
+    };
+    const int dt = f32 ? PP_F32 : PP_F64;
+    { Outs o; int32_t* off = (int32_t*)o.raw((size_t)Cm + 1, 4); std::vector<int32_t> pairs((size_t)2 * ns * C);
+      mark("case aux %s", name("pp_align_lists")); ++g_ncase;
+      const int np_ = pp_align_lists(ns, C, Cm, w.data(), cm, off, pairs.data());
+      mark("pairs %d", np_);
+      if (np_ != ns * C - 2) { fprintf(stderr, "pp_align_lists: %d pairs of %d rows with two skipped\n", np_, ns * C); exit(1); }
+      o.require_filled("pp_align_lists"); }
+    { Outs o; AUX(o, name("pp_align_begin"), pp_align_begin(c, npol, Cm, B)); }
+    { Outs o; AUX(o, name("pp_align_add"), pp_align_add(c, src, dt, dev, ns, npol, C, B, freqs.data(), 0, P.data(), par3.data(), w.data(), cm)); }
+    { Outs o; double* al = o.d((size_t)npol * Cm * B); double* tw = o.d(Cm);
+      AUX(o, name("pp_align_finish"), pp_align_finish(c, 0.0, al, tw, -1)); }
+    { Outs o; AUX(o, name("pp_align_add again"), pp_align_add(c, src, dt, dev, 1, npol, C, B, freqs.data(), 0, P.data(), par3.data(), w.data(), cm)); }
+    { Outs o; double* al = o.d((size_t)npol * Cm * B); double* tw = o.d(Cm);
+      AUX(o, name("pp_align_finish into a slot"), pp_align_finish(c, 0.37, al, tw, 2)); }
+    if (dports) dev_free(dports);
+}
+
+static void aux_align_refusals(int Cm, int B) {
+    mark("case aux context %dx%d for the accumulator's refusals", Cm, B);
+    pp_ctx* c = make_ctx(Cm, B);
+    const int ns = 3, C = Cm + 4;
+    const Outs o;
+    std::vector<double> ports((size_t)ns * 4 * C * B, 0.5), freqs(C, 1400.0), P(ns, 0.003), par3((size_t)ns * 3, 0.0), w((size_t)ns * C, 1.0);
+    std::vector<double> outv((size_t)4 * Cm * B);
+    std::vector<int32_t> cmap((size_t)ns * C, 0);
+    const void* src = ports.data();
+    const double *f = freqs.data(), *Pp = P.data(), *p3 = par3.data(), *wp = w.data();
+    double* out = outv.data();
+#define REF(what, call) AUX(o, "refused: " what, call)
+    REF("pp_align_add before pp_align_begin", pp_align_add(c, src, PP_F64, 0, ns, 1, C, B, f, 0, Pp, p3, wp, cmap.data()));
+    REF("pp_align_finish before pp_align_begin", pp_align_finish(c, 0.0, out, out, -1));
+    for (int B2 : {B + 1, 6, 4098}) REF("pp_align_begin nbin", pp_align_begin(c, 1, Cm, B2));
+    REF("pp_align_begin npol", pp_align_begin(c, 0, Cm, B));
+    REF("pp_align_begin npol", pp_align_begin(c, 5, Cm, B));
+    REF("pp_align_begin nchan", pp_align_begin(c, 1, 0, B));
+    REF("pp_align_begin null", pp_align_begin(nullptr, 1, Cm, B));
+    { Outs g; AUX(g, "pp_align_begin for the refusals", pp_align_begin(c, 1, Cm, B)); }
+    REF("pp_align_add nbin", pp_align_add(c, src, PP_F64, 0, ns, 1, C, B == 64 ? 128 : 64, f, 0, Pp, p3, wp, cmap.data()));
+    REF("pp_align_add npol", pp_align_add(c, src, PP_F64, 0, ns, 4, C, B, f, 0, Pp, p3, wp, cmap.data()));
+    REF("pp_align_add npol 0", pp_align_add(c, src, PP_F64, 0, ns, 0, C, B, f, 0, Pp, p3, wp, cmap.data()));
+    REF("pp_align_add identity with other channels", pp_align_add(c, src, PP_F64, 0, ns, 1, C, B, f, 0, Pp, p3, wp, nullptr));
+    for (int bad : {Cm, -1, INT32_MAX}) {
+        cmap[(size_t)ns * C - 1] = bad;
+        REF("pp_align_add chan_map out of range", pp_align_add(c, src, PP_F64, 0, ns, 1, C, B, f, 0, Pp, p3, wp, cmap.data()));
+    }
+    cmap[(size_t)ns * C - 1] = 0;
+    REF("pp_align_add shape", pp_align_add(c, src, PP_F64, 0, 0, 1, C, B, f, 0, Pp, p3, wp, cmap.data()));
+    REF("pp_align_add dtype", pp_align_add(c, src, 7, 0, ns, 1, C, B, f, 0, Pp, p3, wp, cmap.data()));
+    REF("pp_align_add freqs_stride", pp_align_add(c, src, PP_F64, 0, ns, 1, C, B, f, 5, Pp, p3, wp, cmap.data()));
+    for (int z = 0; z < 6; ++z) {
+#define NZ(i, p) (z == (i) ? nullptr : (p))
+        REF("pp_align_add null", pp_align_add(NZ(5, c), NZ(0, src), PP_F64, 0, ns, 1, C, B, NZ(1, f), 0, NZ(2, Pp), NZ(3, p3), NZ(4, wp), cmap.data()));
+#undef NZ
+    }
+    REF("pp_align_finish null", pp_align_finish(c, 0.0, nullptr, out, -1));
+    REF("pp_align_finish null", pp_align_finish(c, 0.0, out, nullptr, -1));
+    REF("pp_align_finish null", pp_align_finish(nullptr, 0.0, out, out, -1));
+    REF("pp_align_finish slot", pp_align_finish(c, 0.0, out, out, PP_MAX_SLOTS));
+    REF("pp_align_finish rot_phase", pp_align_finish(c, NAN, out, out, -1));
+    {
+        Spec s; s.C = Cm; s.B = B;
+        Batch b(s);
+        mark("case aux refused: a batch is pending (accumulator)");
+        ++g_ncase;
+        mark("enqueue rc %d", pp_fit_enqueue(c, &b.in, &b.out));
+        REF("pending pp_align_begin", pp_align_begin(c, 1, Cm, B));
+        REF("pending pp_align_add", pp_align_add(c, src, PP_F64, 0, ns, 1, C, B, f, 0, Pp, p3, wp, cmap.data()));
+        REF("pending pp_align_finish", pp_align_finish(c, 0.0, out, out, -1));
+        mark("collect rc %d", pp_fit_collect(c));
+    }
+#undef REF
+    MUST(pp_destroy(c));
+}
+
+static void aux_align_cases() {
+    char tag[64];
+    for (int B : {64, 2048, 1000})
+        for (int small : {0, 1}) {
+            const int Cm = 8, ns = small ? 7 : 3;
+            mark("case aux context %dx%d accumulator budget=%s", Cm, B, small ? "small" : "large");
+            pp_ctx* c = make_ctx(Cm, B);
+            snprintf(tag, sizeof tag, "budget=%s", small ? "small" : "large");
+            for (int f32 : {0, 1})
+                for (int dev : {0, 1})
+                    for (int npol : {1, 4})
+                        for (int mapped : {0, 1}) {
+                            // the budget: 2.4 subints' portraits of this shape
+                            if (small) MUST(pp_set_option(c, "max_work_bytes", 2.4 * npol * (mapped ? Cm + 4 : Cm) * B * (f32 ? 4 : 8)));
+                            aux_align_calls(c, B, Cm, ns, f32, dev, npol, mapped, tag);
+                        }
+            MUST(pp_destroy(c));
+        }
+    aux_align_refusals(8, 64);
+    aux_align_refusals(8, 1000);
+}
+
 int main() {
     g_mark = (void (*)(const char*))dlsym(RTLD_DEFAULT, "hip_stub_mark");
     if (!g_mark) fprintf(stderr, "trace_driver: no hip_stub_mark (LD_PRELOAD libhip_stub.so): cases go unnamed\n");
@@ -636,6 +760,7 @@ int main() {
     chain("chain");
     option_cases();
     aux_cases();
+    aux_align_cases();
     printf("trace_driver: done\n");
     return 0;
 }
