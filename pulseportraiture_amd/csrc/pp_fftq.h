@@ -338,13 +338,32 @@ __device__ __forceinline__ void taylor_terms(const bool first, double (&tm)[N], 
 
 // Pieces k0 .. k1 - 1 of the row at nxrow (piece k = elements 64 k .. 64 k + 63, one per lane) into the registers of
 // the next row, read once (load_row_once).  k0 and k1 are compile-time values at every call site.
-template <typename Raw, int R>
+// MID: every piece is addressed as (wave-uniform base) + (the lane's 32-bit offset) + (immediate).  The immediate of a
+// global load reaches -4096 .. 4095 bytes, so a base in the MIDDLE of each 8 KB of the row serves eight 1 KB pieces:
+// two scalar additions a row instead of a 64-bit vector address for every 4 KB, held from one half of the
+// prefetch to the other.
+template <typename Raw, int R, bool MID = false>
 __device__ __forceinline__ void load_row_pieces(Raw (&cur)[1][R], const void* nxrow, const int tid, const int k0, const int k1) {
     const char* gb = reinterpret_cast<const char*>(nxrow);
     const unsigned boff = (unsigned)tid * (unsigned)sizeof(Raw);
+    if constexpr (MID) {
+        constexpr int PIECE = 64 * (int)sizeof(Raw), SPAN = 8192, PER = SPAN / PIECE;
 #pragma unroll
-    for (int k = 0; k < R; ++k)
-        if (k >= k0 && k < k1) cur[0][k] = load_row_once<Raw>(gb + (size_t)(k * 64) * sizeof(Raw) + boff);
+        for (int g = 0; g * PER < R; ++g) {
+            if (!(g * PER < k1 && (g + 1) * PER > k0)) continue;
+            // (pinned to a scalar register pair: left to itself the compiler folds the constant back into the pieces)
+            const char* mid = gb + (g * SPAN + SPAN / 2);
+            asm volatile("" : "+s"(mid));
+            mid = as_global(mid);
+#pragma unroll
+            for (int k = g * PER; k < (g + 1) * PER && k < R; ++k)
+                if (k >= k0 && k < k1) cur[0][k] = load_row_once<Raw>(mid + (ptrdiff_t)(k * PIECE - g * SPAN - SPAN / 2) + boff);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            if (k >= k0 && k < k1) cur[0][k] = load_row_once<Raw>(gb + (size_t)(k * 64) * sizeof(Raw) + boff);
+    }
 }
 
 }  // namespace pp

@@ -190,6 +190,13 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     const cplx* mrow = nullptr;    // the template row and cut of the channel in hand (channel_lookup)
     int n_held = -1, ktn = 0;
     int i_nx = i, n_nx = n;
+    // FASTROW (f64 rows, noise given): the rows of a FULL chunk of one channel, walked without a mask, an `act` list or
+    // per-subint templates, differ from their predecessor by one subint -- row, ph0 and result addresses advance by
+    // nchan_full -- and none of them but the first draws a ticket or looks a channel up.  The chunk's first row (which
+    // sees all that) counts them out, rows 1..30 take the short row top, and the last row is a general one again: it is
+    // the one that moves on to the chunk the ticket names.  At two waves per SIMD a scalar or branch instruction takes
+    // an issue slot of its wave that only the partner wave can fill: the general top walks ~80 of them a row.
+    constexpr bool FASTROW = TWL;
     if (ROWTOP) first_row_landed();
 #pragma unroll 1
     for (int phase = 0; phase < 2; ++phase) {
@@ -203,9 +210,18 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
             put_lane_consts(as_global(a.twB)[2 * tid], as_global(a.twB)[32 * (tid & 15)], as_global(a.twB)[lamr ? lamr : 64]);
         }
     }
+    // (the short tops still to come in this chunk and the row they step from: values of THIS loop only -- the loop's
+    // exit test is not wave-uniform to the compiler, and what it carries out of the loop lives in vector registers.
+    // The walk is kept whole, so a wave back from tail_work finishes its chunk with general rows)
+    unsigned fast_left = 0u;
+    size_t rc_prev = 0;
     for (; rw.more && tail_after != 0; rw.advance(), row = rw.row, i = i_nx, n = n_nx, --tail_after) {
-        rw.draw(a.ticket);
-        rw.peek(nrows, a.ticket_base, a.mwords);
+        // (FASTROW: the walk's steps sit in the general branch of the row top below.  The kernels without it keep
+        // theirs where they were measured)
+        if (!FASTROW) {
+            rw.draw(a.ticket);
+            rw.peek(nrows, a.ticket_base, a.mwords);
+        }
         // (everything derived from the lane number is recomputed per row: held across
         // the row it would cost the registers the prefetched row needs)
         asm volatile("" : "+v"(tid));
@@ -219,18 +235,45 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         } else if (!TWL) {      // (TWL: read where they are used)
             asm volatile("" : "+v"(t1.x), "+v"(t1.y), "+v"(t2.x), "+v"(t2.y), "+v"(wb0.x), "+v"(wb0.y));
         }
-        const int ia = sub_of(a.act, i), ne = a.coff + n * a.cstep;   // true subint, channel
-        const size_t rc = (size_t)ia * a.nchan_full + ne;
-        // loads whose results are needed late are issued before the prefetch (vector
-        // memory returns in order)
-        if (channel_lookup(a, ia, n, ne, M, n_held, mrow, ktn) && mrow != mheld) {
-#pragma unroll
-            for (int j = 0; j < NSL; ++j) {
-                const cplx mval = mrow[kb + 64 * j - 1];   // k <= 448: inside the row
-                if (j < NSL - NML) mv2[j] = mval; else ldsm[64 * (j - (NSL - NML))] = mval;
+        size_t rc;
+        const Tin* nxrow = nullptr;
+        if (FASTROW && fast_left != 0u) {
+            // one subint on in the same chunk and channel: no ticket, no mask word, no look-up; the row after it too
+            --fast_left;
+            rc = rc_prev + (size_t)(unsigned)a.nchan_full;
+            rw.row_nx = rw.row + 1u;
+            rw.bits &= rw.bits - 1u;
+            i_nx = i + 1;
+            nxrow = reinterpret_cast<const Tin*>(a.data) + (rc + (size_t)(unsigned)a.nchan_full) * (2 * M);
+        } else {
+            if (FASTROW) {
+                rw.draw(a.ticket);
+                rw.peek(nrows, a.ticket_base, a.mwords);
             }
-            mheld = mrow;
+            const int ia = sub_of(a.act, i), ne = a.coff + n * a.cstep;   // true subint, channel
+            rc = (size_t)ia * a.nchan_full + ne;
+            // loads whose results are needed late are issued before the prefetch (vector
+            // memory returns in order)
+            if (channel_lookup(a, ia, n, ne, M, n_held, mrow, ktn) && mrow != mheld) {
+#pragma unroll
+                for (int j = 0; j < NSL; ++j) {
+                    const cplx mval = mrow[kb + 64 * j - 1];   // k <= 448: inside the row
+                    if (j < NSL - NML) mv2[j] = mval; else ldsm[64 * (j - (NSL - NML))] = mval;
+                }
+                mheld = mrow;
+            }
+            if (FASTROW) {
+                const bool first_of_chunk = rw.fresh != 0u;
+                rw.next(i, n, i_nx, n_nx, nrows, a.nsub, a.ticket_base, a.ticket, a.mwords);
+                nxrow = next_row_of<M, Tin>(a, rw.more_nx, i_nx, n_nx, rc);
+                // a full chunk (rows 2..31 still to come behind the next one) of one channel, every row in use
+                const bool whole = first_of_chunk && rw.bits == 0xfffffffcu && i + (PP_ROW_CHUNK - 1) < a.nsub &&
+                                   !a.mwords && !a.act && !a.slot;
+                // (a scalar register: the count is tested and stepped at the top of every row)
+                fast_left = (unsigned)__builtin_amdgcn_readfirstlane(whole ? PP_ROW_CHUNK - 2 : 0);
+            }
         }
+        rc_prev = rc;
         const double phin = ROWTOP ? load_uniform(a.ph0 + rc) : a.ph0[rc];
         double sd = 0.0;
         cplx v[R1];
@@ -243,17 +286,18 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         // whole next row in flight from the start, 64 + 64 row registers on top of the
         // template row and the sums do not fit the 256 of two waves per SIMD
         constexpr bool HALVES = F64;
-        const Tin* nxrow = nullptr;
         // (pieces k0 .. k1 - 1 of the next row.  A lambda over the kernel's own variables in every kernel that queues a
         // row in pieces, not a direct call: k_xspec_qf<1024> keeps three more scalar registers alive across its call
         // to tail_work with the direct call -- profiles/r08_refactor_isa.txt)
-        auto load_some = [&](int k0, int k1) { load_row_pieces<Raw>(cur, nxrow, tid, k0, k1); };
-        // (the row after this one is decided HERE, outside the lambda: a walk captured by reference is not
-        // split into registers -- its flags went through scratch memory, whose loads queue behind the
+        auto load_some = [&](int k0, int k1) { load_row_pieces<Raw, R1, FASTROW>(cur, nxrow, tid, k0, k1); };
+        // (the row after this one is decided HERE or in the row top, outside the lambda: a walk captured by reference
+        // is not split into registers -- its flags went through scratch memory, whose loads queue behind the
         // prefetched row -- and at the top of a row everything older than this row's own data has landed,
         // the ticket of the chunk's first row included)
-        rw.next(i, n, i_nx, n_nx, nrows, a.nsub, a.ticket_base, a.ticket, a.mwords);
-        nxrow = next_row_of<M, Tin>(a, rw.more_nx, i_nx, n_nx, rc);
+        if (!FASTROW) {
+            rw.next(i, n, i_nx, n_nx, nrows, a.nsub, a.ticket_base, a.ticket, a.mwords);
+            nxrow = next_row_of<M, Tin>(a, rw.more_nx, i_nx, n_nx, rc);
+        }
         auto prefetch = [&]() {
             __builtin_amdgcn_sched_barrier(0);
             load_some(0, HALVES ? R1 / 2 : R1);

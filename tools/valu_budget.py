@@ -224,7 +224,7 @@ an instruction = one VALU issue slot; FMA counted as one):
   reduction + stores               51      ~30   13 values x (store, 16-term column sum shared by 4 lanes), 2 quad exchanges, scaling, signs
   row top + row walk               87      ~25   18 loads' 64-bit addresses (v_add_co / v_addc pairs: 4 groups of 4 KB reach), lambda, kb,
                                                  the chunk's ticket and mask word; everything that can is scalar (341 s_ instructions a row,
-                                                 which issue beside the vector ones)
+                                                 each taking an issue slot of its wave: DESIGN.md section 4)
   -----------------------------------------------------------------------------------------------
   k_xspec_q1024<double, false>   1103 (4.5 slots kept; SQ_INSTS_VALU / rows = 1044 measured) against ~930 + the 64 lane swaps:
   the kernel is within 6 - 11 % of its operation count; no block is more than ~80 instructions (7 % of a row) above its bound and
