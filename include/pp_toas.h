@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 8
+#define PP_ABI_VERSION 9
 
 /* status codes */
 #define PP_OK 0
@@ -578,6 +578,41 @@ int pp_pca_basis(pp_ctx* ctx, const double* vecs, const double* lam, int nvec, d
 /* proj [nchan][ncomp] = delta . basis[ieig] and reconst [nchan][nbin] = proj . basis[ieig]^T + mean_prof
  * (ppspline.py:119-129; reconstruct_portrait, pplib.py:1536-1553) from the resident rows and basis. */
 int pp_pca_project(pp_ctx* ctx, const int32_t* ieig, int ncomp, double* proj, double* reconst);
+
+/* ---- ppgauss --------------------------------------------------------------- */
+/* The device side of fit_gaussian_portrait (pplib.py:1924-2052), a Levenberg-Marquardt fit whose Jacobian is taken by
+ * forward differences: every column is a whole model portrait (gen_gaussian_portrait, pplib.py:853-930).
+ * pp_gauss_fit_begin makes the data portrait data[nchan][nbin] (`dtype`, host or device; the caller hands over the
+ * good channels only), its channel frequencies freqs[nchan] and 1 / errs[n] (errs[nchan] > 0, the noise level of every
+ * channel; host arrays) resident for the whole fit: no later call uploads the portrait again.  A second begin starts
+ * over; pp_gauss_fit_end releases everything the fit holds.  nbin: even, 8 ... 4096, or a power of two up to 8192. */
+int pp_gauss_fit_begin(pp_ctx* ctx, const void* data, int dtype, int on_device, int nchan,
+                       int nbin, const double* freqs, const double* errs);
+int pp_gauss_fit_end(pp_ctx* ctx);
+
+/* The weighted residual rows of nsets parameter vectors at once (fit_gaussian_portrait_function, pplib.py:1230-1242):
+ *   R[s][n][:] = (data_n - model_n(dc[s], tau_rot[s], alpha[s], comps[s])) / errs[n]
+ * with model = gen_gaussian_portrait of model code `code` ("000" ... "111") about nu_ref; tau_rot[s] is the scattering
+ * time at nu_ref in rotations (0: unscattered), alpha[s] the scattering index, comps[s][ngauss][6] = loc, m_loc, wid,
+ * m_wid, amp, m_amp.  One workgroup per (channel, set); the model rows are formed by the code of
+ * pp_gaussian_portrait, operation for operation.  R stays on the device for pp_gauss_normal; out_or_null
+ * [nsets][nchan][nbin] (host) receives a copy.  Refused, never truncated: ngauss > 16, nsets > 100, nsets nchan nbin 8
+ * bytes above 2 GiB (PP_EINVAL); no resident portrait (PP_ESTATE). */
+int pp_gauss_residuals(pp_ctx* ctx, const char* code, double nu_ref, int nsets, const double* dc,
+                       const double* tau_rot, const double* alpha, int ngauss,
+                       const double* comps, double* out_or_null);
+
+/* Normal equations of a forward-difference Levenberg-Marquardt step from nsets residual rows of nrow samples: with
+ * D_a = (R_{a+1} - R_0) / h[a], a = 0 .. nsets - 2,
+ *   *chi2 = sum R_0^2,   g[a] = sum D_a R_0,   G[a][b] = sum D_a D_b          (over all nrow samples)
+ * R_or_null == NULL takes the rows the last pp_gauss_residuals left (nsets and nrow = nchan nbin must be its; else
+ * PP_ESTATE); a pointer (host, or device with on_device) hands in R[nsets][nrow] -- host rows take the resident rows'
+ * place.  With nsets == 1 only chi2 is written (h, g, G may be NULL).  f64 throughout, a two-stage slab sum without
+ * floating-point atomics: stage one writes the partial sums of runs of samples whose length depends on nrow alone,
+ * stage two adds them in run order, so the same call gives the same bits on every run and every device.  Every
+ * product and every sum is rounded on its own: an entry's error is below nrow 2^-53 sum |terms|. */
+int pp_gauss_normal(pp_ctx* ctx, const double* R_or_null, int on_device, int nsets, int nrow,
+                    const double* h, double* chi2, double* g, double* G);
 
 /* Fill dst[nsub][nchan][nbin] (device pointer, dtype) with
  *   gains[i][n] * rotate(model slot, -phi_i, -DM_i, -GM_i) + N(0, sigma)

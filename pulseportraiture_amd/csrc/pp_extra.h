@@ -457,71 +457,92 @@ __device__ __forceinline__ double gauss_row_value(const GaussArgs& a, const Gaus
     return add_rn(a.dc, sum);
 }
 
+// where a generated row goes: the template's own rows here, the weighted residual against a data row in
+// pp_gaussfit.h -- one(j, v): bin j; two(j, v0, v1): bins 2j and 2j + 1
+struct GaussRowOut {
+    double* out;
+    __device__ __forceinline__ void one(int j, double v) const { out[j] = v; }
+    __device__ __forceinline__ void two(int j, double v0, double v1) const { reinterpret_cast<double2*>(out)[j] = make_double2(v0, v1); }
+};
+
+// one unscattered row of B bins at channel frequency nu (gc: PP_MAX_GAUSS components of workgroup scratch;
+// T threads; the caller synchronises before gc is reused)
+template <typename Out>
+__device__ __forceinline__ void gauss_plain_row(const GaussArgs& a, double nu, int B, GaussComp* gc, int tid, int T, const Out& o) {
+    gauss_components(a, nu, B, gc, tid, T);
+    __syncthreads();
+    for (int j = tid; j < B; j += T) o.one(j, gauss_row_value(a, gc, j, B));
+}
+
 // the unscattered rows at ANY row length B (round 5: general even nbin; the scattering filter then goes through
 // the harmonics -- k_any, k_scatter_harm, k_irfft_any of pp_anybin.h)
 __global__ __launch_bounds__(256) void k_gauss_rows(GaussArgs a, int B) {
     __shared__ GaussComp gc[PP_MAX_GAUSS];
     const int tid = threadIdx.x;
     for (int n = blockIdx.x; n < a.nchan; n += gridDim.x) {
-        gauss_components(a, a.freqs[n], B, gc, tid, 256);
+        gauss_plain_row(a, a.freqs[n], B, gc, tid, 256, GaussRowOut{a.out + (size_t)n * B});
         __syncthreads();
-        double* out = a.out + (size_t)n * B;
-        for (int j = tid; j < B; j += 256) out[j] = gauss_row_value(a, gc, j, B);
+    }
+}
+
+// one row of 2 M bins at channel frequency nu, scattered when the model carries a scattering time (lds, zin, gc:
+// the workgroup's FFT buffers and component scratch; the caller synchronises before they are reused)
+template <int M, typename Out>
+__device__ __forceinline__ void gauss_portrait_row(const GaussArgs& a, double nu, cplx* lds, cplx* zin, GaussComp* gc, int tid,
+                                                   const Out& o) {
+    constexpr int T = FftPlan<M>::T, B = 2 * M;
+    constexpr int PL = FftPlan<M>::PADLOG;
+    gauss_components(a, nu, B, gc, tid, T);
+    __syncthreads();
+    for (int j = tid; j < B; j += T) reinterpret_cast<double*>(zin)[j] = gauss_row_value(a, gc, j, B);
+    __syncthreads();
+    const double taun = (a.tau_ref != 0.0) ? a.tau_ref * pow(nu / a.nu_ref, a.alpha) : 0.0;
+    if (taun == 0.0) {
+        for (int j = tid; j < B; j += T) o.one(j, reinterpret_cast<const double*>(zin)[j]);
+    } else {
+        // irfft(rfft(row) / (1 + 2 pi i k tau_n)): same packing as k_rotate
+        fft_row<M, double>(lds, reinterpret_cast<const double*>(zin), a.twB, tid);
         __syncthreads();
+        const cplx z0 = lds[0];
+        const double y0 = z0.x + z0.y;
+        const double xM = PP_TWO_PI * (double)M * taun;
+        const double yM = (z0.x - z0.y) / (1.0 + xM * xM);     // Re(d_M B_M), d_M real
+        for (int k = tid; k < M; k += T) {
+            cplx yk, ym;
+            if (k == 0) { yk = make_double2(y0, 0.0); ym = make_double2(yM, 0.0); }
+            else {
+                const double xk = PP_TWO_PI * (double)k * taun, dk = 1.0 / (1.0 + xk * xk);
+                const double xm = PP_TWO_PI * (double)(M - k) * taun, dm = 1.0 / (1.0 + xm * xm);
+                yk = cmul(rfft_harmonic<M>(lds, a.twB, k), make_double2(dk, -xk * dk));
+                ym = cmul(rfft_harmonic<M>(lds, a.twB, M - k), make_double2(dm, -xm * dm));
+            }
+            ym.y = -ym.y;
+            const cplx ev = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y + ym.y));
+            cplx od = make_double2(0.5 * (yk.x - ym.x), 0.5 * (yk.y - ym.y));
+            cplx w = a.twB[k];
+            w.y = -w.y;
+            od = cmul(od, w);
+            zin[k] = make_double2(ev.x - od.y, -(ev.y + od.x));
+        }
+        __syncthreads();
+        fft_row<M, cplx>(lds, zin, a.twB, tid);
+        const double inv = 1.0 / (double)M;
+        for (int j = tid; j < M; j += T) {
+            const cplx r = lds[lds_pad<PL>(j)];
+            o.two(j, r.x * inv, -r.y * inv);
+        }
     }
 }
 
 template <int M>
 __global__ __launch_bounds__(FftPlan<M>::T) void k_gauss_portrait(GaussArgs a) {
-    constexpr int T = FftPlan<M>::T, B = 2 * M;
-    constexpr int PL = FftPlan<M>::PADLOG;
+    constexpr int B = 2 * M;
     __shared__ cplx lds[FftPlan<M>::LDS_ELEMS];
     __shared__ cplx zin[M];
     __shared__ GaussComp gc[PP_MAX_GAUSS];
     const int tid = threadIdx.x;
     for (int n = blockIdx.x; n < a.nchan; n += gridDim.x) {
-        const double nu = a.freqs[n];
-        gauss_components(a, nu, B, gc, tid, T);
-        __syncthreads();
-        for (int j = tid; j < B; j += T) reinterpret_cast<double*>(zin)[j] = gauss_row_value(a, gc, j, B);
-        __syncthreads();
-        double* out = a.out + (size_t)n * B;
-        const double taun = (a.tau_ref != 0.0) ? a.tau_ref * pow(nu / a.nu_ref, a.alpha) : 0.0;
-        if (taun == 0.0) {
-            for (int j = tid; j < B; j += T) out[j] = reinterpret_cast<const double*>(zin)[j];
-        } else {
-            // irfft(rfft(row) / (1 + 2 pi i k tau_n)): same packing as k_rotate
-            fft_row<M, double>(lds, reinterpret_cast<const double*>(zin), a.twB, tid);
-            __syncthreads();
-            const cplx z0 = lds[0];
-            const double y0 = z0.x + z0.y;
-            const double xM = PP_TWO_PI * (double)M * taun;
-            const double yM = (z0.x - z0.y) / (1.0 + xM * xM);     // Re(d_M B_M), d_M real
-            for (int k = tid; k < M; k += T) {
-                cplx yk, ym;
-                if (k == 0) { yk = make_double2(y0, 0.0); ym = make_double2(yM, 0.0); }
-                else {
-                    const double xk = PP_TWO_PI * (double)k * taun, dk = 1.0 / (1.0 + xk * xk);
-                    const double xm = PP_TWO_PI * (double)(M - k) * taun, dm = 1.0 / (1.0 + xm * xm);
-                    yk = cmul(rfft_harmonic<M>(lds, a.twB, k), make_double2(dk, -xk * dk));
-                    ym = cmul(rfft_harmonic<M>(lds, a.twB, M - k), make_double2(dm, -xm * dm));
-                }
-                ym.y = -ym.y;
-                const cplx ev = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y + ym.y));
-                cplx od = make_double2(0.5 * (yk.x - ym.x), 0.5 * (yk.y - ym.y));
-                cplx w = a.twB[k];
-                w.y = -w.y;
-                od = cmul(od, w);
-                zin[k] = make_double2(ev.x - od.y, -(ev.y + od.x));
-            }
-            __syncthreads();
-            fft_row<M, cplx>(lds, zin, a.twB, tid);
-            const double inv = 1.0 / (double)M;
-            for (int j = tid; j < M; j += T) {
-                const cplx r = lds[lds_pad<PL>(j)];
-                reinterpret_cast<double2*>(out)[j] = make_double2(r.x * inv, -r.y * inv);
-            }
-        }
+        gauss_portrait_row<M>(a, a.freqs[n], lds, zin, gc, tid, GaussRowOut{a.out + (size_t)n * B});
         __syncthreads();
     }
 }

@@ -97,9 +97,9 @@ __global__ void k_copy_words(unsigned long long* dst, const unsigned long long* 
 static int staged_copy(pp_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st = nullptr);
 __global__ void k_publish_int(int* host_dst, const int* dev_src) { *host_dst = *dev_src; }
 static int publish_int(pp_ctx* c, int* host_dst, const int* dev_src);
-enum KernelFamily { KF_MODEL = 0, KF_XSPEC, KF_PREP, KF_SEED, KF_ACCUM, KF_EVAL, KF_TAYLOR, KF_STEP, KF_FINAL, KF_SYNTH, KF_FPS, KF_SCATMODEL, KF_PCA, KF_COUNT };
+enum KernelFamily { KF_MODEL = 0, KF_XSPEC, KF_PREP, KF_SEED, KF_ACCUM, KF_EVAL, KF_TAYLOR, KF_STEP, KF_FINAL, KF_SYNTH, KF_FPS, KF_SCATMODEL, KF_PCA, KF_GAUSSRES, KF_GAUSSNORM, KF_COUNT };
 static const char* kFamilyNames[KF_COUNT] = {"model_fft", "xspec", "prep", "seed", "accum", "eval", "taylor_solve", "step", "finalize",
-                                            "synth", "fit_phase_shift", "scat_model", "pca_gram"};
+                                            "synth", "fit_phase_shift", "scat_model", "pca_gram", "gauss_resid", "gauss_normal"};
 
 #define PP_NSTAGE 3     // enqueued batches that may be pending at once (staging blocks, work-buffer sets)
 struct pp_ctx {
@@ -168,6 +168,17 @@ struct pp_ctx {
         bool open = false;
         void release() { for (DevBuf* b : {&acc, &totw, &off, &pairs, &harm, &out}) b->release(); open = false; }
     } align;
+    // ppgauss (pp_gauss_fit_begin / pp_gauss_residuals / pp_gauss_normal / pp_gauss_fit_end): what stays on the device
+    // for the whole of a Levenberg-Marquardt fit -- the data portrait as f64, 1 / sigma_n, the channel frequencies --
+    // and the weighted residual rows R[nsets][nchan nbin] of the last pp_gauss_residuals with the reduction's partials
+    struct GaussFit {
+        DevBuf data, isig, freqs, R, part, gram, h;
+        int nchan = 0, nbin = 0;
+        int nsets = 0;              // resident residual rows: sets (0: none)
+        long long nrow = 0;         // ... and samples per set
+        bool open = false;
+        void release() { for (DevBuf* b : {&data, &isig, &freqs, &R, &part, &gram, &h}) b->release(); open = false; nsets = 0; nrow = 0; }
+    } gfit;
     // pinned host staging of the small inputs / the packed outputs of a batch: two sets, so that a
     // deferred batch (pp_fit_enqueue) keeps its own while the next one is being queued
     struct Stage { void* in_host = nullptr; size_t in_cap = 0; void* o_host = nullptr; size_t o_cap = 0;
@@ -397,6 +408,7 @@ extern "C" int pp_destroy(pp_ctx* c) {
     }
     c->pca.release();
     c->align.release();
+    c->gfit.release();
     c->release_buffers();
     if (c->nactive_h) (void)hipHostFree(c->nactive_h);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -2149,3 +2161,4 @@ extern "C" int pp_fit_wait(pp_ctx* c) {
 #include "pp_extra_api.h"
 #include "pp_zap.h"
 #include "pp_pca.h"
+#include "pp_gaussfit.h"

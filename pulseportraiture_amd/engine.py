@@ -143,6 +143,7 @@ class Engine(object):
         self._pending = None    # the submitted batch (_Batch) until wait()
         self._pca_shape = None  # (nchan, nbin) of the centred portrait pca_gram left on the device
         self._align_shape = None  # (npol, nchan_model, nbin) of the resident accumulator (align_begin)
+        self._gauss_shape = None  # (nchan, nbin) of the portrait gauss_fit_begin made resident
         self._lib = _lib.load()
         ctx = C.c_void_p()
         _check(self._lib.pp_create(int(device), C.byref(ctx)), "pp_create")
@@ -872,6 +873,79 @@ class Engine(object):
         _check(self._lib.pp_zap_median(self._ctx, _dp(nz), g.ctypes.data_as(c_uint8_p), nsub, nchan, float(nstd),
                                        zap.ctypes.data_as(c_uint8_p)), "pp_zap_median")
         return zap
+
+    # limits of the Gaussian-component fit's entry points (pp_gaussfit.h)
+    GAUSS_FIT_MAX_SETS = 100
+    GAUSS_FIT_MAX_GAUSS = 16
+
+    def gauss_fit_begin(self, data, freqs, errs):
+        """Make the data portrait data[nchan,nbin] (NumPy or a device tensor, f64 or f32; the good
+        channels only), its frequencies and 1 / errs[nchan] resident for a Gaussian-component fit
+        (fit_gaussian_portrait, pplib.py:1924-2052); gauss_fit_end releases them."""
+        self._gauss_shape = None
+        src, dtype, on_dev, shape, keep = _array_arg(data, "gauss_fit_begin: device data")
+        if len(shape) != 2:
+            raise ValueError("data must be [nchan,nbin]")
+        nchan, nbin = shape
+        freqs, errs = _f64(freqs, (nchan,)), _f64(errs, (nchan,))
+        _check(self._lib.pp_gauss_fit_begin(self._ctx, src, dtype, on_dev, nchan, nbin, _dp(freqs), _dp(errs)),
+               "pp_gauss_fit_begin")
+        self._gauss_shape = (nchan, nbin)
+        del keep
+
+    def gauss_fit_end(self):
+        self._gauss_shape = None
+        _check(self._lib.pp_gauss_fit_end(self._ctx), "pp_gauss_fit_end")
+
+    def gauss_residuals(self, code, nu_ref, dc, tau_rot, alpha, comps, fetch=False):
+        """The weighted residual rows (data - model(set s)) / errs of nsets parameter sets against
+        the resident portrait, left on the device for gauss_normal: dc, tau_rot [rot at nu_ref],
+        alpha [nsets] and comps [nsets,ngauss,6] = loc, m_loc, wid, m_wid, amp, m_amp
+        (fit_gaussian_portrait_function, pplib.py:1230-1242).  fetch=True returns them as
+        [nsets,nchan,nbin]."""
+        comps = np.ascontiguousarray(comps, dtype=np.float64)
+        if comps.ndim != 3 or comps.shape[2] != 6:
+            raise ValueError("comps must be [nsets,ngauss,6]")
+        nsets, ngauss = comps.shape[:2]
+        dc, tau_rot, alpha = (_f64(v, (nsets,)) for v in (dc, tau_rot, alpha))
+        out = None
+        if fetch:
+            if self._gauss_shape is None:
+                raise EngineError("gauss_residuals: no data portrait is resident (gauss_fit_begin first)")
+            out = np.empty((nsets,) + self._gauss_shape)
+        _check(self._lib.pp_gauss_residuals(self._ctx, str(code).encode(), float(nu_ref), nsets, _dp(dc),
+                                            _dp(tau_rot), _dp(alpha), ngauss, _dp(comps), _dp(out)),
+               "pp_gauss_residuals")
+        return out
+
+    def gauss_normal(self, h, rows=None, nsets=None, nrow=None):
+        """(chi2, g, G) of a forward-difference step from the residual rows R[nsets,nrow]: with
+        D_a = (R_{a+1} - R_0) / h[a], chi2 = sum R_0^2, g = D R_0, G = D D^T.  rows None: the rows
+        the last gauss_residuals left on the device (nsets = len(h) + 1 of the resident shape);
+        else rows [nsets,nrow], NumPy or a device f64 tensor.  Summed in a fixed order: the same
+        call returns the same bits."""
+        h = np.zeros(0) if h is None else np.ascontiguousarray(h, dtype=np.float64).reshape(-1)
+        src, on_dev, keep = None, 0, None
+        if rows is not None:
+            src, dtype, on_dev, shape, keep = _array_arg(rows, "gauss_normal: device rows")
+            if dtype != PP_F64 or len(shape) != 2:
+                raise ValueError("rows must be float64 [nsets,nrow]")
+            nsets, nrow = shape
+        else:
+            nsets = len(h) + 1 if nsets is None else int(nsets)
+            if nrow is None:
+                if self._gauss_shape is None:
+                    raise EngineError("gauss_normal: no resident residual rows (gauss_residuals first)")
+                nrow = self._gauss_shape[0] * self._gauss_shape[1]
+        if len(h) != nsets - 1:
+            raise ValueError("h must hold nsets - 1 steps")
+        K = nsets - 1
+        chi2, g, G = np.empty(1), np.empty(K), np.empty((K, K))
+        _check(self._lib.pp_gauss_normal(self._ctx, src, on_dev, int(nsets), int(nrow), _dp(h) if K else None,
+                                         _dp(chi2), _dp(g) if K else None, _dp(G) if K else None),
+               "pp_gauss_normal")
+        del keep
+        return float(chi2[0]), g, G
 
     def synth_portraits(self, dst, freqs, P, inj, sigma, seed, first_subint=0,
                         slot=0, gains=None):

@@ -64,6 +64,32 @@ def read_gmodel(path):
         return parse_gmodel(fh.read())
 
 
+def format_gmodel(name, model_code, nu_ref, model_params, fit_flags, alpha, fit_alpha):
+    """The text of a .gmodel file: the bytes the reference's write_model writes
+    (pplib.py:2852-2863).  model_params = [DC, TAU[s], (loc, m_loc, wid, m_wid, amp,
+    m_amp) * ngauss], fit_flags one 0/1 flag for each."""
+    model_params = np.asarray(model_params, dtype=np.float64)
+    flags = [int(f) for f in fit_flags]
+    lines = ["MODEL   %s\n" % name, "CODE    %s\n" % model_code, "FREQ    %.5f\n" % nu_ref,
+             "DC     % .8f %d\n" % (model_params[0], flags[0]), "TAU    % .8f %d\n" % (model_params[1], flags[1]),
+             "ALPHA  % .3f      %d\n" % (alpha, int(fit_alpha))]
+    for igauss in range((len(model_params) - 2) // 6):
+        comp = model_params[2 + igauss * 6:8 + igauss * 6]
+        fit_comp = flags[2 + igauss * 6:8 + igauss * 6]
+        line = (igauss + 1,) + tuple(v for pair in zip(comp, fit_comp) for v in pair)
+        lines.append("COMP%02d % .8f %d  % .8f %d  % .8f %d  % .8f %d  % .8f %d  % .8f %d\n" % line)
+    return "".join(lines)
+
+
+def write_gmodel(filename, name, model_code, nu_ref, model_params, fit_flags, alpha, fit_alpha, append=False,
+                 quiet=False):
+    """Write a Gaussian-component model file (the reference's write_model, pplib.py:2828-2865)."""
+    with open(filename, "a" if append else "w") as outfile:
+        outfile.write(format_gmodel(name, model_code, nu_ref, model_params, fit_flags, alpha, fit_alpha))
+    if not quiet:
+        print("%s written." % filename)
+
+
 def _evolve(freqs, nu_ref, value, evol, code):
     if code == '0':   # power law, computed in logs like the reference
         return np.exp(np.outer(np.log(freqs) - np.log(nu_ref), evol) +

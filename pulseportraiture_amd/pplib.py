@@ -5,8 +5,10 @@ pplib.py for: module settings (:45-83), RCSTRINGS (:111-119), DataBunch
 (:125-136), fit_phase_shift (:2054-2100), the legacy fit_portrait (:2102-2204),
 and the small host-side helpers the callers use between fits
 (get_bin_centers :671-684, DM_delay :2577-2590, phase_transform :2592-2616,
-guess_fit_freq :2618-2632).  All array arithmetic of the fits themselves runs
-in HIP kernels through pulseportraiture_amd.engine.
+guess_fit_freq :2618-2632), and the two Gaussian-component fits of ppgauss
+(fit_gaussian_profile :1842-1922, fit_gaussian_portrait :1924-2052; their driver
+is pulseportraiture_amd.gaussfit).  All array arithmetic of the fits themselves
+runs in HIP kernels through pulseportraiture_amd.engine.
 """
 import sys
 
@@ -256,3 +258,23 @@ def fit_portrait(data, model, init_params, P, freqs, nu_fit=None, nu_out=None,
                      covariance=r.covariance_matrix[0, 1], chi2=r.chi2,
                      red_chi2=r.red_chi2, snr=r.snr, duration=r.duration,
                      nfeval=r.nfeval, return_code=r.return_code)
+
+
+# ---- Gaussian-component fits (ppgauss) ---------------------------------------------
+def fit_gaussian_profile(data, init_params, errs, fit_flags=None, fit_scattering=False, quiet=True, **kwargs):
+    """Fit Gaussian components to a profile (pplib.py:1842-1922): init_params = [DC, tau [bin],
+    (loc, wid, amp) x ngauss].  Returns fitted_params, fit_errs, residuals, chi2, dof.  The
+    residuals and the normal equations of every iteration are formed on the GPU."""
+    from . import gaussfit
+    return gaussfit.fit_gaussian_profile(data, init_params, errs, fit_flags, fit_scattering, quiet, **kwargs)
+
+
+def fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs, fit_flags, fit_scattering_index,
+                          phases, freqs, nu_ref, join_params=[], P=None, quiet=True, **kwargs):
+    """Fit evolving Gaussian components to a portrait (pplib.py:1924-2052): init_params = [DC,
+    tau [bin], (loc, m_loc, wid, m_wid, amp, m_amp) x ngauss].  Returns fitted_params, fit_errs,
+    scattering_index, scattering_index_err, chi2, dof.  Joined fits (join_params) are not
+    available.  The residuals and the normal equations of every iteration are formed on the GPU."""
+    from . import gaussfit
+    return gaussfit.fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs, fit_flags,
+                                          fit_scattering_index, phases, freqs, nu_ref, join_params, P, quiet, **kwargs)

@@ -751,6 +751,137 @@ static void aux_align_cases() {
     aux_align_refusals(8, 1000);
 }
 
+// ---- the Gaussian-component fit: pp_gauss_fit_begin / pp_gauss_residuals / pp_gauss_normal / pp_gauss_fit_end ------
+// (after aux_align_cases(), so that everything in front keeps its place in the trace)  Every array exactly as long as
+// the entry points read or write: the portrait f64 / f32, host / device; one, two and nine parameter sets with sets that
+// differ in tau; the reduction on the resident rows, on host rows and on device rows
+static void aux_gauss_calls(pp_ctx* c, int B, int C, int f32, int dev, const char* tag) {
+    const size_t esz = f32 ? 4 : 8, nrow = (size_t)C * B;
+    std::vector<unsigned char> port(nrow * esz);
+    for (size_t j = 0; j < nrow; ++j) {
+        const double v = 0.5 + (j % 13) * 0.01;
+        if (f32) ((float*)port.data())[j] = (float)v; else ((double*)port.data())[j] = v;
+    }
+    void* dport = dev ? dev_copy(port.data(), port.size()) : nullptr;
+    std::vector<double> freqs(C), errs(C, 0.05);
+    for (int j = 0; j < C; ++j) freqs[j] = 1100.0 + 800.0 * (j + 0.5) / C;
+    char nm[200];
+    auto name = [&](const char* fn, int nsets) {
+        snprintf(nm, sizeof nm, "%s %s %dx%d %s %s nsets=%d", fn, tag, C, B, f32 ? "f32" : "f64", dev ? "device" : "host", nsets);
+        return nm;
+    };
+    { Outs o; AUX(o, name("pp_gauss_fit_begin", 0), pp_gauss_fit_begin(c, dev ? dport : (const void*)port.data(), f32 ? PP_F32 : PP_F64, dev, C, B, freqs.data(), errs.data())); }
+    const int ng = 2;
+    for (int nsets : {1, 2, 9}) {
+        std::vector<double> dc(nsets, 0.1), tau(nsets, 0.0), alpha(nsets, -4.0), comps((size_t)nsets * ng * 6), h(nsets > 1 ? nsets - 1 : 0, 1e-6);
+        const double comp0[12] = {0.3, 0.0, 0.02, 0.0, 1.0, 0.0, 0.6, 0.0, 0.05, 0.0, 0.5, -1.0};
+        for (int s = 0; s < nsets; ++s) {
+            for (int q = 0; q < 12; ++q) comps[(size_t)s * 12 + q] = comp0[q] + 1e-6 * s;
+            if (s % 2) tau[s] = 1e-3;
+        }
+        { Outs o; double* R = o.d((size_t)nsets * nrow);
+          AUX(o, name("pp_gauss_residuals", nsets), pp_gauss_residuals(c, "010", 1500.0, nsets, dc.data(), tau.data(), alpha.data(), ng, comps.data(), R)); }
+        { Outs o; AUX(o, name("pp_gauss_residuals resident only", nsets), pp_gauss_residuals(c, "000", 1500.0, nsets, dc.data(), tau.data(), alpha.data(), ng, comps.data(), nullptr)); }
+        const int K = nsets - 1;
+        { Outs o; double* chi2 = o.d(1); double* g = K ? o.d(K) : nullptr; double* G = K ? o.d((size_t)K * K) : nullptr;
+          AUX(o, name("pp_gauss_normal resident", nsets), pp_gauss_normal(c, nullptr, 0, nsets, (int)nrow, K ? h.data() : nullptr, chi2, g, G)); }
+        std::vector<double> rows((size_t)nsets * 77, 0.25);
+        { Outs o; double* chi2 = o.d(1); double* g = K ? o.d(K) : nullptr; double* G = K ? o.d((size_t)K * K) : nullptr;
+          AUX(o, name("pp_gauss_normal host rows", nsets), pp_gauss_normal(c, rows.data(), 0, nsets, 77, K ? h.data() : nullptr, chi2, g, G)); }
+        { Outs o; double* chi2 = o.d(1); double* g = K ? o.d(K) : nullptr; double* G = K ? o.d((size_t)K * K) : nullptr;
+          void* drows = dev_copy(rows.data(), rows.size() * 8);
+          AUX(o, name("pp_gauss_normal device rows", nsets), pp_gauss_normal(c, (const double*)drows, 1, nsets, 77, K ? h.data() : nullptr, chi2, g, G));
+          dev_free(drows); }
+    }
+    { Outs o; AUX(o, name("pp_gauss_fit_end", 0), pp_gauss_fit_end(c)); }
+    if (dport) dev_free(dport);
+}
+
+static void aux_gauss_refusals(int C, int B) {
+    mark("case aux context %dx%d for the Gaussian fit's refusals", C, B);
+    pp_ctx* c = make_ctx(C, B);
+    const Outs o;
+    const int big = 101;
+    std::vector<double> port((size_t)C * B, 0.5), freqs(C, 1400.0), errs(C, 0.05), bad(C, 0.05), sc(big, 0.0), comps((size_t)big * 17 * 6, 0.1), h(big, 1e-6);
+    std::vector<double> outv((size_t)big * big + (size_t)2 * C * B);
+    bad[C - 1] = 0.0;
+    const double *f = freqs.data(), *e = errs.data(), *z = sc.data(), *cp = comps.data();
+    double* out = outv.data();
+#define REF(what, call) AUX(o, "refused: " what, call)
+    REF("pp_gauss_residuals before pp_gauss_fit_begin", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr));
+    REF("pp_gauss_normal without resident rows", pp_gauss_normal(c, nullptr, 0, 1, C * B, nullptr, out, nullptr, nullptr));
+    for (int B2 : {B + 1, 6, 8194}) REF("pp_gauss_fit_begin nbin", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B2, f, e));
+    REF("pp_gauss_fit_begin nchan", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, 0, B, f, e));
+    REF("pp_gauss_fit_begin dtype", pp_gauss_fit_begin(c, port.data(), 7, 0, C, B, f, e));
+    REF("pp_gauss_fit_begin errs", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, f, bad.data()));
+    REF("pp_gauss_fit_begin freqs", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, bad.data(), e));
+    REF("pp_gauss_fit_begin null", pp_gauss_fit_begin(nullptr, port.data(), PP_F64, 0, C, B, f, e));
+    REF("pp_gauss_fit_begin null", pp_gauss_fit_begin(c, nullptr, PP_F64, 0, C, B, f, e));
+    REF("pp_gauss_fit_begin null", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, nullptr, e));
+    REF("pp_gauss_fit_begin null", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, f, nullptr));
+    REF("pp_gauss_residuals after a refused begin", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr));
+    { Outs g; AUX(g, "pp_gauss_fit_begin for the refusals", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, f, e)); }
+    REF("pp_gauss_normal before pp_gauss_residuals", pp_gauss_normal(c, nullptr, 0, 1, C * B, nullptr, out, nullptr, nullptr));
+    REF("pp_gauss_residuals ngauss 17", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 17, cp, nullptr));
+    REF("pp_gauss_residuals ngauss 0", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 0, cp, nullptr));
+    REF("pp_gauss_residuals nsets 101", pp_gauss_residuals(c, "000", 1500.0, 101, z, z, z, 1, cp, nullptr));
+    REF("pp_gauss_residuals nsets 0", pp_gauss_residuals(c, "000", 1500.0, 0, z, z, z, 1, cp, nullptr));
+    REF("pp_gauss_residuals code", pp_gauss_residuals(c, "020", 1500.0, 1, z, z, z, 1, cp, nullptr));
+    for (int k = 0; k < 6; ++k) {
+#define NZ(i, p) (k == (i) ? nullptr : (p))
+        REF("pp_gauss_residuals null", pp_gauss_residuals(NZ(0, c), NZ(1, "000"), 1500.0, 1, NZ(2, z), NZ(3, z), NZ(4, z), 1, NZ(5, cp), nullptr));
+#undef NZ
+    }
+    { Outs g; AUX(g, "pp_gauss_residuals for the refusals", pp_gauss_residuals(c, "000", 1500.0, 2, z, z, z, 1, cp, nullptr)); }
+    REF("pp_gauss_normal other nsets than resident", pp_gauss_normal(c, nullptr, 0, 3, C * B, h.data(), out, out, out));
+    REF("pp_gauss_normal other nrow than resident", pp_gauss_normal(c, nullptr, 0, 2, C * B - 1, h.data(), out, out, out));
+    REF("pp_gauss_normal nsets 101", pp_gauss_normal(c, port.data(), 0, 101, 2, h.data(), out, out, out));
+    REF("pp_gauss_normal nsets 0", pp_gauss_normal(c, port.data(), 0, 0, 2, h.data(), out, out, out));
+    REF("pp_gauss_normal nrow", pp_gauss_normal(c, port.data(), 0, 2, 0, h.data(), out, out, out));
+    h[0] = 0.0;
+    REF("pp_gauss_normal zero step", pp_gauss_normal(c, nullptr, 0, 2, C * B, h.data(), out, out, out));
+    h[0] = 1e-6;
+    REF("pp_gauss_normal null", pp_gauss_normal(nullptr, nullptr, 0, 2, C * B, h.data(), out, out, out));
+    REF("pp_gauss_normal null", pp_gauss_normal(c, nullptr, 0, 2, C * B, nullptr, out, out, out));
+    REF("pp_gauss_normal null", pp_gauss_normal(c, nullptr, 0, 2, C * B, h.data(), nullptr, out, out));
+    REF("pp_gauss_normal null", pp_gauss_normal(c, nullptr, 0, 2, C * B, h.data(), out, nullptr, out));
+    REF("pp_gauss_normal null", pp_gauss_normal(c, nullptr, 0, 2, C * B, h.data(), out, out, nullptr));
+    REF("pp_gauss_fit_end null", pp_gauss_fit_end(nullptr));
+    {
+        Spec s; s.C = C; s.B = B;
+        Batch b(s);
+        mark("case aux refused: a batch is pending (Gaussian fit)");
+        ++g_ncase;
+        mark("enqueue rc %d", pp_fit_enqueue(c, &b.in, &b.out));
+        REF("pending pp_gauss_fit_begin", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, f, e));
+        REF("pending pp_gauss_residuals", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr));
+        REF("pending pp_gauss_normal", pp_gauss_normal(c, nullptr, 0, 2, C * B, h.data(), out, out, out));
+        REF("pending pp_gauss_fit_end", pp_gauss_fit_end(c));
+        mark("collect rc %d", pp_fit_collect(c));
+    }
+    { Outs g; AUX(g, "pp_gauss_fit_end", pp_gauss_fit_end(c)); }
+    REF("pp_gauss_residuals after pp_gauss_fit_end", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr));
+#undef REF
+    MUST(pp_destroy(c));
+}
+
+static void aux_gauss_cases() {
+    char tag[64];
+    for (int B : {64, 2048, 1000})
+        for (int profile : {0, 1}) {
+            const int C = 3;
+            mark("case aux context %dx%d Gaussian fit profile=%d", C, B, profile);
+            pp_ctx* c = make_ctx(C, B);
+            MUST(pp_set_option(c, "profile", profile));
+            snprintf(tag, sizeof tag, "profile=%d", profile);
+            for (int f32 : {0, 1})
+                for (int dev : {0, 1}) aux_gauss_calls(c, B, C, f32, dev, tag);
+            MUST(pp_destroy(c));
+        }
+    aux_gauss_refusals(8, 64);
+    aux_gauss_refusals(8, 1000);
+}
+
 int main() {
     g_mark = (void (*)(const char*))dlsym(RTLD_DEFAULT, "hip_stub_mark");
     if (!g_mark) fprintf(stderr, "trace_driver: no hip_stub_mark (LD_PRELOAD libhip_stub.so): cases go unnamed\n");
@@ -761,6 +892,7 @@ int main() {
     option_cases();
     aux_cases();
     aux_align_cases();
+    aux_gauss_cases();
     printf("trace_driver: done\n");
     return 0;
 }
