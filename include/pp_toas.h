@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 9
+#define PP_ABI_VERSION 10
 
 /* status codes */
 #define PP_OK 0
@@ -590,6 +590,13 @@ int pp_gauss_fit_begin(pp_ctx* ctx, const void* data, int dtype, int on_device, 
                        int nbin, const double* freqs, const double* errs);
 int pp_gauss_fit_end(pp_ctx* ctx);
 
+/* A joined fit (gen_gaussian_portrait's join_ichans, pplib.py:923-929): one model fitted to njoin bands at once, every
+ * band with a phase offset and a Delta-DM of its own.  band_of_chan[nchan] (host) names the band of every resident
+ * channel, 0 .. njoin - 1, or -1 for a channel in none; P [s] turns the Delta-DMs into rotations.  Valid only while a
+ * fit is open; the map stays resident until pp_gauss_fit_begin or pp_gauss_fit_end clears it.  Refused: no open fit
+ * (PP_ESTATE); njoin outside 1..16, an index outside [-1, njoin), P not positive and finite (PP_EINVAL). */
+int pp_gauss_fit_join(pp_ctx* ctx, int njoin, const int* band_of_chan, double P);
+
 /* The weighted residual rows of nsets parameter vectors at once (fit_gaussian_portrait_function, pplib.py:1230-1242):
  *   R[s][n][:] = (data_n - model_n(dc[s], tau_rot[s], alpha[s], comps[s])) / errs[n]
  * with model = gen_gaussian_portrait of model code `code` ("000" ... "111") about nu_ref; tau_rot[s] is the scattering
@@ -597,10 +604,15 @@ int pp_gauss_fit_end(pp_ctx* ctx);
  * m_wid, amp, m_amp.  One workgroup per (channel, set); the model rows are formed by the code of
  * pp_gaussian_portrait, operation for operation.  R stays on the device for pp_gauss_normal; out_or_null
  * [nsets][nchan][nbin] (host) receives a copy.  Refused, never truncated: ngauss > 16, nsets > 100, nsets nchan nbin 8
- * bytes above 2 GiB (PP_EINVAL); no resident portrait (PP_ESTATE). */
+ * bytes above 2 GiB (PP_EINVAL); no resident portrait (PP_ESTATE).
+ * join_or_null [nsets][njoin][2] = (phase [rot], Delta-DM [cm^-3 pc]) of every set and band of a joined fit: the model
+ * row of channel n in band j is rotated by phi_n = phase_sj + Dconst DM_sj (nu_n^-2 - nu_ref^-2) / P after it has been
+ * scattered (rotate_data's sign: positive to earlier phase), within the row's one pass through its harmonics; a row
+ * with phi_n == 0 is computed exactly as without a join.  NULL with a resident band map means all zeros; a pointer
+ * without one is refused (PP_ESTATE). */
 int pp_gauss_residuals(pp_ctx* ctx, const char* code, double nu_ref, int nsets, const double* dc,
                        const double* tau_rot, const double* alpha, int ngauss,
-                       const double* comps, double* out_or_null);
+                       const double* comps, double* out_or_null, const double* join_or_null);
 
 /* Normal equations of a forward-difference Levenberg-Marquardt step from nsets residual rows of nrow samples: with
  * D_a = (R_{a+1} - R_0) / h[a], a = 0 .. nsets - 2,

@@ -485,11 +485,14 @@ __global__ __launch_bounds__(256) void k_gauss_rows(GaussArgs a, int B) {
     }
 }
 
-// one row of 2 M bins at channel frequency nu, scattered when the model carries a scattering time (lds, zin, gc:
-// the workgroup's FFT buffers and component scratch; the caller synchronises before they are reused)
+// one row of 2 M bins at channel frequency nu, scattered when the model carries a scattering time and then rotated
+// by phin rotations (a joined fit's band offset, pp_gaussfit.h; positive to earlier phase, as in k_rotate) -- lds, zin,
+// gc: the workgroup's FFT buffers and component scratch; the caller synchronises before they are reused.  The
+// reference scatters, lets irfft drop the imaginary Nyquist part and only then rotates (pplib.py:915-929): the
+// Nyquist term is Re(d_M B_M) cos(2 pi M phin).  A row with phin == 0 goes through the arithmetic it always did.
 template <int M, typename Out>
 __device__ __forceinline__ void gauss_portrait_row(const GaussArgs& a, double nu, cplx* lds, cplx* zin, GaussComp* gc, int tid,
-                                                   const Out& o) {
+                                                   const Out& o, double phin = 0.0) {
     constexpr int T = FftPlan<M>::T, B = 2 * M;
     constexpr int PL = FftPlan<M>::PADLOG;
     gauss_components(a, nu, B, gc, tid, T);
@@ -497,7 +500,8 @@ __device__ __forceinline__ void gauss_portrait_row(const GaussArgs& a, double nu
     for (int j = tid; j < B; j += T) reinterpret_cast<double*>(zin)[j] = gauss_row_value(a, gc, j, B);
     __syncthreads();
     const double taun = (a.tau_ref != 0.0) ? a.tau_ref * pow(nu / a.nu_ref, a.alpha) : 0.0;
-    if (taun == 0.0) {
+    const bool rot = phin != 0.0;       // (the same for every thread of the workgroup)
+    if (taun == 0.0 && !rot) {
         for (int j = tid; j < B; j += T) o.one(j, reinterpret_cast<const double*>(zin)[j]);
     } else {
         // irfft(rfft(row) / (1 + 2 pi i k tau_n)): same packing as k_rotate
@@ -506,15 +510,21 @@ __device__ __forceinline__ void gauss_portrait_row(const GaussArgs& a, double nu
         const cplx z0 = lds[0];
         const double y0 = z0.x + z0.y;
         const double xM = PP_TWO_PI * (double)M * taun;
-        const double yM = (z0.x - z0.y) / (1.0 + xM * xM);     // Re(d_M B_M), d_M real
+        double yM = (z0.x - z0.y) / (1.0 + xM * xM);           // Re(d_M B_M), d_M real
+        if (rot) yM *= unit_phasor((double)M, phin).x;
         for (int k = tid; k < M; k += T) {
             cplx yk, ym;
             if (k == 0) { yk = make_double2(y0, 0.0); ym = make_double2(yM, 0.0); }
             else {
+                // (tau_n == 0: the filter is exactly 1)
                 const double xk = PP_TWO_PI * (double)k * taun, dk = 1.0 / (1.0 + xk * xk);
                 const double xm = PP_TWO_PI * (double)(M - k) * taun, dm = 1.0 / (1.0 + xm * xm);
                 yk = cmul(rfft_harmonic<M>(lds, a.twB, k), make_double2(dk, -xk * dk));
                 ym = cmul(rfft_harmonic<M>(lds, a.twB, M - k), make_double2(dm, -xm * dm));
+                if (rot) {
+                    yk = cmul(yk, unit_phasor((double)k, phin));
+                    ym = cmul(ym, unit_phasor((double)(M - k), phin));
+                }
             }
             ym.y = -ym.y;
             const cplx ev = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y + ym.y));

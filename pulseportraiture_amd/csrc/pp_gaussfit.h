@@ -5,11 +5,17 @@
 // parameter each for a forward-difference Jacobian -- in one launch, the model rows by the very code of
 // k_gauss_rows / k_gauss_portrait (pp_extra.h).  pp_gauss_normal reduces them to chi^2, J^T r and J^T J by a
 // two-stage slab sum in a fixed order, without floating-point atomics: the same call gives the same bits.
+//
+// A joined fit (gen_gaussian_portrait's join_ichans, pplib.py:923-929) fits one model to several bands at once, every
+// band with a phase offset and a Delta-DM of its own: pp_gauss_fit_join makes the channels' band indices resident, and
+// pp_gauss_residuals then rotates the model row of channel n of set s by phi_n = phase_sj + Dconst DM_sj (nu_n^-2 -
+// nu_ref^-2) / P, j the channel's band, inside the row's own pass through its harmonics (gauss_portrait_row).
 
 namespace pp {
 
 constexpr int GFIT_MAX_GAUSS = 16;       // components of a fitted model
 constexpr int GFIT_MAX_SETS = 100;       // parameter sets per pp_gauss_residuals / pp_gauss_normal
+constexpr int GFIT_MAX_JOIN = 16;        // bands of a joined fit
 constexpr int GN_TJ = 32;                // samples of every set staged in LDS per step of the reduction
 constexpr int GN_T = 256;                // threads of a reduction workgroup
 constexpr int GN_ACC = (GFIT_MAX_SETS * GFIT_MAX_SETS + GN_T - 1) / GN_T;     // pair sums held per thread
@@ -25,7 +31,21 @@ struct GaussFitArgs {
     double nu_ref;
     int nchan, ngauss, nsets;
     int code_loc, code_wid, code_amp;
+    const int* band;          // [nchan] band of every channel, -1: in none (null: no joined fit)
+    const double* join;       // [nsets][njoin][2]: phase, Delta-DM of every set and band (null: all zero)
+    double P;                 // the period the Delta-DMs turn into rotations with
+    int njoin;
 };
+
+// the rotation of channel n (frequency nu) in set s of a joined fit, k_rotate's expression with nu_DM = nu_ref;
+// 0 outside joined fits and for a channel in no band
+__device__ __forceinline__ double gauss_fit_rotation(const GaussFitArgs& f, int s, int n, double nu) {
+    if (!f.band || !f.join) return 0.0;
+    const int j = f.band[n];
+    if (j < 0) return 0.0;
+    const double* pj = f.join + ((size_t)s * f.njoin + j) * 2;
+    return pj[0] + PP_DCONST * pj[1] * (1.0 / (nu * nu) - 1.0 / (f.nu_ref * f.nu_ref)) / f.P;
+}
 
 // the template arguments of parameter set s
 __device__ __forceinline__ GaussArgs gauss_fit_set(const GaussFitArgs& f, int s) {
@@ -54,8 +74,10 @@ __global__ __launch_bounds__(FftPlan<M>::T) void k_gauss_resid(GaussFitArgs f) {
     __shared__ GaussComp gc[PP_MAX_GAUSS];
     const int n = blockIdx.x, s = blockIdx.y;
     const GaussArgs a = gauss_fit_set(f, s);
-    gauss_portrait_row<M>(a, f.freqs[n], lds, zin, gc, threadIdx.x,
-                          GaussResidOut{f.data + (size_t)n * B, f.R + ((size_t)s * f.nchan + n) * B, f.isig[n]});
+    const double nu = f.freqs[n];
+    gauss_portrait_row<M>(a, nu, lds, zin, gc, threadIdx.x,
+                          GaussResidOut{f.data + (size_t)n * B, f.R + ((size_t)s * f.nchan + n) * B, f.isig[n]},
+                          gauss_fit_rotation(f, s, n, nu));
 }
 
 // general row lengths: the unscattered model rows of every set into R (k_gauss_rows' row); a scattered set's rows
@@ -71,6 +93,29 @@ __global__ __launch_bounds__(256) void k_gauss_resid_finish(GaussFitArgs f, int 
     double* row = f.R + ((size_t)s * f.nchan + n) * B;
     const GaussResidOut o{f.data + (size_t)n * B, row, f.isig[n]};
     for (int j = threadIdx.x; j < B; j += 256) o.one(j, row[j]);
+}
+
+// general row lengths, a set of a joined fit with a rotation somewhere: k_scatter_harm's filter with the scattering
+// time of the row, then the row's rotation -- h_nk <- h_nk / (1 + 2 pi i k tau_n) e^{2 pi i k phi_n}; DC unchanged,
+// Nyquist Re(d_M B_M) cos(2 pi M phi_n) (gauss_portrait_row).  harm: the harmonics of set s's rows
+__global__ __launch_bounds__(256) void k_gauss_join_harm(cplx* harm, GaussFitArgs f, int s, int M) {
+    const int n = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > M || k == 0) return;
+    const double nu = f.freqs[n];
+    const double tau_ref = f.scal[f.nsets + s];
+    const double taun = (tau_ref != 0.0) ? tau_ref * pow(nu / f.nu_ref, f.scal[2 * f.nsets + s]) : 0.0;
+    const double phin = gauss_fit_rotation(f, s, n, nu);
+    cplx* h = harm + (size_t)n * (M + 1);
+    const double xk = PP_TWO_PI * (double)k * taun, dk = 1.0 / (1.0 + xk * xk);
+    if (k == M) {
+        double yM = h[M].x * dk;
+        if (phin != 0.0) yM *= unit_phasor((double)M, phin).x;
+        h[M] = make_double2(yM, 0.0);
+    } else {
+        cplx y = cmul(h[k], make_double2(dk, -xk * dk));
+        if (phin != 0.0) y = cmul(y, unit_phasor((double)k, phin));
+        h[k] = y;
+    }
 }
 
 template <typename Tin>
@@ -161,6 +206,7 @@ extern "C" int pp_gauss_fit_begin(pp_ctx* c, const void* data, int dtype, int on
     pp_ctx::GaussFit& F = c->gfit;
     F.open = false;             // (a refused begin leaves no fit open either)
     F.nsets = 0;
+    F.njoin = 0;                // (... and no band map)
     if (!nbin_any_ok(nbin)) return nbin_refuse("pp_gauss_fit_begin", nbin);
     if (nchan < 1) return fail(PP_EINVAL, "pp_gauss_fit_begin: bad shape %d x %d", nchan, nbin);
     if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "pp_gauss_fit_begin: dtype %d", dtype);
@@ -202,9 +248,28 @@ extern "C" int pp_gauss_fit_end(pp_ctx* c) {
     return PP_OK;
 }
 
+extern "C" int pp_gauss_fit_join(pp_ctx* c, int njoin, const int* band_of_chan, double P) {
+    if (int busy_ = ctx_busy(c, "pp_gauss_fit_join")) return busy_;
+    if (!c || !band_of_chan) return fail(PP_EINVAL, "pp_gauss_fit_join: null argument");
+    pp_ctx::GaussFit& F = c->gfit;
+    if (!F.open) return fail(PP_ESTATE, "pp_gauss_fit_join: no fit is open (pp_gauss_fit_begin first)");
+    if (njoin < 1 || njoin > GFIT_MAX_JOIN) return fail(PP_EINVAL, "pp_gauss_fit_join: %d bands, 1..%d are joined", njoin, GFIT_MAX_JOIN);
+    for (int n = 0; n < F.nchan; ++n)
+        if (band_of_chan[n] < -1 || band_of_chan[n] >= njoin)
+            return fail(PP_EINVAL, "pp_gauss_fit_join: band_of_chan[%d] = %d is outside [-1, %d)", n, band_of_chan[n], njoin);
+    if (!(P > 0.0) || std::isinf(P)) return fail(PP_EINVAL, "pp_gauss_fit_join: P = %g is no period", P);
+    HIP_TRY(hipSetDevice(c->device));
+    F.njoin = 0;
+    int rc;
+    if ((rc = upload(c, F.band, band_of_chan, (size_t)F.nchan * sizeof(int)))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (the caller's array is free again)
+    F.njoin = njoin; F.P = P;
+    return PP_OK;
+}
+
 extern "C" int pp_gauss_residuals(pp_ctx* c, const char* code, double nu_ref, int nsets, const double* dc,
                                   const double* tau_rot, const double* alpha, int ngauss, const double* comps,
-                                  double* out_or_null) {
+                                  double* out_or_null, const double* join_or_null) {
     if (int busy_ = ctx_busy(c, "pp_gauss_residuals")) return busy_;
     if (!c || !code || !dc || !tau_rot || !alpha || !comps) return fail(PP_EINVAL, "pp_gauss_residuals: null argument");
     pp_ctx::GaussFit& F = c->gfit;
@@ -213,6 +278,9 @@ extern "C" int pp_gauss_residuals(pp_ctx* c, const char* code, double nu_ref, in
     if (nsets < 1 || nsets > GFIT_MAX_SETS) return fail(PP_EINVAL, "pp_gauss_residuals: %d parameter sets, 1..%d per call", nsets, GFIT_MAX_SETS);
     for (int j = 0; j < 3; ++j)
         if (code[j] != '0' && code[j] != '1') return fail(PP_EINVAL, "pp_gauss_residuals: model code '%.3s'", code);
+    if (join_or_null && !F.njoin)
+        return fail(PP_ESTATE, "pp_gauss_residuals: join parameters without a resident band map (pp_gauss_fit_join first)");
+    const int njoin = join_or_null ? F.njoin : 0;
     const int nchan = F.nchan, nbin = F.nbin, M = nbin / 2;
     const size_t nrow = (size_t)nchan * nbin;
     if ((double)nsets * (double)nrow * 8.0 > kGaussFitMaxBytes)
@@ -220,17 +288,21 @@ extern "C" int pp_gauss_residuals(pp_ctx* c, const char* code, double nu_ref, in
     HIP_TRY(hipSetDevice(c->device));
     F.nsets = 0;
     int rc;
-    std::vector<double> scal(3 * (size_t)nsets);
+    // (the join table rides behind the three scalars of every set)
+    const size_t njp = (size_t)nsets * njoin * 2;
+    std::vector<double> scal(3 * (size_t)nsets + njp);
     std::copy(dc, dc + nsets, scal.begin());
     std::copy(tau_rot, tau_rot + nsets, scal.begin() + nsets);
     std::copy(alpha, alpha + nsets, scal.begin() + 2 * (size_t)nsets);
+    if (njp) std::copy(join_or_null, join_or_null + njp, scal.begin() + 3 * (size_t)nsets);
     if ((rc = upload(c, c->x0, scal.data(), scal.size() * 8))) return rc;
     if ((rc = upload(c, c->misc, comps, (size_t)nsets * ngauss * 48))) return rc;
     if ((rc = F.R.reserve((size_t)nsets * nrow * 8))) return rc;
     const cplx* tw = nullptr;
     if ((rc = get_twiddles(c, nbin, &tw))) return rc;
     GaussFitArgs f{F.freqs.as<double>(), F.data.as<double>(), F.isig.as<double>(), c->misc.as<double>(), c->x0.as<double>(), tw,
-                   F.R.as<double>(), nu_ref, nchan, ngauss, nsets, code[0] - '0', code[1] - '0', code[2] - '0'};
+                   F.R.as<double>(), nu_ref, nchan, ngauss, nsets, code[0] - '0', code[1] - '0', code[2] - '0',
+                   njoin ? F.band.as<int>() : nullptr, njoin ? c->x0.as<double>() + 3 * (size_t)nsets : nullptr, F.P, njoin};
     const dim3 grid((unsigned)nchan, (unsigned)nsets);
     {
         Prof pr(c, KF_GAUSSRES);
@@ -239,14 +311,20 @@ extern "C" int pp_gauss_residuals(pp_ctx* c, const char* code, double nu_ref, in
             HIP_TRY(hipGetLastError());
             const size_t H = (size_t)M + 1;
             for (int s = 0; s < nsets; ++s) {
-                if (tau_rot[s] == 0.0) continue;
+                // (a set whose join parameters are all zero is an unjoined one, and goes the way it always did)
+                bool rot = false;
+                for (int q = 0; q < 2 * njoin; ++q) rot = rot || join_or_null[(size_t)s * njoin * 2 + q] != 0.0;
+                if (tau_rot[s] == 0.0 && !rot) continue;
                 // (gauss_generate's route: chirp-z there, 1 / (1 + 2 pi i k tau_n), and back)
                 double* rows = F.R.as<double>() + (size_t)s * nrow;
                 if ((rc = c->seedbuf.reserve((size_t)nchan * H * sizeof(cplx)))) return rc;
                 cplx* harm = c->seedbuf.as<cplx>();
                 if ((rc = harmonics_any(c, rows, PP_F64, 1, nchan, nbin, harm))) return rc;
-                hipLaunchKernelGGL(k_scatter_harm, dim3((unsigned)((H + 255) / 256), nchan), dim3(256), 0, c->stream, harm,
-                                   (const double*)F.freqs.as<double>(), nu_ref, tau_rot[s], alpha[s], M);
+                if (rot)
+                    hipLaunchKernelGGL(k_gauss_join_harm, dim3((unsigned)((H + 255) / 256), nchan), dim3(256), 0, c->stream, harm, f, s, M);
+                else
+                    hipLaunchKernelGGL(k_scatter_harm, dim3((unsigned)((H + 255) / 256), nchan), dim3(256), 0, c->stream, harm,
+                                       (const double*)F.freqs.as<double>(), nu_ref, tau_rot[s], alpha[s], M);
                 HIP_TRY(hipGetLastError());
                 if ((rc = irfft_any(c, nbin, harm, nchan, rows))) return rc;
             }

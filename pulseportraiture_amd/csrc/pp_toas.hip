@@ -172,12 +172,14 @@ struct pp_ctx {
     // for the whole of a Levenberg-Marquardt fit -- the data portrait as f64, 1 / sigma_n, the channel frequencies --
     // and the weighted residual rows R[nsets][nchan nbin] of the last pp_gauss_residuals with the reduction's partials
     struct GaussFit {
-        DevBuf data, isig, freqs, R, part, gram, h;
+        DevBuf data, isig, freqs, R, part, gram, h, band;
         int nchan = 0, nbin = 0;
+        int njoin = 0;              // bands of a joined fit (pp_gauss_fit_join; 0: none), band[nchan] their map
+        double P = 1.0;             // ... and its period
         int nsets = 0;              // resident residual rows: sets (0: none)
         long long nrow = 0;         // ... and samples per set
         bool open = false;
-        void release() { for (DevBuf* b : {&data, &isig, &freqs, &R, &part, &gram, &h}) b->release(); open = false; nsets = 0; nrow = 0; }
+        void release() { for (DevBuf* b : {&data, &isig, &freqs, &R, &part, &gram, &h, &band}) b->release(); open = false; nsets = 0; nrow = 0; njoin = 0; }
     } gfit;
     // pinned host staging of the small inputs / the packed outputs of a batch: two sets, so that a
     // deferred batch (pp_fit_enqueue) keeps its own while the next one is being queued

@@ -144,6 +144,7 @@ class Engine(object):
         self._pca_shape = None  # (nchan, nbin) of the centred portrait pca_gram left on the device
         self._align_shape = None  # (npol, nchan_model, nbin) of the resident accumulator (align_begin)
         self._gauss_shape = None  # (nchan, nbin) of the portrait gauss_fit_begin made resident
+        self._gauss_njoin = 0     # bands of the map gauss_fit_join made resident
         self._lib = _lib.load()
         ctx = C.c_void_p()
         _check(self._lib.pp_create(int(device), C.byref(ctx)), "pp_create")
@@ -883,6 +884,7 @@ class Engine(object):
         channels only), its frequencies and 1 / errs[nchan] resident for a Gaussian-component fit
         (fit_gaussian_portrait, pplib.py:1924-2052); gauss_fit_end releases them."""
         self._gauss_shape = None
+        self._gauss_njoin = 0
         src, dtype, on_dev, shape, keep = _array_arg(data, "gauss_fit_begin: device data")
         if len(shape) != 2:
             raise ValueError("data must be [nchan,nbin]")
@@ -895,26 +897,51 @@ class Engine(object):
 
     def gauss_fit_end(self):
         self._gauss_shape = None
+        self._gauss_njoin = 0
         _check(self._lib.pp_gauss_fit_end(self._ctx), "pp_gauss_fit_end")
 
-    def gauss_residuals(self, code, nu_ref, dc, tau_rot, alpha, comps, fetch=False):
+    GAUSS_FIT_MAX_JOIN = 16
+
+    def gauss_fit_join(self, band_of_chan, P, njoin=None):
+        """Make the open fit a joined one (gen_gaussian_portrait's join_ichans, pplib.py:923-929):
+        band_of_chan[nchan] is the band of every resident channel, 0 .. njoin - 1 (njoin None: its
+        largest entry + 1), or -1 for a channel in no band; P [s] turns the bands' Delta-DMs into
+        rotations.  gauss_residuals then takes the bands' (phase, Delta-DM) as `join`."""
+        if self._gauss_shape is None:
+            raise EngineError("gauss_fit_join: no fit is open (gauss_fit_begin first)")
+        band = np.ascontiguousarray(band_of_chan, dtype=np.intc).reshape(-1)
+        if band.shape != (self._gauss_shape[0],):
+            raise ValueError("band_of_chan must hold one entry per resident channel")
+        njoin = (int(band.max()) + 1 if len(band) else 0) if njoin is None else int(njoin)
+        _check(self._lib.pp_gauss_fit_join(self._ctx, njoin, band.ctypes.data_as(C.POINTER(C.c_int)), float(P)),
+               "pp_gauss_fit_join")
+        self._gauss_njoin = njoin
+
+    def gauss_residuals(self, code, nu_ref, dc, tau_rot, alpha, comps, fetch=False, join=None):
         """The weighted residual rows (data - model(set s)) / errs of nsets parameter sets against
         the resident portrait, left on the device for gauss_normal: dc, tau_rot [rot at nu_ref],
         alpha [nsets] and comps [nsets,ngauss,6] = loc, m_loc, wid, m_wid, amp, m_amp
         (fit_gaussian_portrait_function, pplib.py:1230-1242).  fetch=True returns them as
-        [nsets,nchan,nbin]."""
+        [nsets,nchan,nbin].  join [nsets,njoin,2] = (phase [rot], Delta-DM) of every set and band
+        of a joined fit (gauss_fit_join first); None there means no rotation."""
         comps = np.ascontiguousarray(comps, dtype=np.float64)
         if comps.ndim != 3 or comps.shape[2] != 6:
             raise ValueError("comps must be [nsets,ngauss,6]")
         nsets, ngauss = comps.shape[:2]
         dc, tau_rot, alpha = (_f64(v, (nsets,)) for v in (dc, tau_rot, alpha))
+        if join is not None:
+            join = np.ascontiguousarray(join, dtype=np.float64)
+            if join.ndim != 3 or join.shape[0] != nsets or join.shape[2] != 2:
+                raise ValueError("join must be [nsets,njoin,2]")
+            if self._gauss_njoin and join.shape[1] != self._gauss_njoin:
+                raise ValueError("join holds %d bands, the resident band map %d" % (join.shape[1], self._gauss_njoin))
         out = None
         if fetch:
             if self._gauss_shape is None:
                 raise EngineError("gauss_residuals: no data portrait is resident (gauss_fit_begin first)")
             out = np.empty((nsets,) + self._gauss_shape)
         _check(self._lib.pp_gauss_residuals(self._ctx, str(code).encode(), float(nu_ref), nsets, _dp(dc),
-                                            _dp(tau_rot), _dp(alpha), ngauss, _dp(comps), _dp(out)),
+                                            _dp(tau_rot), _dp(alpha), ngauss, _dp(comps), _dp(out), _dp(join)),
                "pp_gauss_residuals")
         return out
 

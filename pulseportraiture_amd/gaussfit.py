@@ -21,7 +21,10 @@ sum D_a D_b with D_a = (R_{a+1} - R_0) / h_a.  engine_evaluator runs it on the d
 data portrait resident); numpy_evaluator is the host restatement for tests.
 
 A parameter vector is the reference's: [DC, tau [bin], (loc, m_loc, wid, m_wid, amp,
-m_amp) x ngauss, scattering_index].
+m_amp) x ngauss, scattering_index].  A joined fit -- one model for njoin bands, each with a
+phase offset and a Delta-DM of its own (pplib.py:1992-2017) -- carries them in front of the
+scattering index, as the reference does: [..., phase1, DM1, ..., phase_njoin, DM_njoin,
+scattering_index].
 """
 import numpy as np
 
@@ -71,13 +74,14 @@ def external_covariance(cov_internal, p, lo, hi):
     return cov_internal * np.outer(grad, grad)
 
 
-def portrait_bounds(nparam):
+def portrait_bounds(nparam, njoin=0):
     """(lo, hi) of a portrait parameter vector (pplib.py:1964-2020): tau >= 0,
-    0 <= wid <= wid_max, amp >= 0, everything else free."""
+    0 <= wid <= wid_max, amp >= 0, everything else -- the 2 njoin join parameters too -- free."""
     lo, hi = np.full(nparam, -np.inf), np.full(nparam, np.inf)
+    nmodel = nparam - 1 - 2 * njoin
     lo[1] = 0.0
-    lo[4:nparam - 1:6], hi[4:nparam - 1:6] = 0.0, wid_max
-    lo[6:nparam - 1:6] = 0.0
+    lo[4:nmodel:6], hi[4:nmodel:6] = 0.0, wid_max
+    lo[6:nmodel:6] = 0.0
     return lo, hi
 
 
@@ -165,20 +169,25 @@ def levenberg_marquardt(evaluate, x0, vary, lo, hi, nsample, max_iter=100, xtol=
 
 
 # ---- evaluators ---------------------------------------------------------------
-def _model_of(vec, code, nu_ref, nbin):
+def _model_of(vec, code, nu_ref, nbin, njoin=0):
     """The parsed-.gmodel dict of a portrait parameter vector, tau in bins (period = nbin)."""
     vec = np.asarray(vec, dtype=np.float64)
-    return dict(params=vec[:-1], code=code, nu_ref=nu_ref, alpha=vec[-1], ngauss=(len(vec) - 3) // 6)
+    nmodel = len(vec) - 1 - 2 * njoin
+    return dict(params=vec[:nmodel], code=code, nu_ref=nu_ref, alpha=vec[-1], ngauss=(nmodel - 2) // 6)
 
 
-def host_residuals(sets, data, errs, code, freqs, nu_ref):
+def host_residuals(sets, data, errs, code, freqs, nu_ref, join_ichans=None, P=None):
     """(data - gen_gaussian_portrait(set)) / errs of every parameter vector, raveled
-    (fit_gaussian_portrait_function, pplib.py:1230-1242) -> [nsets, nchan nbin]."""
+    (fit_gaussian_portrait_function, pplib.py:1230-1242) -> [nsets, nchan nbin].  join_ichans
+    and the period P: the bands of a joined fit, their parameters in the vectors."""
     data = np.asarray(data, dtype=np.float64)
     nbin = data.shape[-1]
     sig = np.asarray(errs, dtype=np.float64)
     sig = sig[:, None] if sig.ndim == 1 else sig
-    return np.array([((data - gmodel.gaussian_portrait(_model_of(v, code, nu_ref, nbin), freqs, nbin, P=float(nbin)))
+    njoin = 0 if join_ichans is None else len(join_ichans)
+    return np.array([((data - gmodel.gaussian_portrait(_model_of(v, code, nu_ref, nbin, njoin), freqs, nbin, P=float(nbin),
+                                                       join_ichans=join_ichans if njoin else None,
+                                                       join_params=v[len(v) - 1 - 2 * njoin:len(v) - 1], P_join=P))
                       / sig).ravel() for v in np.atleast_2d(sets)])
 
 
@@ -189,30 +198,49 @@ def normal_equations(R, h):
     return float(R[0] @ R[0]), D @ R[0], D @ D.T
 
 
-def numpy_evaluator(data, errs, code, freqs, nu_ref):
+def numpy_evaluator(data, errs, code, freqs, nu_ref, join_ichans=None, P=None):
     """The evaluator on the host (gmodel.gaussian_portrait): what the device does, restated."""
     def evaluate(sets, h):
-        return normal_equations(host_residuals(sets, data, errs, code, freqs, nu_ref), h)
+        return normal_equations(host_residuals(sets, data, errs, code, freqs, nu_ref, join_ichans, P), h)
     return evaluate
 
 
-def _set_args(sets, nbin):
+def _set_args(sets, nbin, njoin=0):
+    """The arguments of Engine.gauss_residuals for parameter vectors: (dc, tau_rot, alpha, comps)
+    and, for a joined fit, the keyword join [nsets,njoin,2]."""
     sets = np.atleast_2d(np.asarray(sets, dtype=np.float64))
-    ng = (sets.shape[1] - 3) // 6
-    return sets[:, 0], sets[:, 1] / float(nbin), sets[:, -1], sets[:, 2:-1].reshape(len(sets), ng, 6)
+    nmodel = sets.shape[1] - 1 - 2 * njoin
+    args = (sets[:, 0], sets[:, 1] / float(nbin), sets[:, -1], sets[:, 2:nmodel].reshape(len(sets), (nmodel - 2) // 6, 6))
+    return args, (dict(join=sets[:, nmodel:-1].reshape(len(sets), njoin, 2)) if njoin else {})
 
 
-def engine_evaluator(eng, code, nu_ref, nbin):
-    """The evaluator on the device, against the portrait Engine.gauss_fit_begin made resident: one
-    gauss_residuals launch for all the sets, one gauss_normal."""
+def engine_evaluator(eng, code, nu_ref, nbin, njoin=0):
+    """The evaluator on the device, against the portrait Engine.gauss_fit_begin made resident (and
+    the band map of Engine.gauss_fit_join, njoin bands): one gauss_residuals launch for all the
+    sets, one gauss_normal."""
     def evaluate(sets, h):
         sets = np.atleast_2d(sets)
         if len(sets) > eng.GAUSS_FIT_MAX_SETS:
             raise ValueError("%d varied parameters: at most %d fit in one launch" %
                              (len(sets) - 1, eng.GAUSS_FIT_MAX_SETS - 1))
-        eng.gauss_residuals(code, nu_ref, *_set_args(sets, nbin))
+        args, kw = _set_args(sets, nbin, njoin)
+        eng.gauss_residuals(code, nu_ref, *args, **kw)
         return eng.gauss_normal(h)
     return evaluate
+
+
+def band_of_channels(join_ichans, nchan):
+    """band_of_chan[nchan] of the reference's join_ichans (one index list per band): the band of
+    every channel, -1 for a channel in none.  No channel may sit in two bands."""
+    band = np.full(nchan, -1, dtype=np.intc)
+    for ij, ichans in enumerate(join_ichans):
+        ichans = np.asarray(ichans, dtype=int).reshape(-1)
+        if len(ichans) and (ichans.min() < 0 or ichans.max() >= nchan):
+            raise ValueError("join_ichans[%d] names a channel outside 0..%d" % (ij, nchan - 1))
+        if np.any(band[ichans] >= 0) or len(np.unique(ichans)) != len(ichans):
+            raise ValueError("join_ichans[%d] names a channel twice" % ij)
+        band[ichans] = ij
+    return band
 
 
 # ---- the reference's two fits --------------------------------------------------
@@ -234,47 +262,72 @@ def _channel_errs(errs, nchan):
 def fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs, fit_flags,
                           fit_scattering_index, phases, freqs, nu_ref, join_params=[], P=None, quiet=True,
                           evaluator=None, engine=None):
-    """fit_gaussian_portrait (pplib.py:1924-2052).  evaluator: a stand-in for the device
-    (numpy_evaluator); engine: the Engine to run on (default the process-wide one)."""
-    if len(join_params):
-        raise NotImplementedError("fit_gaussian_portrait: joined multi-band fits (join_params) are not available")
+    """fit_gaussian_portrait (pplib.py:1924-2052).  join_params = [join_ichans, values, flags]
+    (one index list per band; phase1, DM1, phase2, ... and one flag for each) makes it a joined
+    fit, which needs the period P [s]; fitted_params and fit_errs then end with the join
+    parameters, as the reference's do.  evaluator: a stand-in for the device (numpy_evaluator,
+    for a joined fit one built with join_ichans and P); engine: the Engine to run on (default
+    the process-wide one)."""
     data = np.asarray(data)
     nchan, nbin = data.shape
+    join_ichans, join_x0, join_vary = [], np.zeros(0), np.zeros(0, dtype=bool)
+    if len(join_params):
+        if P is None:
+            raise NotImplementedError("fit_gaussian_portrait: a joined fit (join_params) cannot turn its DMs into "
+                                      "rotations without the period: P is missing")
+        join_ichans = [np.asarray(ic, dtype=int).reshape(-1) for ic in join_params[0]]
+        join_x0 = np.asarray(join_params[1], dtype=np.float64).reshape(-1)
+        join_vary = np.asarray(join_params[2]).reshape(-1) != 0
+        if len(join_x0) != 2 * len(join_ichans) or len(join_vary) != len(join_x0):
+            raise ValueError("join_params must hold a phase and a DM, and a flag for each, for every band")
+        if not (np.isfinite(P) and P > 0.0):
+            raise ValueError("P = %r is no period" % (P,))
+        band = band_of_channels(join_ichans, nchan)
+    njoin = len(join_ichans)
     if len(phases) != nbin:
         raise ValueError("phases must have one entry per bin")
-    x0 = np.append(np.asarray(init_params, dtype=np.float64), float(scattering_index))
-    vary = np.append(np.asarray(fit_flags) != 0, bool(fit_scattering_index))
-    if len(x0) < 9 or (len(x0) - 3) % 6 or len(vary) != len(x0):
+    init_params = np.asarray(init_params, dtype=np.float64)
+    if len(init_params) < 8 or (len(init_params) - 2) % 6 or len(fit_flags) != len(init_params):
         raise ValueError("init_params and fit_flags must hold 2 + 6 ngauss values")
-    lo, hi = portrait_bounds(len(x0))
+    x0 = np.concatenate([init_params, join_x0, [float(scattering_index)]])
+    vary = np.concatenate([np.asarray(fit_flags) != 0, join_vary, [bool(fit_scattering_index)]])
+    lo, hi = portrait_bounds(len(x0), njoin)
     sig = _channel_errs(errs, nchan)
     freqs = np.asarray(freqs, dtype=np.float64)
     eng = None
     if evaluator is None:
         from .engine import default_engine
         eng = engine or default_engine()
-        ng = (len(x0) - 3) // 6
+        ng = (len(init_params) - 2) // 6
         if ng > eng.GAUSS_FIT_MAX_GAUSS:
             raise ValueError("%d components: at most %d are fitted" % (ng, eng.GAUSS_FIT_MAX_GAUSS))
+        if njoin > eng.GAUSS_FIT_MAX_JOIN:
+            raise ValueError("%d bands: at most %d are joined" % (njoin, eng.GAUSS_FIT_MAX_JOIN))
+        if vary.sum() + 1 > eng.GAUSS_FIT_MAX_SETS:
+            raise ValueError("%d varied parameters: at most %d fit in one launch" % (vary.sum(), eng.GAUSS_FIT_MAX_SETS - 1))
         eng.gauss_fit_begin(data, freqs, sig)
-        evaluator = engine_evaluator(eng, str(model_code), float(nu_ref), nbin)
+        evaluator = engine_evaluator(eng, str(model_code), float(nu_ref), nbin, njoin)
     try:
+        if eng is not None and njoin:
+            eng.gauss_fit_join(band, float(P), njoin)
         r = levenberg_marquardt(evaluator, x0, vary, lo, hi, nchan * nbin)
         residuals = None
         if eng is not None:
-            residuals = eng.gauss_residuals(str(model_code), float(nu_ref), *_set_args(r.x, nbin), fetch=True)[0]
+            args, kw = _set_args(r.x, nbin, njoin)
+            residuals = eng.gauss_residuals(str(model_code), float(nu_ref), *args, fetch=True, **kw)[0]
     finally:
         if eng is not None:
             eng.gauss_fit_end()
     if residuals is None:
-        residuals = host_residuals(r.x, data, sig, str(model_code), freqs, float(nu_ref))[0].reshape(nchan, nbin)
+        residuals = host_residuals(r.x, data, sig, str(model_code), freqs, float(nu_ref), join_ichans if njoin else None,
+                                   P)[0].reshape(nchan, nbin)
     residuals = residuals * sig[:, None]
     if not quiet:
         print("---------------------------------------------------------------")
         print("Gaussian Portrait Fit")
         print("---------------------------------------------------------------")
         print("fit status:", r.message)
-        print("Gaussians:", (len(x0) - 3) // 6)
+        print("Gaussians:", (len(init_params) - 2) // 6)
         print("DoF:", r.dof)
         print("reduced chi-sq: %.2g" % (r.chi2 / r.dof))
         print("residuals mean: %.3g" % np.mean(residuals))

@@ -9,7 +9,7 @@ Scattered models (TAU != 0) are convolved in the Fourier domain
 """
 import numpy as np
 
-from .pplib import get_bin_centers, scattering_alpha
+from .pplib import Dconst, get_bin_centers, scattering_alpha
 
 # parameters of the reference's examples/example.gmodel (data, not code):
 # three Gaussians, power-law evolution of loc / wid / amp about 1300 MHz
@@ -120,8 +120,11 @@ def gaussian_components(nbin, loc, wid):
     return np.where(ok, fact * val, 0.0)
 
 
-def gaussian_portrait(model, freqs, nbin, P=None):
-    """nchan x nbin portrait of a parsed .gmodel at the given frequencies."""
+def gaussian_portrait(model, freqs, nbin, P=None, join_ichans=None, join_params=None, P_join=None):
+    """nchan x nbin portrait of a parsed .gmodel at the given frequencies.  join_ichans (one list
+    of channel indices per band) with join_params = [phase1, DM1, phase2, DM2, ...] rotate every
+    band of the finished portrait by its phase and DM about the model's nu_ref with the period
+    P_join [s], as gen_gaussian_portrait does for a joined fit (pplib.py:923-929)."""
     freqs = np.asarray(freqs, dtype=np.float64)
     p, code, nu_ref = model['params'], model['code'], model['nu_ref']
     locs = _evolve(freqs, nu_ref, p[2::6], p[3::6], code[0])
@@ -135,6 +138,17 @@ def gaussian_portrait(model, freqs, nbin, P=None):
         k = np.arange(nbin // 2 + 1)
         scat = 1.0 / (1.0 + 2j * np.pi * np.outer(taus, k))
         port = np.fft.irfft(scat * np.fft.rfft(port, axis=-1), axis=-1)
+    if join_ichans is not None and len(join_ichans):
+        if P_join is None:
+            raise ValueError("need the period P_join to rotate the bands of a joined model")
+        join_params = np.asarray(join_params, dtype=np.float64)
+        k = np.arange(nbin // 2 + 1)
+        for ij, ichans in enumerate(join_ichans):
+            ichans = np.asarray(ichans, dtype=int)
+            # rotate_data (pplib.py:2338-2426): a second transform, after irfft has dropped the imaginary Nyquist part
+            phis = join_params[2 * ij] + Dconst * join_params[2 * ij + 1] / P_join * (freqs[ichans] ** -2.0 - nu_ref ** -2.0)
+            port[ichans] = np.fft.irfft(np.fft.rfft(port[ichans], axis=-1) * np.exp(2.0j * np.pi * np.outer(phis, k)),
+                                        axis=-1)
     return port
 
 

@@ -1,17 +1,19 @@
 """ppgauss: Gaussian-component (.gmodel) templates fitted on the GPU.
 
 `DataPortrait.make_gaussian_model`, `fit_profile`, `model_iteration`, `check_convergence`,
-`write_model` and `write_errfile` reproduce the reference's (ppgauss.py:28-372) for a single
-band: the initial profile fit, the flag logic, the portrait fit, and the loop that measures the
-phase and DM left between data and model, rotates the data by them and fits again.  Every pass
+`write_model` and `write_errfile` reproduce the reference's (ppgauss.py:28-372): the initial
+profile fit, the flag logic, the portrait fit, and the loop that measures the phase and DM left
+between data and model, rotates the data by them and fits again.  A DataPortrait of several
+bands (pplib.DataPortrait's metafile branch) is fitted jointly, the reference's "njoin"
+branches: every band's phase offset and Delta-DM are parameters of the same fit, the data are
+not rotated between iterations, and the join parameters are written beside the model.  Every pass
 over the nchan x nbin portrait runs in HIP kernels through pulseportraiture_amd.engine: the
 residual rows of all forward-difference parameter sets in one launch and their reduction to
 the normal equations (pplib.fit_gaussian_portrait), the model portraits, the rotations and
 the (phase, DM) fit of check_convergence.  The Levenberg-Marquardt driver itself -- a linear
 solve in at most 100 unknowns per iteration -- is the host's (gaussfit.py).
 
-Not available: joined multi-band fits (-M / -j, which the reference marks BETA), the
-interactive component selector and every plot.  Components are either fitted automatically
+Not available: the interactive component selector and every plot.  Components are either fitted automatically
 (auto_gauss, the reference's own branch) or handed in (`init_params`, what the reference's
 window would have returned before its profile fit).
 """
@@ -107,8 +109,6 @@ class DataPortrait(_NormalizingPortrait):
         rotate-and-refit iterations after the initial fit.  residplot is not available."""
         if residplot:
             raise NotImplementedError("make_gaussian_model(residplot=...): plots are not available")
-        if self.njoin:
-            raise NotImplementedError("make_gaussian_model: joined multi-band fits are not available")
         if modelfile:
             if outfile is None:
                 outfile = modelfile
@@ -173,7 +173,8 @@ class DataPortrait(_NormalizingPortrait):
             if not quiet:
                 print("\n...iteration %d..." % (self.itern - self.niter + 1))
             eng = self._engine()
-            for name, fr in (("port", self.freqs[0]), ("portx", self.freqsxs[0])):
+            # (a joined fit carries the bands' offsets as parameters: its data stay where they are)
+            for name, fr in (("port", self.freqs[0]), ("portx", self.freqsxs[0])) if not self.njoin else ():
                 rot = eng.rotate_portraits(np.asarray(getattr(self, name))[None], fr, self.Ps[0], phi=self.phi, DM=self.DM,
                                            nu_DM=self.nu_fit)
                 setattr(self, name, rot[0])
@@ -188,6 +189,14 @@ class DataPortrait(_NormalizingPortrait):
                 self.write_model(outfile=outfile, quiet=quiet)
             if writeerrfile:
                 self.write_errfile(errfile=errfile, quiet=quiet)
+        if self.njoin:
+            # data and model as they are without the bands' offsets (ppgauss.py:206-224)
+            back = -np.asarray(self.join_params, dtype=np.float64)
+            self.port = self._rotate_bands(self.port, self.join_ichans, self.freqs[0], back, self.nu_ref)
+            self.portx = self._rotate_bands(self.portx, self.join_ichanxs, self.freqsxs[0], back, self.nu_ref)
+            self.model = self._rotate_bands(self.model, self.join_ichans, self.freqs[0], back, self.nu_ref)
+            self.model_masked = self.model * self.masks[0, 0]
+            self.modelx = np.compress(self.masks[0, 0].mean(axis=1), self.model, axis=0)
         if not quiet:
             print("")
             print("Residuals mean: %.2e" % (self.portx - self.modelx).mean())
@@ -208,12 +217,23 @@ class DataPortrait(_NormalizingPortrait):
             self.fitted_params, self.fit_errs, self.chi2, self.dof = fgp.fitted_params, fgp.fit_errs, fgp.chi2, fgp.dof
             self.scattering_index, self.scattering_index_err = fgp.scattering_index, fgp.scattering_index_err
             self.fgp = fgp
-            self.model_params = self.fitted_params[:]
-            self.model_param_errs = self.fit_errs[:]
-            mdl = dict(params=np.asarray(self.fitted_params, dtype=np.float64), code=self.model_code, nu_ref=self.nu_ref,
+            if self.njoin:
+                self.model_params = self.fitted_params[:-self.njoin * 2]
+                self.model_param_errs = self.fit_errs[:-self.njoin * 2]
+                self.join_params = self.fitted_params[-self.njoin * 2:]
+                self.join_param_errs = self.fit_errs[-self.njoin * 2:]
+                self.all_join_params[1] = self.join_params
+                self.write_join_parameters()
+            else:
+                self.model_params = self.fitted_params[:]
+                self.model_param_errs = self.fit_errs[:]
+            mdl = dict(params=np.asarray(self.model_params, dtype=np.float64), code=self.model_code, nu_ref=self.nu_ref,
                        alpha=self.scattering_index, ngauss=self.ngauss)
             # (tau is in bins: a period of nbin makes it rotations)
             self.model = eng.gaussian_portrait(mdl, self.freqs[0], self.nbin, P=float(self.nbin))
+            if self.njoin:
+                # every band of the model rotated by its offsets (gen_gaussian_portrait's join_ichans, pplib.py:923-929)
+                self.model = self._rotate_bands(self.model, self.join_ichans, self.freqs[0], self.join_params, self.nu_ref)
             self.model_masked = self.model * self.masks[0, 0]
             self.modelx = np.compress(self.masks[0, 0].mean(axis=1), self.model, axis=0)
             self.duration = time.time() - start
@@ -223,7 +243,13 @@ class DataPortrait(_NormalizingPortrait):
     def check_convergence(self, efac=1.0, quiet=False):
         """Check for convergence (ppgauss.py:278-334): whether the phase and DM in the data, as
         measured by the fitted model, are within the errors (times efac) of the measurements."""
-        portx, modelx = np.copy(self.portx), np.copy(self.modelx)
+        if self.njoin:
+            # measured with the bands' offsets taken out of both
+            back = -np.asarray(self.join_params, dtype=np.float64)
+            portx = self._rotate_bands(self.portx, self.join_ichanxs, self.freqsxs[0], back, self.nu_ref)
+            modelx = self._rotate_bands(self.modelx, self.join_ichanxs, self.freqsxs[0], back, self.nu_ref)
+        else:
+            portx, modelx = np.copy(self.portx), np.copy(self.modelx)
         # Currently, fit_phase_shift returns an unbounded phase
         phase_guess = fit_phase_shift(portx.mean(axis=0), modelx.mean(axis=0)).phase       # unweighted mean
         phase_guess %= 1

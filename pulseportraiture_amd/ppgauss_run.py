@@ -7,7 +7,11 @@ placed component (--autogauss wid), or from components given with --gauss loc,wi
 -- the scripted equivalent of drawing them in the reference's window; the profile fit then refines
 them.  The model is fitted on the device (DataPortrait.make_gaussian_model) and written as a
 .gmodel (default datafile.gmodel) with its error file, which pptoas_run, ppzap_run -m and the
-reference read."""
+reference read.
+
+Several observations from different bands (the reference's -M metafile and -j joinfile) are the
+business of `python -m pulseportraiture_amd.ppgauss_join_run`, which shares this module's options
+and its fit; here they stay refused."""
 import argparse
 import sys
 
@@ -19,15 +23,24 @@ from .ppzap_run import list_datafiles
 MODULE = "pulseportraiture_amd.ppgauss_run"
 
 
-def parser():
+JOIN_MODULE = "pulseportraiture_amd.ppgauss_join_run"
+
+
+def parser(joined=False):
+    """The options of ppgauss_run; joined=True: of ppgauss_join_run, where -M and -j are the input
+    and -d is not."""
     ap = argparse.ArgumentParser(
-        prog="python -m " + MODULE,
-        description="Generate a Gaussian-component model pulse portrait (the reference's ppgauss.py command line).")
+        prog="python -m " + (JOIN_MODULE if joined else MODULE),
+        description="Generate a Gaussian-component model pulse portrait (the reference's ppgauss.py command line)" +
+                    (" from several bands at once, each with a phase offset and a Delta-DM of its own." if joined else "."))
     ap.add_argument("-d", "--datafile", default=None, metavar="archive",
-                    help="One .npz archive (the fields of a DataBunch) from which to generate the Gaussian model, or "
+                    help="Not used here: python -m %s fits one archive." % MODULE if joined else
+                         "One .npz archive (the fields of a DataBunch) from which to generate the Gaussian model, or "
                          "a metafile naming one.")
     ap.add_argument("-M", "--metafile", default=None, metavar="metafile",
-                    help="Not available: fits of several observations from different bands.")
+                    help="List of .npz archive filenames, one per band (for instance every band's ppalign_run average), "
+                         "from which to generate one Gaussian model." if joined else
+                         "Not available here: python -m %s fits several observations from different bands." % JOIN_MODULE)
     ap.add_argument("-I", "--improve", dest="modelfile", default=None, metavar="modelfile",
                     help="Improve/iterate on a model given input data.  The argument to -I is a ppgauss-format "
                          "modelfile.  Use -o and -e to avoid overwriting and --niter to specify a number of iterations.  "
@@ -37,7 +50,9 @@ def parser():
     ap.add_argument("-e", "--errfile", default=None, metavar="errfile",
                     help="Name of parameter error file name. [default=outfile_errs]")
     ap.add_argument("-j", "--joinfile", default=None, metavar="joinfile",
-                    help="Not available: join parameters to align the files of a metafile.")
+                    help="File of join parameters to start the alignment of the metafile's archives from, as written by "
+                         "an earlier run; the fitted ones are appended to it. [default=model_name.join]" if joined else
+                         "Not available here: join parameters to align the files of a metafile (python -m %s)." % JOIN_MODULE)
     ap.add_argument("-m", "--model_name", default=None, metavar="model_name",
                     help="Name given to model. [default=the archive's source name]")
     ap.add_argument("--nu_ref", default=None, metavar="nu_ref",
@@ -100,13 +115,24 @@ def refusal(opts, datafiles=None):
     """The message for a request this command cannot honour, or None."""
     if opts.metafile is not None:
         return ("-M/--metafile: fits of several observations from different bands (BETA in the reference) are not "
-                "available; give one archive with -d")
+                "available here; give one archive with -d, or the metafile to python -m " + JOIN_MODULE)
     if opts.joinfile is not None:
-        return "-j/--joinfile: joined multi-band fits are not available"
-    if opts.figure:
-        return "--figure: plots are not available"
+        return "-j/--joinfile: joined multi-band fits are not available here, but with python -m " + JOIN_MODULE
     if opts.datafile is None:
         return "no archive: give one with -d"
+    msg = fit_refusal(opts)
+    if msg is not None:
+        return msg
+    if datafiles is not None and len(datafiles) != 1:
+        return ("-d names a metafile of %d archives: joining several bands is not available here (python -m %s -M does "
+                "it); give one archive" % (len(datafiles), JOIN_MODULE))
+    return None
+
+
+def fit_refusal(opts):
+    """The message for a request about the fit itself that neither command honours, or None."""
+    if opts.figure:
+        return "--figure: plots are not available"
     if opts.normalize is not None and opts.normalize not in ("mean", "max", "prof", "rms", "abs"):
         return "Unknown normalization choice, '%s'." % opts.normalize
     if opts.modelfile is None and not float(opts.auto_gauss) and not opts.gauss:
@@ -118,17 +144,13 @@ def refusal(opts, datafiles=None):
             parse_gauss(opts.gauss)
         except ValueError as e:
             return str(e)
-    if datafiles is not None and len(datafiles) != 1:
-        return ("-d names a metafile of %d archives: joining several bands is not available; give one archive" %
-                len(datafiles))
     return None
 
 
-def load_portrait(datafile):
-    """The DataPortrait of an .npz archive.  An archive without SNRs gets them measured on the
+def load_bunch(datafile):
+    """The DataBunch of an .npz archive.  An archive without SNRs gets them measured on the
     device (Engine.channel_snrs), one without noise_stds its power-spectrum noise."""
     from .engine import default_engine
-    from .ppgauss import DataPortrait
     from .pptoas import _load
     with np.load(datafile, allow_pickle=True) as z:
         has_snrs = "SNRs" in z.files
@@ -139,7 +161,13 @@ def load_portrait(datafile):
         data.noise_stds = eng.channel_noise(sub.reshape(-1, sub.shape[-1]))[0].reshape(sub.shape[:-1])
     if not has_snrs:
         data.SNRs = eng.channel_snrs(sub.reshape(-1, sub.shape[-1])).reshape(sub.shape[:-1])
-    return DataPortrait(data, quiet=True)
+    return data
+
+
+def load_portrait(datafile):
+    """The DataPortrait of an .npz archive (load_bunch)."""
+    from .ppgauss import DataPortrait
+    return DataPortrait(load_bunch(datafile), quiet=True)
 
 
 def main(argv=None):
@@ -152,17 +180,21 @@ def main(argv=None):
     if msg is not None:
         print("ppgauss_run: " + msg, file=sys.stderr)
         return 2
-    datafile = datafiles[0]
+    return fit_and_write(load_portrait(datafiles[0]), opts, opts.datafile + ".gmodel")
+
+
+def fit_and_write(dp, opts, default_outfile):
+    """Fit the model the options ask for to the DataPortrait dp and write it (with its error
+    file) to -o, or without -o and -I to default_outfile."""
     nu_ref = np.float64(opts.nu_ref) if opts.nu_ref else None
     bw_ref = np.float64(opts.bw_ref) if opts.bw_ref else None
     tau = np.float64(opts.tau)
     fixscat = opts.fixscat and opts.fixalpha            # (--fitalpha implies --fitscat)
-    dp = load_portrait(datafile)
     if opts.normalize is not None:
         dp.normalize_portrait(opts.normalize)
     outfile = opts.outfile
     if outfile is None and opts.modelfile is None:
-        outfile = opts.datafile + ".gmodel"
+        outfile = default_outfile
     if opts.modelfile is not None:
         dp.make_gaussian_model(modelfile=opts.modelfile, fixalpha=opts.fixalpha, model_code=opts.model_code,
                                niter=int(opts.niter), writemodel=True, outfile=outfile, writeerrfile=True,

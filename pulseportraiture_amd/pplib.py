@@ -55,18 +55,26 @@ class DataPortrait(object):
     """Holder of the data a model is fit to, built FROM ARRAYS.
 
     The reference's DataPortrait (pplib.py:138-650) loads PSRCHIVE archives and
-    carries joining / normalising / plotting methods; only its single-archive
-    field layout (pplib.py:306-327) is part of the fit path and is what this
-    class provides: every key of the load_data DataBunch as an attribute, plus
-    port, portx, freqsxs, noise_stdsxs, SNRsxs.  `data` is a DataBunch with the
-    load_data fields (see pulseportraiture_amd.pptoas.data_from_arrays)."""
+    carries joining / normalising / plotting methods.  `data` is a DataBunch with the
+    load_data fields (see pulseportraiture_amd.pptoas.data_from_arrays) and gives the
+    reference's single-archive field layout (pplib.py:306-327): every key of the
+    DataBunch as an attribute, plus port, portx, freqsxs, noise_stdsxs, SNRsxs.  A list
+    of DataBunches, one per band, stands for the reference's metafile (pplib.py:163-299):
+    the bands' first subints are concatenated and sorted by frequency, and the "join"
+    attributes say which channels came from which band and how the bands are to be
+    aligned -- a phase offset and a Delta-DM each, fitted along with a Gaussian model
+    (ppgauss).  joinfile: a file like the one write_join_parameters writes, with
+    parameters to start from; metafile=name: what such a list is called (datafile)."""
 
     def __init__(self, data=None, joinfile=None, quiet=False, **kwargs):
-        if data is None or not isinstance(data, dict):
-            raise RuntimeError("DataPortrait needs a DataBunch built from arrays "
-                               "(PSRFITS loading requires PSRCHIVE)")
         self.init_params = []
         self.joinfile = joinfile
+        if isinstance(data, (list, tuple)) and len(data) and all(isinstance(d, dict) for d in data):
+            self._init_joined(list(data), kwargs.get("metafile"))
+            return
+        if data is None or not isinstance(data, dict):
+            raise RuntimeError("DataPortrait needs a DataBunch built from arrays, or a list of them "
+                               "(PSRFITS loading requires PSRCHIVE)")
         self.njoin = 0
         self.join_params = []
         self.join_ichans = []
@@ -86,6 +94,149 @@ class DataPortrait(object):
         self.SNRsxs = np.asarray(self.SNRs)[0, 0, self.ok_ichans[0]]
         if data.get("flux_prof") is not None:
             self.flux_profx = data["flux_prof"][self.ok_ichans[0]]
+
+    def _init_joined(self, bunches, metafile=None):
+        """The metafile branch (pplib.py:163-299): band 1 is the phase reference (phase fixed
+        at 0, Delta-DM free), every other band starts at minus its profile's shift against band
+        1's and has both free.  metafile: the name the list of bands goes by (datafile)."""
+        self.datafiles = [str(d.get("filename", "arrays")) for d in bunches]
+        self.metafile = self.datafile = metafile or "metafile"
+        self.njoin = len(bunches)
+        join_params, join_fit_flags = [], []
+        self.join_nchans, self.join_nchanxs = [0], [0]
+        self.join_ichans, self.join_ichanxs = [], []
+        self.nchan = self.nchanx = 0
+        self.lofreq, self.hifreq = np.inf, 0.0
+        Ps, refprof = 0.0, None
+        cat = dict((k, []) for k in ("freqs", "freqsxs", "masks", "port", "portx", "flux_prof", "flux_profx", "noise_stds",
+                                     "noise_stdsxs", "SNRs", "SNRsxs", "weights", "weightsxs"))
+        for ifile, data in enumerate(bunches):
+            name = self.datafiles[ifile]
+            if data["nsub"] != 1:
+                raise ValueError("%s: a band of a joined fit holds one subint, not %d" % (name, data["nsub"]))
+            if data.get("noise_stds") is None:
+                raise ValueError("%s: a band of a joined fit needs its noise_stds" % name)
+            ok = np.asarray(data["ok_ichans"][0], dtype=int)
+            sub = np.asarray(data["subints"], dtype=np.float64)[0, 0]
+            mask = np.asarray(data["masks"], dtype=np.float64)[0, 0] * np.ones(sub.shape)
+            weights = np.asarray(data["weights"], dtype=np.float64)[0]
+            prof = data.get("prof")
+            if prof is None:
+                prof = np.average(sub[ok], axis=0, weights=weights[ok])
+            if ifile == 0:
+                self.nbin, self.phases = data["nbin"], data["phases"]
+                refprof = prof
+                self.source = data.get("source") or "noname"
+                join_params += [0.0, 0.0]
+                join_fit_flags += [0, 1]
+            else:
+                if data["nbin"] != self.nbin:
+                    raise ValueError("%s: %d bins, %s has %d" % (name, data["nbin"], self.datafiles[0], self.nbin))
+                join_params += [-fit_phase_shift(prof, refprof, Ns=self.nbin).phase, 0.0]
+                join_fit_flags += [1, 1]
+            self.nchan += data["nchan"]
+            self.nchanx += len(ok)
+            self.join_nchans.append(self.nchan)
+            self.join_nchanxs.append(self.nchanx)
+            freqs = np.asarray(data["freqs"], dtype=np.float64)
+            Ps += np.mean(data["Ps"])
+            self.lofreq = min(self.lofreq, freqs.min() - abs(data["bw"]) / (2 * data["nchan"]))
+            self.hifreq = max(self.hifreq, freqs.max() + abs(data["bw"]) / (2 * data["nchan"]))
+            flux_prof = data.get("flux_prof")
+            if flux_prof is None or not len(flux_prof):
+                flux_prof = sub.mean(axis=1)
+            noise, snrs = np.asarray(data["noise_stds"])[0, 0], np.asarray(data["SNRs"])[0, 0]
+            # (port is the masked data, portx the good channels' own)
+            for key, keyx, full, good in (("freqs", "freqsxs", freqs[0], freqs[0]), ("port", "portx", sub * mask, sub),
+                                          ("flux_prof", "flux_profx", flux_prof, flux_prof),
+                                          ("noise_stds", "noise_stdsxs", noise, noise), ("SNRs", "SNRsxs", snrs, snrs),
+                                          ("weights", "weightsxs", weights, weights)):
+                cat[key].extend(np.asarray(full))
+                cat[keyx].extend(np.asarray(good)[ok])
+            cat["masks"].extend(mask)
+        self.Ps = [Ps / len(bunches)]
+        self.bw = self.hifreq - self.lofreq
+        freqs, freqsxs = np.array(cat["freqs"]), np.array(cat["freqsxs"])
+        self.nu0 = freqs.mean()
+        self.isort, self.isortx = np.argsort(freqs), np.argsort(freqsxs)
+        for ijoin in range(self.njoin):
+            self.join_ichans.append(np.where((self.isort >= self.join_nchans[ijoin]) &
+                                             (self.isort < self.join_nchans[ijoin + 1]))[0])
+            self.join_ichanxs.append(np.where((self.isortx >= self.join_nchanxs[ijoin]) &
+                                              (self.isortx < self.join_nchanxs[ijoin + 1]))[0])
+        self.masks = np.array([[np.array(cat["masks"])[self.isort]]])
+        self.port = np.array(cat["port"])[self.isort]
+        self.portx = np.array(cat["portx"])[self.isortx]
+        self.flux_prof = np.array(cat["flux_prof"])[self.isort]
+        self.flux_profx = np.array(cat["flux_profx"])[self.isortx]
+        self.noise_stds = np.array([[np.array(cat["noise_stds"])[self.isort]]])
+        self.noise_stdsxs = np.array(cat["noise_stdsxs"])[self.isortx]
+        self.SNRs = np.array([[np.array(cat["SNRs"])[self.isort]]])
+        self.SNRsxs = np.array(cat["SNRsxs"])[self.isortx]
+        self.weights = np.array([np.array(cat["weights"])[self.isort]])
+        self.weightsxs = np.array([np.array(cat["weightsxs"])[self.isortx]])
+        self.freqs = np.array([freqs[self.isort]])
+        self.freqsxs = [freqsxs[self.isortx]]
+        self.ok_ichans = [np.flatnonzero(self.weights[0] > 0)]
+        self.join_params = np.array(join_params, dtype=np.float64)
+        self.join_fit_flags = np.array(join_fit_flags)
+        if self.joinfile:
+            self.read_joinfile()
+        self.all_join_params = [self.join_ichanxs, self.join_params, self.join_fit_flags]
+        if len(bunches) == 1:
+            self.data = bunches[0]
+
+    def read_joinfile(self):
+        """Take the phases and Delta-DMs of the joinfile's last njoin lines (pplib.py:282-297):
+        archive name, phase [, its error], DM [, its error] -- the four-column layout
+        write_join_parameters writes, and the older one without errors."""
+        with open(self.joinfile, "r") as fh:
+            lines = [line.split() for line in fh.readlines()[-len(self.datafiles):]]
+        try:
+            for tok in lines:
+                ijoin = self.datafiles.index(tok[0])
+                phi = np.double(tok[1])
+                DM = float(tok[3]) if len(tok) > 3 else float(tok[2])
+                self.join_params[ijoin * 2] = phi
+                self.join_params[ijoin * 2 + 1] = DM
+        except (ValueError, IndexError):
+            print("Bad join file.")
+
+    def apply_joinfile(self, nu_ref, undo=False):
+        """Rotate every band of port and portx by minus its join parameters about nu_ref [MHz], the
+        fitted model's reference frequency (pplib.py:329-348); undo=True rotates the other way."""
+        sign = (-1) ** int(undo)
+        params = -np.asarray(self.join_params, dtype=np.float64) * sign
+        self.port = self._rotate_bands(self.port, self.join_ichans, self.freqs[0], params, nu_ref)
+        self.portx = self._rotate_bands(self.portx, self.join_ichanxs, self.freqsxs[0], params, nu_ref)
+
+    def _rotate_bands(self, port, ichans, freqs, params, nu_ref):
+        """port with the channels ichans[i] of every band i rotated by (params[2 i], params[2 i + 1])
+        = (phase, DM) about nu_ref, on the device."""
+        eng = getattr(self, "engine", None) or default_engine()
+        out = np.array(port, dtype=np.float64)
+        for ii, ic in enumerate(ichans):
+            if len(ic):
+                out[ic] = eng.rotate_portraits(out[ic][None], np.asarray(freqs)[ic], self.Ps[0], phi=params[2 * ii],
+                                               DM=params[2 * ii + 1], nu_DM=nu_ref)[0]
+        return out
+
+    def format_join_parameters(self):
+        """The text write_join_parameters appends (pplib.py:509-520)."""
+        text = "# archive name" + " " * 32 + "-phase offset & err [rot]" + " " * 2 + "-delta-DM & err [cm**-3 pc]\n"
+        for ifile, datafile in enumerate(self.datafiles):
+            text += (datafile + " " * abs(45 - len(datafile)) + "% .10f" % self.join_params[ifile * 2] + " " +
+                     "%.10f" % self.join_param_errs[::2][ifile] + "  " + "% .6f" % self.join_params[ifile * 2 + 1] + " " +
+                     "%.6f" % self.join_param_errs[1::2][ifile] + "\n")
+        return text
+
+    def write_join_parameters(self):
+        """Append the join parameters to the joinfile, or to <model_name>.join (pplib.py:486-521).
+        NB, as in the reference: they are the "opposite" of how they rotate the data with e.g.
+        rotate_data (use a negative), and the Delta-DMs are offsets, not Doppler corrected."""
+        joinfile = self.joinfile if self.joinfile is not None else self.model_name + ".join"
+        with open(joinfile, "a") as jf:
+            jf.write(self.format_join_parameters())
 
 
 # ---- small host helpers ------------------------------------------------------
@@ -273,8 +424,8 @@ def fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs,
                           phases, freqs, nu_ref, join_params=[], P=None, quiet=True, **kwargs):
     """Fit evolving Gaussian components to a portrait (pplib.py:1924-2052): init_params = [DC,
     tau [bin], (loc, m_loc, wid, m_wid, amp, m_amp) x ngauss].  Returns fitted_params, fit_errs,
-    scattering_index, scattering_index_err, chi2, dof.  Joined fits (join_params) are not
-    available.  The residuals and the normal equations of every iteration are formed on the GPU."""
+    scattering_index, scattering_index_err, chi2, dof.  join_params = [join_ichans, values, flags] with the period
+    P makes it a joined multi-band fit (pplib.py:1992-2017).  The residuals and the normal equations of every iteration are formed on the GPU."""
     from . import gaussfit
     return gaussfit.fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs, fit_flags,
                                           fit_scattering_index, phases, freqs, nu_ref, join_params, P, quiet, **kwargs)

@@ -754,7 +754,8 @@ static void aux_align_cases() {
 // ---- the Gaussian-component fit: pp_gauss_fit_begin / pp_gauss_residuals / pp_gauss_normal / pp_gauss_fit_end ------
 // (after aux_align_cases(), so that everything in front keeps its place in the trace)  Every array exactly as long as
 // the entry points read or write: the portrait f64 / f32, host / device; one, two and nine parameter sets with sets that
-// differ in tau; the reduction on the resident rows, on host rows and on device rows
+// differ in tau; the reduction on the resident rows, on host rows and on device rows; then the same fit joined
+// (pp_gauss_fit_join: a band map of exactly C entries with a channel in no band, a join table of exactly nsets x njoin x 2)
 static void aux_gauss_calls(pp_ctx* c, int B, int C, int f32, int dev, const char* tag) {
     const size_t esz = f32 ? 4 : 8, nrow = (size_t)C * B;
     std::vector<unsigned char> port(nrow * esz);
@@ -780,8 +781,8 @@ static void aux_gauss_calls(pp_ctx* c, int B, int C, int f32, int dev, const cha
             if (s % 2) tau[s] = 1e-3;
         }
         { Outs o; double* R = o.d((size_t)nsets * nrow);
-          AUX(o, name("pp_gauss_residuals", nsets), pp_gauss_residuals(c, "010", 1500.0, nsets, dc.data(), tau.data(), alpha.data(), ng, comps.data(), R)); }
-        { Outs o; AUX(o, name("pp_gauss_residuals resident only", nsets), pp_gauss_residuals(c, "000", 1500.0, nsets, dc.data(), tau.data(), alpha.data(), ng, comps.data(), nullptr)); }
+          AUX(o, name("pp_gauss_residuals", nsets), pp_gauss_residuals(c, "010", 1500.0, nsets, dc.data(), tau.data(), alpha.data(), ng, comps.data(), R, nullptr)); }
+        { Outs o; AUX(o, name("pp_gauss_residuals resident only", nsets), pp_gauss_residuals(c, "000", 1500.0, nsets, dc.data(), tau.data(), alpha.data(), ng, comps.data(), nullptr, nullptr)); }
         const int K = nsets - 1;
         { Outs o; double* chi2 = o.d(1); double* g = K ? o.d(K) : nullptr; double* G = K ? o.d((size_t)K * K) : nullptr;
           AUX(o, name("pp_gauss_normal resident", nsets), pp_gauss_normal(c, nullptr, 0, nsets, (int)nrow, K ? h.data() : nullptr, chi2, g, G)); }
@@ -792,6 +793,25 @@ static void aux_gauss_calls(pp_ctx* c, int B, int C, int f32, int dev, const cha
           void* drows = dev_copy(rows.data(), rows.size() * 8);
           AUX(o, name("pp_gauss_normal device rows", nsets), pp_gauss_normal(c, (const double*)drows, 1, nsets, 77, K ? h.data() : nullptr, chi2, g, G));
           dev_free(drows); }
+    }
+    {
+        const int njoin = 2;
+        std::vector<int> band(C);
+        for (int j = 0; j < C; ++j) band[j] = (j == C - 1) ? -1 : j % njoin;
+        { Outs o; AUX(o, name("pp_gauss_fit_join", 0), pp_gauss_fit_join(c, njoin, band.data(), 0.003)); }
+        for (int nsets : {1, 5}) {
+            std::vector<double> dc(nsets, 0.1), tau(nsets, 0.0), alpha(nsets, -4.0), comps((size_t)nsets * ng * 6, 0.0), join((size_t)nsets * njoin * 2, 0.0);
+            const double comp0[12] = {0.3, 0.0, 0.02, 0.0, 1.0, 0.0, 0.6, 0.0, 0.05, 0.0, 0.5, -1.0};
+            for (int s = 0; s < nsets; ++s) {
+                for (int q = 0; q < 12; ++q) comps[(size_t)s * 12 + q] = comp0[q];
+                if (s % 2) tau[s] = 1e-3;
+                // (set 0 and set 1 carry no rotation -- with and without tau --, the later ones a phase or a DM)
+                if (s >= 2) join[((size_t)s * njoin + s % njoin) * 2 + s / 2 % 2] = (s / 2 % 2) ? 1e-3 : 0.1;
+            }
+            { Outs o; double* R = o.d((size_t)nsets * nrow);
+              AUX(o, name("pp_gauss_residuals joined", nsets), pp_gauss_residuals(c, "010", 1500.0, nsets, dc.data(), tau.data(), alpha.data(), ng, comps.data(), R, join.data())); }
+            { Outs o; AUX(o, name("pp_gauss_residuals joined, no table", nsets), pp_gauss_residuals(c, "000", 1500.0, nsets, dc.data(), tau.data(), alpha.data(), ng, comps.data(), nullptr, nullptr)); }
+        }
     }
     { Outs o; AUX(o, name("pp_gauss_fit_end", 0), pp_gauss_fit_end(c)); }
     if (dport) dev_free(dport);
@@ -808,7 +828,7 @@ static void aux_gauss_refusals(int C, int B) {
     const double *f = freqs.data(), *e = errs.data(), *z = sc.data(), *cp = comps.data();
     double* out = outv.data();
 #define REF(what, call) AUX(o, "refused: " what, call)
-    REF("pp_gauss_residuals before pp_gauss_fit_begin", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr));
+    REF("pp_gauss_residuals before pp_gauss_fit_begin", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr, nullptr));
     REF("pp_gauss_normal without resident rows", pp_gauss_normal(c, nullptr, 0, 1, C * B, nullptr, out, nullptr, nullptr));
     for (int B2 : {B + 1, 6, 8194}) REF("pp_gauss_fit_begin nbin", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B2, f, e));
     REF("pp_gauss_fit_begin nchan", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, 0, B, f, e));
@@ -819,20 +839,42 @@ static void aux_gauss_refusals(int C, int B) {
     REF("pp_gauss_fit_begin null", pp_gauss_fit_begin(c, nullptr, PP_F64, 0, C, B, f, e));
     REF("pp_gauss_fit_begin null", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, nullptr, e));
     REF("pp_gauss_fit_begin null", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, f, nullptr));
-    REF("pp_gauss_residuals after a refused begin", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr));
+    REF("pp_gauss_residuals after a refused begin", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr, nullptr));
     { Outs g; AUX(g, "pp_gauss_fit_begin for the refusals", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, f, e)); }
     REF("pp_gauss_normal before pp_gauss_residuals", pp_gauss_normal(c, nullptr, 0, 1, C * B, nullptr, out, nullptr, nullptr));
-    REF("pp_gauss_residuals ngauss 17", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 17, cp, nullptr));
-    REF("pp_gauss_residuals ngauss 0", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 0, cp, nullptr));
-    REF("pp_gauss_residuals nsets 101", pp_gauss_residuals(c, "000", 1500.0, 101, z, z, z, 1, cp, nullptr));
-    REF("pp_gauss_residuals nsets 0", pp_gauss_residuals(c, "000", 1500.0, 0, z, z, z, 1, cp, nullptr));
-    REF("pp_gauss_residuals code", pp_gauss_residuals(c, "020", 1500.0, 1, z, z, z, 1, cp, nullptr));
+    REF("pp_gauss_residuals ngauss 17", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 17, cp, nullptr, nullptr));
+    REF("pp_gauss_residuals ngauss 0", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 0, cp, nullptr, nullptr));
+    REF("pp_gauss_residuals nsets 101", pp_gauss_residuals(c, "000", 1500.0, 101, z, z, z, 1, cp, nullptr, nullptr));
+    REF("pp_gauss_residuals nsets 0", pp_gauss_residuals(c, "000", 1500.0, 0, z, z, z, 1, cp, nullptr, nullptr));
+    REF("pp_gauss_residuals code", pp_gauss_residuals(c, "020", 1500.0, 1, z, z, z, 1, cp, nullptr, nullptr));
     for (int k = 0; k < 6; ++k) {
 #define NZ(i, p) (k == (i) ? nullptr : (p))
-        REF("pp_gauss_residuals null", pp_gauss_residuals(NZ(0, c), NZ(1, "000"), 1500.0, 1, NZ(2, z), NZ(3, z), NZ(4, z), 1, NZ(5, cp), nullptr));
+        REF("pp_gauss_residuals null", pp_gauss_residuals(NZ(0, c), NZ(1, "000"), 1500.0, 1, NZ(2, z), NZ(3, z), NZ(4, z), 1, NZ(5, cp), nullptr, nullptr));
 #undef NZ
     }
-    { Outs g; AUX(g, "pp_gauss_residuals for the refusals", pp_gauss_residuals(c, "000", 1500.0, 2, z, z, z, 1, cp, nullptr)); }
+    { Outs g; AUX(g, "pp_gauss_residuals for the refusals", pp_gauss_residuals(c, "000", 1500.0, 2, z, z, z, 1, cp, nullptr, nullptr)); }
+    {
+        std::vector<int> band(C, 0), low(C, 0), high(C, 0);
+        low[0] = -2; high[C - 1] = 2;
+        REF("pp_gauss_residuals join table without a band map", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr, z));
+        REF("pp_gauss_fit_join njoin 0", pp_gauss_fit_join(c, 0, band.data(), 0.003));
+        REF("pp_gauss_fit_join njoin 17", pp_gauss_fit_join(c, 17, band.data(), 0.003));
+        REF("pp_gauss_fit_join index below -1", pp_gauss_fit_join(c, 2, low.data(), 0.003));
+        REF("pp_gauss_fit_join index njoin", pp_gauss_fit_join(c, 2, high.data(), 0.003));
+        REF("pp_gauss_fit_join P 0", pp_gauss_fit_join(c, 2, band.data(), 0.0));
+        REF("pp_gauss_fit_join P negative", pp_gauss_fit_join(c, 2, band.data(), -1.0));
+        REF("pp_gauss_fit_join P infinite", pp_gauss_fit_join(c, 2, band.data(), HUGE_VAL));
+        REF("pp_gauss_fit_join P nan", pp_gauss_fit_join(c, 2, band.data(), NAN));
+        REF("pp_gauss_fit_join null", pp_gauss_fit_join(nullptr, 2, band.data(), 0.003));
+        REF("pp_gauss_fit_join null", pp_gauss_fit_join(c, 2, nullptr, 0.003));
+        REF("pp_gauss_residuals join table after refused joins", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr, z));
+        { Outs g; AUX(g, "pp_gauss_fit_join for the refusals", pp_gauss_fit_join(c, 2, band.data(), 0.003)); }
+        { Outs g; AUX(g, "pp_gauss_residuals joined for the refusals", pp_gauss_residuals(c, "000", 1500.0, 2, z, z, z, 1, cp, nullptr, z)); }
+        // (a second begin clears the band map)
+        { Outs g; AUX(g, "pp_gauss_fit_begin again", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, f, e)); }
+        REF("pp_gauss_residuals join table after a second begin", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr, z));
+        { Outs g; AUX(g, "pp_gauss_residuals for the refusals, again", pp_gauss_residuals(c, "000", 1500.0, 2, z, z, z, 1, cp, nullptr, nullptr)); }
+    }
     REF("pp_gauss_normal other nsets than resident", pp_gauss_normal(c, nullptr, 0, 3, C * B, h.data(), out, out, out));
     REF("pp_gauss_normal other nrow than resident", pp_gauss_normal(c, nullptr, 0, 2, C * B - 1, h.data(), out, out, out));
     REF("pp_gauss_normal nsets 101", pp_gauss_normal(c, port.data(), 0, 101, 2, h.data(), out, out, out));
@@ -854,13 +896,15 @@ static void aux_gauss_refusals(int C, int B) {
         ++g_ncase;
         mark("enqueue rc %d", pp_fit_enqueue(c, &b.in, &b.out));
         REF("pending pp_gauss_fit_begin", pp_gauss_fit_begin(c, port.data(), PP_F64, 0, C, B, f, e));
-        REF("pending pp_gauss_residuals", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr));
+        REF("pending pp_gauss_residuals", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr, nullptr));
+        { std::vector<int> band(C, 0); REF("pending pp_gauss_fit_join", pp_gauss_fit_join(c, 1, band.data(), 0.003)); }
         REF("pending pp_gauss_normal", pp_gauss_normal(c, nullptr, 0, 2, C * B, h.data(), out, out, out));
         REF("pending pp_gauss_fit_end", pp_gauss_fit_end(c));
         mark("collect rc %d", pp_fit_collect(c));
     }
     { Outs g; AUX(g, "pp_gauss_fit_end", pp_gauss_fit_end(c)); }
-    REF("pp_gauss_residuals after pp_gauss_fit_end", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr));
+    REF("pp_gauss_residuals after pp_gauss_fit_end", pp_gauss_residuals(c, "000", 1500.0, 1, z, z, z, 1, cp, nullptr, nullptr));
+    { std::vector<int> band(C, 0); REF("pp_gauss_fit_join after pp_gauss_fit_end", pp_gauss_fit_join(c, 1, band.data(), 0.003)); }
 #undef REF
     MUST(pp_destroy(c));
 }
