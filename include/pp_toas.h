@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 10
+#define PP_ABI_VERSION 11
 
 /* status codes */
 #define PP_OK 0
@@ -435,6 +435,33 @@ int pp_fit_phase_shift_batch(pp_ctx* ctx, const double* data,
                              const double* model, const double* noise,
                              int nprof, int nbin, double lo, double hi, int Ns,
                              double* out7);
+
+/* Narrowband scattering fit of nprof (data, model) profile pairs: a phase and a scattering time each,
+ * fitted jointly.  The reference planned it as fit_phase_shift_scat (pptoas.py:988-991) and never wrote
+ * it; it is fit_portrait_full (pptoaslib.py:928-1096) on a one-channel portrait with fit_flags
+ * [1,0,0,1,0].  With B_k = 1 / (1 + 2 pi i k tau), tau in rotations, over the harmonics k = 1 .. nbin/2:
+ *   C = Re sum_k d_k conj(m_k) conj(B_k) e^{2 pi i k phi} / sigma_F^2,  S = sum_k |B_k|^2 |m_k|^2 / sigma_F^2,
+ *   f = -C^2 / S is minimised over (phi, tau) or, with log10_tau != 0, over (phi, log10 tau).
+ * guess [nprof][2]: phi (NaN = an Ns-point grid over [lo, hi] at the guessed tau, fit_phase_shift against
+ * the scattered model) and tau or log10 tau.  noise [nprof] or null: time-domain sigma, NaN / < 0 =
+ * measured from the top quarter of the power spectrum.  Any even nbin from 8 to 4096.
+ * out [nprof][PP_NBS_NOUT]:
+ *   0 phi [rot, in [-0.5, 0.5)]   1 phi_err     2 tau or log10 tau [rot]   3 its error
+ *   4 scale                       5 scale_err   6 snr = scale sqrt(S)      7 red_chi2 = (Sd + f) / (nbin - 3)
+ *   8 covariance of (phi, tau)    9 nfeval      10 return_code (PP_RC_*)
+ * The errors and the covariance come from the Hessian that includes the amplitude
+ * (fit_portrait_full_function_2deriv_with_scales).  return_code: PP_RC_STALL converged to rounding;
+ * PP_RC_MAXITER 64 evaluations spent; PP_RC_NAN for NaN / Inf input, an all-zero data or model row, a
+ * Hessian that is not positive definite, a linear tau more than 3 tau_err below zero, or a fitted S/N
+ * below 6 (no detection: the tail would be fitted to the noise) -- phi, tau, their errors and the
+ * covariance are NaN then.  PP_RC_NAN also marks a numerically singular (phi, tau) Hessian, which is what
+ * unscattered data give (at tau = 0 a scattering time and a delay are the same thing to second order in
+ * chi^2): the covariance is NaN, the error of tau is +infinity, and phi, phi_err, scale_err are the values
+ * at that fixed tau -- fit_phase_shift's.  A pair's outputs depend on that pair alone, bit for bit. */
+#define PP_NBS_NOUT 11
+int pp_fit_phase_tau_batch(pp_ctx* ctx, const double* data, const double* model, const double* noise,
+                           const double* guess, int nprof, int nbin, double lo, double hi, int Ns,
+                           int log10_tau, double* out);
 
 /* The reference's initial phase guess of nsub subints (pptoas.py:421-457), data side
  * fused into one read of the portraits:

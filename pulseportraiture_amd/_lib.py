@@ -16,7 +16,7 @@ PP_OK, PP_EINVAL, PP_EHIP, PP_ENOMEM, PP_ESTATE, PP_ENOTSUP = 0, -1, -2, -3, -4,
 PP_F64, PP_F32 = 0, 1
 PP_MAX_SLOTS = 64
 PP_RECORD_WIDTH = 18
-ABI_VERSION = 10
+ABI_VERSION = 11
 PP_METHOD_TRUST_NCG, PP_METHOD_NEWTON = 0, 1
 PP_NORMS = {None: 0, 'mean': 1, 'max': 2, 'prof': 3, 'rms': 4, 'abs': 5}
 
@@ -84,6 +84,9 @@ SYMBOLS = {
                                            c_double_p, C.c_int, C.c_int,
                                            C.c_double, C.c_double, C.c_int,
                                            c_double_p]),
+    "pp_fit_phase_tau_batch": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                         C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                         c_double_p]),
     "pp_reference_phase_seed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, c_double_p, C.c_int64, c_double_p, c_double_p,
                                           C.c_double, C.c_double, c_double_p, c_double_p, C.c_double,

@@ -508,18 +508,43 @@ class Engine(object):
         d = _f64(np.atleast_2d(data))
         nprof, nbin = d.shape
         m = _f64(np.atleast_2d(model), (nprof, nbin))
-        if noise is None:
-            nz = np.full(nprof, np.nan)
-        elif isinstance(noise, np.ndarray) and noise.dtype.kind == "f":
-            nz = _f64(noise, (nprof,))
-        else:
-            nz = _f64([np.nan if v is None else v for v in
-                       np.broadcast_to(np.asarray(noise, dtype=object), (nprof,))])
+        nz = self._noise_arg(noise, nprof)
         out = np.empty((nprof, 7))
         with self._fps_finish(finish):
             _check(self._lib.pp_fit_phase_shift_batch(
                 self._ctx, _dp(d), _dp(m), _dp(nz), nprof, nbin, float(bounds[0]),
                 float(bounds[1]), int(Ns), _dp(out)), "pp_fit_phase_shift_batch")
+        return out
+
+    @staticmethod
+    def _noise_arg(noise, nprof):
+        if noise is None:
+            return np.full(nprof, np.nan)
+        if isinstance(noise, np.ndarray) and noise.dtype.kind == "f":
+            return _f64(noise, (nprof,))
+        return _f64([np.nan if v is None else v for v in
+                     np.broadcast_to(np.asarray(noise, dtype=object), (nprof,))])
+
+    def fit_phase_tau_batch(self, data, model, noise=None, tau_guess=0.0, phi_guess=None,
+                            log10_tau=True, bounds=(-0.5, 0.5), Ns=100):
+        """Narrowband scattering fit of nprof profile pairs: a phase and a scattering time
+        [rot] each, fitted jointly -- fit_portrait_full on a one-channel portrait with
+        fit_flags [1,0,0,1,0].  tau_guess (scalar or [nprof]) is tau, or log10 tau under
+        log10_tau; phi_guess None / NaN asks for an Ns-point grid over `bounds` at the
+        guessed tau.  Returns [nprof, 11]: phi, phi_err, tau (or log10 tau), tau_err,
+        scale, scale_err, snr, red_chi2, cov_phi_tau, nfeval, return_code
+        (include/pp_toas.h, pp_fit_phase_tau_batch)."""
+        d = _f64(np.atleast_2d(data))
+        nprof, nbin = d.shape
+        m = _f64(np.atleast_2d(model), (nprof, nbin))
+        nz = self._noise_arg(noise, nprof)
+        guess = np.empty((nprof, 2))
+        guess[:, 0] = np.nan if phi_guess is None else np.asarray(phi_guess, dtype=np.float64)
+        guess[:, 1] = np.asarray(tau_guess, dtype=np.float64)
+        out = np.empty((nprof, 11))
+        _check(self._lib.pp_fit_phase_tau_batch(
+            self._ctx, _dp(d), _dp(m), _dp(nz), _dp(guess), nprof, nbin, float(bounds[0]),
+            float(bounds[1]), int(Ns), int(bool(log10_tau)), _dp(out)), "pp_fit_phase_tau_batch")
         return out
 
     def reference_phase_seed(self, ports, freqs, P, weights, model_profs, phi=0.0, DM=0.0, GM=0.0,
@@ -992,7 +1017,7 @@ class Engine(object):
             C.c_int64(int(first_subint))), "pp_synth_portraits")
 
     def kernel_times(self, reset=False):
-        n = 16
+        n = 32
         names = (C.c_char_p * n)()
         secs = (C.c_double * n)()
         cnt = (C.c_int64 * n)()

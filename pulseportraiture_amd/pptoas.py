@@ -375,6 +375,41 @@ _ARCHIVE_ARRAYS = ("nu_fits", "nu_refs", "phis", "phi_errs", "TOAs", "TOA_errs",
 # the result lists that take the field of _archive_meta of the same name, wideband and narrowband alike, and
 # those get_narrowband_TOAs fills with one [nsub, nchan] array per archive
 _ARCHIVE_META = ("obs", "doppler_fs", "ok_isubs", "epochs", "MJDs", "Ps")
+def narrowband_tau_guesses(freqs, P, nbin, log10_tau, scat_guess=None, model_tau=None, model_nu_ref=None,
+                           alpha=None):
+    """The scattering-time guess of every channel of a narrowband scattering fit [rot, or
+    log10 rot under log10_tau] (pptoas.py:938-962, with the channel's own frequency where
+    the reference's sketch names an undefined nu_fit_tau): scat_guess = (tau [s], its
+    frequency [MHz], alpha) scaled to the channel, else the Gaussian model's tau [s] scaled
+    from its reference frequency with `alpha`, else 0.  Under log10_tau a guess of 0
+    becomes 1 / nbin."""
+    freqs = np.asarray(freqs, dtype=np.float64)
+    if scat_guess is not None:
+        tau_s, nu_ref, alpha = scat_guess
+        tau = (tau_s / P) * (freqs / nu_ref) ** alpha
+    elif model_tau is not None:
+        tau = (model_tau / P) * (freqs / model_nu_ref) ** (scattering_alpha if alpha is None else alpha)
+    else:
+        tau = np.zeros(len(freqs))
+    if log10_tau:
+        tau = np.log10(np.where(tau == 0.0, 1.0 / nbin, tau))
+    return tau
+
+
+def narrowband_scat_flags(tau, tau_err, phi_tau_cov, P, doppler_factor, log10_tau):
+    """The TOA flags of a narrowband scattering fit (pptoas.py:1046-1060; the Doppler
+    factor in both branches -- the reference leaves it undefined in the linear one):
+    the scattering time in microseconds in the barycentric frame and its error."""
+    df = doppler_factor
+    if log10_tau:
+        flags = {'scat_time': 10 ** tau * P / df * 1e6, 'log10_scat_time': tau + np.log10(P / df),
+                 'log10_scat_time_err': tau_err}
+    else:
+        flags = {'scat_time': tau * P / df * 1e6, 'scat_time_err': tau_err * P / df * 1e6}
+    flags['phi_tau_cov'] = phi_tau_cov
+    return flags
+
+
 _NARROWBAND_ARRAYS = ("phis", "phi_errs", "TOAs", "TOA_errs", "taus", "tau_errs", "scales", "scale_errs",
                       "channel_snrs", "profile_fluxes", "profile_flux_errs", "covariances", "channel_red_chi2s",
                       "nfevals", "rcs")
@@ -1048,20 +1083,32 @@ class GetTOAs(object):
         """One TOA per channel (pptoas.py:744-1120): every good channel of every
         good subint is fitted for a phase shift and an amplitude against its
         template profile -- fit_phase_shift, bounds [-0.5, 0.5], Ns = 100 -- in one
-        device batch per archive.  As in the reference, scattering fits are not
-        implemented here; print_phase / print_flux cannot work in the reference's
-        narrowband path (it reads fields fit_phase_shift does not return) and raise."""
+        device batch per archive.  print_phase / print_flux cannot work in the
+        reference's narrowband path (it reads fields fit_phase_shift does not return)
+        and raise.
+
+        fit_scat=True fits a scattering time per channel as well -- the fit the
+        reference sketches here (the commented-out fit_phase_shift_scat call,
+        pptoas.py:988-991) and does not implement: fit_portrait_full on a one-channel
+        portrait, Engine.fit_phase_tau_batch.  The template is the Gaussian model
+        without its scattering (a spline model as it is); the guess of every channel is
+        narrowband_tau_guesses', at the channel's own frequency (the sketch names a
+        nu_fit_tau it never defines); the phase guess is fit_phase_shift's grid against
+        the template scattered by that guess.  It fills taus, tau_errs, covariances
+        (2 x 2), nfevals and rcs and adds the flags of narrowband_scat_flags.  A channel
+        whose fit fails (return code 3: not detected, singular) is reported on stderr
+        and gets no TOA."""
         if quiet is None:
             quiet = self.quiet
-        if fit_scat or tscrunch or show_plot or print_phase or print_flux:
-            raise NotImplementedError("fit_scat / tscrunch / show_plot / print_phase / print_flux "
+        if tscrunch or show_plot or print_phase or print_flux:
+            raise NotImplementedError("tscrunch / show_plot / print_phase / print_flux "
                                       "are not available for narrowband TOAs")
         if not quiet:
             print("You are using an experimental functionality of pptoas!")
-        self.nfit = 1
-        self.fit_phi, self.fit_tau = True, False
-        self.fit_flags = [1, 0]
-        self.log10_tau = False
+        self.nfit = 2 if fit_scat else 1
+        self.fit_phi, self.fit_tau = True, bool(fit_scat)
+        self.fit_flags = [1, int(self.fit_tau)]
+        self.log10_tau = log10_tau = bool(log10_tau and fit_scat)
         self.scat_guess = scat_guess
         self.tscrunch = tscrunch
         self.add_instrumental_response = add_instrumental_response
@@ -1093,15 +1140,21 @@ class GetTOAs(object):
             covariances = np.zeros([nsub, nchan, self.nfit, self.nfit])
             nfevals, rcs = z2("int"), z2("int")
             # ---- gather every (subint, good channel) profile pair ----
-            profs, mprofs, noises, where = [], [], [], []
+            profs, mprofs, noises, where, tau_guesses = [], [], [], [], []
             sub_all = np.asarray(d.subints)
             if d.dmc:
                 sub_all = sub_all.copy()
                 sub_all[ok_isubs, 0] = _dededisperse(eng, _take_subints(sub_all, ok_isubs), d, ok_isubs)
             for isub in ok_isubs:
                 ich = np.asarray(d.ok_ichans[isub], dtype=int)
-                model = np.asarray(self._model_for(d.freqs[isub], nbin, d.Ps[isub]))
+                model = np.asarray(self._model_for(d.freqs[isub], nbin, d.Ps[isub], unscattered=fit_scat))
                 modelx = model[ich]
+                if fit_scat:
+                    gm = self._gmodel()
+                    tau_guesses.append(narrowband_tau_guesses(
+                        d.freqs[isub, ich], d.Ps[isub], nbin, log10_tau, self.scat_guess,
+                        None if gm is None else self.gparams[1], None if gm is None else self.model_nu_ref,
+                        None if gm is None else self.alpha))
                 if use_ird:
                     from .pptoaslib import instrumental_response_port_FT
                     resp = instrumental_response_port_FT(nbin, d.freqs[isub, ich], self.ird['DM'],
@@ -1115,14 +1168,33 @@ class GetTOAs(object):
                               else np.asarray(d.noise_stds)[isub, 0, ich])
                 where += [(isub, ichan) for ichan in ich]
             t0 = time.time()
-            out = eng.fit_phase_shift_batch(np.concatenate(profs), np.concatenate(mprofs),
-                                            np.concatenate(noises).astype(np.float64),
-                                            bounds=(-0.5, 0.5), Ns=100, finish='simplex')
+            if fit_scat:
+                scat = eng.fit_phase_tau_batch(np.concatenate(profs), np.concatenate(mprofs),
+                                               np.concatenate(noises).astype(np.float64),
+                                               tau_guess=np.concatenate(tau_guesses), log10_tau=log10_tau,
+                                               bounds=(-0.5, 0.5), Ns=100)
+                out = scat[:, [0, 1, 4, 5, 6, 7]]
+            else:
+                out = eng.fit_phase_shift_batch(np.concatenate(profs), np.concatenate(mprofs),
+                                                np.concatenate(noises).astype(np.float64),
+                                                bounds=(-0.5, 0.5), Ns=100, finish='simplex')
             fit_duration = time.time() - t0
             # ---- TOA bookkeeping (pptoas.py:994-1088) ----
-            for (isub, ichan), r in zip(where, out):
+            for j, ((isub, ichan), r) in enumerate(zip(where, out)):
                 phase, phase_err, scale, scale_err, snr, red_chi2 = r[:6]
                 P = d.Ps[isub]
+                scat_flags = {}
+                if fit_scat:
+                    from .pptoaslib import phase_tau_covariance
+                    nfevals[isub, ichan], rcs[isub, ichan] = int(scat[j, 9]), int(scat[j, 10])
+                    if rcs[isub, ichan] not in (0, 1, 2, 4):
+                        sys.stderr.write("Fit 'failed' with return code %d: NaN, singular or undetected -- %s "
+                                         "subint %d channel %d\n" % (rcs[isub, ichan], fname, isub, ichan))
+                        continue
+                    taus[isub, ichan], tau_errs[isub, ichan] = scat[j, 2], scat[j, 3]
+                    covariances[isub, ichan] = phase_tau_covariance(scat[j])
+                    scat_flags = narrowband_scat_flags(scat[j, 2], scat[j, 3], scat[j, 8], P,
+                                                       d.doppler_factors[isub], log10_tau)
                 TOA_MJD = d.epochs[isub] + MJD(0, (phase * P + d.backend_delay) / (3600 * 24.))
                 TOA_err = phase_err * P * 1e6
                 phis[isub, ichan], phi_errs[isub, ichan] = phase, phase_err
@@ -1130,11 +1202,12 @@ class GetTOAs(object):
                 scales[isub, ichan], scale_errs[isub, ichan] = scale, scale_err
                 channel_snrs[isub, ichan] = snr
                 channel_red_chi2s[isub] = red_chi2     # (the reference assigns the whole row)
-                toa_flags = {'be': d.backend, 'fe': d.frontend, 'f': d.frontend + "_" + d.backend,
-                             'nbin': int(nbin), 'bw': abs(d.bw) / nchan, 'subint': int(isub),
-                             'chan': int(ichan), 'tobs': d.subtimes[isub],
-                             'tmplt': self.modelfile if isinstance(self.modelfile, str)
-                             else self.model_name, 'snr': snr, 'gof': red_chi2}
+                toa_flags = dict(scat_flags)
+                toa_flags.update({'be': d.backend, 'fe': d.frontend, 'f': d.frontend + "_" + d.backend,
+                                  'nbin': int(nbin), 'bw': abs(d.bw) / nchan, 'subint': int(isub),
+                                  'chan': int(ichan), 'tobs': d.subtimes[isub],
+                                  'tmplt': self.modelfile if isinstance(self.modelfile, str)
+                                  else self.model_name, 'snr': snr, 'gof': red_chi2})
                 if print_parangle:
                     toa_flags['par_angle'] = d.parallactic_angles[isub]
                 for k, v in addtnl_toa_flags.items():

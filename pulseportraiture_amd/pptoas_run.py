@@ -152,8 +152,9 @@ def parser():
     ap.add_argument("--fix_DM", dest="fit_DM", action="store_false", help="Do not fit for DM.")
     ap.add_argument("--fit_dt4", dest="fit_GM", action="store_true",
                     help="Fit for delays that scale as nu**-4 (GM).")
-    ap.add_argument("--fit_scat", action="store_true", help="Fit for scattering timescale and index.")
-    ap.add_argument("--no_logscat", dest="log10_tau", action="store_false",
+    ap.add_argument("--fit_scat", action="store_true",
+                    help="Fit for scattering timescale and index (with --narrowband: a timescale per channel).")
+    ap.add_argument("--no_logscat", "--no_log10_tau", dest="log10_tau", action="store_false",
                     help="Fit the scattering timescale itself, not its log10.")
     ap.add_argument("--scat_guess", default=None, metavar="tau,freq,alpha",
                     help="Initial scattering timescale [s], its reference frequency [MHz] and index.")
@@ -223,6 +224,13 @@ def get_toas_kwargs(opts):
                 quiet=opts.quiet, seed=opts.seed)
 
 
+def get_narrowband_kwargs(opts):
+    """get_narrowband_TOAs keyword arguments of the parsed options."""
+    kw = get_toas_kwargs(opts)
+    return {k: kw[k] for k in ("fit_scat", "log10_tau", "scat_guess", "print_phase", "print_flux",
+                               "print_parangle", "addtnl_toa_flags", "method", "quiet")}
+
+
 def one_DM_toas(gt):
     """TOA_list with every TOA's DM replaced by its archive's mean DM offset plus DM0, its
     error by that offset's error, and the flag DM_mean (TOA_list holds the archives' TOAs in
@@ -261,13 +269,10 @@ def run(opts):
         dist.init_process_group(backend, timeout=timedelta(seconds=PG_TIMEOUT_S))
     try:
         gt = GetTOAs(opts.datafiles, opts.modelfile, quiet=opts.quiet)
-        kw = get_toas_kwargs(opts)
         if opts.narrowband:
-            kw = {k: kw[k] for k in ("fit_scat", "log10_tau", "scat_guess", "print_phase", "print_flux",
-                                     "print_parangle", "addtnl_toa_flags", "method", "quiet")}
-            gt.get_narrowband_TOAs(**kw)
+            gt.get_narrowband_TOAs(**get_narrowband_kwargs(opts))
         else:
-            gt.get_TOAs(distributed=world > 1, **kw)
+            gt.get_TOAs(distributed=world > 1, **get_toas_kwargs(opts))
         if rank == 0:
             toas = one_DM_toas(gt) if (opts.one_DM and not opts.narrowband) else gt.TOA_list
             write_TOAs(toas, inf_is_zero=True, SNR_cutoff=opts.snr_cutoff, outfile=opts.outfile, append=True)

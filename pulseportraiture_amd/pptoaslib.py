@@ -152,6 +152,48 @@ def _fit_with_bounds(eng, data, freqs, P, init_params, errs, nu_fits, nu_outs, f
     return res
 
 
+def phase_tau_covariance(row):
+    """The 2 x 2 covariance of (phi, tau) from a row of Engine.fit_phase_tau_batch."""
+    return np.array([[row[1] ** 2, row[8]], [row[8], row[3] ** 2]])
+
+
+def fit_phase_shift_scat(prof, model_prof, param_guesses, P, err, fit_flags=[1, 1], bounds=None,
+                         log10_tau=True, option=0, sub_id=None, method='trust-ncg', is_toa=True,
+                         quiet=True):
+    """Fit a phase and a scattering time between a data and a model profile: the
+    narrowband fit the reference planned under this name (the commented-out call at
+    pptoas.py:988-991) and never wrote.  It is fit_portrait_full on a one-channel
+    portrait with fit_flags [1,0,0,1,0], done by Engine.fit_phase_tau_batch.
+
+    param_guesses = [phi, tau] with tau in [rot] or [log10 rot]; a phi of None / NaN is
+    found by fit_phase_shift's grid against the model scattered by the guess.  err is
+    the time-domain noise (None: measured).  P, bounds, option, method and is_toa are
+    accepted for the planned signature: the answer is in rotations, one frequency has
+    no reference frequency to choose, and every method is run to the optimum.
+    fit_flags = [1, 0] delegates to fit_phase_shift."""
+    import time
+    if not fit_flags[0]:
+        raise ValueError("fit_phase_shift_scat: the phase is always fitted")
+    if not fit_flags[1]:
+        from .pplib import fit_phase_shift
+        return fit_phase_shift(prof, model_prof, err, bounds=[-0.5, 0.5] if bounds is None else bounds)
+    prof = np.asarray(prof, dtype=np.float64)
+    start = time.time()
+    phi_guess, tau_guess = param_guesses
+    row = default_engine().fit_phase_tau_batch(
+        prof[None], np.asarray(model_prof, dtype=np.float64)[None], noise=None if err is None else [err],
+        tau_guess=tau_guess, phi_guess=None if phi_guess is None else [phi_guess], log10_tau=log10_tau)[0]
+    duration = time.time() - start
+    r = DataBunch(phase=row[0], phi=row[0], phi_err=row[1], tau=row[2], tau_err=row[3], scale=row[4],
+                  scale_err=row[5], snr=row[6], chi2=row[7] * (len(prof) - 3), red_chi2=row[7],
+                  covariance_matrix=phase_tau_covariance(row), nfeval=int(row[9]),
+                  return_code=int(row[10]), duration=duration)
+    if r.return_code not in (0, 1, 2, 4):
+        sys.stderr.write("Fit 'failed' with return code %d: NaN, singular or undetected%s\n"
+                         % (r.return_code, "" if sub_id is None else " -- %s" % sub_id))
+    return r
+
+
 def rotate_portrait_full(port, phi, DM, GM, freqs, nu_DM=np.inf, nu_GM=np.inf, P=None):
     """Rotate / dedisperse a portrait by (phi, DM, GM) on the GPU
     (pptoaslib.py:52-81)."""

@@ -387,6 +387,15 @@ static void aux_host_calls(pp_ctx* c, int ns, int C, int B, const char* tag) {
         Outs o; double* out7 = o.d((size_t)nprof * 7);
         AUX(o, name(with_noise ? "pp_fit_phase_shift_batch noise" : "pp_fit_phase_shift_batch"),
             pp_fit_phase_shift_batch(c, data.data(), model.data(), with_noise ? noise.data() : nullptr, nprof, B, -0.5, 0.5, 20, out7));
+        // the narrowband scattering fit: guess [nprof][2] (a NaN phase asks for the grid), out [nprof][PP_NBS_NOUT]
+        for (int log10_tau : {0, 1}) {
+            std::vector<double> guess((size_t)nprof * 2);
+            for (int i = 0; i < nprof; ++i) { guess[2 * i] = (i & 1) ? 0.1 : NAN; guess[2 * i + 1] = log10_tau ? -2.0 : 0.0; }
+            Outs o2; double* outs = o2.d((size_t)nprof * PP_NBS_NOUT);
+            AUX(o2, name(log10_tau ? "pp_fit_phase_tau_batch log10" : "pp_fit_phase_tau_batch"),
+                pp_fit_phase_tau_batch(c, data.data(), model.data(), with_noise ? noise.data() : nullptr, guess.data(), nprof, B, -0.5, 0.5, 20,
+                                       log10_tau, outs));
+        }
     }
     // templates generated on the device: to the host, to a device buffer, into a slot; then the response on that slot
     const double comps[12] = {0.3, 0.0, 0.02, 0.0, 1.0, 0.0, 0.6, 0.0, 0.05, 0.0, 0.5, -1.0};
@@ -451,6 +460,7 @@ static void aux_refusals(int C, int B) {
         REF("pp_align_accumulate nbin", pp_align_accumulate(c, src, PP_F64, 0, ns, C, B2, f, 0, P, p3, w, out, out));
         REF("pp_channel_red_chi2 nbin", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B2, nullptr, f, 0, P, p5, n3, sc, er, out));
         REF("pp_fit_phase_shift_batch nbin", pp_fit_phase_shift_batch(c, mp, mp, nullptr, ns, B2, -0.5, 0.5, 20, out));
+        REF("pp_fit_phase_tau_batch nbin", pp_fit_phase_tau_batch(c, mp, mp, nullptr, mp, ns, B2, -0.5, 0.5, 20, 1, out));
         REF("pp_rfft_rows nbin", pp_rfft_rows(c, src, PP_F64, ns, B2, out));
         REF("pp_channel_noise nbin", pp_channel_noise(c, src, PP_F64, 0, ns, B2, PP_NORM_NONE, nullptr, out, out));
         REF("pp_channel_snrs nbin", pp_channel_snrs(c, src, PP_F64, 0, ns, B2, 3.25, out));
@@ -470,6 +480,9 @@ static void aux_refusals(int C, int B) {
     REF("pp_reference_phase_seed Ns", pp_reference_phase_seed(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 0, out));
     REF("pp_fit_phase_shift_batch nprof", pp_fit_phase_shift_batch(c, mp, mp, nullptr, 0, B, -0.5, 0.5, 20, out));
     REF("pp_fit_phase_shift_batch Ns", pp_fit_phase_shift_batch(c, mp, mp, nullptr, ns, B, -0.5, 0.5, 0, out));
+    REF("pp_fit_phase_tau_batch nprof", pp_fit_phase_tau_batch(c, mp, mp, nullptr, mp, 0, B, -0.5, 0.5, 20, 1, out));
+    REF("pp_fit_phase_tau_batch Ns", pp_fit_phase_tau_batch(c, mp, mp, nullptr, mp, ns, B, -0.5, 0.5, 0, 1, out));
+    REF("pp_fit_phase_tau_batch bounds", pp_fit_phase_tau_batch(c, mp, mp, nullptr, mp, ns, B, 0.5, -0.5, 20, 1, out));
     REF("pp_rfft_rows nrows", pp_rfft_rows(c, src, PP_F64, 0, B, out));
     REF("pp_synth_portraits nsub", pp_synth_portraits(c, 0, out, PP_F64, 0, f, P, p3, nullptr, 0.05, 7, 0));
     REF("pp_channel_noise nrows", pp_channel_noise(c, src, PP_F64, 0, 0, B, PP_NORM_NONE, nullptr, out, out));
@@ -508,6 +521,7 @@ static void aux_refusals(int C, int B) {
         REF("pp_channel_red_chi2 null", pp_channel_red_chi2(NZ(8, c), NZ(0, src), PP_F64, 0, ns, C, B, nullptr, NZ(1, f), 0, NZ(2, P), NZ(3, p5), NZ(4, n3), NZ(5, sc),
                                                            NZ(7, er), NZ(6, out)));
         REF("pp_fit_phase_shift_batch null", pp_fit_phase_shift_batch(NZ(8, c), NZ(0, mp), NZ(1, mp), nullptr, ns, B, -0.5, 0.5, 20, NZ(6, out)));
+        REF("pp_fit_phase_tau_batch null", pp_fit_phase_tau_batch(NZ(8, c), NZ(0, mp), NZ(1, mp), nullptr, NZ(2, mp), ns, B, -0.5, 0.5, 20, 1, NZ(6, out)));
         REF("pp_rfft_rows null", pp_rfft_rows(NZ(8, c), NZ(0, src), PP_F64, ns, B, NZ(6, out)));
         REF("pp_synth_portraits null", pp_synth_portraits(NZ(8, c), 0, NZ(6, out), PP_F64, ns, NZ(1, f), NZ(2, P), NZ(3, p3), nullptr, 0.05, 7, 0));
         REF("pp_channel_noise null", pp_channel_noise(NZ(8, c), NZ(0, src), PP_F64, 0, ns, B, PP_NORM_NONE, nullptr, NZ(6, out), NZ(7, out)));
@@ -565,6 +579,7 @@ static void aux_refusals(int C, int B) {
         ++g_ncase;
         mark("enqueue rc %d", pp_fit_enqueue(c, &b.in, &b.out));
         REF("pending pp_fit_phase_shift_batch", pp_fit_phase_shift_batch(c, mp, mp, nullptr, ns, B, -0.5, 0.5, 20, out));
+        REF("pending pp_fit_phase_tau_batch", pp_fit_phase_tau_batch(c, mp, mp, nullptr, mp, ns, B, -0.5, 0.5, 20, 1, out));
         REF("pending pp_reference_phase_seed", pp_reference_phase_seed(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 20, out));
         REF("pending pp_synth_portraits", pp_synth_portraits(c, 0, out, PP_F64, ns, f, P, p3, nullptr, 0.05, 7, 0));
         REF("pending pp_rotate_portraits", pp_rotate_portraits(c, src, out, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY));
