@@ -606,6 +606,29 @@ int pp_pca_basis(pp_ctx* ctx, const double* vecs, const double* lam, int nvec, d
  * (ppspline.py:119-129; reconstruct_portrait, pplib.py:1536-1553) from the resident rows and basis. */
 int pp_pca_project(pp_ctx* ctx, const int32_t* ieig, int ncomp, double* proj, double* reconst);
 
+/* ---- wavelet smoothing (ppspline's smoothed templates) ----------------------- */
+/* wavelet_smooth (pplib.py:1621-1666) of rows[nrows][nbin] (`dtype`, host or device) with the db8 wavelet: the
+ * stationary wavelet transform with periodic boundary to nlevel levels, the threshold
+ *   lopt = fact * median(|cA_L u cD_L|) / 0.6745 * sqrt(2 ln nbin)
+ * applied to the coarsest approximation and every level's details (threshtype 0: hard, 0 where |c| < lopt;
+ * 1: soft, c max(1 - lopt / |c|, 0)), and the inverse transform.  filt[16]: the orthonormal low-pass taps in
+ * PyWavelets' rec_lo order (checked: sum sqrt 2, orthonormal to 1e-12).  nlevel and fact are host arrays read with
+ * their strides: 0 = one value for every row, 1 = one per row; 2^nlevel must divide nbin.  out[nrows][nbin] is f64,
+ * on the device when the rows are.  nbin: even, 16 ... 4096.  Every row's result depends on that row alone. */
+int pp_wavelet_smooth(pp_ctx* ctx, const void* rows, int dtype, int on_device, int nrows, int nbin,
+                      const double* filt, int threshtype, const int32_t* nlevel, int64_t nlevel_stride,
+                      const double* fact, int64_t fact_stride, void* out);
+
+/* smart_smooth (pplib.py:1668-1735) of the same rows: for every level 1 ... try_nlevels, scipy.optimize.brute of
+ * fit_wavelet_smooth_function (:1737-1761) over 30 factors in [0, 3] with its Nelder-Mead finish; the level of the
+ * smallest value; the final smooth, zeroed when its reduced chi^2 against the row is further than rchi2_tol from 1.
+ * A row of zeros stays zero (level 0).  Host arrays: info5[nrows][5] = { level, fact, -fun, reduced chi^2 of the
+ * final smooth, objective evaluations }, stats4[nrows][4] = pp_pca_basis's statistics of the smoothed row,
+ * raw_noise[nrows] (or NULL) = get_noise_PS of the row itself, find_significant_eigvec's noise. */
+int pp_smart_smooth(pp_ctx* ctx, const void* rows, int dtype, int on_device, int nrows, int nbin,
+                    const double* filt, int threshtype, int try_nlevels, double rchi2_tol, void* out,
+                    double* info5, double* stats4, double* raw_noise);
+
 /* ---- ppgauss --------------------------------------------------------------- */
 /* The device side of fit_gaussian_portrait (pplib.py:1924-2052), a Levenberg-Marquardt fit whose Jacobian is taken by
  * forward differences: every column is a whole model portrait (gen_gaussian_portrait, pplib.py:853-930).

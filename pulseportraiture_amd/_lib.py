@@ -132,6 +132,10 @@ SYMBOLS = {
                               C.c_double, C.c_double, c_double_p, c_double_p]),
     "pp_pca_basis": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p]),
     "pp_pca_project": (C.c_int, [C.c_void_p, c_int32_p, C.c_int, c_double_p, c_double_p]),
+    "pp_wavelet_smooth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int,
+                                    c_int32_p, C.c_int64, c_double_p, C.c_int64, C.c_void_p]),
+    "pp_smart_smooth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int,
+                                  C.c_int, C.c_double, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     "pp_gauss_fit_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p,
                                      c_double_p]),
     "pp_gauss_fit_end": (C.c_int, [C.c_void_p]),

@@ -973,6 +973,50 @@ __device__ __forceinline__ void fps_bsum(double (&out)[NV], double* scratch, int
     }
 }
 
+// What scipy.optimize.fmin does for ONE dimension from x0 (scipy/optimize/_optimize.py _minimize_neldermead, operation
+// by operation: rho 1, chi 2, psi 1/2, sigma 1/2; second vertex 1.05 x0, or 0.00025 when x0 = 0; xtol = ftol = 1e-4,
+// at most 200 iterations / evaluations).  feval(x) is the same in every thread that calls this.  Returns the best
+// vertex; f0: its value, fcalls: the evaluations spent.  Shared by k_fps (finish == 1) and pp_wavelet.h.
+template <typename F>
+__device__ __forceinline__ double nelder_mead_1d(const double x0, F&& feval, double& f0, int& fcalls) {
+    double sim0 = x0, sim1 = (x0 != 0.0) ? mul_rn(1.05, x0) : 0.00025;
+    f0 = feval(sim0);
+    double f1 = feval(sim1);
+    fcalls = 2;
+    int iterations = 1;
+    auto order = [&]() {           // argsort of two values, stable
+        if (f1 < f0) { const double t = sim0; sim0 = sim1; sim1 = t; const double u = f0; f0 = f1; f1 = u; }
+    };
+    order();
+    while (fcalls < 200 && iterations < 200) {
+        if (fabs(sim1 - sim0) <= 1e-4 && fabs(f0 - f1) <= 1e-4) break;
+        const double xbar = sim0;
+        const double xr = sub_rn(mul_rn(2.0, xbar), sim1);
+        const double fxr = feval(xr); ++fcalls;
+        bool shrink = false;
+        if (fxr < f0) {
+            const double xe = sub_rn(mul_rn(3.0, xbar), mul_rn(2.0, sim1));
+            const double fxe = feval(xe); ++fcalls;
+            if (fxe < fxr) { sim1 = xe; f1 = fxe; } else { sim1 = xr; f1 = fxr; }
+        } else if (fxr < f1) {      // (f0 <= fxr: outside contraction)
+            const double xc = sub_rn(mul_rn(1.5, xbar), mul_rn(0.5, sim1));
+            const double fxc = feval(xc); ++fcalls;
+            if (fxc <= fxr) { sim1 = xc; f1 = fxc; } else shrink = true;
+        } else {                    // inside contraction
+            const double xcc = add_rn(mul_rn(0.5, xbar), mul_rn(0.5, sim1));
+            const double fxcc = feval(xcc); ++fcalls;
+            if (fxcc < f1) { sim1 = xcc; f1 = fxcc; } else shrink = true;
+        }
+        if (shrink) {
+            sim1 = add_rn(sim0, mul_rn(0.5, sub_rn(sim1, sim0)));
+            f1 = feval(sim1); ++fcalls;
+        }
+        ++iterations;
+        order();
+    }
+    return sim0;
+}
+
 // The 1-D fit of profile pair i: dspec(k) = the data profile's harmonic k, m[k] the model's, X[0 .. M) the work array
 // of their cross-spectrum (LDS where it fits).  Threads: 256 (NVW = 1) or one wave standing in for them (NVW = 4).
 template <int NVW, typename DF>
@@ -1042,40 +1086,9 @@ __device__ __forceinline__ void fps_body(const FpsArgs& a, const int i, const in
         // _minimize_neldermead: rho 1, chi 2, psi 1/2, sigma 1/2; second vertex
         // 1.05 x0, or 0.00025 when x0 = 0).  The reference's phase IS this simplex's
         // best vertex, ~1e-5 rot from the maximum of the correlation.
-        double sim0 = phi, sim1 = (phi != 0.0) ? mul_rn(1.05, phi) : 0.00025;
-        double f0 = feval(sim0), f1 = feval(sim1);
-        int fcalls = 2, iterations = 1;
-        auto order = [&]() {           // argsort of two values, stable
-            if (f1 < f0) { const double t = sim0; sim0 = sim1; sim1 = t; const double u = f0; f0 = f1; f1 = u; }
-        };
-        order();
-        while (fcalls < 200 && iterations < 200) {
-            if (fabs(sim1 - sim0) <= 1e-4 && fabs(f0 - f1) <= 1e-4) break;
-            const double xbar = sim0;
-            const double xr = sub_rn(mul_rn(2.0, xbar), sim1);
-            const double fxr = feval(xr); ++fcalls;
-            bool shrink = false;
-            if (fxr < f0) {
-                const double xe = sub_rn(mul_rn(3.0, xbar), mul_rn(2.0, sim1));
-                const double fxe = feval(xe); ++fcalls;
-                if (fxe < fxr) { sim1 = xe; f1 = fxe; } else { sim1 = xr; f1 = fxr; }
-            } else if (fxr < f1) {      // (f0 <= fxr: outside contraction)
-                const double xc = sub_rn(mul_rn(1.5, xbar), mul_rn(0.5, sim1));
-                const double fxc = feval(xc); ++fcalls;
-                if (fxc <= fxr) { sim1 = xc; f1 = fxc; } else shrink = true;
-            } else {                    // inside contraction
-                const double xcc = add_rn(mul_rn(0.5, xbar), mul_rn(0.5, sim1));
-                const double fxcc = feval(xcc); ++fcalls;
-                if (fxcc < f1) { sim1 = xcc; f1 = fxcc; } else shrink = true;
-            }
-            if (shrink) {
-                sim1 = add_rn(sim0, mul_rn(0.5, sub_rn(sim1, sim0)));
-                f1 = feval(sim1); ++fcalls;
-            }
-            ++iterations;
-            order();
-        }
-        phi = sim0;
+        double f0_;
+        int fcalls_;
+        phi = nelder_mead_1d(phi, feval, f0_, fcalls_);
     } else {
     // polish: safeguarded Newton on f(phi) = -Re sum X e / err2 inside +-1 grid step
     double lo = phi - h, hi = phi + h;

@@ -181,6 +181,12 @@ struct pp_ctx {
         bool open = false;
         void release() { for (DevBuf* b : {&data, &isig, &freqs, &R, &part, &gram, &h, &band}) b->release(); open = false; nsets = 0; nrow = 0; njoin = 0; }
     } gfit;
+    // wavelet smoothing (pp_wavelet.h): a run's rows as f64, the coefficients and threshold scales of every level, the
+    // rows' own noise, one smoothed row per workgroup, the stages' values per (row, level) and the results
+    struct Wl {
+        DevBuf x64, coef, med, noise, live, srow, out, small, fgrid, lev, par, idx;
+        void release() { for (DevBuf* b : {&x64, &coef, &med, &noise, &live, &srow, &out, &small, &fgrid, &lev, &par, &idx}) b->release(); }
+    } wl;
     // pinned host staging of the small inputs / the packed outputs of a batch: two sets, so that a
     // deferred batch (pp_fit_enqueue) keeps its own while the next one is being queued
     struct Stage { void* in_host = nullptr; size_t in_cap = 0; void* o_host = nullptr; size_t o_cap = 0;
@@ -411,6 +417,7 @@ extern "C" int pp_destroy(pp_ctx* c) {
     c->pca.release();
     c->align.release();
     c->gfit.release();
+    c->wl.release();
     c->release_buffers();
     if (c->nactive_h) (void)hipHostFree(c->nactive_h);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -2165,3 +2172,4 @@ extern "C" int pp_fit_wait(pp_ctx* c) {
 #include "pp_pca.h"
 #include "pp_gaussfit.h"
 #include "pp_nbscat.h"
+#include "pp_wavelet.h"

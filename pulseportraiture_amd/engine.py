@@ -888,6 +888,63 @@ class Engine(object):
                                         _dp(reconst)), "pp_pca_project")
         return proj, reconst
 
+    # ---- wavelet smoothing (pplib.wavelet_smooth / smart_smooth, pplib.py:1621-1761) ----
+    THRESHTYPES = {"hard": 0, "soft": 1}
+
+    def _smooth_args(self, rows, threshtype, what):
+        if threshtype not in self.THRESHTYPES:
+            raise ValueError("threshtype must be 'hard' or 'soft'")
+        src, dtype, on_dev, shape, keep = _array_arg(rows, what + ": device rows")
+        if len(shape) != 2:
+            raise ValueError("rows must be [nrows,nbin]")
+        if on_dev:
+            import torch
+            out = torch.empty(shape, dtype=torch.float64, device=rows.device)
+            dst = C.c_void_p(out.data_ptr())
+        else:
+            out = np.empty(shape)
+            dst = C.c_void_p(out.ctypes.data)
+        return src, dtype, on_dev, shape, keep, out, dst
+
+    def wavelet_smooth(self, rows, nlevel=5, threshtype="hard", fact=1.0):
+        """pplib.wavelet_smooth (pplib.py:1621-1666) of every row of rows [nrows,nbin] (NumPy or a device
+        tensor, f64 or f32) with the db8 wavelet: stationary wavelet transform to nlevel levels, the threshold
+        fact * median(|cA_L u cD_L|) / 0.6745 * sqrt(2 ln nbin) on every coefficient, inverse transform.  nlevel
+        and fact: one value, or one per row.  nbin even, 16 ... 4096, a multiple of 2^nlevel.  Returns f64 rows,
+        on the device when the input is."""
+        from . import wavelets
+        src, dtype, on_dev, shape, keep, out, dst = self._smooth_args(rows, threshtype, "wavelet_smooth")
+        nrows, nbin = shape
+        lv = np.ascontiguousarray(np.atleast_1d(nlevel), dtype=np.int32)
+        fc = np.ascontiguousarray(np.atleast_1d(fact), dtype=np.float64).reshape(-1)
+        for name, a in (("nlevel", lv), ("fact", fc)):
+            if a.size not in (1, nrows):
+                raise ValueError("%s: one value or one per row" % name)
+        h = wavelets.rec_lo()
+        _check(self._lib.pp_wavelet_smooth(self._ctx, src, dtype, on_dev, nrows, nbin, _dp(h),
+                                           self.THRESHTYPES[threshtype], lv.ctypes.data_as(c_int32_p),
+                                           0 if lv.size == 1 else 1, _dp(fc), 0 if fc.size == 1 else 1, dst),
+               "pp_wavelet_smooth")
+        return out
+
+    def smart_smooth(self, rows, try_nlevels, rchi2_tol=0.1, threshtype="hard"):
+        """pplib.smart_smooth (pplib.py:1668-1735) of every row of rows [nrows,nbin] (even nbin, 16 ... 4096, a
+        multiple of 2^try_nlevels): per level 1 ... try_nlevels the brute search over 30 factors with its simplex
+        finish, the best level, the final smooth, zeroed when its reduced chi^2 is further than rchi2_tol from 1.
+        Returns (smoothed rows, info) with info a dict of per-row arrays: level (0 for a row of zeros), fact,
+        snr (-fun), red_chi2, nfev, stats [nrows,4] (pca_basis's statistics of the smoothed row) and raw_noise
+        (get_noise of the row itself)."""
+        from . import wavelets
+        src, dtype, on_dev, shape, keep, out, dst = self._smooth_args(rows, threshtype, "smart_smooth")
+        nrows, nbin = shape
+        info, stats, noise = np.empty((nrows, 5)), np.empty((nrows, 4)), np.empty(nrows)
+        h = wavelets.rec_lo()
+        _check(self._lib.pp_smart_smooth(self._ctx, src, dtype, on_dev, nrows, nbin, _dp(h),
+                                         self.THRESHTYPES[threshtype], int(try_nlevels), float(rchi2_tol), dst,
+                                         _dp(info), _dp(stats), _dp(noise)), "pp_smart_smooth")
+        return out, dict(level=info[:, 0].astype(int), fact=info[:, 1].copy(), snr=info[:, 2].copy(),
+                         red_chi2=info[:, 3].copy(), nfev=info[:, 4].astype(int), stats=stats, raw_noise=noise)
+
     def zap_median(self, noise, good, nstd):
         """get_zap_channels' clip (ppzap.py:18-47) of every subint at once: noise and
         good [nsub,nchan] (good != 0: a channel in ok_ichans).  Returns the uint8

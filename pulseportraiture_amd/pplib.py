@@ -238,6 +238,25 @@ class DataPortrait(object):
         with open(joinfile, "a") as jf:
             jf.write(self.format_join_parameters())
 
+    def smooth_portrait(self, smart=False, **kwargs):
+        """Smooth the portrait data with wavelet_smooth's defaults, or with smart_smooth (smart=True, at most 8
+        levels) -- pplib.py:400-424, with the reference's side effects: port, noise_stds[0,0], flux_prof, and
+        portx, noise_stdsxs, flux_profx.  **kwargs go to wavelet_smooth / smart_smooth."""
+        eng = kwargs.get("engine") or default_engine()
+        if smart:
+            kwargs = dict(kwargs, try_nlevels=min(8, int(np.log2(self.nbin))))
+
+        def smooth(port):
+            return np.asarray((smart_smooth if smart else wavelet_smooth)(port, **kwargs))
+        # full portrait
+        self.port = smooth(self.port)
+        self.noise_stds[0, 0] = eng.channel_noise(self.port)[0]
+        self.flux_prof = self.port.mean(axis=1)
+        # condensed portrait
+        self.portx = smooth(self.portx)
+        self.noise_stdsxs = np.asarray(eng.channel_noise(self.portx)[0], dtype=np.float64)
+        self.flux_profx = self.portx.mean(axis=1)
+
 
 # ---- small host helpers ------------------------------------------------------
 def get_bin_centers(nbin, lo=0.0, hi=1.0):
@@ -343,6 +362,96 @@ def get_noise(data, method=default_noise_method, frac=4, chans=False):
     kc = int((1 - frac ** -1) * power.shape[-1])
     noise = np.sqrt(power[:, kc:].mean(axis=-1))
     return noise if chans else noise[0]
+
+
+# ---- wavelet smoothing -----------------------------------------------------------
+def _as_rows(port):
+    a = port if hasattr(port, "data_ptr") else np.asarray(port)
+    one_prof = len(a.shape) == 1
+    return (a.reshape(1, -1) if one_prof else a), one_prof
+
+
+def wavelet_smooth(port, wavelet='db8', nlevel=5, threshtype='hard', fact=1.0, engine=None):
+    """The wavelet-denoised version of a portrait [nchan,nbin] or a profile [nbin] (pplib.py:1621-1666),
+    on the device (Engine.wavelet_smooth).  Only the 'db8' wavelet is built."""
+    if getattr(wavelet, "name", wavelet) != 'db8':
+        raise NotImplementedError("wavelet_smooth: only the 'db8' wavelet is available")
+    rows, one_prof = _as_rows(port)
+    out = (engine or default_engine()).wavelet_smooth(rows, nlevel=int(nlevel), threshtype=threshtype,
+                                                      fact=float(np.asarray(fact).reshape(-1)[0]))
+    return out[0] if one_prof else out
+
+
+def smart_smooth(port, try_nlevels=None, rchi2_tol=0.1, return_info=False, engine=None, **kwargs):
+    """wavelet_smooth applied the reference's automated way (pplib.py:1668-1735): per profile the level and
+    threshold factor of the highest pseudo-S/N whose reduced chi^2 against the profile stays within rchi2_tol of
+    1, on the device (Engine.smart_smooth).  try_nlevels = 0 and odd nbin return port as it is (a single profile of
+    odd length as a one-row portrait, the reference's quirk); an even nbin
+    that is no power of two gets one level; the default is log2(nbin) levels.  **kwargs as the reference reads
+    them: threshtype is used, nlevel and fact are dropped, and a 'wavelet' key fails as it does there (it looks
+    up kwargs['wave']).  return_info=True also returns Engine.smart_smooth's per-row dictionary (None where
+    nothing ran)."""
+    if try_nlevels == 0:
+        return (port, None) if return_info else port
+    rows, one_prof = _as_rows(port)
+    nbin = int(rows.shape[-1])
+    if nbin % 2 != 0:
+        # (the reference has rebound a single profile to a one-row portrait by now, and returns that)
+        port = np.array([port]) if one_prof else port
+        return (port, None) if return_info else port
+    elif np.modf(np.log2(nbin))[0] != 0.0:
+        try_nlevels = 1
+    elif try_nlevels is None:
+        try_nlevels = int(np.log2(nbin))
+    if 'wavelet' in kwargs:
+        kwargs['wave']
+    threshtype = kwargs.get('threshtype', 'hard')
+    out, info = (engine or default_engine()).smart_smooth(rows, int(try_nlevels), rchi2_tol=rchi2_tol,
+                                                         threshtype=threshtype)
+    out = out[0] if one_prof else out
+    return (out, info) if return_info else out
+
+
+def find_significant_eigvec(eigvec, check_max=10, return_max=10, snr_cutoff=150.0, check_crossings=True,
+                            check_acorr=True, return_smooth=True, engine=None, **kwargs):
+    """Which eigenvectors (the columns of eigvec [nbin,ncomp]) are significant, from their smoothed versions
+    and S/N (pplib.py:1555-1619): the signal and the crossings come from the smoothed vector, the noise from the
+    vector itself.  All examined vectors are smoothed in one device call; smoothed vectors are not renormalised
+    and only those found significant are returned in smooth_eigvec.  Returns ieig, or (ieig, smooth_eigvec)
+    with return_smooth.  check_acorr cannot take effect (the reference's branch is unreachable); **kwargs go to
+    smart_smooth."""
+    from .ppspline import significant_eigvec
+    eigvec = np.asarray(eigvec, dtype=np.float64)
+    nbin = eigvec.shape[0]
+    ncheck = min(max(check_max, return_max), eigvec.shape[1])
+    rows = np.ascontiguousarray(eigvec.T[:ncheck])
+    sm, info = smart_smooth(rows, return_info=True, engine=engine, **kwargs)
+    stats = smooth_stats(rows, sm, info)
+    ieig, _ = significant_eigvec(stats, nbin, check_max=check_max, return_max=return_max, snr_cutoff=snr_cutoff,
+                                 check_crossings=check_crossings)
+    if not return_smooth:
+        return ieig
+    smooth_eigvec = np.zeros(eigvec.shape)
+    if len(ieig):
+        smooth_eigvec[:, ieig] = np.asarray(sm)[ieig].T
+    return ieig, smooth_eigvec
+
+
+def smooth_stats(rows, smoothed, info):
+    """find_significant_eigvec's numbers of smoothed vectors, shaped like Engine.pca_basis's stats: the power
+    sum_{k>=1} |rfft|^2, max |.| and crossings of the SMOOTHED vector, the noise of the vector ITSELF.  With
+    info None (nothing was smoothed: odd nbin or try_nlevels 0) everything is measured here on the host."""
+    if info is not None:
+        stats = np.array(info["stats"], dtype=np.float64)
+        stats[:, 1] = info["raw_noise"]
+        return stats
+    stats = np.zeros((len(rows), 4))
+    for i, (raw, ev) in enumerate(zip(np.asarray(rows), np.asarray(smoothed))):
+        a = np.abs(ev)
+        sg = np.sign(a - 0.1 * a.max())
+        stats[i] = [np.sum(np.abs(np.fft.rfft(ev)[1:]) ** 2), get_noise(raw), a.max(),
+                    np.sum(sg[1:] != sg[:-1]) - np.sum(sg == 0)]
+    return stats
 
 
 def gaussian_profile(nbin, loc, wid):

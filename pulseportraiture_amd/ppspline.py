@@ -2,7 +2,8 @@
 
 `DataPortrait.make_spline_model` and `write_model` reproduce the reference's
 (ppspline.py:34-232 with pplib.pca :1497-1534 and find_significant_eigvec
-:1555-1619) for smooth=False.  The passes over the nchan x nbin portrait --
+:1555-1619) for smooth=False; `make_smooth_spline_model` is its smooth=True, the
+wavelet smoothing of pplib.smart_smooth on the device.  The passes over the nchan x nbin portrait --
 weighted mean profile, centring, the covariance (or its dual, whichever is smaller),
 the eigenvectors' statistics, projection, reconstruction and the model portraits --
 run in HIP kernels through pulseportraiture_amd.engine.  Two third-party calls stay
@@ -134,16 +135,31 @@ class DataPortrait(pplib.DataPortrait):
                           sfac=1.0, max_nbreak=None, model_name=None, quiet=False, **kwargs):
         """Make a model based on PCA and B-spline interpolation (ppspline.py:34-204).
 
-        The arguments are the reference's.  smooth=True is not available: callers pass
-        smooth=False.  rchi2_tol only matters to the smoothing.  **kwargs: check_crossings
-        (find_significant_eigvec's; default True) and engine (the Engine to run on; default
+        The arguments are the reference's.  smooth=True is refused here: callers pass smooth=False, or call
+        make_smooth_spline_model for the smoothed model.  rchi2_tol only matters to the smoothing.  **kwargs:
+        check_crossings (find_significant_eigvec's; default True) and engine (the Engine to run on; default
         the process-wide one)."""
         if smooth:
             raise NotImplementedError(
                 "make_spline_model(smooth=True): the wavelet smoothing of the mean profile and the "
-                "eigenvectors needs PyWavelets, which was not available to pin it against the "
-                "reference; pass smooth=False")
-        eng = kwargs.get("engine") or default_engine()
+                "eigenvectors was pinned without PyWavelets and lives beside this method; call "
+                "make_smooth_spline_model(...) (command: ppspline_smooth_run), or pass smooth=False")
+        self._make_model(False, max_ncomp, snr_cutoff, rchi2_tol, k, sfac, max_nbreak, model_name, quiet, kwargs)
+
+    def make_smooth_spline_model(self, max_ncomp=10, snr_cutoff=150.0, rchi2_tol=0.1, k=3, sfac=1.0,
+                                 max_nbreak=None, model_name=None, quiet=False, **kwargs):
+        """The reference's make_spline_model(smooth=True) (ppspline.py:34-204): the examined eigenvectors and the
+        mean profile are wavelet-smoothed (pplib.smart_smooth, rchi2_tol) on the device; significance is decided
+        from the smoothed vectors; projection, reconstruction and the model use the smoothed basis, and
+        smooth_mean_prof / smooth_eigvec are set (write_model then writes those).  An odd nbin falls back to the
+        unsmoothed model, as in the reference.  **kwargs: check_crossings, engine, and whatever else goes to
+        smart_smooth (try_nlevels, threshtype)."""
+        self._make_model(True, max_ncomp, snr_cutoff, rchi2_tol, k, sfac, max_nbreak, model_name, quiet, kwargs)
+
+    def _make_model(self, smooth, max_ncomp, snr_cutoff, rchi2_tol, k, sfac, max_nbreak, model_name, quiet, kwargs):
+        kwargs = dict(kwargs)
+        eng = kwargs.pop("engine", None) or default_engine()
+        check_crossings = kwargs.pop("check_crossings", True)
         port = self.portx
         if getattr(self, "noise_stdsxs", None) is None:
             self.noise_stdsxs = eng.channel_noise(port)[0]
@@ -151,6 +167,12 @@ class DataPortrait(pplib.DataPortrait):
         pca_weights = SNRs / np.sum(SNRs)
         freqs = np.asarray(self.freqsxs[0], dtype=np.float64)
         nchanx, nbin = (int(v) for v in port.shape)
+        if smooth and nbin % 2 != 0:
+            print("nbin = %d is odd; cannot wavelet_smooth.\n" % nbin)
+            smooth = False
+        elif smooth and np.modf(np.log2(nbin))[0] != 0.0:
+            print("nbin = %d is not a power of two; can only try wavelet_smooth to one level; recommend "
+                  "resampling to a power-of-two number of phase bins.\n" % nbin)
         if not quiet:
             print("Performing principal component analysis on data with %d dimensions and %d "
                   "measurements..." % (nbin, nchanx))
@@ -162,26 +184,45 @@ class DataPortrait(pplib.DataPortrait):
         nvec = min(CHECK_MAX, len(eigval))
         eigvec, stats = eng.pca_basis(vecs[:, :nvec], eigval[:nvec])
         return_max = 10 if max_ncomp is None else min(max_ncomp, 10)
+        basis, base_prof = eigvec, mean_prof        # what the projection and the model are built on
+        if smooth:
+            # find_significant_eigvec(return_smooth=True): the signal and the crossings of the SMOOTHED vectors,
+            # the noise of the vectors themselves; then the mean profile (ppspline.py:91-102)
+            raw = np.ascontiguousarray(eigvec.T[:nvec])
+            sm, info = pplib.smart_smooth(raw, rchi2_tol=rchi2_tol, return_info=True, engine=eng, **kwargs)
+            stats = pplib.smooth_stats(raw, sm, info)
         ieig, ev_snrs = significant_eigvec(stats, nbin, check_max=CHECK_MAX, return_max=return_max,
-                                           snr_cutoff=snr_cutoff,
-                                           check_crossings=kwargs.get("check_crossings", True))
+                                           snr_cutoff=snr_cutoff, check_crossings=check_crossings)
+        if smooth:
+            smooth_eigvec = np.zeros(eigvec.shape)
+            if len(ieig):
+                smooth_eigvec[:, ieig] = np.asarray(sm)[ieig].T
+            smooth_mean_prof = np.asarray(pplib.smart_smooth(mean_prof, rchi2_tol=rchi2_tol, engine=eng))
+            basis, base_prof = smooth_eigvec, smooth_mean_prof
         ncomp = len(ieig)
         nfreq = len(self.freqs[0])
         if ncomp == 0:          # the model is the constant average portrait
             proj_port = np.asarray(port)[:, :0]
-            modelx = reconst_port = np.tile(mean_prof, len(freqs)).reshape(len(freqs), nbin)
-            model = np.tile(mean_prof, nfreq).reshape(nfreq, nbin)
+            modelx = reconst_port = np.tile(base_prof, len(freqs)).reshape(len(freqs), nbin)
+            model = np.tile(base_prof, nfreq).reshape(nfreq, nbin)
             (tck, u) = [np.array([]), np.array([]), 0], np.array([])
             fp, ier, msg = None, None, None
         else:
-            proj_port, reconst_port = eng.pca_project(ieig)
+            if smooth:
+                # (the resident basis is the unsmoothed one: nchan x nbin x ncomp products of the smoothed
+                # columns, about the unsmoothed mean as reconstruct_portrait has it -- ppspline.py:119-124)
+                delta_port = np.asarray(port, dtype=np.float64) - mean_prof
+                proj_port = np.dot(delta_port, smooth_eigvec[:, ieig])
+                reconst_port = np.dot(proj_port, smooth_eigvec[:, ieig].T) + mean_prof
+            else:
+                proj_port, reconst_port = eng.pca_project(ieig)
             tck, u, fp, ier, msg = fit_spline_curve(proj_port, pca_weights, freqs, self.bw, SNRs,
                                                     np.asarray(self.noise_stdsxs, dtype=np.float64),
                                                     k=k, sfac=sfac, max_nbreak=max_nbreak, quiet=quiet)
             if ier > 1:
                 print("Something went wrong in si.splprep for %s:\n%s" % (self.source, msg))
-            modelx = eng.spline_portrait(mean_prof, eigvec[:, ieig], tck, freqs)
-            model = eng.spline_portrait(mean_prof, eigvec[:, ieig], tck, self.freqs[0])
+            modelx = eng.spline_portrait(base_prof, basis[:, ieig], tck, freqs)
+            model = eng.spline_portrait(base_prof, basis[:, ieig], tck, self.freqs[0])
         self.ieig = ieig
         self.ncomp = ncomp
         self.eigvec = eigvec
@@ -189,6 +230,12 @@ class DataPortrait(pplib.DataPortrait):
         self.eigvec_stats = stats
         self.ev_snrs = ev_snrs
         self.mean_prof = mean_prof
+        for name in ("smooth_mean_prof", "smooth_eigvec"):      # (a model made without smoothing carries neither)
+            if hasattr(self, name):
+                delattr(self, name)
+        if smooth:
+            self.smooth_mean_prof = smooth_mean_prof
+            self.smooth_eigvec = smooth_eigvec
         self.proj_port = proj_port
         self.reconst_port = reconst_port
         self.tck, self.u, self.fp, self.ier, self.msg = tck, u, fp, ier, msg
@@ -209,10 +256,13 @@ class DataPortrait(pplib.DataPortrait):
     def write_model(self, outfile, quiet=False):
         """Write the model to outfile: the pickle (protocol 2) of [model_name, source,
         datafile, mean_prof, eigvec[:, ieig], tck] (ppspline.py:206-232), what
-        splmodel.read_spline_model and the reference read back."""
-        eigvec = self.eigvec[:, self.ieig] if len(self.ieig) else self.eigvec[:, []]
+        splmodel.read_spline_model and the reference read back; the smoothed mean profile and
+        eigenvectors where make_smooth_spline_model made them."""
+        smooth = hasattr(self, "smooth_eigvec")
+        basis, mean_prof = (self.smooth_eigvec, self.smooth_mean_prof) if smooth else (self.eigvec, self.mean_prof)
+        eigvec = basis[:, self.ieig] if len(self.ieig) else basis[:, []]
         with open(outfile, "wb") as of:
-            pickle.dump([self.model_name, self.source, self.datafile, self.mean_prof, eigvec, self.tck],
+            pickle.dump([self.model_name, self.source, self.datafile, mean_prof, eigvec, self.tck],
                         of, protocol=2)
         if not quiet:
             print("Wrote modelfile %s." % outfile)

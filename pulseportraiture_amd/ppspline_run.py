@@ -13,13 +13,15 @@ import numpy as np
 from .ppzap_run import list_datafiles
 
 MODULE = "pulseportraiture_amd.ppspline_run"
+SMOOTH_MODULE = "pulseportraiture_amd.ppspline_smooth_run"
 
 
-def parser():
+def parser(smooth=False):
+    """The options of ppspline_run; smooth=True: those of ppspline_smooth_run (the same, -s and -T in effect)."""
     ap = argparse.ArgumentParser(
-        prog="python -m " + MODULE,
+        prog="python -m " + (SMOOTH_MODULE if smooth else MODULE),
         description="Make a pulse portrait model using PCA & B-spline interpolation (the reference's "
-                    "ppspline.py command line), without smoothing.")
+                    "ppspline.py command line), " + ("with its wavelet smoothing (-s)." if smooth else "without smoothing."))
     ap.add_argument("-d", "--datafile", required=True, metavar="archive",
                     help="One .npz archive (the fields of a DataBunch) from which to make the model, or a "
                          "metafile naming one.  The data should be averaged and aligned.")
@@ -33,14 +35,18 @@ def parser():
                          "(off-pulse noise), 'prof' (mean profile flux) [default], or 'abs' (sqrt{vector "
                          "modulus})).")
     ap.add_argument("-s", "--smooth", action="store_true",
-                    help="Not available: the wavelet smoothing needs PyWavelets.")
+                    help="Smooth the eigenvectors and mean profile [recommended]: what this command does, with or "
+                         "without the flag." if smooth else
+                         "Not available here (it was pinned without PyWavelets and lives in "
+                         "ppspline_smooth_run): use that command.")
     ap.add_argument("-n", "--max_ncomp", default=10, metavar="max_ncomp",
                     help="Maximum number of principal components to use in PCA reconstruction of the data; "
                          "limited to a maximum of 10 by the B-spline representation.")
     ap.add_argument("-S", "--snr", dest="snr_cutoff", default=150.0, metavar="snr_cutoff",
                     help="S/N ratio cutoff for determining 'significant' eigenprofiles. [default=150.0]")
     ap.add_argument("-T", "--rchi2_tol", default=0.1, metavar="tolerance",
-                    help="Tolerance of the smoothing [default=0.1]; without -s it has no effect.")
+                    help="Tolerance parameter for smoothing.  Bigger value = more smoothing. [default=0.1]" if smooth
+                    else "Tolerance of the smoothing [default=0.1]; it takes effect in ppspline_smooth_run.")
     ap.add_argument("-k", "--degree", dest="k", default=3, metavar="degree",
                     help="Degree of the spline.  Cubic splines (k=3) are recommended [default]. 1 <= k <= 5.")
     ap.add_argument("-f", "--sfac", default=1.0, metavar="smooth_factor",
@@ -54,11 +60,12 @@ def parser():
     return ap
 
 
-def refusal(opts, datafiles=None):
+def refusal(opts, datafiles=None, smooth=False):
     """The message for a request this command cannot honour, or None."""
-    if opts.smooth:
-        return ("-s/--smooth: the wavelet smoothing needs PyWavelets, which was not available to pin it "
-                "against the reference; models are made without smoothing")
+    if opts.smooth and not smooth:
+        return ("-s/--smooth: the wavelet smoothing was pinned without PyWavelets and lives beside this "
+                "command; run python -m %s (DataPortrait.make_smooth_spline_model) with the same "
+                "options" % SMOOTH_MODULE)
     if opts.archive is not None:
         return "-a/--archive needs PSRCHIVE, which this package does not use"
     if opts.make_plots:
@@ -87,24 +94,28 @@ def load_portrait(datafile):
     return DataPortrait(data, quiet=True)
 
 
-def main(argv=None):
+def main(argv=None, smooth=False):
+    """smooth=True: ppspline_smooth_run -- the same flow through make_smooth_spline_model."""
     argv = list(sys.argv[1:] if argv is None else argv)
-    opts = parser().parse_args(argv)
-    msg = refusal(opts)
+    opts = parser(smooth).parse_args(argv)
+    msg = refusal(opts, smooth=smooth)
     if msg is None:
         datafiles = [f for f in list_datafiles(opts.datafile) if f.strip()]
-        msg = refusal(opts, datafiles)
+        msg = refusal(opts, datafiles, smooth=smooth)
     if msg is not None:
-        print("ppspline_run: " + msg, file=sys.stderr)
+        print(("ppspline_smooth_run: " if smooth else "ppspline_run: ") + msg, file=sys.stderr)
         return 2
     datafile = datafiles[0]
     max_nbreak = None if opts.max_nbreak is None else int(opts.max_nbreak)
     dp = load_portrait(datafile)
     if opts.norm in ("mean", "max", "prof", "rms", "abs"):
         dp.normalize_portrait(opts.norm)
-    dp.make_spline_model(max_ncomp=int(opts.max_ncomp), smooth=False, snr_cutoff=float(opts.snr_cutoff),
-                         rchi2_tol=float(opts.rchi2_tol), k=int(opts.k), sfac=float(opts.sfac),
-                         max_nbreak=max_nbreak, model_name=opts.model_name, quiet=opts.quiet)
+    kw = dict(max_ncomp=int(opts.max_ncomp), snr_cutoff=float(opts.snr_cutoff), rchi2_tol=float(opts.rchi2_tol),
+              k=int(opts.k), sfac=float(opts.sfac), max_nbreak=max_nbreak, model_name=opts.model_name, quiet=opts.quiet)
+    if smooth:
+        dp.make_smooth_spline_model(**kw)
+    else:
+        dp.make_spline_model(smooth=False, **kw)
     modelfile = opts.datafile + ".spl" if opts.modelfile is None else opts.modelfile
     dp.write_model(modelfile, quiet=opts.quiet)
     return 0
