@@ -239,6 +239,9 @@ int pp_model_nharm(pp_ctx* ctx, int slot);
 /* DC harmonic of every channel of the slot's template, dc[nchan] (host): nbin x the
  * profile mean the flux estimate of get_TOAs uses (pptoas.py:554-575) */
 int pp_model_dc(pp_ctx* ctx, int slot, double* dc);
+/* nchan and nbin of the slot's template (PP_ESTATE: the slot is not set): what a caller that hands a
+ * destination to pp_fake_portraits sizes it by */
+int pp_model_shape(pp_ctx* ctx, int slot, int* nchan, int* nbin);
 
 /* Gaussian-component template portraits synthesised on the device (.gmodel
  * files: read_model / gen_gaussian_portrait / gaussian_profile / evolve_parameter,
@@ -685,6 +688,23 @@ int pp_gauss_normal(pp_ctx* ctx, const double* R_or_null, int on_device, int nse
 int pp_synth_portraits(pp_ctx* ctx, int slot, void* dst, int dtype, int nsub,
                        const double* freqs, const double* P, const double* inj,
                        const double* gains, double sigma, uint64_t seed, int64_t first_subint);
+
+/* Simulated observations (make_fake_pulsar, pplib.py:3183-3378): fill dst[nsub][npol][nchan][nbin] (device pointer,
+ * dtype; nchan and nbin are the model slot's) with
+ *   amps[i][p][n] * irfft_k(m[n][k] e^{-2 pi i k delays[i][n]}) + sigmas[n] * z(seed, first_subint + i, p, n, bin)
+ * m being the slot's spectrum and z unit normal deviates of a counter-based RNG.  delays is host [nsub][nchan] in
+ * rotations, positive = later -- any delay law the caller can write down (dispersion about a centre frequency, the
+ * DM(nu) power laws of add_DM_nu, ...); amps is host [nsub][npol][nchan] (scales times the scintillation pattern of
+ * add_scintillation, pplib.py:1146-1174) or NULL (= 1); sigmas is host [nchan] or NULL (= 0).  The model is the same
+ * in every polarisation: a row's inverse transform is taken once and its npol copies differ in amplitude and noise.
+ * Values are formed in f64 and cast on the store: the f32 output is the rounded f64 output.  sigmas[n] == 0 gives the
+ * noise-free row exactly and amps == 0 gives sigmas z exactly.  A subint's bits depend on (seed, first_subint + i) and
+ * its own arguments only, not on nsub or on how a long observation is cut into calls.  Refused: an unset slot
+ * (PP_ESTATE); nsub or npol < 1, npol > 65536, a delay that is not finite, a sigma that is negative, NaN or infinite
+ * (PP_EINVAL) -- checked on the host before anything is launched. */
+int pp_fake_portraits(pp_ctx* ctx, int slot, void* dst, int dtype, int nsub, int npol,
+                      const double* delays, const double* amps, const double* sigmas,
+                      uint64_t seed, int64_t first_subint);
 
 /* ---- measurement --------------------------------------------------------- */
 /* Accumulated HIP-event time per kernel family since the last reset (only

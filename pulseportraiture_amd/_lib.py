@@ -70,6 +70,7 @@ SYMBOLS = {
                                C.c_int, C.c_int]),
     "pp_model_nharm": (C.c_int, [C.c_void_p, C.c_int]),
     "pp_model_dc": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "pp_model_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pp_fit_portrait_batch": (C.c_int, [C.c_void_p, C.POINTER(FitIn),
                                         C.POINTER(FitOut)]),
     "pp_fit_submit": (C.c_int, [C.c_void_p, C.POINTER(FitIn), C.POINTER(FitOut)]),
@@ -98,6 +99,8 @@ SYMBOLS = {
     "pp_synth_portraits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
                                      C.c_double, C.c_uint64, C.c_int64]),
+    "pp_fake_portraits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    c_double_p, c_double_p, c_double_p, C.c_uint64, C.c_int64]),
     "pp_gaussian_portrait": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, C.c_char_p,
                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
                                        c_double_p, C.c_void_p, C.c_int]),

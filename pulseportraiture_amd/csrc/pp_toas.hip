@@ -807,6 +807,14 @@ extern "C" int pp_model_dc(pp_ctx* c, int slot, double* dc) {
     return PP_OK;
 }
 
+extern "C" int pp_model_shape(pp_ctx* c, int slot, int* nchan, int* nbin) {
+    if (!c || !nchan || !nbin) return fail(PP_EINVAL, "pp_model_shape: null argument");
+    if (slot < 0 || slot >= PP_MAX_SLOTS || !c->slots[slot].set) return fail(PP_ESTATE, "pp_model_shape: slot %d not set", slot);
+    *nchan = c->slots[slot].nchan;
+    *nbin = c->slots[slot].nbin;
+    return PP_OK;
+}
+
 extern "C" int pp_model_nharm(pp_ctx* c, int slot) {
     if (!c || slot < 0 || slot >= PP_MAX_SLOTS || !c->slots[slot].set) return fail(PP_ESTATE, "slot not set");
     return c->slots[slot].Kt;
@@ -2173,3 +2181,4 @@ extern "C" int pp_fit_wait(pp_ctx* c) {
 #include "pp_gaussfit.h"
 #include "pp_nbscat.h"
 #include "pp_wavelet.h"
+#include "pp_fake.h"

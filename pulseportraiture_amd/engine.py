@@ -1073,6 +1073,41 @@ class Engine(object):
             _dp(P), _dp(inj), _dp(gains), float(sigma), C.c_uint64(int(seed)),
             C.c_int64(int(first_subint))), "pp_synth_portraits")
 
+    def model_shape(self, slot=0):
+        """(nchan, nbin) of the template in `slot`."""
+        nchan, nbin = C.c_int(0), C.c_int(0)
+        _check(self._lib.pp_model_shape(self._ctx, int(slot), C.byref(nchan), C.byref(nbin)), "pp_model_shape")
+        return nchan.value, nbin.value
+
+    def fake_portraits(self, dst, delays, amps=None, sigmas=None, seed=0, first_subint=0, slot=0):
+        """Fill a CUDA tensor dst[nsub,npol,nchan,nbin] (or [nsub,nchan,nbin]: npol = 1), f32 or f64, with
+        simulated subints of the template in `slot`: amps[i,p,n] x the template delayed by delays[i,n]
+        rotations (positive = later) + sigmas[n] x unit normal noise keyed on (seed, first_subint + i, p, n,
+        bin).  amps [nsub,npol,nchan] (None: 1) and sigmas [nchan] (None: 0) are host arrays."""
+        if not _is_device_array(dst):
+            raise EngineError("fake_portraits needs a CUDA tensor destination")
+        shape = tuple(int(s) for s in dst.shape)
+        if len(shape) == 3:
+            shape = (shape[0], 1) + shape[1:]
+        if len(shape) != 4 or min(shape) < 1:
+            raise EngineError("fake_portraits: dst must be [nsub,npol,nchan,nbin] or [nsub,nchan,nbin], not %s" %
+                              (tuple(dst.shape),))
+        nsub, npol, nchan, nbin = shape
+        if (nchan, nbin) != self.model_shape(slot):
+            raise EngineError("fake_portraits: dst holds %d x %d rows, the template in slot %d is %d x %d" %
+                              ((nchan, nbin, int(slot)) + self.model_shape(slot)))
+        if dst.element_size() not in (4, 8) or not dst.is_floating_point() or not dst.is_contiguous():
+            raise EngineError("fake_portraits: dst must be a contiguous float32 or float64 tensor")
+        if delays is None:
+            raise EngineError("fake_portraits: delays is None")
+        delays = _f64(delays, (nsub, nchan))
+        amps = _f64(amps, (nsub, npol, nchan))
+        sigmas = _f64(sigmas, (nchan,))
+        _check(self._lib.pp_fake_portraits(
+            self._ctx, int(slot), C.c_void_p(dst.data_ptr()), PP_F64 if dst.element_size() == 8 else PP_F32,
+            nsub, npol, _dp(delays), _dp(amps), _dp(sigmas), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            C.c_int64(int(first_subint))), "pp_fake_portraits")
+
     def kernel_times(self, reset=False):
         n = 32
         names = (C.c_char_p * n)()

@@ -538,3 +538,224 @@ def fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs,
     from . import gaussfit
     return gaussfit.fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs, fit_flags,
                                           fit_scattering_index, phases, freqs, nu_ref, join_params, P, quiet, **kwargs)
+
+
+# ---- simulated observations (make_fake_pulsar) ---------------------------------------
+fake_chunk_subints = None     # subints generated on the device at once; None: sized from free HBM
+
+
+def scattering_times(tau, alpha, freqs, nu_tau):
+    """Scattering times over frequency: tau (nu / nu_tau)**alpha (pplib.py:4049-4053)."""
+    return tau * (np.asarray(freqs, dtype=np.float64) / nu_tau) ** alpha
+
+
+def scintillation_pattern(nchan, params):
+    """The amplitude per channel add_scintillation multiplies a portrait by: a sum of squared sinusoids
+    across the band, one for each (amp, cycles, phase) triplet of params (pplib.py:1162-1167)."""
+    pattern = np.zeros(int(nchan))
+    for isin in range(len(params) // 3):
+        a, w, p = params[isin * 3:isin * 3 + 3]
+        pattern += a * np.sin(np.linspace(0, w * np.pi, nchan) + p * np.pi) ** 2
+    return pattern
+
+
+def add_scintillation(port, params=None, random=True, nsin=2, amax=1.0, wmax=3.0):
+    """Add fake scintillation to an nchan x nbin portrait (pplib.py:1146-1174): params are triplets of
+    amplitude, cycles across the band and phase [cycles]; with params None and random, nsin triplets are
+    drawn from uniform [0, amax], chi-squared with wmax degrees of freedom and uniform [0, 1] (NumPy's
+    global generator, as in the reference)."""
+    port = np.asarray(port)
+    if params is None and random is False:
+        return port
+    if params is None:
+        params = []
+        for isin in range(nsin):
+            params += [np.random.uniform(0, amax), np.random.chisquare(wmax), np.random.uniform(0, 1)]
+    return np.transpose(np.transpose(port) * scintillation_pattern(len(port), params))
+
+
+def _DM_nu_term(freqs, xs, Cs, nu_ref):
+    """sum_j C_j (nu**x_j - nu_ref**x_j) per channel, Cs padded with ones as add_DM_nu pads them
+    (pplib.py:2537-2542)."""
+    xs = list(np.atleast_1d(xs))
+    if not hasattr(Cs, "__iter__"):
+        Cs = np.ones(len(xs))
+    if len(Cs) < len(xs):
+        Cs = list(Cs) + list(np.ones(len(xs) - len(Cs)))
+    freqs = np.asarray(freqs, dtype=np.float64)
+    term = np.zeros(freqs.shape)
+    for C, x in zip(Cs, xs):
+        term = term + C * (freqs ** x - np.float64(nu_ref) ** x)
+    return term
+
+
+def add_DM_nu(port, phase=0.0, DM=None, P=None, freqs=None, xs=[-2.0], Cs=[1.0], nu_ref=np.inf):
+    """Rotate a portrait with a power-law DM(nu): rotate_portrait with the frequency term
+    sum_j C_j (nu**x_j - nu_ref**x_j) in place of nu**-2 - nu_ref**-2 (pplib.py:2509-2546).  Host NumPy."""
+    pFFT = np.fft.rfft(np.asarray(port, dtype=np.float64), axis=1)
+    k = np.arange(pFFT.shape[1])
+    if DM is None and freqs is None:
+        phis = np.full(len(pFFT), phase, dtype=np.float64)
+    else:
+        phis = phase + Dconst * DM / P * _DM_nu_term(freqs, xs, Cs, nu_ref)
+    return np.fft.irfft(pFFT * np.exp(2.0j * np.pi * np.outer(phis, k)), np.shape(port)[1], axis=1)
+
+
+def fake_pulsar_tables(model, par, nsub=1, npol=1, nchan=512, nu0=1500.0, bw=800.0, tsub=300.0, phase=0.0,
+                       dDM=0.0, start_MJD=None, noise_stds=1.0, scales=1.0, dedispersed=False, t_scat=0.0,
+                       alpha=scattering_alpha, scint=False, xs=None, Cs=None, nu_DM=np.inf, rng=None):
+    """Everything make_fake_pulsar works out on the host, in f64, before the device forms the portraits:
+    a DataBunch of freqs [nchan], Ps [nsub], epochs (MJD), delays [nsub,nchan] (rotations, positive = later: phase,
+    dDM and the DM(nu) law), disp_delays [nchan] (the ephemeris DM's delay about nu0 that a dispersed archive carries on
+    top, zeros for a dedispersed one), amps [nsub,npol,nchan], sigmas [nchan], dmc and the parsed model with the
+    scattering it is to carry.
+    model: a parsed .gmodel (gmodel.parse_gmodel); par: a parfile.psr_par; rng: the generator of the
+    scintillation draws."""
+    from .pptoas import MJD
+    chanwidth = bw / nchan
+    lofreq = nu0 - (bw / 2)
+    freqs = np.linspace(lofreq + (chanwidth / 2.0), lofreq + bw - (chanwidth / 2.0), nchan)
+
+    def per_channel(v, what):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim == 0:
+            return v * np.ones(nchan)
+        if v.shape != (nchan,):
+            raise ValueError("len(%s) != nchan" % what)
+        return v.copy()
+    sigmas = per_channel(noise_stds, "noise_stds")
+    scales = per_channel(scales, "scales")
+    P, DM = np.float64(par.P0), np.float64(par.DM)
+    Ps = np.full(nsub, P)
+    # epochs: seconds added to the start, subint centres (pplib.py:3310-3320)
+    start = MJD(np.float64(par.PEPOCH)) if start_MJD is None else MJD(start_MJD)
+    epochs = [start + MJD(0, (tsub / 2.0 + i * tsub) / 86400.0) for i in range(nsub)]
+    # delays
+    D = Dconst / P
+    nu2 = freqs ** -2.0 - np.float64(nu0) ** -2.0
+    if xs is None:
+        delay = phase + D * dDM * nu2
+    else:
+        delay = phase_transform(phase, DM + dDM, nu0, nu_DM, P) + D * dDM * _DM_nu_term(freqs, xs, Cs, nu_DM)
+    delays = np.tile(delay, (nsub, 1))
+    # what PSRCHIVE's dededisperse() puts back, as a rotation of its own after the rows are made (see make_fake_pulsar)
+    disp_delays = np.zeros(nchan) if dedispersed else D * DM * nu2
+    # scattering rides in the model; the modelfile's own overrides t_scat (pplib.py:3351)
+    model = dict(model)
+    model["params"] = np.array(model["params"], dtype=np.float64)
+    if t_scat and not model["params"][1]:
+        model["params"][1] = t_scat * (model["nu_ref"] / np.float64(nu0)) ** alpha
+        model["alpha"] = np.float64(alpha)
+    # amplitudes: scales times the scintillation pattern, drawn once per (subint, polarisation)
+    amps = np.empty((nsub, npol, nchan))
+    for i in range(nsub):
+        for ip in range(npol):
+            if scint is False or scint is None:
+                pattern = 1.0
+            elif scint is True:
+                if rng is None:
+                    rng = np.random.default_rng()
+                params = []
+                for isin in range(3):
+                    params += [rng.uniform(0, 1.0), rng.chisquare(5.0), rng.uniform(0, 1)]
+                pattern = scintillation_pattern(nchan, params)
+            else:
+                pattern = scintillation_pattern(nchan, list(scint))
+            amps[i, ip] = scales * pattern
+    return DataBunch(freqs=freqs, Ps=Ps, epochs=epochs, delays=delays, disp_delays=disp_delays, amps=amps,
+                     sigmas=sigmas, dmc=1 if dedispersed else 0, DM=DM, nu0=np.float64(nu0), model=model)
+
+
+def _fake_chunk(eng, nsub, sub_bytes):
+    """Subints generated on the device at once: fake_chunk_subints, or what fits half of the free HBM."""
+    if fake_chunk_subints is not None:
+        return max(1, min(int(nsub), int(fake_chunk_subints)))
+    import torch
+    free_b, _ = torch.cuda.mem_get_info(eng.device)
+    return max(1, min(int(nsub), int(0.5 * free_b // max(sub_bytes, 1))))
+
+
+def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.npz", nsub=1, npol=1, nchan=512, nbin=2048,
+                     nu0=1500.0, bw=800.0, tsub=300.0, phase=0.0, dDM=0.0, start_MJD=None, weights=None,
+                     noise_stds=1.0, scales=1.0, dedispersed=False, t_scat=0.0, alpha=scattering_alpha,
+                     scint=False, xs=None, Cs=None, nu_DM=np.inf, state="Stokes", telescope="GBT",
+                     quiet=False, seed=None, dtype=np.float32, engine=None):
+    """Generate fake pulsar data on the GPU and write them as an .npz archive (pplib.py:3183-3378).
+
+    modelfile is the .gmodel file of the Gaussian-component model; ephemeris a .par file (parfile.psr_par:
+    PSR or PSRJ, RAJ, DECJ, F0 or P0, PEPOCH, DM); outfile the .npz to write -- the fields of
+    pptoas.data_from_arrays, which every command here reads -- or None.  nsub, npol, nchan, nbin, nu0 [MHz], bw
+    [MHz], tsub [s] shape the data.  phase [rot] delays every subint, with respect to nu0; dDM [cm**-3 pc] is added
+    to the ephemeris DM, about nu0.  start_MJD: an MJD, a float, or None for PEPOCH.  weights [nsub,nchan] are
+    stored, the data are not zeroed.  noise_stds and scales: a float or one value per channel.  dedispersed=True
+    stores the archive dedispersed (dmc = 1), else the ephemeris DM's delay about nu0 is in the data (dmc = 0):
+    the finished rows are rotated once more on the device (Engine.rotate_portraits, the convention of
+    pptoas._dededisperse), which is what PSRCHIVE's dededisperse() does to the reference's archive.  (One rotation by
+    the summed delay is not the same thing: every inverse transform keeps the real part of the Nyquist harmonic only,
+    and the two differ by up to 3e-3 of the peak for the example model at 64 bins.)  t_scat [s] at nu0 with index alpha scatters the data, unless
+    the modelfile has a TAU of its own.  scint=True multiplies every (subint, polarisation) by a random pattern
+    (add_scintillation's, nsin=3, amax=1, wmax=5); a list is its parameter triplets.  xs, Cs, nu_DM simulate a
+    DM(nu) as add_DM_nu does.  seed seeds the scintillation draws (numpy.random.default_rng) and the device's
+    noise; None draws one and prints it.  dtype: np.float32 or np.float64.  Returns the DataBunch.
+
+    The portraits are formed on the device (Engine.fake_portraits): the model's spectrum, a host table of delays,
+    amplitudes per (subint, polarisation, channel) and noise per channel; the polarisations are the same model
+    with noise of their own, as in the reference.  Long observations are generated in chunks of subints; the
+    archive's bits do not depend on the chunk size.
+
+    Limits.  There is no predictor: every subint's period is 1 / F0, whatever F1 or binary parameters the
+    ephemeris holds.  The .npz stores epochs as float days (about 0.6 us near MJD 57000); the DataBunch returned
+    keeps day and fraction apart.
+
+    Two departures from the reference as it stands.  (1) With xs None the reference passes the unrotated model
+    on (its line 3342) and silently drops phase and dDM; here they are honoured, delay = phase + Dconst dDM
+    (nu**-2 - nu0**-2) / P, which is what its docstring describes and its example relies on.  (2) With xs given
+    the reference overwrites `phase` by phase_transform(...) inside its loop over subints and polarisations, so the
+    transform compounds; here it is applied once to the caller's phase."""
+    from . import parfile
+    from .gmodel import read_gmodel
+    from .pptoas import data_from_arrays
+    import torch
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("dtype must be float32 or float64")
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0] >> np.uint64(1))
+        if not quiet:
+            print("seed = %d" % seed)
+    seed = int(seed)
+    par = parfile.psr_par(ephemeris)
+    t = fake_pulsar_tables(read_gmodel(modelfile), par, nsub=nsub, npol=npol, nchan=nchan, nu0=nu0, bw=bw, tsub=tsub,
+                           phase=phase, dDM=dDM, start_MJD=start_MJD, noise_stds=noise_stds, scales=scales,
+                           dedispersed=dedispersed, t_scat=t_scat, alpha=alpha, scint=scint, xs=xs, Cs=Cs,
+                           nu_DM=nu_DM, rng=np.random.default_rng(seed))
+    weights = np.ones([nsub, nchan]) if weights is None else np.asarray(weights, dtype=np.float64)
+    if weights.shape != (nsub, nchan):
+        raise ValueError("weights must be nsub x nchan")
+    eng = engine or default_engine()
+    slot = 0
+    eng.set_model_gaussian(t.model, t.freqs, nbin, P=t.Ps[0], slot=slot)
+    subints = np.empty((nsub, npol, nchan, nbin), dtype=dtype)
+    chunk = _fake_chunk(eng, nsub, npol * nchan * nbin * dtype.itemsize)
+    dev = torch.empty((chunk, npol, nchan, nbin), dtype=torch.float32 if dtype.itemsize == 4 else torch.float64,
+                      device="cuda:%d" % eng.device)
+    for s0 in range(0, nsub, chunk):
+        n = min(chunk, nsub - s0)
+        eng.fake_portraits(dev[:n], t.delays[s0:s0 + n], amps=t.amps[s0:s0 + n], sigmas=t.sigmas, seed=seed,
+                           first_subint=s0, slot=slot)
+        if not t.dmc:
+            # PSRCHIVE's dededisperse(): the finished rows, noise and all, delayed by the ephemeris DM about nu0
+            eng.rotate_portraits(dev[:n].view(n * npol, nchan, nbin), t.freqs, t.Ps[0], DM=-float(t.DM), nu_DM=float(nu0))
+        subints[s0:s0 + n] = dev[:n].cpu().numpy()
+    del dev
+    fields = dict(subints=subints, freqs=np.tile(t.freqs, (nsub, 1)), Ps=t.Ps, weights=weights, DM=float(t.DM),
+                  dmc=int(t.dmc), doppler_factors=np.ones(nsub), telescope=str(telescope), bw=float(bw),
+                  nu0=float(nu0), subtimes=np.full(nsub, float(tsub)), source=str(par.PSR))
+    if outfile is not None:
+        np.savez(outfile, epochs=np.array([e.in_days() for e in t.epochs]), **fields)
+        if not quiet:
+            print("\nUnloaded %s.\n" % outfile)
+    data = data_from_arrays(epochs=t.epochs, filename="arrays" if outfile is None else str(outfile), **fields)
+    data.state = "Intensity" if npol == 1 else state
+    data.seed = seed
+    return data

@@ -373,6 +373,17 @@ static void aux_rows_calls(pp_ctx* c, const AuxCfg& k, const char* tag) {
       AUX(o, name("pp_synth_portraits"), pp_synth_portraits(c, k.dev, dst, in.dtype(), ns, in.freqs.data(), in.P.data(), inj.data(),
           k.dev ? in.scales.data() : nullptr, 0.05, 7, 3));
       dev_free(dst); }
+    // simulated observations: delays [ns][C], amps [ns][npol][C] and sigmas [C] sized exactly, with and without the optional ones
+    for (int npol : {1, 3}) {
+        Outs o; void* dst = dev_copy(nullptr, in.nrow * npol * B * in.esz);
+        std::vector<double> delays((size_t)ns * C, 0.25), amps((size_t)ns * npol * C, 1.5), sigmas(C, 0.05);
+        snprintf(nm, sizeof nm, "pp_fake_portraits %s %dx%dx%d %s slot %d", tag, ns * npol, C, B, k.f32 ? "f32" : "f64", k.dev);
+        AUX(o, nm, pp_fake_portraits(c, k.dev, dst, in.dtype(), ns, npol, delays.data(), npol == 1 ? nullptr : amps.data(),
+                                     npol == 1 ? nullptr : sigmas.data(), 7, 3));
+        dev_free(dst); }
+    { Outs o; int shape[2] = {0, 0};
+      AUX(o, "pp_model_shape", pp_model_shape(c, k.dev, &shape[0], &shape[1]));
+      if (shape[0] != C || shape[1] != B) { fprintf(stderr, "pp_model_shape: %d x %d, not %d x %d\n", shape[0], shape[1], C, B); exit(1); } }
 }
 
 // the entry points whose inputs are all double precision on the host
@@ -538,6 +549,26 @@ static void aux_refusals(int C, int B) {
     // slots
     REF("pp_synth_portraits unset slot", pp_synth_portraits(c, 9, out, PP_F64, ns, f, P, p3, nullptr, 0.05, 7, 0));
     REF("pp_synth_portraits slot out of range", pp_synth_portraits(c, PP_MAX_SLOTS, out, PP_F64, ns, f, P, p3, nullptr, 0.05, 7, 0));
+    {   // pp_fake_portraits: its own preamble (the arrays sized for ns x 2 x C)
+        std::vector<double> dl((size_t)ns * C, 0.1), am((size_t)ns * 2 * C, 1.0), sg(C, 0.05), bad;
+        REF("pp_fake_portraits unset slot", pp_fake_portraits(c, 9, out, PP_F64, ns, 2, dl.data(), am.data(), sg.data(), 7, 0));
+        REF("pp_fake_portraits slot out of range", pp_fake_portraits(c, -1, out, PP_F64, ns, 2, dl.data(), am.data(), sg.data(), 7, 0));
+        REF("pp_fake_portraits npol", pp_fake_portraits(c, 0, out, PP_F64, ns, 0, dl.data(), am.data(), sg.data(), 7, 0));
+        REF("pp_fake_portraits nsub", pp_fake_portraits(c, 0, out, PP_F64, 0, 2, dl.data(), am.data(), sg.data(), 7, 0));
+        REF("pp_fake_portraits dtype", pp_fake_portraits(c, 0, out, 7, ns, 2, dl.data(), am.data(), sg.data(), 7, 0));
+        REF("pp_fake_portraits null delays", pp_fake_portraits(c, 0, out, PP_F64, ns, 2, nullptr, am.data(), sg.data(), 7, 0));
+        REF("pp_fake_portraits null dst", pp_fake_portraits(c, 0, nullptr, PP_F64, ns, 2, dl.data(), am.data(), sg.data(), 7, 0));
+        REF("pp_fake_portraits null context", pp_fake_portraits(nullptr, 0, out, PP_F64, ns, 2, dl.data(), am.data(), sg.data(), 7, 0));
+        bad = sg; bad[C - 1] = -0.5;
+        REF("pp_fake_portraits negative sigma", pp_fake_portraits(c, 0, out, PP_F64, ns, 2, dl.data(), am.data(), bad.data(), 7, 0));
+        bad = sg; bad[0] = NAN;
+        REF("pp_fake_portraits NaN sigma", pp_fake_portraits(c, 0, out, PP_F64, ns, 2, dl.data(), am.data(), bad.data(), 7, 0));
+        bad = dl; bad[(size_t)ns * C - 1] = INFINITY;
+        REF("pp_fake_portraits infinite delay", pp_fake_portraits(c, 0, out, PP_F64, ns, 2, bad.data(), am.data(), sg.data(), 7, 0));
+        int nc = 0, nb = 0;
+        REF("pp_model_shape unset slot", pp_model_shape(c, 9, &nc, &nb));
+        REF("pp_model_shape null", pp_model_shape(c, 0, nullptr, &nb));
+    }
     REF("pp_channel_red_chi2 unset slot", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B, badslot.data(), f, 0, P, p5, n3, sc, er, out));
     REF("pp_channel_red_chi2 slot of another shape", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C / 2, B, nullptr, f, 0, P, p5, n3, sc, er, out));
     REF("pp_model_apply_response unset slot", pp_model_apply_response(c, 9, mp, nullptr));
@@ -582,6 +613,7 @@ static void aux_refusals(int C, int B) {
         REF("pending pp_fit_phase_tau_batch", pp_fit_phase_tau_batch(c, mp, mp, nullptr, mp, ns, B, -0.5, 0.5, 20, 1, out));
         REF("pending pp_reference_phase_seed", pp_reference_phase_seed(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 20, out));
         REF("pending pp_synth_portraits", pp_synth_portraits(c, 0, out, PP_F64, ns, f, P, p3, nullptr, 0.05, 7, 0));
+        REF("pending pp_fake_portraits", pp_fake_portraits(c, 0, out, PP_F64, ns, 1, w, nullptr, nullptr, 7, 0));
         REF("pending pp_rotate_portraits", pp_rotate_portraits(c, src, out, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY));
         REF("pending pp_align_accumulate", pp_align_accumulate(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, w, out, out));
         REF("pending pp_channel_red_chi2", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, out));
