@@ -706,6 +706,35 @@ int pp_fake_portraits(pp_ctx* ctx, int slot, void* dst, int dtype, int nsub, int
                       const double* delays, const double* amps, const double* sigmas,
                       uint64_t seed, int64_t first_subint);
 
+/* ---- time, frequency and polarisation scrunching ---------------------------- */
+#define PP_POL_KEEP  0   /* every polarisation is kept */
+#define PP_POL_SUM01 1   /* Coherence -> Intensity: src[s][0] + src[s][1], one output polarisation */
+#define PP_POL_FIRST 2   /* Stokes -> Intensity: polarisation 0 only; the others are not read */
+
+/* What load_data hands to PSRCHIVE -- tscrunch, fscrunch, pscrunch (pplib.py:2650-2814, the calls at :2692, :2709 and :2713) -- as
+ * one pass over src[nsub][npol][nchan][nbin] (`dtype`, host or device):
+ *   dst [gt][p'][gf][b] = sum_{s in T_gt} sum_{c in F_gf} weights[s][c] * src[s][p][c][b]  /  wout[gt][gf]
+ *   wout[gt][gf]        = sum_{s in T_gt} sum_{c in F_gf} weights[s][c]
+ * The groups are contiguous runs given by offsets: T_gt = [t_off[gt], t_off[gt+1]) over subints, F_gf = [f_off[gf],
+ * f_off[gf+1]) over channels; t_off[ngt+1] and f_off[ngf+1] ascend strictly from 0 to nsub / nchan.  Singleton
+ * groups leave an axis alone.  pol_mode is one of PP_POL_*; p' = p for PP_POL_KEEP, otherwise there is one output
+ * polarisation.  weights [nsub][nchan] (host): a row of weight 0 or NaN is skipped and its samples are not read (a
+ * zapped channel may hold anything), a negative weight counts; a cell whose total weight is not positive is all
+ * zeros and has wout = 0.  Of a host input only the polarisations the mode reads are copied to the device.
+ * dst [ngt][npol'][ngf][nbin] is f64, on the host or the device like src; wout [ngt][ngf]
+ * is a host array.
+ * The order of summation is part of the interface: every output element is the f64 sum of its members in ascending
+ * (s, c) order -- fma(w, x, sum), for PP_POL_SUM01 fma(w, x0 + x1, sum) -- divided once at the end.  Its bits do not
+ * depend on the launch, on how a host input is cut into runs (option max_work_bytes: a time group that straddles
+ * two runs carries its partial sums on the device), on whether src was on the device or on the other groups of the
+ * call.  No atomics.
+ * PP_EINVAL -- checked on the host before anything is launched -- for null pointers, offsets that are not as above,
+ * PP_POL_SUM01 with fewer than two polarisations, an unknown pol_mode or dtype, and nbin that is not even in
+ * [8, 4096] or a power of two. */
+int pp_scrunch(pp_ctx* ctx, const void* src, int dtype, int on_device, int nsub, int npol, int nchan,
+               int nbin, const double* weights, int ngt, const int32_t* t_off, int ngf,
+               const int32_t* f_off, int pol_mode, double* dst, double* wout);
+
 /* ---- measurement --------------------------------------------------------- */
 /* Accumulated HIP-event time per kernel family since the last reset (only
  * while option "profile" = 1): names[i] points to a static string.

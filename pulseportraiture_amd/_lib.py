@@ -18,6 +18,7 @@ PP_MAX_SLOTS = 64
 PP_RECORD_WIDTH = 18
 ABI_VERSION = 11
 PP_METHOD_TRUST_NCG, PP_METHOD_NEWTON = 0, 1
+PP_POL = {'keep': 0, 'sum01': 1, 'first': 2}
 PP_NORMS = {None: 0, 'mean': 1, 'max': 2, 'prof': 3, 'rms': 4, 'abs': 5}
 
 c_double_p = C.POINTER(C.c_double)
@@ -147,6 +148,8 @@ SYMBOLS = {
                                      c_double_p, C.c_int, c_double_p, c_double_p, c_double_p]),
     "pp_gauss_normal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p,
                                   c_double_p, c_double_p]),
+    "pp_scrunch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p,
+                             C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, C.c_void_p, c_double_p]),
     "pp_kernel_times": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p),
                                   c_double_p, C.POINTER(C.c_int64)]),
     "pp_kernel_times_reset": (C.c_int, [C.c_void_p]),

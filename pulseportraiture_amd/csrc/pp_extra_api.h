@@ -792,3 +792,119 @@ extern "C" int pp_model_apply_response(pp_ctx* c, int slot, const double* rconst
     HIP_TRY(hipGetLastError());
     return model_publish(c, slot);
 }
+
+// ---- time / frequency / polarisation scrunching (pp_scrunch.h) -----------------
+// The run [in.nsub subints from subint s0] of a pp_scrunch call: the member lists of the time groups gt_lo .. that
+// meet it, in ascending (subint, channel) order, and the pass.  `out`: where those groups' rows are (group gt_lo first)
+static int scrunch_run(pp_ctx* c, const Ports& in, int s0, const void* dsrc, const double* weights, const int32_t* t_off,
+                       int ngf, const int32_t* f_off, int pol_mode, int gt_lo, int gt_hi, const double* wtot, double* out) {
+    const int n = in.nsub, nchan = in.nchan, npol = in.npol, ngt = gt_hi - gt_lo + 1;
+    const int npo = pol_mode == PP_POL_KEEP ? npol : 1;
+    std::vector<ScrunchMember> mem;
+    std::vector<int> meta((size_t)ngt * ngf + 1 + ngt);         // off[ngt ngf + 1], then tflag[ngt]
+    int* off = meta.data();
+    int* tflag = off + (size_t)ngt * ngf + 1;
+    off[0] = 0;
+    for (int g = 0; g < ngt; ++g) {
+        const int gt = gt_lo + g;
+        const int sa = std::max((int)t_off[gt], s0), sb = std::min((int)t_off[gt + 1], s0 + n);
+        tflag[g] = (t_off[gt] < s0 ? 1 : 0) | (t_off[gt + 1] <= s0 + n ? 2 : 0);
+        for (int gf = 0; gf < ngf; ++gf) {
+            if (wtot[(size_t)gt * ngf + gf] > 0.0)
+                for (int s = sa; s < sb; ++s)
+                    for (int ch = f_off[gf]; ch < f_off[gf + 1]; ++ch) {
+                        const double w = weights[(size_t)s * nchan + ch];
+                        if (w == 0.0 || w != w) continue;
+                        mem.push_back(ScrunchMember{w, ((long long)(s - s0) * npol) * nchan + ch});
+                    }
+            off[(size_t)g * ngf + gf + 1] = (int)mem.size();
+        }
+    }
+    int rc;
+    if (!mem.empty()) if ((rc = upload(c, c->seedbuf, mem.data(), mem.size() * sizeof(ScrunchMember)))) return rc;
+    if ((rc = upload(c, c->misc, meta.data(), meta.size() * sizeof(int)))) return rc;
+    if ((rc = upload(c, c->sdraw, wtot + (size_t)gt_lo * ngf, (size_t)ngt * ngf * 8))) return rc;
+    ScrunchArgs a{dsrc, out, c->seedbuf.as<ScrunchMember>(), c->misc.as<int>(), c->sdraw.as<double>(),
+                  c->misc.as<int>() + (size_t)ngt * ngf + 1, ngt, npo, ngf, nchan, in.nbin};
+    // one thread per 16 input bytes of an output row; outputs too small to give every compute unit a 256-thread
+    // workgroup go out as single waves
+    const int V = 16 / (int)in.esz();
+    const long long nitems = (long long)ngt * npo * ngf * ((in.nbin + V - 1) / V);
+    const int T = nitems >= 256LL * std::max(c->ncu, 1) ? 256 : 64;
+    const unsigned grid = (unsigned)std::min<long long>((nitems + T - 1) / T, 1LL << 22);
+    {
+        Prof pr(c, KF_SCRUNCH);
+        with_dtype(in.dtype, [&](auto t) {
+            if (pol_mode == PP_POL_SUM01) hipLaunchKernelGGL((k_scrunch<decltype(t), true>), dim3(grid), dim3(T), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_scrunch<decltype(t), false>), dim3(grid), dim3(T), 0, c->stream, a);
+        });
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (the lists are free again)
+    return PP_OK;
+}
+
+extern "C" int pp_scrunch(pp_ctx* c, const void* src, int dtype, int on_device, int nsub, int npol, int nchan, int nbin,
+                          const double* weights, int ngt, const int32_t* t_off, int ngf, const int32_t* f_off,
+                          int pol_mode, double* dst, double* wout) {
+    if (int busy_ = ctx_busy(c, "pp_scrunch")) return busy_;
+    if (!c || !src || !weights || !t_off || !f_off || !dst || !wout) return fail(PP_EINVAL, "pp_scrunch: null argument");
+    if (!nbin_any_ok(nbin)) return nbin_refuse("pp_scrunch", nbin);
+    if (nsub < 1 || npol < 1 || nchan < 1 || (long long)nsub * nchan > INT_MAX) return fail(PP_EINVAL, "pp_scrunch: bad shape");
+    if (dtype != PP_F64 && dtype != PP_F32) return fail(PP_EINVAL, "pp_scrunch: dtype %d", dtype);
+    if (on_device && (((uintptr_t)src & 7) || ((uintptr_t)dst & 15)))
+        return fail(PP_EINVAL, "pp_scrunch: a device src must be 8-byte aligned and a device dst 16-byte aligned");
+    if (pol_mode != PP_POL_KEEP && pol_mode != PP_POL_SUM01 && pol_mode != PP_POL_FIRST) return fail(PP_EINVAL, "pp_scrunch: pol_mode %d", pol_mode);
+    if (pol_mode == PP_POL_SUM01 && npol < 2) return fail(PP_EINVAL, "pp_scrunch: PP_POL_SUM01 needs two polarisations, the input has %d", npol);
+    auto offsets_ok = [](const int32_t* o, int ng, int n) {
+        if (ng < 1 || ng > n || o[0] != 0 || o[ng] != n) return false;
+        for (int g = 0; g < ng; ++g) if (o[g + 1] <= o[g]) return false;
+        return true;
+    };
+    if (!offsets_ok(t_off, ngt, nsub)) return fail(PP_EINVAL, "pp_scrunch: t_off must ascend strictly from 0 to nsub = %d in %d groups", nsub, ngt);
+    if (!offsets_ok(f_off, ngf, nchan)) return fail(PP_EINVAL, "pp_scrunch: f_off must ascend strictly from 0 to nchan = %d in %d groups", nchan, ngf);
+    HIP_TRY(hipSetDevice(c->device));
+    // total weights: the members' sequential sum, on the host (the weights are here)
+    for (int gt = 0; gt < ngt; ++gt)
+        for (int gf = 0; gf < ngf; ++gf) {
+            double W = 0.0;
+            for (int s = t_off[gt]; s < t_off[gt + 1]; ++s)
+                for (int ch = f_off[gf]; ch < f_off[gf + 1]; ++ch) {
+                    const double w = weights[(size_t)s * nchan + ch];
+                    if (!(w == 0.0 || w != w)) W += w;
+                }
+            wout[(size_t)gt * ngf + gf] = W > 0.0 ? W : 0.0;
+        }
+    const Ports in{src, dtype, on_device, nsub, nchan, nbin, nullptr, 0, nullptr, nullptr, 0, npol};
+    const int npo = pol_mode == PP_POL_KEEP ? npol : 1;
+    const size_t slab = (size_t)npo * ngf * nbin;           // doubles of one time group's output
+    int rc;
+    if (on_device) return scrunch_run(c, in, 0, src, weights, t_off, ngf, f_off, pol_mode, 0, ngt - 1, wout, dst);
+    // a host input goes through in runs of whole subints; a run of n subints meets at most n time groups, whose
+    // rows it holds in c->X.  A group that goes on into the next run moves to the front of that buffer.  Only the
+    // polarisations the mode reads cross to the device -- the first (PP_POL_FIRST) or the first two (PP_POL_SUM01) of
+    // every subint, by a pitched copy --, so the run on the device has `dpol` of them
+    const int dpol = pol_mode == PP_POL_FIRST ? 1 : pol_mode == PP_POL_SUM01 ? 2 : npol;
+    const Ports din{src, dtype, 0, nsub, nchan, nbin, nullptr, 0, nullptr, nullptr, 0, dpol};
+    const int cap = din.cap(c, (double)slab * 8 + 24.0 * nchan);
+    if ((rc = c->X.reserve((size_t)std::min(cap, ngt) * slab * 8))) return rc;
+    int gt = 0;                                             // the first group the next run meets
+    return for_runs(nsub, cap, [&](Run r) {
+        Ports run = din;
+        run.nsub = r.n;
+        int rc, gt_hi = gt;
+        while (t_off[gt_hi + 1] < r.s0 + r.n) ++gt_hi;
+        if ((rc = c->data.reserve((size_t)r.n * din.sub_bytes()))) return rc;
+        HIP_TRY(hipMemcpy2DAsync(c->data.p, din.sub_bytes(), r.at((const char*)src, in.sub_bytes()), in.sub_bytes(), din.sub_bytes(),
+                                 (size_t)r.n, hipMemcpyHostToDevice, c->stream));
+        if ((rc = scrunch_run(c, run, r.s0, c->data.p, weights, t_off, ngf, f_off, pol_mode, gt, gt_hi, wout, c->X.as<double>()))) return rc;
+        const bool open = t_off[gt_hi + 1] > r.s0 + r.n;     // the last group goes on
+        const int ndone = gt_hi - gt + (open ? 0 : 1);
+        if (ndone) HIP_TRY(hipMemcpyAsync(dst + (size_t)gt * slab, c->X.p, (size_t)ndone * slab * 8, hipMemcpyDeviceToHost, c->stream));
+        if (open && gt_hi > gt)
+            HIP_TRY(hipMemcpyAsync(c->X.p, c->X.as<double>() + (size_t)(gt_hi - gt) * slab, slab * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        gt = open ? gt_hi : gt_hi + 1;
+        return (int)PP_OK;
+    });
+}

@@ -1108,6 +1108,49 @@ class Engine(object):
             nsub, npol, _dp(delays), _dp(amps), _dp(sigmas), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
             C.c_int64(int(first_subint))), "pp_fake_portraits")
 
+    def scrunch(self, ports, weights, t_off=None, f_off=None, pol_mode="keep"):
+        """Weighted sums over contiguous groups of subints and channels (what load_data hands to
+        PSRCHIVE's tscrunch / pscrunch / fscrunch, pplib.py:2692, :2709, :2713) of ports[nsub,npol,nchan,nbin]
+        (or [nsub,nchan,nbin]: one polarisation; NumPy or a device tensor, f32 or f64):
+        out[gt,p',gf] = sum of weights[s,c] * ports[s,p,c] over the group's members / wout[gt,gf],
+        wout = the members' summed weight.  t_off / f_off: group offsets, ascending from 0 to nsub /
+        nchan (None: every subint / channel on its own).  pol_mode: 'keep', 'sum01' (Coherence ->
+        Intensity) or 'first' (Stokes -> Intensity).  A weight of 0 or NaN skips the row unread; a
+        cell without positive total weight is zero.  Returns (out, wout): out is f64, a device tensor
+        when ports was one, with the polarisation axis ports had; wout is a NumPy array.  The sum runs
+        in ascending (s, c) order in f64: its bits do not depend on how the call is cut up."""
+        if pol_mode not in _lib.PP_POL:
+            raise ValueError("pol_mode must be one of 'keep', 'sum01', 'first'")
+        src, dtype, on_dev, shape, keep = _array_arg(ports, "scrunch: device ports")
+        three = len(shape) == 3
+        if three:
+            shape = (shape[0], 1) + tuple(shape[1:])
+        if len(shape) != 4:
+            raise ValueError("ports must be [nsub,npol,nchan,nbin] or [nsub,nchan,nbin]")
+        nsub, npol, nchan, nbin = (int(v) for v in shape)
+        w = _f64(weights, (nsub, nchan))
+        t_off = np.ascontiguousarray(np.arange(nsub + 1) if t_off is None else t_off, dtype=np.int32)
+        f_off = np.ascontiguousarray(np.arange(nchan + 1) if f_off is None else f_off, dtype=np.int32)
+        if t_off.ndim != 1 or f_off.ndim != 1 or len(t_off) < 2 or len(f_off) < 2:
+            raise ValueError("t_off and f_off must be 1-D offset arrays")
+        ngt, ngf = len(t_off) - 1, len(f_off) - 1
+        oshape = (ngt, npol if pol_mode == "keep" else 1, ngf, nbin)
+        if three:
+            oshape = (ngt, ngf, nbin)
+        if on_dev:
+            import torch
+            out = torch.empty(oshape, dtype=torch.float64, device=ports.device)
+            dst = C.c_void_p(out.data_ptr())
+        else:
+            out = np.empty(oshape)
+            dst = C.c_void_p(out.ctypes.data)
+        wout = np.empty((ngt, ngf))
+        _check(self._lib.pp_scrunch(self._ctx, src, dtype, on_dev, nsub, npol, nchan, nbin, _dp(w), ngt,
+                                    t_off.ctypes.data_as(c_int32_p), ngf, f_off.ctypes.data_as(c_int32_p),
+                                    _lib.PP_POL[pol_mode], dst, _dp(wout)), "pp_scrunch")
+        del keep
+        return out, wout
+
     def kernel_times(self, reset=False):
         n = 32
         names = (C.c_char_p * n)()

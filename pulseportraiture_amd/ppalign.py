@@ -319,15 +319,15 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunc
 
     metafile: a text file of .npz archive names, or a list of names or DataBunches.
     initial_guess: the .npz archive (or DataBunch) of the initial alignment guess.
-    fit_dm=False fits a phase only.  tscrunch=True needs PSRCHIVE and raises.  pscrunch=False
+    fit_dm=False fits a phase only.  tscrunch=True scrunches every archive to one subint on the device
+    before it is aligned (scrunch.tscrunch), as the reference does via load_data(tscrunch=tscrunch).  pscrunch=False
     returns the average Stokes portraits (alignment and weights from total intensity; archives
     of one polarisation are skipped).  SNR_cutoff filters archives by prof_SNR.  outfile defaults
     to <metafile>.algnd.npz.  norm, rot_phase, place (overrides rot_phase), niter, quiet as in the
     reference.  Returns (aligned_port[npol,nchan,nbin], total_weights[nchan])."""
-    if tscrunch:
-        raise RuntimeError("tscrunch=True needs PSRCHIVE, which this package does not use")
     eng = engine or default_engine()
     from .pptoas import _to_device_once
+    from .scrunch import tscrunch as _tscrunch
     from .ppzap_run import list_datafiles
     if isinstance(metafile, str):
         datafiles = [f for f in list_datafiles(metafile) if f.strip()]
@@ -356,6 +356,8 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunc
             label = datafile if isinstance(datafile, str) else datafile.get("filename", "arrays")
             try:
                 data, _ = load_archive(datafile, eng)
+                if tscrunch:
+                    data = _tscrunch(data, engine=eng)
                 state = getattr(data, "state", None) or ("Stokes" if data.npol == 4 else "Intensity")
                 if not pscrunch and data.npol == 1:
                     raise IndexError

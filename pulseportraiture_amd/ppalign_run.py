@@ -60,7 +60,7 @@ def parser():
 def refusal(opts):
     """The message for an option this command cannot honour, or None."""
     if opts.tscrunch:
-        return "-T/--tscr needs PSRCHIVE, which this package does not use"
+        return "-T/--tscr needs PSRCHIVE, which this package does not use: scrunch the archives with ppscrunch_run -T first"
     if opts.palign:
         return "-P/--palign goes to psradd -P, which this package does not use"
     if opts.smooth:

@@ -193,8 +193,12 @@ def _load(datafile):
                   "backend", "frontend", "source"):
             if k in kw:
                 kw[k] = kw[k].item()
+        # (what an archive may carry beside the fields of data_from_arrays: ppalign.EXTRA_FIELDS)
+        extras = {k: kw.pop(k).item() for k in ("prof_SNR", "state") if k in kw}
         kw.setdefault("filename", str(datafile))
-        return data_from_arrays(**kw), str(datafile)
+        data = data_from_arrays(**kw)
+        data.update(extras)
+        return data, str(datafile)
     raise RuntimeError("Cannot load_data(%s): PSRFITS archives need PSRCHIVE; pass a "
                        "DataBunch (data_from_arrays) or an .npz of its fields." % datafile)
 
@@ -247,8 +251,11 @@ def _take_subints(subints, ok_isubs):
     """[nok, nchan, nbin] total-intensity portraits of the good subints, without
     copying the archive when they are a contiguous run (fancy indexing would copy
     gigabytes before the H2D transfer even starts)."""
-    a = np.asarray(subints)
     idx = np.asarray(ok_isubs, dtype=int)
+    if hasattr(subints, "is_cuda"):
+        # (a device tensor -- an archive scrunched on the device -- stays there)
+        return subints[idx.tolist(), 0].contiguous()
+    a = np.asarray(subints)
     if len(idx) and np.array_equal(idx, np.arange(idx[0], idx[0] + len(idx))):
         return np.ascontiguousarray(a[idx[0]:idx[0] + len(idx), 0])
     return np.ascontiguousarray(a[idx, 0])
@@ -271,15 +278,32 @@ def _load_or_skip(datafile, quiet):
     return data, fname
 
 
-def _good_channel_counts(datafile):
+def _tscrunched(eng, d, on_device=True):
+    """The archive scrunched to one subint on the device (scrunch.tscrunch): what the reference gets from
+    load_data(tscrunch=True) (pptoas.py:256-265).  on_device: host subints go to the device first where they fit, and
+    the scrunched tensor stays there for the fit."""
+    from .scrunch import tscrunch
+    if on_device:
+        d = DataBunch(**{k: v for k, v in d.items()})
+        d.subints = _to_device_once(eng, d.subints)
+    return tscrunch(d, engine=eng)
+
+
+def _good_channel_counts(datafile, tscrunch=False):
     """Good-channel counts of an archive's good subints, from its weights alone (the
-    portraits are not read); [] for an archive get_TOAs cannot load."""
+    portraits are not read); [] for an archive get_TOAs cannot load.  tscrunch: of the one
+    subint the archive is scrunched to -- the channels whose summed weight is positive."""
     if isinstance(datafile, dict):
+        if tscrunch:
+            n = int((np.nansum(np.asarray(datafile["weights"], dtype=np.float64), axis=0) > 0).sum())
+            return [n] if n else []
         return [len(datafile["ok_ichans"][i]) for i in datafile["ok_isubs"]]
     if not str(datafile).endswith(".npz"):
         return []
     with np.load(datafile, allow_pickle=True) as z:
-        if "weights" in z.files:
+        if "weights" in z.files and tscrunch:
+            counts = (np.nansum(np.atleast_2d(np.asarray(z["weights"], dtype=np.float64)), axis=0) > 0).sum()
+        elif "weights" in z.files:
             counts = (np.asarray(z["weights"], dtype=np.float64) > 0).sum(axis=-1)
         else:               # (data_from_arrays: every channel of every subint is good)
             with z.zip.open("subints.npy") as f:
@@ -287,7 +311,7 @@ def _good_channel_counts(datafile):
                 read = np.lib.format.read_array_header_1_0 if version == (1, 0) else \
                     np.lib.format.read_array_header_2_0
                 shape = read(f)[0]
-            counts = np.full(shape[0], shape[-2])
+            counts = np.full(1 if tscrunch else shape[0], shape[-2])
     return [int(c) for c in np.atleast_1d(counts) if c > 0]
 
 
@@ -652,8 +676,10 @@ class GetTOAs(object):
                  method='trust-ncg', bounds=None, nu_fits=None, show_plot=False,
                  quiet=None, seed='reference', distributed=False):
         """Same arguments as the reference (pptoas.py:150-156), plus `seed` and
-        `distributed`.  Not supported here: tscrunch and show_plot (they raise) -- they
-        live in PSRCHIVE / the plotting code.
+        `distributed`.  tscrunch=True scrunches every archive to one subint on the device
+        after loading (scrunch.tscrunch: the archive's weights, the epoch rule of that
+        module) and fits the scrunched tensor where it is: one TOA per archive.  Not
+        supported here: show_plot (it raises) -- it lives in the plotting code.
 
         seed='reference' (default -- a drop-in returns the reference's numbers): the
         reference's initial guesses, formed the way it forms them (pptoas.py:421-457:
@@ -686,8 +712,8 @@ class GetTOAs(object):
         on the batch it is fitted in."""
         if quiet is None:
             quiet = self.quiet
-        if tscrunch or show_plot:
-            raise NotImplementedError("tscrunch / plots are outside the accelerated path")
+        if show_plot:
+            raise NotImplementedError("plots are outside the accelerated path")
         if seed not in ('device', 'reference'):
             raise ValueError("seed must be 'device' or 'reference'")
         rank, world = _process_group() if distributed else (0, 1)
@@ -728,6 +754,8 @@ class GetTOAs(object):
             if loaded is None:
                 continue
             d, fname = loaded
+            if tscrunch:
+                d = _tscrunched(eng, d)
             self.ok_idatafiles.append(iarch)
             a, arrays, toas, fit_duration = self._fit_archive(eng, d, fname, d.ok_isubs, last_fl, opt)
             last_fl = a.carry
@@ -1025,17 +1053,23 @@ class GetTOAs(object):
         try:
             eng = self._engine(True)
             mode, lo, hi = shard_plan(len(datafiles), rank, world)
+            if self.tscrunch and mode != "archives":
+                # one subint per archive: whole archives only, every rank scrunches its own
+                from .dist import shard_range
+                mode, (lo, hi) = "archives", shard_range(len(datafiles), rank, world)
             walk_quiet = quiet or rank != 0
             carry = None
             if mode == "archives" and self.fit_DM and self.fit_GM:
                 # the flags left over from the archives before this rank's (their weights only)
                 for df_ in datafiles[:lo]:
-                    carry = subint_fit_flags(_good_channel_counts(df_), self.fit_flags, carry)[1]
+                    carry = subint_fit_flags(_good_channel_counts(df_, self.tscrunch), self.fit_flags, carry)[1]
             for iarch in range(lo, hi):
                 loaded = _load_or_skip(datafiles[iarch], walk_quiet)
                 if loaded is None:
                     continue
                 d, fname = loaded
+                if self.tscrunch:
+                    d = _tscrunched(eng, d)
                 ok_isubs = np.asarray(d.ok_isubs, dtype=int)
                 nchx = [len(d.ok_ichans[isub]) for isub in ok_isubs]
                 j0, j1 = shard_subints(mode, len(ok_isubs), rank, world)
@@ -1100,8 +1134,8 @@ class GetTOAs(object):
         and gets no TOA."""
         if quiet is None:
             quiet = self.quiet
-        if tscrunch or show_plot or print_phase or print_flux:
-            raise NotImplementedError("tscrunch / show_plot / print_phase / print_flux "
+        if show_plot or print_phase or print_flux:
+            raise NotImplementedError("show_plot / print_phase / print_flux "
                                       "are not available for narrowband TOAs")
         if not quiet:
             print("You are using an experimental functionality of pptoas!")
@@ -1116,7 +1150,7 @@ class GetTOAs(object):
                        (self.ird['DM'] or len(self.ird['wids'])))
         start = time.time()
         datafiles = self.datafiles if datafile is None else [datafile]
-        eng = default_engine()
+        eng = self._engine(False)
         for iarch, datafile in enumerate(datafiles):
             try:
                 d, fname = _load(datafile)
@@ -1128,6 +1162,9 @@ class GetTOAs(object):
                 if not quiet:
                     print("No subints to fit for %s.  Skipping it." % fname)
                 continue
+            if tscrunch:
+                # (the profiles are gathered on the host below: host subints in, host subints out)
+                d = _tscrunched(eng, d, on_device=False)
             self.ok_idatafiles.append(iarch)
             nsub, nchan, nbin = d.nsub, d.nchan, d.nbin
             meta = _archive_meta(d, fname, None)
@@ -1247,9 +1284,13 @@ class GetTOAs(object):
         list over its fitted subints)."""
         if show:
             raise NotImplementedError("plots are outside the accelerated path")
-        eng = default_engine()
+        eng = self._engine(False)
         for iarch, ok_idatafile in enumerate(self.ok_idatafiles):
             data, fname = _load(self.datafiles[ok_idatafile])
+            if getattr(self, "tscrunch", False):
+                # the fit was of the scrunched archive: so is its residual (the reference reloads with
+                # load_data(..., tscrunch=self.tscrunch), pptoas.py:1305-1306)
+                data = _tscrunched(eng, data)
             d = data
             ok_isubs = np.asarray(self.ok_isubs[iarch], dtype=int)
             nok = len(ok_isubs)

@@ -187,7 +187,7 @@ def refusal(opts):
     if opts.psrchive:
         return "--psrchive needs PSRCHIVE, which this package does not use"
     if opts.tscrunch:
-        return "-T/--tscrunch needs PSRCHIVE, which this package does not use"
+        return "-T/--tscrunch needs PSRCHIVE, which this package does not use: scrunch the archives with ppscrunch_run -T first"
     if opts.showplot or opts.saveplot:
         return "--showplot/--saveplot: plots are not available"
     if opts.format is not None and opts.format.lower() == "princeton":

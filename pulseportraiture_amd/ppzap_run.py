@@ -64,7 +64,7 @@ def parser():
 def refusal(opts):
     """The message for an option this command cannot honour, or None."""
     if opts.tscrunch:
-        return "-T/--tscrunch needs PSRCHIVE, which this package does not use"
+        return "-T/--tscrunch needs PSRCHIVE, which this package does not use: scrunch the archives with ppscrunch_run -T first"
     if opts.hist:
         return "--hist: plots are not available"
     if opts.gpus < 1:

@@ -381,6 +381,37 @@ static void aux_rows_calls(pp_ctx* c, const AuxCfg& k, const char* tag) {
         AUX(o, nm, pp_fake_portraits(c, k.dev, dst, in.dtype(), ns, npol, delays.data(), npol == 1 ? nullptr : amps.data(),
                                      npol == 1 ? nullptr : sigmas.data(), 7, 3));
         dev_free(dst); }
+    // scrunching: weights [ns][C], offsets [3], dst [2][1][2][B] and wout [2][2] sized exactly; the first of the two time
+    // groups is longer than a run of the small budget: it straddles runs and carries its partial sums
+    for (int mode : {PP_POL_KEEP, PP_POL_FIRST}) {
+        Outs o;
+        const int32_t t_off[3] = {0, ns - 1, ns}, f_off[3] = {0, C / 2, C};
+        std::vector<double> w((size_t)ns * C, 1.25);
+        w[1] = 0.0;
+        const size_t nout = (size_t)4 * B;
+        double* wout = o.d(4);
+        double* dst = k.dev ? (double*)dev_copy(nullptr, nout * 8) : o.d(nout);
+        snprintf(nm, sizeof nm, "pp_scrunch %s %dx%dx%d %s %s mode %d", tag, ns, C, B, k.f32 ? "f32" : "f64", k.dev ? "device" : "host", mode);
+        AUX(o, nm, pp_scrunch(c, in.src(), in.dtype(), k.dev, ns, 1, C, B, w.data(), 2, t_off, 2, f_off, mode, dst, wout));
+        if (k.dev) dev_free(dst);
+    }
+    // ... and Coherence -> Intensity of three polarisations (the third is not read, and not copied): src [ns][3][C][B] of its own,
+    // sized exactly; the second polarisation's rows lie a plane behind the first's
+    {
+        Outs o;
+        const int32_t t_off[3] = {0, ns - 1, ns}, f_off[3] = {0, C / 2, C};
+        std::vector<double> w((size_t)ns * C, 0.75);
+        w[(size_t)ns * C - 1] = 0.0;
+        std::vector<unsigned char> src3((size_t)ns * 3 * C * B * in.esz, 0);
+        void* dsrc3 = k.dev ? dev_copy(src3.data(), src3.size()) : nullptr;
+        const size_t nout = (size_t)4 * B;
+        double* wout = o.d(4);
+        double* dst = k.dev ? (double*)dev_copy(nullptr, nout * 8) : o.d(nout);
+        snprintf(nm, sizeof nm, "pp_scrunch %s %dx3x%dx%d %s %s sum01", tag, ns, C, B, k.f32 ? "f32" : "f64", k.dev ? "device" : "host");
+        AUX(o, nm, pp_scrunch(c, k.dev ? dsrc3 : (const void*)src3.data(), in.dtype(), k.dev, ns, 3, C, B, w.data(), 2, t_off, 2, f_off,
+                              PP_POL_SUM01, dst, wout));
+        if (k.dev) { dev_free(dst); dev_free(dsrc3); }
+    }
     { Outs o; int shape[2] = {0, 0};
       AUX(o, "pp_model_shape", pp_model_shape(c, k.dev, &shape[0], &shape[1]));
       if (shape[0] != C || shape[1] != B) { fprintf(stderr, "pp_model_shape: %d x %d, not %d x %d\n", shape[0], shape[1], C, B); exit(1); } }
