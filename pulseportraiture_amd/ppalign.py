@@ -14,8 +14,11 @@ archive to the last of the last one (Engine.align_begin / align_add / align_fini
 """
 import numpy as np
 
+from .archive import data_from_arrays, load_archive, named_datafiles, write_archive as write_npz
 from .engine import default_engine
 from .pplib import Dconst, guess_fit_freq, fit_phase_shift, gaussian_profile, get_noise, get_SNR
+from .pptoas import _to_device_once
+from .scrunch import tscrunch as _tscrunch
 
 
 def normalize_portrait(port, method="rms", weights=None, return_norms=False):
@@ -168,49 +171,11 @@ def align_subints(ports, freqs, Ps, noise_stds, model_port, weights=None, SNRs=N
 # ---------------------------------------------------------------------------
 # the walk over archives (ppalign.py:54-243)
 # ---------------------------------------------------------------------------
-# what an .npz archive may carry beside the fields of data_from_arrays
-EXTRA_FIELDS = ("prof_SNR", "state")
-
-
-def load_archive(datafile, engine=None):
-    """(DataBunch, name) of one archive as align_archives takes it: a DataBunch, or an .npz of
-    its fields (pptoas._load) which may also hold prof_SNR (the archive's own S/N, e.g. PSRCHIVE's)
-    and state ('Intensity', 'Stokes' or 'Coherence').  Noise and S/N per channel that the archive
-    lacks are measured on the device, as ppspline_run.load_portrait does.  RuntimeError: it cannot
-    be loaded."""
-    from .pptoas import _load, data_from_arrays
-    from .ppzap_run import LOAD_ERRORS
-    extras, has_snrs = {}, True
-    try:
-        if isinstance(datafile, dict):
-            data, name = _load(datafile)
-            extras = {k: datafile[k] for k in EXTRA_FIELDS if k in datafile}
-        else:
-            if not str(datafile).endswith(".npz"):
-                _load(datafile)         # (raises: PSRFITS needs PSRCHIVE)
-            with np.load(datafile, allow_pickle=True) as z:
-                kw = {k: z[k] for k in z.files}
-            has_snrs = "SNRs" in kw
-            for k in ("DM", "dmc", "backend_delay", "telescope", "telescope_code", "backend", "frontend", "source") + \
-                    EXTRA_FIELDS:
-                if k in kw:
-                    kw[k] = kw[k].item()
-            extras = {k: kw.pop(k) for k in EXTRA_FIELDS if k in kw}
-            kw.setdefault("filename", str(datafile))
-            data, name = data_from_arrays(**kw), str(datafile)
-    except LOAD_ERRORS + (TypeError, KeyError) as err:
-        raise RuntimeError("Cannot load_data(%s): %s" % (datafile, err))
-    eng = engine or default_engine()
-    sub = np.asarray(data.subints)
-    rows = sub.reshape(-1, sub.shape[-1])
-    if data.noise_stds is None:
-        data.noise_stds = eng.channel_noise(rows)[0].reshape(sub.shape[:-1])
-    if not has_snrs or data.SNRs is None:
-        data.SNRs = eng.channel_snrs(rows).reshape(sub.shape[:-1])
-    for k, v in extras.items():
-        data[k] = v
-        setattr(data, k, v)
-    return data, name
+def state_of(data):
+    """The polarisation state of an archive as the alignment takes it: its own, or Stokes for four polarisations and
+    Intensity for anything else.  (scrunch.state_of is another rule -- two polarisations are Coherence there -- and
+    the two give different averages.)"""
+    return getattr(data, "state", None) or ("Stokes" if data.npol == 4 else "Intensity")
 
 
 def _intensity(sub, state):
@@ -250,7 +215,7 @@ def initial_template(initial_guess, pscrunch=True, engine=None):
     The bunch's freqs[0] and ok_ichans[0] are the model's channels."""
     eng = engine or default_engine()
     data, name = load_archive(initial_guess, eng)
-    state = getattr(data, "state", None) or ("Stokes" if data.npol == 4 else "Intensity")
+    state = state_of(data)
     if not pscrunch and data.npol == 1:
         raise IndexError(name)
     isubs = np.arange(data.nsub)
@@ -293,18 +258,13 @@ def write_archive(outfile, aligned_port, total_weights, model_data):
     """The averaged portrait as an .npz of DataBunch fields (what the reference unloads into the
     initial guess's archive, ppalign.py:227-242): one subint, DM = 0, dmc = 0, weights 1 where
     anything was added."""
-    npol, nchan, nbin = aligned_port.shape
-    epoch = model_data.epochs[0]
-    np.savez(outfile, subints=aligned_port[None], freqs=np.asarray(model_data.freqs, dtype=np.float64)[:1],
-             Ps=np.asarray(model_data.Ps, dtype=np.float64)[:1],
-             epochs=np.array([epoch.in_days() if hasattr(epoch, "in_days") else float(epoch)]),
-             weights=(total_weights > 0).astype(np.float64)[None], DM=0.0, dmc=0,
-             nu0=float(model_data.nu0), bw=float(model_data.bw), telescope=str(model_data.telescope),
-             telescope_code=str(model_data.telescope_code), backend=str(model_data.backend),
-             frontend=str(model_data.frontend), source=str(model_data.source),
-             backend_delay=float(model_data.backend_delay))
-    # (np.savez appends .npz to a name without it)
-    return outfile if str(outfile).endswith(".npz") else str(outfile) + ".npz"
+    return write_npz(outfile, dict(
+        subints=aligned_port[None], freqs=np.asarray(model_data.freqs, dtype=np.float64)[:1],
+        Ps=np.asarray(model_data.Ps, dtype=np.float64)[:1], epochs=model_data.epochs[:1],
+        weights=(total_weights > 0).astype(np.float64)[None], DM=0.0, dmc=0, nu0=float(model_data.nu0),
+        bw=float(model_data.bw), telescope=str(model_data.telescope), telescope_code=str(model_data.telescope_code),
+        backend=str(model_data.backend), frontend=str(model_data.frontend), source=str(model_data.source),
+        backend_delay=float(model_data.backend_delay)))
 
 
 def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunch=True,
@@ -326,11 +286,8 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunc
     to <metafile>.algnd.npz.  norm, rot_phase, place (overrides rot_phase), niter, quiet as in the
     reference.  Returns (aligned_port[npol,nchan,nbin], total_weights[nchan])."""
     eng = engine or default_engine()
-    from .pptoas import _to_device_once
-    from .scrunch import tscrunch as _tscrunch
-    from .ppzap_run import list_datafiles
     if isinstance(metafile, str):
-        datafiles = [f for f in list_datafiles(metafile) if f.strip()]
+        datafiles = named_datafiles(metafile)
         if outfile is None:
             outfile = metafile + ".algnd.npz"
     else:
@@ -358,7 +315,7 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunc
                 data, _ = load_archive(datafile, eng)
                 if tscrunch:
                     data = _tscrunch(data, engine=eng)
-                state = getattr(data, "state", None) or ("Stokes" if data.npol == 4 else "Intensity")
+                state = state_of(data)
                 if not pscrunch and data.npol == 1:
                     raise IndexError
                 if not pscrunch and state == "Coherence":
@@ -515,7 +472,6 @@ def _align_one_archive(eng, data, state, npol, model_port, model_freqs, model_ok
 def _like(data, subints, weights):
     """A DataBunch of `subints` on the channels, periods and epochs of `data`, DM = 0 and stored dispersed
     (make_constant_portrait's DM=0.0, dmc=False)."""
-    from .pptoas import data_from_arrays
     n = len(subints)
     return data_from_arrays(subints, np.asarray(data.freqs)[:n], np.asarray(data.Ps)[:n], list(data.epochs)[:n],
                             weights=weights, DM=0.0, dmc=0, telescope=data.telescope,
@@ -539,7 +495,7 @@ def scrunched_profile(archive, engine=None):
     make_constant_portrait(profile=None) takes from PSRCHIVE's T-, P- and F-scrunch, up to a scale)."""
     eng = engine or default_engine()
     data, _ = load_archive(archive, eng)
-    state = getattr(data, "state", None) or ("Stokes" if data.npol == 4 else "Intensity")
+    state = state_of(data)
     isubs = np.arange(data.nsub)
     ports = _dedispersed(eng, _intensity(np.asarray(data.subints, dtype=np.float64), state), data, isubs)
     w = np.asarray(data.weights, dtype=np.float64)
@@ -559,7 +515,7 @@ def average_guess(datafiles, quiet=True, engine=None):
             data, name = load_archive(datafile, eng)
         except RuntimeError:
             continue
-        state = getattr(data, "state", None) or ("Stokes" if data.npol == 4 else "Intensity")
+        state = state_of(data)
         if first is None:
             first = data
             model_freqs = np.asarray(data.freqs, dtype=np.float64)[0]

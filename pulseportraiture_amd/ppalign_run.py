@@ -71,13 +71,14 @@ def refusal(opts):
 def initial_guess(opts, datafiles):
     """The initial guess as align_archives takes it (ppalign.py:341-368)."""
     from . import ppalign
+    from .archive import load_archive
     from .pplib import gaussian_profile
     if opts.initial_guess is None and opts.fwhm is None:
         return ppalign.average_guess(datafiles, quiet=opts.quiet)
     if opts.fwhm is not None:
-        first, _ = ppalign.load_archive(datafiles[0])
+        first, _ = load_archive(datafiles[0])
         return ppalign.constant_portrait(first, gaussian_profile(first.nbin, 0.5, float(opts.fwhm)))
-    guess, _ = ppalign.load_archive(opts.initial_guess)
+    guess, _ = load_archive(opts.initial_guess)
     if guess.nchan == 1:       # a constant portrait of its average profile on the first archive's channels
         return ppalign.constant_portrait(datafiles[0], ppalign.scrunched_profile(guess))
     return guess
@@ -97,12 +98,12 @@ def main(argv=None):
         print("ppalign_run: " + msg, file=sys.stderr)
         return 2
     from . import ppalign
-    from .ppzap_run import list_datafiles
+    from .archive import named_datafiles
     rot_phase = np.float64(opts.rot_phase)
     place = None
     if opts.place is not None:
         rot_phase, place = 0.0, np.float64(opts.place)
-    datafiles = [f for f in list_datafiles(opts.metafile) if f.strip()]
+    datafiles = named_datafiles(opts.metafile)
     outfile = opts.metafile + ".algnd.npz" if opts.outfile is None else opts.outfile
     if not datafiles:
         print("ppalign_run: %s names no archive" % opts.metafile, file=sys.stderr)

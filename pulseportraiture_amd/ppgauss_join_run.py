@@ -12,7 +12,7 @@ directory); a joinfile given with -j also provides the parameters to start from.
 import sys
 
 from . import ppgauss_run
-from .ppzap_run import list_datafiles
+from .archive import named_datafiles
 
 MODULE = ppgauss_run.JOIN_MODULE
 MAX_BANDS = 16          # Engine.GAUSS_FIT_MAX_JOIN
@@ -47,7 +47,7 @@ def main(argv=None):
     opts = parser().parse_args(argv)
     msg = refusal(opts)
     if msg is None:
-        datafiles = [f.strip() for f in list_datafiles(opts.metafile) if f.strip()]
+        datafiles = [f.strip() for f in named_datafiles(opts.metafile)]
         msg = refusal(opts, datafiles)
     if msg is not None:
         print("ppgauss_join_run: " + msg, file=sys.stderr)

@@ -17,8 +17,8 @@ import sys
 
 import numpy as np
 
+from .archive import load_archive_file, named_datafiles
 from .pplib import default_model
-from .ppzap_run import list_datafiles
 
 MODULE = "pulseportraiture_amd.ppgauss_run"
 
@@ -148,20 +148,9 @@ def fit_refusal(opts):
 
 
 def load_bunch(datafile):
-    """The DataBunch of an .npz archive.  An archive without SNRs gets them measured on the
-    device (Engine.channel_snrs), one without noise_stds its power-spectrum noise."""
-    from .engine import default_engine
-    from .pptoas import _load
-    with np.load(datafile, allow_pickle=True) as z:
-        has_snrs = "SNRs" in z.files
-    data, _ = _load(datafile)
-    eng = default_engine()
-    sub = np.asarray(data.subints)
-    if data.noise_stds is None:
-        data.noise_stds = eng.channel_noise(sub.reshape(-1, sub.shape[-1]))[0].reshape(sub.shape[:-1])
-    if not has_snrs:
-        data.SNRs = eng.channel_snrs(sub.reshape(-1, sub.shape[-1])).reshape(sub.shape[:-1])
-    return data
+    """The DataBunch of an .npz archive, with the noise and S/N it lacks measured on the device
+    (archive.load_archive_file: a file that cannot be read raises NumPy's own error)."""
+    return load_archive_file(datafile)[0]
 
 
 def load_portrait(datafile):
@@ -175,7 +164,7 @@ def main(argv=None):
     opts = parser().parse_args(argv)
     msg = refusal(opts)
     if msg is None:
-        datafiles = [f for f in list_datafiles(opts.datafile) if f.strip()]
+        datafiles = named_datafiles(opts.datafile)
         msg = refusal(opts, datafiles)
     if msg is not None:
         print("ppgauss_run: " + msg, file=sys.stderr)

@@ -14,7 +14,14 @@ import sys
 
 import numpy as np
 
-from .engine import default_engine
+
+def default_engine(device=0):
+    """engine.default_engine.  The engine (and with it the HIP library) is loaded by the first call that needs a
+    device, not by importing this module: DataBunch and the host helpers here stand below modules that never touch
+    one."""
+    from .engine import default_engine as engine_default
+    return engine_default(device)
+
 
 # ---- settings (pplib.py:45-83); Dconst must be bit-identical ---------------
 Dconst_exact = 4.148808e3
@@ -611,7 +618,7 @@ def fake_pulsar_tables(model, par, nsub=1, npol=1, nchan=512, nu0=1500.0, bw=800
     scattering it is to carry.
     model: a parsed .gmodel (gmodel.parse_gmodel); par: a parfile.psr_par; rng: the generator of the
     scintillation draws."""
-    from .pptoas import MJD
+    from .archive import MJD
     chanwidth = bw / nchan
     lofreq = nu0 - (bw / 2)
     freqs = np.linspace(lofreq + (chanwidth / 2.0), lofreq + bw - (chanwidth / 2.0), nchan)
@@ -684,7 +691,7 @@ def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.npz", nsub=1, np
 
     modelfile is the .gmodel file of the Gaussian-component model; ephemeris a .par file (parfile.psr_par:
     PSR or PSRJ, RAJ, DECJ, F0 or P0, PEPOCH, DM); outfile the .npz to write -- the fields of
-    pptoas.data_from_arrays, which every command here reads -- or None.  nsub, npol, nchan, nbin, nu0 [MHz], bw
+    archive.data_from_arrays, which every command here reads -- or None.  nsub, npol, nchan, nbin, nu0 [MHz], bw
     [MHz], tsub [s] shape the data.  phase [rot] delays every subint, with respect to nu0; dDM [cm**-3 pc] is added
     to the ephemeris DM, about nu0.  start_MJD: an MJD, a float, or None for PEPOCH.  weights [nsub,nchan] are
     stored, the data are not zeroed.  noise_stds and scales: a float or one value per channel.  dedispersed=True
@@ -713,8 +720,8 @@ def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.npz", nsub=1, np
     the reference overwrites `phase` by phase_transform(...) inside its loop over subints and polarisations, so the
     transform compounds; here it is applied once to the caller's phase."""
     from . import parfile
+    from .archive import data_from_arrays, write_archive
     from .gmodel import read_gmodel
-    from .pptoas import data_from_arrays
     import torch
     dtype = np.dtype(dtype)
     if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -752,7 +759,7 @@ def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.npz", nsub=1, np
                   dmc=int(t.dmc), doppler_factors=np.ones(nsub), telescope=str(telescope), bw=float(bw),
                   nu0=float(nu0), subtimes=np.full(nsub, float(tsub)), source=str(par.PSR))
     if outfile is not None:
-        np.savez(outfile, epochs=np.array([e.in_days() for e in t.epochs]), **fields)
+        write_archive(outfile, dict(fields, epochs=t.epochs))
         if not quiet:
             print("\nUnloaded %s.\n" % outfile)
     data = data_from_arrays(epochs=t.epochs, filename="arrays" if outfile is None else str(outfile), **fields)
@@ -774,6 +781,7 @@ def load_data(filename, state=None, dedisperse=False, dededisperse=False, tscrun
     returned after remove_baseline, and the fit ignores the DC term.  state conversions other than to 'Intensity'
     raise.  refresh_arch and return_arch have nothing to act on."""
     from . import scrunch as sc
+    from .archive import load_archive
     if rm_baseline:
         raise NotImplementedError("load_data(rm_baseline=True): baseline removal is PSRCHIVE's; an .npz archive holds "
                                   "the data it returned after remove_baseline")
@@ -782,9 +790,8 @@ def load_data(filename, state=None, dedisperse=False, dededisperse=False, tscrun
         data = DataBunch(**{k: v for k, v in filename.items()})
         data.setdefault("filename", "arrays")
         if data.get("noise_stds") is None or data.get("SNRs") is None:
-            sc._measured(eng, data)
+            sc.measured(eng, data)      # (S/N 0 for a dead row, as in the scrunched bunches that follow)
     else:
-        from .ppalign import load_archive
         data, _ = load_archive(filename, eng)
     if not quiet:
         print("\nReading data from %s on source %s..." % (data.filename, data.source))

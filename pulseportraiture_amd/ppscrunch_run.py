@@ -7,15 +7,9 @@ import argparse
 import os
 import sys
 
-import numpy as np
+from . import archive
 
 MODULE = "pulseportraiture_amd.ppscrunch_run"
-
-# what an archive written here holds: the fields of data_from_arrays, and what ppalign.load_archive reads beside them
-ARRAY_FIELDS = ("subints", "freqs", "Ps", "weights", "noise_stds", "SNRs", "doppler_factors", "subtimes",
-                "parallactic_angles")
-SCALAR_FIELDS = ("DM", "dmc", "backend_delay", "telescope", "telescope_code", "backend", "frontend", "bw", "nu0",
-                 "source", "state")
 
 
 def parser():
@@ -59,15 +53,11 @@ def output_name(datafile, ext):
 
 
 def write_archive(outfile, data):
-    """The DataBunch as an .npz pptoas._load and ppalign.load_archive read back: the fields of data_from_arrays plus
-    state, noise_stds and SNRs; epochs as float days."""
-    sub = data.subints
-    fields = {k: np.asarray(data[k]) for k in ARRAY_FIELDS if k != "subints" and data.get(k) is not None}
-    fields["subints"] = sub.cpu().numpy() if hasattr(sub, "is_cuda") else np.asarray(sub)
-    fields["epochs"] = np.array([e.in_days() for e in data.epochs])
-    fields.update({k: data[k] for k in SCALAR_FIELDS if data.get(k) is not None})
-    np.savez(outfile, **fields)
-    return outfile if str(outfile).endswith(".npz") else str(outfile) + ".npz"
+    """The DataBunch as an .npz archive.load_bunch and archive.load_archive read back: the fields of data_from_arrays
+    (noise_stds and SNRs among them) plus state; epochs as float days.  Not prof_SNR: that was the S/N of the archive
+    before it was scrunched."""
+    names = archive.ARRAY_FIELDS + archive.SCALAR_FIELDS + archive.EXTRA_FIELDS
+    return archive.write_archive(outfile, {k: data.get(k) for k in names if k != "prof_SNR"})
 
 
 def scrunched(data, opts, engine=None):
@@ -93,10 +83,8 @@ def main(argv=None):
         print("ppscrunch_run: " + msg, file=sys.stderr)
         return 2
     from .engine import default_engine
-    from .ppalign import load_archive
-    from .ppzap_run import list_datafiles
     from .scrunch import state_of
-    datafiles = [f for f in list_datafiles(opts.datafiles) if f.strip()]
+    datafiles = archive.named_datafiles(opts.datafiles)
     if opts.outfile is not None and len(datafiles) != 1:
         print("ppscrunch_run: -o names one output, %s names %d archives" % (opts.datafiles, len(datafiles)), file=sys.stderr)
         return 2
@@ -104,7 +92,7 @@ def main(argv=None):
     written = []
     for datafile in datafiles:
         try:
-            data, _ = load_archive(datafile, eng)
+            data, _ = archive.load_archive(datafile, eng)
         except RuntimeError as err:
             if not opts.quiet:
                 print("Cannot load_data(%s).  Skipping it." % datafile)

@@ -8,9 +8,7 @@ DataPortrait.make_spline_model(smooth=False) on the device and written as a .spl
 import argparse
 import sys
 
-import numpy as np
-
-from .ppzap_run import list_datafiles
+from .archive import load_archive_file, named_datafiles
 
 MODULE = "pulseportraiture_amd.ppspline_run"
 SMOOTH_MODULE = "pulseportraiture_amd.ppspline_smooth_run"
@@ -77,21 +75,10 @@ def refusal(opts, datafiles=None, smooth=False):
 
 
 def load_portrait(datafile):
-    """The DataPortrait of an .npz archive.  An archive without SNRs gets them measured on the
-    device (Engine.channel_snrs), one without noise_stds its power-spectrum noise."""
-    from .engine import default_engine
+    """The DataPortrait of an .npz archive, with the noise and S/N it lacks measured on the device
+    (archive.load_archive_file: a file that cannot be read raises NumPy's own error)."""
     from .ppspline import DataPortrait
-    from .pptoas import _load
-    with np.load(datafile, allow_pickle=True) as z:
-        has_snrs = "SNRs" in z.files
-    data, _ = _load(datafile)
-    eng = default_engine()
-    sub = np.asarray(data.subints)
-    if data.noise_stds is None:
-        data.noise_stds = eng.channel_noise(sub.reshape(-1, sub.shape[-1]))[0].reshape(sub.shape[:-1])
-    if not has_snrs:
-        data.SNRs = eng.channel_snrs(sub.reshape(-1, sub.shape[-1])).reshape(sub.shape[:-1])
-    return DataPortrait(data, quiet=True)
+    return DataPortrait(load_archive_file(datafile)[0], quiet=True)
 
 
 def main(argv=None, smooth=False):
@@ -100,7 +87,7 @@ def main(argv=None, smooth=False):
     opts = parser(smooth).parse_args(argv)
     msg = refusal(opts, smooth=smooth)
     if msg is None:
-        datafiles = [f for f in list_datafiles(opts.datafile) if f.strip()]
+        datafiles = named_datafiles(opts.datafile)
         msg = refusal(opts, datafiles, smooth=smooth)
     if msg is not None:
         print(("ppspline_smooth_run: " if smooth else "ppspline_run: ") + msg, file=sys.stderr)

@@ -14,6 +14,7 @@ import sys
 
 import numpy as np
 
+from .archive import LOAD_ERRORS, list_datafiles, load_bunch
 from .pptoas_run import PG_TIMEOUT_S, _backend, launch
 
 MODULE = "pulseportraiture_amd.ppzap_run"
@@ -74,28 +75,6 @@ def refusal(opts):
     return None
 
 
-def list_datafiles(datafiles):
-    """The archives named by -d: the lines of a metafile when -d names a text file (the
-    reference asks `file` whether it is ASCII, pplib.py:3015-3031), else -d itself."""
-    try:
-        with open(datafiles, "rb") as f:
-            head = f.read(1 << 16)
-    except OSError:
-        return [datafiles]
-    try:
-        if b"\0" in head:
-            return [datafiles]
-        head.decode("utf-8")
-    except UnicodeDecodeError:
-        return [datafiles]
-    with open(datafiles) as f:
-        return [line.rstrip("\n") for line in f]
-
-
-# what loading an archive that is missing, not an .npz of DataBunch fields, or damaged raises
-LOAD_ERRORS = (RuntimeError, OSError, ValueError)
-
-
 def _summary(nzap, nchan, what, opts):
     """The reference's closing line, or (no channel examined, where the reference divides by
     zero) a message and exit code 1."""
@@ -112,12 +91,11 @@ def noise_method(opts):
     """ppzap.py:200-241, with each zap list paired with its own archive."""
     from .engine import default_engine
     from .ppzap import get_zap_channels, print_paz_cmds
-    from .pptoas import _load
     nstd = float(opts.nstd)
     nchan, names, zap_channels = 0, [], []
     for datafile in list_datafiles(opts.datafiles):
         try:
-            data, _ = _load(datafile)
+            data, _ = load_bunch(datafile)
         except LOAD_ERRORS:
             if not opts.quiet:
                 print("Cannot load_data(%s).  Skipping it." % datafile)

@@ -16,6 +16,7 @@ periods from the anchor, so the summed profile's bin 0 has the anchor's pulse ph
 dP is the drift of the period over the group.  PSRCHIVE snaps with the predictor, which an .npz does not have."""
 import numpy as np
 
+from .archive import MJD, measure
 from .engine import default_engine
 from .pplib import DataBunch
 
@@ -54,7 +55,6 @@ def _wmean(x, w):
 def group_epoch(epochs, Ws, P):
     """The epoch rule of this module's docstring for one time group: epochs (MJD objects), their summed weights and
     the group's period [s].  A group without a good member gets the plain mean of its epochs, not snapped."""
-    from .pptoas import MJD
     Ws = np.asarray(Ws, dtype=np.float64)
     offs = np.array([(e - epochs[0]).in_days() for e in epochs])
     good = np.where(Ws > 0)[0]
@@ -66,16 +66,17 @@ def group_epoch(epochs, Ws, P):
     return epochs[r] + MJD(0, float(k * P / 86400.0))
 
 
-def _measured(eng, d):
-    """noise_stds and SNRs of d's rows, on the device (get_noise and get_SNR of every row); a row of zeros -- a dead
-    cell -- has no noise to divide by: its S/N is 0."""
-    rows = d.subints.reshape(-1, d.nbin)
+def measured(eng, d):
+    """noise_stds and SNRs [nsub,npol,nchan] of d's rows, on the device (archive.measure).  Here, and for the bunch that
+    pplib.load_data is handed, a row of zeros -- a dead cell, with no noise to divide by -- has S/N 0, not the NaN
+    that a loaded archive gets."""
+    measure(eng, d)
     shape = (d.nsub, d.npol, d.nchan)
-    d.noise_stds = eng.channel_noise(rows)[0].reshape(shape)
-    d.SNRs = np.nan_to_num(eng.channel_snrs(rows), nan=0.0).reshape(shape)
+    d.noise_stds = d.noise_stds.reshape(shape)
+    d.SNRs = np.nan_to_num(d.SNRs, nan=0.0).reshape(shape)
 
 
-def _finish(eng, d, new, subints, weights, measure=True):
+def _finish(eng, d, new, subints, weights, remeasure=True):
     """The new bunch: d's fields, `new` over them, and what follows from the weights as in data_from_arrays."""
     out = DataBunch(**{k: v for k, v in d.items()})
     out.update(new)
@@ -84,8 +85,8 @@ def _finish(eng, d, new, subints, weights, measure=True):
     out.update(subints=subints, weights=weights, nsub=nsub, npol=npol, nchan=nchan, nbin=nbin, ok_ichans=ok_ichans,
                ok_isubs=np.array([i for i in range(nsub) if len(ok_ichans[i])], dtype=int),
                masks=(weights > 0)[:, None, :, None], integration_length=float(np.sum(out["subtimes"])))
-    if measure:
-        _measured(eng, out)
+    if remeasure:
+        measured(eng, out)
     return out
 
 
@@ -162,7 +163,7 @@ def pscrunch(d, engine=None):
         raise ValueError("unknown polarisation state '%s'" % state)
     if state == "Intensity" or int(d.npol) == 1:
         return _finish(eng, d, dict(state="Intensity"), _subints4(d), np.asarray(d.weights, dtype=np.float64),
-                       measure=d.noise_stds is None)
+                       remeasure=d.noise_stds is None)
     # (weight 1 for every row that counts: the rows themselves, not a weighted mean; zapped rows come out as zeros)
     w = _live(d.weights)
     out, _ = eng.scrunch(_subints4(d), (w != 0).astype(np.float64), pol_mode="sum01" if state == "Coherence" else "first")
@@ -185,7 +186,7 @@ def dedisperse(d, engine=None):
     eng = engine or default_engine()
     w = np.asarray(d.weights, dtype=np.float64)
     if d.dmc:
-        return _finish(eng, d, {}, _subints4(d), w, measure=d.noise_stds is None)
+        return _finish(eng, d, {}, _subints4(d), w, remeasure=d.noise_stds is None)
     return _finish(eng, d, dict(dmc=1), _rotated(eng, d, +1.0) if d.DM else _subints4(d), w)
 
 
@@ -194,5 +195,5 @@ def dededisperse(d, engine=None):
     eng = engine or default_engine()
     w = np.asarray(d.weights, dtype=np.float64)
     if not d.dmc:
-        return _finish(eng, d, {}, _subints4(d), w, measure=d.noise_stds is None)
+        return _finish(eng, d, {}, _subints4(d), w, remeasure=d.noise_stds is None)
     return _finish(eng, d, dict(dmc=0), _rotated(eng, d, -1.0) if d.DM else _subints4(d), w)

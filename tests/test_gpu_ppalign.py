@@ -366,7 +366,7 @@ def _write_archives(g, tmp):
 
 
 def test_ppalign_run_equals_the_golden(tmp_path):
-    from pulseportraiture_amd.pptoas import _load
+    from pulseportraiture_amd.archive import load_bunch as _load
     g, gc = _golden("ppalign_same"), _golden("ppalign_same_norms")
     meta = _write_archives(g, str(tmp_path))
     out = _run("ppalign_run", ["-M", meta, "-I", "init.npz", "--niter", "2", "-N", "prof", "-C", "10", "-o", "out.npz"],
@@ -387,7 +387,7 @@ def test_ppalign_run_with_a_gaussian_guess_and_with_none(tmp_path):
     is the weighted mean of the dedispersed subints, formed here in NumPy."""
     from oracle import pptoas_oracle as orc
     from pulseportraiture_amd import ppalign
-    from pulseportraiture_amd.pptoas import _load
+    from pulseportraiture_amd.archive import load_bunch as _load
     g = _golden("ppalign_mapped")
     meta = _write_archives(g, str(tmp_path))
     _run("ppalign_run", ["-M", meta, "-g", "0.05", "-o", "gauss.npz"], tmp_path)

@@ -170,7 +170,7 @@ def test_a_delay_of_one_bin_is_a_roll(eng, npol, nbin):
 @pytest.mark.parametrize("nbin", [32, 100])
 def test_an_archive_does_not_depend_on_the_chunk_size(eng, tmp_path, monkeypatch, nbin):
     from pulseportraiture_amd import pplib
-    from pulseportraiture_amd.pptoas import _load
+    from pulseportraiture_amd.archive import load_bunch as _load
     out = []
     for chunk in (1, 3, None):
         monkeypatch.setattr(pplib, "fake_chunk_subints", chunk)

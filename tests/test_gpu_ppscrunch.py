@@ -238,7 +238,7 @@ def _run(module, args, cwd, timeout=300):
 
 
 def test_get_TOAs_tscrunch_end_to_end(tmp_path):
-    from pulseportraiture_amd import pptoas, scrunch
+    from pulseportraiture_amd import archive, pptoas, scrunch
     from pulseportraiture_amd.engine import default_engine
     eng = default_engine()
     name = _fake_archive(tmp_path / "fake.npz", seed=11)
@@ -247,7 +247,7 @@ def test_get_TOAs_tscrunch_end_to_end(tmp_path):
     gt.get_TOAs(tscrunch=True, **kw)
     assert len(gt.TOA_list) == 1 and len(gt.phis[0]) == 1
     # the same archive scrunched by the sequential restatement, through the path that was there before
-    d, _ = pptoas._load(name)
+    d, _ = archive.load_bunch(name)
     ref, anchor = _scrunched_by_the_test(eng, d)
     own = scrunch.tscrunch(d, engine=eng)
     # the product's bookkeeping against the test's
@@ -289,12 +289,12 @@ def test_get_TOAs_tscrunch_end_to_end(tmp_path):
 
 
 def test_align_archives_tscrunch_equals_prescrunched_copies(tmp_path):
-    from pulseportraiture_amd import ppalign, scrunch
+    from pulseportraiture_amd import archive, ppalign, scrunch
     from pulseportraiture_amd.engine import default_engine
     eng = default_engine()
     names = [_fake_archive(tmp_path / ("fake%d.npz" % i), seed=20 + i) for i in range(2)]
     got, gotw = ppalign.align_archives(names, names[0], tscrunch=True, outfile=str(tmp_path / "a.npz"), quiet=True, engine=eng)
-    copies = [scrunch.tscrunch(ppalign.load_archive(n, eng)[0], engine=eng) for n in names]
+    copies = [scrunch.tscrunch(archive.load_archive(n, eng)[0], engine=eng) for n in names]
     assert all(c.nsub == 1 for c in copies)
     want, wantw = ppalign.align_archives(copies, names[0], outfile=str(tmp_path / "b.npz"), quiet=True, engine=eng)
     assert np.array_equal(got, want) and np.array_equal(gotw, wantw) and got.any()
@@ -304,7 +304,7 @@ def test_archive_operations_on_host_arrays_and_device_tensors_agree(tmp_path):
     """Every archive operation on a dispersed two-polarisation archive, from host subints and from a device tensor: the
     same kernels in the same order, so the same bits; and load_data's fully scrunched profile is the restatement's."""
     import torch
-    from pulseportraiture_amd import pplib, ppalign, scrunch
+    from pulseportraiture_amd import archive, pplib, ppalign, scrunch
     from pulseportraiture_amd.engine import default_engine
     from pulseportraiture_amd.pplib import DataBunch, make_fake_pulsar
     eng = default_engine()
@@ -314,7 +314,7 @@ def test_archive_operations_on_host_arrays_and_device_tensors_agree(tmp_path):
     name = str(tmp_path / "coh.npz")
     make_fake_pulsar(GMODEL, PARFILE, outfile=name, nsub=4, npol=2, nchan=16, nbin=128, weights=w, noise_stds=0.01,
                      state="Coherence", seed=5, quiet=True, engine=eng)
-    host, _ = ppalign.load_archive(name, eng)
+    host, _ = archive.load_archive(name, eng)
     host.state = "Coherence"
     dev = DataBunch(**{k: v for k, v in host.items()})
     dev.subints = torch.from_numpy(np.ascontiguousarray(host.subints)).to("cuda:0")

@@ -73,7 +73,8 @@ def test_gaussian_profile_is_the_references():
 
 def test_the_output_archive_round_trips(tmp_path):
     from pulseportraiture_amd.ppalign import write_archive
-    from pulseportraiture_amd.pptoas import _load, data_from_arrays
+    from pulseportraiture_amd.archive import load_bunch as _load
+    from pulseportraiture_amd.pptoas import data_from_arrays
     rng = np.random.default_rng(3)
     port = rng.standard_normal((4, 6, 32))
     totw = np.array([2.0, 0.0, 1.5, -1.0, 3.0, 0.0])

@@ -9,7 +9,7 @@ import sys
 import numpy as np
 import pytest
 
-from pulseportraiture_amd import _lib, pplib, pptoas, ppscrunch_run, scrunch
+from pulseportraiture_amd import _lib, archive, pplib, pptoas, ppscrunch_run, scrunch
 from pulseportraiture_amd.pptoas import MJD
 from tests import scrunch_refs as sr
 
@@ -198,7 +198,7 @@ def test_ppscrunch_run_parser_and_round_trip(tmp_path):
     eng = NumpyEngine()
     t = ppscrunch_run.scrunched(_bunch(), ppscrunch_run.parser().parse_args("-d a --setnsub 2 -p".split()), eng)
     name = ppscrunch_run.write_archive(str(tmp_path / "t.scr.npz"), t)
-    back, fname = pptoas._load(name)
+    back, fname = archive.load_bunch(name)
     assert fname == name and back.state == "Intensity"
     for k in ("subints", "freqs", "Ps", "weights", "noise_stds", "SNRs", "doppler_factors", "subtimes",
               "parallactic_angles", "ok_isubs", "masks"):
@@ -266,14 +266,14 @@ def test_get_TOAs_tscrunch_fits_one_subint_per_archive():
 
 def test_good_channel_counts_of_the_scrunched_subint(tmp_path):
     d = _bunch()
-    assert pptoas._good_channel_counts(d, tscrunch=True) == [6] and pptoas._good_channel_counts(d) == [5, 5, 5, 5]
+    assert archive.good_channel_counts(d, tscrunch=True) == [6] and archive.good_channel_counts(d) == [5, 5, 5, 5]
     w = np.zeros((3, 5))
     w[0, 1] = w[2, 1] = w[1, 4] = 1.0
     np.savez(tmp_path / "w.npz", subints=np.zeros((3, 1, 5, 8)), weights=w)
-    assert pptoas._good_channel_counts(str(tmp_path / "w.npz"), tscrunch=True) == [2]
-    assert pptoas._good_channel_counts(str(tmp_path / "w.npz")) == [1, 1, 1]
+    assert archive.good_channel_counts(str(tmp_path / "w.npz"), tscrunch=True) == [2]
+    assert archive.good_channel_counts(str(tmp_path / "w.npz")) == [1, 1, 1]
     np.savez(tmp_path / "g.npz", subints=np.zeros((3, 1, 5, 8)))
-    assert pptoas._good_channel_counts(str(tmp_path / "g.npz"), tscrunch=True) == [5]
+    assert archive.good_channel_counts(str(tmp_path / "g.npz"), tscrunch=True) == [5]
 
 
 class _ZapEngine(NumpyEngine):

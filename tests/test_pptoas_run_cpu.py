@@ -11,7 +11,7 @@ import time
 import numpy as np
 import pytest
 
-from pulseportraiture_amd import pptoas, pptoas_run
+from pulseportraiture_amd import archive, pptoas, pptoas_run
 from pulseportraiture_amd.dist import shard_range
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -80,11 +80,11 @@ def test_good_channel_counts_read_weights_only(tmp_path):
     w[3, :4] = 0
     f = tmp_path / "a.npz"
     np.savez(f, subints=np.zeros((4, 1, 6, 8)), weights=w)
-    assert pptoas._good_channel_counts(str(f)) == [1, 6, 2]
+    assert archive.good_channel_counts(str(f)) == [1, 6, 2]
     g = tmp_path / "b.npz"
     np.savez(g, subints=np.zeros((3, 1, 5, 8)))
-    assert pptoas._good_channel_counts(str(g)) == [5, 5, 5]
-    assert pptoas._good_channel_counts(str(tmp_path / "x.fits")) == []
+    assert archive.good_channel_counts(str(g)) == [5, 5, 5]
+    assert archive.good_channel_counts(str(tmp_path / "x.fits")) == []
 
 
 # ---------------------------------------------------------------------------

@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-from pulseportraiture_amd import ppzap_run
+from pulseportraiture_amd import archive, ppzap_run
 from pulseportraiture_amd.ppzap import print_paz_cmds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,8 +84,8 @@ def test_archives_that_cannot_be_loaded_are_skipped(tmp_path, capsys, monkeypatc
     assert ppzap_run.main(["-d", "x.fits"]) == 1
     assert capsys.readouterr().out == "Cannot load_data(x.fits).  Skipping it.\nNothing to zap.\n"
     (tmp_path / "list.txt").write_text("x.fits\nmissing.npz\n")
-    assert ppzap_run.list_datafiles("list.txt") == ["x.fits", "missing.npz"]
+    assert archive.list_datafiles("list.txt") == ["x.fits", "missing.npz"]
     assert ppzap_run.main(["-d", "list.txt"]) == 1
     assert capsys.readouterr().out == ("Cannot load_data(x.fits).  Skipping it.\n"
                                        "Cannot load_data(missing.npz).  Skipping it.\nNothing to zap.\n")
-    assert ppzap_run.list_datafiles("absent.txt") == ["absent.txt"]
+    assert archive.list_datafiles("absent.txt") == ["absent.txt"]
