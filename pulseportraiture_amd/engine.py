@@ -184,6 +184,32 @@ class Engine(object):
         _check(self._lib.pp_get_option(self._ctx, name.encode(), C.byref(v)), "pp_get_option(%s)" % name)
         return v.value
 
+    @contextlib.contextmanager
+    def options(self, **values):
+        """The named engine options set to `values` for the calls made inside the block, and back
+        to what get_option reported on entry after it -- also when the block raises.  An unknown
+        name raises before anything is changed; blocks nest."""
+        saved = [(name, self.get_option(name)) for name in values]
+        try:
+            for name, _ in saved:
+                self.set_option(name, values[name])
+            yield
+        finally:
+            for name, was in reversed(saved):
+                self.set_option(name, was)
+
+    @contextlib.contextmanager
+    def profiled(self):
+        """Kernel timing (option `profile`) switched on and the counters cleared for the calls made
+        inside the block; yields a dict that holds kernel_times() of those calls after the block."""
+        times = {}
+        with self.options(profile=1):
+            self.kernel_times(reset=True)
+            try:
+                yield times
+            finally:
+                times.update(self.kernel_times(reset=True))
+
     def synchronize(self):
         _check(self._lib.pp_synchronize(self._ctx), "pp_synchronize")
 
@@ -486,16 +512,6 @@ class Engine(object):
                "pp_rfft_rows")
         return out
 
-    @contextlib.contextmanager
-    def _fps_finish(self, finish):
-        """The `fps_finish` option (how fit_phase_shift ends: SciPy's simplex, or Newton) set for
-        the calls made inside, and back to its default after them."""
-        self.set_option("fps_finish", 1 if finish == 'simplex' else 0)
-        try:
-            yield
-        finally:
-            self.set_option("fps_finish", 0)
-
     def fit_phase_shift_batch(self, data, model, noise=None, bounds=(-0.5, 0.5),
                               Ns=100, finish='newton'):
         """1-D FFTFIT of nprof profile pairs: Ns-point brute grid over `bounds` (both
@@ -510,7 +526,7 @@ class Engine(object):
         m = _f64(np.atleast_2d(model), (nprof, nbin))
         nz = self._noise_arg(noise, nprof)
         out = np.empty((nprof, 7))
-        with self._fps_finish(finish):
+        with self.options(fps_finish=1 if finish == 'simplex' else 0):
             _check(self._lib.pp_fit_phase_shift_batch(
                 self._ctx, _dp(d), _dp(m), _dp(nz), nprof, nbin, float(bounds[0]),
                 float(bounds[1]), int(Ns), _dp(out)), "pp_fit_phase_shift_batch")
@@ -558,7 +574,7 @@ class Engine(object):
         w = _f64(weights, (nsub, nchan))
         mp = _f64(np.broadcast_to(np.asarray(model_profs, dtype=np.float64), (nsub, nbin)))
         out = np.empty((nsub, 7))
-        with self._fps_finish(finish):
+        with self.options(fps_finish=1 if finish == 'simplex' else 0):
             _check(self._lib.pp_reference_phase_seed(
                 self._ctx, src, dtype, on_dev, nsub, nchan, nbin, _dp(freqs), fstride, _dp(P), _dp(par),
                 float(nu_DM), float(nu_GM), _dp(w), _dp(mp), float(bounds[0]), float(bounds[1]), int(Ns),
@@ -1175,7 +1191,8 @@ def default_engine(device=0):
 
 
 _WHILE_PENDING = ("poll", "wait", "close")      # what may be called while a submitted batch runs
-_WHILE_QUEUED = ("enqueue", "fit_batch", "collect", "close", "set_option", "get_option", "kernel_times", "synchronize")
+_WHILE_QUEUED = ("enqueue", "fit_batch", "collect", "close", "set_option", "get_option", "options", "profiled",
+                 "kernel_times", "synchronize")
 
 
 def _fresh_waits(fn):

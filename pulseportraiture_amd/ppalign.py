@@ -454,13 +454,9 @@ def _align_one_archive(eng, data, state, npol, model_port, model_freqs, model_ok
     # Taylor model of every channel's sums, whose certificate admits a truncation of ~1e-10 at hundreds of harmonics and
     # a DM that is off by a few 1e-4 -- plenty for a TOA, but the average is the next iteration's template and is held to
     # 1e-12 of the reference's
-    taylor = eng.get_option("taylor")
-    eng.set_option("taylor", 0)
-    try:
+    with eng.options(taylor=0):
         phase, DM, nu_ref, scales, _ = fit_subints(eng, ports, f2, Ps, errs, wts, snrs, mask, templates, DM_guess,
                                                    fit_dm, slots=slots, host_ports=host)
-    finally:
-        eng.set_option("taylor", taylor)
     with np.errstate(divide="ignore", invalid="ignore"):
         w_acc = np.where(added & (mask > 0), scales / errs ** 2.0, 0.0)
     eng.align_add(dev4, f2, Ps, phase, DM, nu_ref, w_acc, cmap)

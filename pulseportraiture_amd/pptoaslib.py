@@ -102,7 +102,6 @@ def _fit_with_bounds(eng, data, freqs, P, init_params, errs, nu_fits, nu_outs, f
     nu_fits = [fmean if (v is None or (isinstance(v, float) and np.isnan(v))) else float(v) for v in nu_fits]
     common = dict(errs=errs, nu_fits=[nu_fits], log10_tau=log10_tau, option=option, is_toa=is_toa)
     active = {}
-    max_iter = eng.get_option("max_iter")       # (the caller's setting: restored after the evaluate-only calls)
     nfeval, duration = 0, 0.0
     for _ in range(12):
         fl = [1 if (f and j not in active) else 0 for j, f in enumerate(flags)]
@@ -125,12 +124,9 @@ def _fit_with_bounds(eng, data, freqs, P, init_params, errs, nu_fits, nu_outs, f
             continue
         x = xs
         # gradient of the full problem at x: may a fixed parameter move back inside?
-        eng.set_option("max_iter", 0)
-        try:
+        with eng.options(max_iter=0):       # (evaluate only; the caller's setting comes back)
             r = eng.fit_batch(data, freqs, P, x, nu_outs=[nu_fits], fit_flags=flags, objective=True,
                               method='newton', **common)
-        finally:
-            eng.set_option("max_iter", max_iter)
         g = r["obj_grad"][0]
         nfeval += int(r["nfeval"][0])
         duration += r["duration"]
@@ -140,11 +136,8 @@ def _fit_with_bounds(eng, data, freqs, P, init_params, errs, nu_fits, nu_outs, f
         for j in free:
             del active[j]
     # post-fit stage at x with the caller's flags and output frequencies
-    eng.set_option("max_iter", 0)
-    try:
+    with eng.options(max_iter=0):
         res = eng.fit_batch(data, freqs, P, x, nu_outs=[nu_outs], fit_flags=flags, method='newton', **common)
-    finally:
-        eng.set_option("max_iter", max_iter)
     res["return_code"][:] = 2 if not active else 0     # (TNC's table: XCONVERGED / LOCALMINIMUM at a bound)
     # what the whole bounded fit cost, not its closing evaluate-only call
     res["nfeval"][:] = nfeval + int(res["nfeval"][0])

@@ -12,22 +12,16 @@ SciPy's f64 splev from a long-double de Boor recurrence, floored at 1e-13 of the
 the construction is, else 1e-13 of the scale (eigenvectors: scaled by lam_max / gap).
 With PP_AUX_PARITY_OUT set, every measured deviation is written there beside its bar as JSON
 (profiles/aux_kernels_parity.json)."""
-import json
-import os
 
 import numpy as np
 import pytest
 
 from tests import aux_refs as ar
+from tests.gpu_support import default_eng, measured_writer
 
 pytestmark = pytest.mark.gpu
 
-MEASURED = {}
-
-
-def _eng():
-    from pulseportraiture_amd.engine import default_engine
-    return default_engine()
+MEASURED, _write_measured = measured_writer("PP_AUX_PARITY_OUT")
 
 
 def _err():
@@ -40,15 +34,6 @@ def _rec(section, key, deviation, bar):
     MEASURED.setdefault(section, {})[key] = dict(deviation=deviation, bar=bar,
                                                  of_bar=deviation / bar if bar > 0 else (0.0 if deviation == 0 else float("inf")))
     print("%-28s %-34s dev %.3e  bar %.3e" % (section, key, deviation, bar))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_measured():
-    yield
-    out = os.environ.get("PP_AUX_PARITY_OUT")
-    if out and MEASURED:
-        with open(out, "w") as f:
-            json.dump(MEASURED, f, indent=1, sort_keys=True)
 
 
 # =====================================================================================================
@@ -88,7 +73,7 @@ def test_zap_median_equals_the_clip_at_every_size(nchan, nstd):
         _rec("zap margins", "nchan %d nstd %d" % (nchan, nstd), margin.min(), 1e-9)
     if nchan >= 255 and nstd == 3:
         assert min(rounds) >= 3 and want.any(axis=1).all()          # (several rounds run at size)
-    got = _eng().zap_median(x, good, nstd)
+    got = default_eng().zap_median(x, good, nstd)
     assert got.dtype == np.uint8 and got.shape == want.shape
     assert got.tobytes() == want.tobytes(), np.argwhere(got != want)[:10]
 
@@ -139,7 +124,7 @@ def _structured(nchan):
 @pytest.mark.parametrize("nchan", [1000, 4096])
 def test_zap_median_structured_rows(nchan):
     rows = _structured(nchan)
-    eng = _eng()
+    eng = default_eng()
     for x, _, _ in rows.values():
         assert np.array_equal(x * 8.0, np.round(x * 8.0))
     a, b = (_alive_after_first_round(*rows[k]) for k in ("alive parity a", "alive parity b"))
@@ -170,7 +155,7 @@ def test_zap_median_structured_rows(nchan):
 
 def test_zap_row_does_not_depend_on_its_batch():
     x, good = _zap_rows(1000)
-    eng = _eng()
+    eng = default_eng()
     six = eng.zap_median(x, good, 3)
     assert six[3].any()
     alone = eng.zap_median(x[3:4], good[3:4], 3)
@@ -200,7 +185,7 @@ def test_get_zap_channels_with_given_noise():
 
 def test_zap_median_refuses_more_than_4096_channels():
     with pytest.raises(_err()):
-        _eng().zap_median(np.ones((1, 4097)), np.ones((1, 4097)), 3)
+        default_eng().zap_median(np.ones((1, 4097)), np.ones((1, 4097)), 3)
 
 
 @pytest.mark.parametrize("nchan", [300, 1000])
@@ -212,7 +197,7 @@ def test_zap_nan_or_inf_in_an_alive_channel_flags_nothing_in_that_row(nchan, bad
     x[4, nchan - 1], good[4, nchan - 1] = bad, False          # (in a channel that is not good it is not looked at)
     want, rounds, margin = _clip_rows(x, good, 3)
     assert not want[2].any() and np.isnan(margin[2]) and want[4].any() and margin[[0, 1, 3, 4, 5]].min() >= 1e-9
-    got = _eng().zap_median(x, good, 3)
+    got = default_eng().zap_median(x, good, 3)
     assert got.tobytes() == want.tobytes()
 
 
@@ -257,7 +242,7 @@ def _rel(got, want):
 def test_channel_noise_and_norms_at_the_remaining_lengths(nbin, dtype, rtol):
     import torch
     x, want, norms_ref = _noise_ref(nbin, dtype)
-    eng = _eng()
+    eng = default_eng()
     tag = "nbin %d %s" % (nbin, np.dtype(dtype).name)
     if dtype is np.float64:
         # NumPy's own f64 distance from a long-double DFT of the same harmonics: what the 1e-12 stands on
@@ -313,7 +298,7 @@ def test_channel_snrs_and_noise_on_special_rows(nbin, dtype, rtol):
     names, x = _special_rows(nbin)
     x = x.astype(dtype)
     x64 = x.astype(np.float64)
-    eng = _eng()
+    eng = default_eng()
     assert x64[2].max() == 0.0 and x64[2].sum() < 0 and x64[1].max() < 0
     for fudge in (3.25, 1.0):
         want = np.array([ar.snr(r, fudge) for r in x64])
@@ -347,16 +332,16 @@ def test_channel_snrs_and_noise_on_special_rows(nbin, dtype, rtol):
 def test_channel_noise_and_snrs_refuse_other_lengths(nbin):
     x = np.ones((2, nbin))
     with pytest.raises(_err()):
-        _eng().channel_noise(x)
+        default_eng().channel_noise(x)
     with pytest.raises(_err()):
-        _eng().channel_snrs(x)
+        default_eng().channel_snrs(x)
 
 
 @pytest.mark.parametrize("nbin", [256, 1000])
 def test_channel_noise_split_of_host_rows_gives_the_same_bits(nbin):
     """max_work_bytes of about three rows: 11 x 24 host rows go through channel_noise_rows' runs, which offset the
     divisors, norms, noise and S/N by the run's first row."""
-    eng = _eng()
+    eng = default_eng()
     rng = np.random.default_rng(nbin)
     x = _noise_rows(nbin, shape=(11, 24), seed=9)
     x[4, 7] = 0.0
@@ -366,11 +351,8 @@ def test_channel_noise_split_of_host_rows_gives_the_same_bits(nbin):
         return eng.channel_noise(x, norm="prof", weights=w) + eng.channel_noise(x, norm=None) + (eng.channel_snrs(x),)
     whole = run()
     per_row = nbin * 8 + (0 if nbin == 256 else (nbin // 2 + 1) * 16) + 24
-    eng.set_option("max_work_bytes", 3.4 * per_row)
-    try:
+    with eng.options(max_work_bytes=3.4 * per_row):
         split = run()
-    finally:
-        eng.set_option("max_work_bytes", 96e9)
     assert len({tuple(np.round(r, 6)) for r in whole[1]}) == 11           # (every subint has divisors of its own)
     for a, b in zip(whole, split):
         assert a.tobytes() == b.tobytes()
@@ -419,7 +401,7 @@ def _curves(eng, t, cs, k, freqs, nbin=64):
 def test_spline_evaluator_against_splev_and_de_boor(k, ninner):
     import scipy.interpolate as si
     rng = np.random.default_rng(100 * k + ninner)
-    eng = _eng()
+    eng = default_eng()
     t, inner = _knots(k, ninner, rng)
     if ninner >= 7:
         assert (np.diff(t[k + 1:-k - 1]) == 0).sum() == (3 if k >= 3 else 1)
@@ -453,7 +435,7 @@ def test_spline_evaluator_where_fpbspl_meets_equal_knots(k):
     t, inner = _knots(k, 7, rng, at_the_ends=True)
     freqs = _spline_freqs(inner, rng)
     cs = rng.standard_normal((3, len(t) - k - 1)) * 5.0
-    got = _curves(_eng(), t, cs, k, freqs)
+    got = _curves(default_eng(), t, cs, k, freqs)
     worst = 0.0
     for c, g in zip(cs, got):
         f64 = si.splev(freqs, (t, c, k), der=0, ext=0)
@@ -469,7 +451,7 @@ def test_spline_evaluator_where_fpbspl_meets_equal_knots(k):
 def test_spline_portrait_dot_product(nbin, ncomp, k, ninner):
     """Random mean profile and eigenvectors: np.dot(proj, eigvec.T) + mean_prof with the device's own curve values."""
     rng = np.random.default_rng(nbin + ncomp)
-    eng = _eng()
+    eng = default_eng()
     t, inner = _knots(k, ninner, rng)
     freqs = _spline_freqs(inner, rng)
     cs = rng.standard_normal((ncomp, len(t) - k - 1)) * 3.0
@@ -484,7 +466,7 @@ def test_spline_portrait_dot_product(nbin, ncomp, k, ninner):
 
 def test_set_model_spline_slot_fits_as_the_uploaded_portrait():
     rng = np.random.default_rng(12)
-    eng = _eng()
+    eng = default_eng()
     k, ncomp, nbin, C = 5, 10, 1000, 16
     t, _ = _knots(k, 7, rng)
     ph = (np.arange(nbin) + 0.5) / nbin
@@ -508,7 +490,7 @@ def test_set_model_spline_slot_fits_as_the_uploaded_portrait():
 
 
 def test_spline_refusals():
-    eng, rng = _eng(), np.random.default_rng(0)
+    eng, rng = default_eng(), np.random.default_rng(0)
     f = np.linspace(1100.0, 1900.0, 4)
 
     def call(ncomp, k, nknots, how):
@@ -539,7 +521,7 @@ def _pm_rows(nchan, nbin, rng, offset=False):
 def test_gram_matrix_exact_with_five_tile_rows(nchan, nbin):
     rng = np.random.default_rng(nchan * 10000 + nbin)
     port = _pm_rows(nchan, nbin, rng)[0]
-    eng = _eng()
+    eng = default_eng()
     mean_prof, gram, fact = eng.pca_gram(port, np.ones(nchan))
     assert fact == nchan - 1.0 and not mean_prof.any()
     want = (np.dot(port, port.T) if nchan < nbin else np.dot(port.T, port)) * (1.0 / fact)
@@ -564,7 +546,7 @@ def test_projection_exact_with_one_hot_vectors(nchan, nbin, nvec, ieig):
     bins = [b % nbin for b in BINS16[:nvec]]
     vecs = np.zeros((nbin, nvec))
     vecs[bins, np.arange(nvec)] = 1.0
-    eng = _eng()
+    eng = default_eng()
     mean_prof, gram, fact = eng.pca_gram(port, np.ones(nchan))
     np.testing.assert_array_equal(mean_prof, off)
     basis, stats = eng.pca_basis(vecs, np.arange(nvec, 0, -1.0))
@@ -579,7 +561,7 @@ def test_projection_exact_with_one_hot_vectors(nchan, nbin, nvec, ieig):
 
 
 def test_pca_refusals():
-    eng, E = _eng(), _err()
+    eng, E = default_eng(), _err()
     rng = np.random.default_rng(2)
     port = _pm_rows(80, 64, rng)[0]
     # a refused pca_gram leaves nothing resident: pca_basis and pca_project need a pca_gram first
@@ -612,7 +594,7 @@ def test_back_projection_on_the_dual_side(nchan, nbin):
     port = (10.0 + 3.0 * nu) * np.exp(-0.5 * ((ph - 0.3 - 0.01 * nu) / (0.03 + 0.005 * nu)) ** 2) + \
         2.0 * nu ** 2 * np.exp(-0.5 * ((ph - 0.6) / 0.05) ** 2) + 0.05 * rng.standard_normal((nchan, nbin))
     w = rng.uniform(0.5, 2.0, nchan)
-    eng = _eng()
+    eng = default_eng()
     tag = "%d x %d" % (nchan, nbin)
     mean_prof, gram, fact = eng.pca_gram(port, w)
     mref, delta, S, fref = ar.pca_centre(port, w)
@@ -690,7 +672,7 @@ def _crafted_vectors(nbin, rng):
 @pytest.mark.parametrize("nchan,nbin", [(300, 264), (600, 520)])
 def test_eigenvector_statistics_with_samples_on_the_threshold(nchan, nbin):
     rng = np.random.default_rng(nbin)
-    eng = _eng()
+    eng = default_eng()
     eng.pca_gram(_pm_rows(nchan, nbin, rng)[0], np.ones(nchan))
     vecs = _crafted_vectors(nbin, rng)
     basis, stats = eng.pca_basis(vecs, np.arange(vecs.shape[1], 0, -1.0))

@@ -7,13 +7,13 @@ set, between its three stored variants (trust-ncg, Newton-CG, trust-ncg from a s
 floor of 1e-13: phi in rotations, tau as stored (rot or log10 rot), everything else relative.  The bars are computed
 here from the golden.  With PP_NBSCAT_PARITY_OUT set, the spreads, the bars and the device's largest deviations are
 written there (profiles/nbscat_parity.json)."""
-import json
 import os
 
 import numpy as np
 import pytest
 
 from tests import nbscat_ref as nr
+from tests.gpu_support import default_eng, dump_measured
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +23,6 @@ MODEL = os.path.join(GOLDEN, "example.gmodel")
 FITS = np.load(os.path.join(GOLDEN, "nbscat_fits.npz"))
 NAMES = nr.COLS[:9]
 MEASURED = {}
-
-
-def _eng():
-    from pulseportraiture_amd.engine import default_engine
-    return default_engine()
 
 
 def deviation(a, b):
@@ -68,12 +63,10 @@ def _within(section, got, want, cols=range(9)):
 @pytest.fixture(scope="module", autouse=True)
 def _write_measured():
     yield
-    out = os.environ.get("PP_NBSCAT_PARITY_OUT")
-    if out and MEASURED:
-        with open(out, "w") as f:
-            json.dump(dict(fields=list(NAMES), reference_spread=dict(zip(NAMES, map(float, SPREAD))),
-                           bars=dict(zip(NAMES, map(float, BARS))), device_max_deviation=MEASURED), f, indent=1,
-                      sort_keys=True)
+    if MEASURED:
+        dump_measured("PP_NBSCAT_PARITY_OUT",
+                      dict(fields=list(NAMES), reference_spread=dict(zip(NAMES, map(float, SPREAD))),
+                           bars=dict(zip(NAMES, map(float, BARS))), device_max_deviation=MEASURED))
 
 
 # ---- fit level: every golden case ---------------------------------------------------------------------
@@ -85,7 +78,7 @@ def test_fit_level_parity_on_all_golden_cases():
         for l10 in (True, False):
             sel = [j for j, i in enumerate(rows) if bool(l10s[i]) == l10]
             idx = rows[sel]
-            got[idx] = _eng().fit_phase_tau_batch(FITS["prof_%d" % nbin][sel], FITS["mprof_%d" % nbin][sel],
+            got[idx] = default_eng().fit_phase_tau_batch(FITS["prof_%d" % nbin][sel], FITS["mprof_%d" % nbin][sel],
                                                   noise=FITS["sigma"][idx], tau_guess=FITS["guess"][idx], log10_tau=l10)
     assert len(got) == 24 and np.all(got[:, 10] == 2), got[:, 10]
     assert np.all(got[:, 9] >= 3) and np.all(got[:, 9] <= 64)
@@ -120,7 +113,7 @@ def synth(nbin, nprof=37):
 @pytest.mark.parametrize("nbin", SIZES)
 def test_sizes_batch_of_37_against_the_restatement(nbin):
     s = synth(nbin)
-    got = _eng().fit_phase_tau_batch(s["data"], s["model"], noise=s["sigma"], tau_guess=s["guess"], log10_tau=True)
+    got = default_eng().fit_phase_tau_batch(s["data"], s["model"], noise=s["sigma"], tau_guess=s["guess"], log10_tau=True)
     assert np.all(got[:, 10] == 2), got[:, 10]
     _within("sizes_nbin%d_nprof37" % nbin, got, s["want"])
 
@@ -130,7 +123,7 @@ def test_sizes_one_profile_linear_tau_against_the_restatement(nbin):
     s = synth(nbin)
     i = 5
     want = nr.fit(s["data"][i], s["model"][i], s["sigma"][i], 1.3 * s["tau"][i], None, False)
-    got = _eng().fit_phase_tau_batch(s["data"][i], s["model"][i], noise=s["sigma"][i:i + 1],
+    got = default_eng().fit_phase_tau_batch(s["data"][i], s["model"][i], noise=s["sigma"][i:i + 1],
                                      tau_guess=1.3 * s["tau"][i], log10_tau=False)
     assert got.shape == (1, 11) and got[0, 10] == 2
     _within("sizes_nbin%d_nprof1_linear" % nbin, got[0], want)
@@ -140,7 +133,7 @@ def test_sizes_one_profile_linear_tau_against_the_restatement(nbin):
 def test_batch_independence(nbin):
     """Profile 17 of the 37 fitted alone equals itself in the batch, bit for bit, in every output."""
     s = synth(nbin)
-    e = _eng()
+    e = default_eng()
     batch = e.fit_phase_tau_batch(s["data"], s["model"], noise=s["sigma"], tau_guess=s["guess"], log10_tau=True)
     alone = e.fit_phase_tau_batch(s["data"][17], s["model"][17], noise=s["sigma"][17:18], tau_guess=s["guess"][17],
                                   log10_tau=True)
@@ -150,7 +143,7 @@ def test_batch_independence(nbin):
 def test_measured_noise_matches_the_restatement():
     """noise = None: sigma from the top quarter of the power spectrum, as fit_phase_shift_batch measures it."""
     s = synth(256)
-    got = _eng().fit_phase_tau_batch(s["data"][:3], s["model"][:3], noise=None, tau_guess=s["guess"][:3], log10_tau=True)
+    got = default_eng().fit_phase_tau_batch(s["data"][:3], s["model"][:3], noise=None, tau_guess=s["guess"][:3], log10_tau=True)
     want = np.array([nr.fit(s["data"][i], s["model"][i], None, s["guess"][i], None, True) for i in range(3)])
     _within("measured_noise", got, want)
 
@@ -163,7 +156,7 @@ def test_degenerate_rows_do_not_disturb_their_neighbours(log10_tau):
     n = 12
     data, model = s["data"][:n].copy(), s["model"][:n].copy()
     guess = s["guess"][:n] if log10_tau else 10.0 ** s["guess"][:n]
-    e = _eng()
+    e = default_eng()
     clean = e.fit_phase_tau_batch(data, model, noise=s["sigma"][:n], tau_guess=guess, log10_tau=log10_tau)
     assert np.all(clean[:, 10] == 2)
     bad = {2: "zero data", 5: "zero model", 7: "nan", 10: "noise only"}
@@ -191,7 +184,7 @@ def test_degenerate_rows_do_not_disturb_their_neighbours(log10_tau):
 
 def test_argument_checks_return_before_device_work():
     from pulseportraiture_amd.engine import EngineError
-    e = _eng()
+    e = default_eng()
     x = np.ones((2, 256))
     for kw, a in ((dict(Ns=0), x), (dict(), np.ones((2, 255))), (dict(), np.ones((2, 4098))), (dict(), np.ones((2, 6)))):
         with pytest.raises(EngineError):
@@ -218,7 +211,7 @@ def test_tau_to_zero_agrees_with_the_phase_only_fit():
     device reports that as a singular Hessian -- return code 3, no covariance, tau_err infinite -- with the phase,
     its error and the amplitude's at the fixed tau it ended on, which is the phase-only fit."""
     data, model, sigma = _unscattered()
-    e = _eng()
+    e = default_eng()
     got = e.fit_phase_tau_batch(data, model, noise=sigma, tau_guess=0.0, log10_tau=False)
     fps = e.fit_phase_shift_batch(data, model, noise=sigma, finish='newton')
     assert np.all(np.abs(got[:, 2]) <= 3.0 * got[:, 3]), got[:, 2:4]

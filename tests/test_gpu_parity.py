@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.gpu_support import eng  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -19,14 +21,6 @@ FPF = sorted(os.path.basename(p)[:-4] for p in
              glob.glob(os.path.join(GOLDEN, "fpf_40x100_*.npz")) +
              glob.glob(os.path.join(GOLDEN, "fpf_24x1536_*.npz")))
 PHI_BAR, DM_BAR = 1e-9, 1e-6
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pulseportraiture_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
 
 
 def _load(name):
@@ -79,8 +73,7 @@ def test_rfft_rows(eng, nbin, dtype):
 @pytest.mark.parametrize("name", FPF)
 def test_objective_at_fixed_points(eng, name):
     g = _load(name)
-    eng.set_option("max_iter", 0)
-    try:
+    with eng.options(max_iter=0):
         eng.set_model(g["model"])
         for i, p in enumerate(g["obj_points"]):
             r = eng.fit_batch(g["data"][None], g["freqs"], float(g["P"]), p,
@@ -94,8 +87,6 @@ def test_objective_at_fixed_points(eng, name):
             hs = np.abs(g["obj_hess"][i]).max()
             np.testing.assert_allclose(r["obj_hess"][0], g["obj_hess"][i],
                                        rtol=1e-8, atol=1e-11 * hs)
-    finally:
-        eng.set_option("max_iter", 64)
 
 
 def _golden_fit(g, method):
@@ -270,11 +261,10 @@ def test_harmonic_truncation_is_parity_safe(eng):
              init_params=gss["init_params"], errs=inp["errs"],
              nu_fits=[gss["nu_fit"]] * 3)
     kw = dict(errs=g["errs"], nu_fits=[list(g["nu_fits"])], fit_flags=[1, 1, 0, 0, 0])
-    eng.set_option("harm_eps", 0.0)
-    k_full = eng.set_model(g["model"])
-    full = eng.fit_batch(g["data"][None], g["freqs"], float(g["P"]),
-                         g["init_params"], **kw)
-    eng.set_option("harm_eps", 2.0 ** -50)
+    with eng.options(harm_eps=0.0):
+        k_full = eng.set_model(g["model"])
+        full = eng.fit_batch(g["data"][None], g["freqs"], float(g["P"]),
+                             g["init_params"], **kw)
     k_cut = eng.set_model(g["model"])
     cut = eng.fit_batch(g["data"][None], g["freqs"], float(g["P"]),
                         g["init_params"], **kw)
@@ -404,9 +394,8 @@ def test_device_generator_matches_host_formula(eng):
     from tests.synth_host import model_portrait, device_recipe_host, P_EXAMPLE
     C, B, N = 16, 256, 3
     freqs, model = model_portrait(C, B)
-    eng.set_option("harm_eps", 0.0)
-    eng.set_model(model)
-    eng.set_option("harm_eps", 2.0 ** -50)
+    with eng.options(harm_eps=0.0):
+        eng.set_model(model)
     inj = np.array([[0.1, 2e-4, 0.0], [-0.32, 34.56789 + 4e-4, 0.0], [0.45, 0.0, 0.2]])
     P = np.full(N, P_EXAMPLE)
     for dt, tol in ((torch.float64, 1e-11), (torch.float32, 5e-6)):
@@ -855,12 +844,9 @@ def test_poor_guess_falls_back_to_evaluations(eng):
     bad0[0] += 6e-3
     bad0[1] += 4e-3
     bad = eng.fit_batch(g["data"][None], g["freqs"], float(g["P"]), bad0, **kw)
-    eng.set_option("taylor", 0)
-    try:
+    with eng.options(taylor=0):
         plain = eng.fit_batch(g["data"][None], g["freqs"], float(g["P"]),
                               g["init_params"], **kw)
-    finally:
-        eng.set_option("taylor", 1)
     assert good["npass"][0] == 1 and bad["npass"][0] >= 3 and plain["npass"][0] >= 3
     for r in (good, bad, plain):
         assert _dphi(r["params"][0, 0], float(g["out_phi"])) < PHI_BAR
@@ -960,11 +946,8 @@ def test_sub_batching_and_model_slots(eng):
     kw = dict(errs=np.full((N, C), 0.05), nu_fits=nuf, fit_flags=[1, 1, 0, 0, 0],
               model_slot=slots)
     whole = eng.fit_batch(data, freqs, P, np.array(x0), **kw)
-    eng.set_option("max_work_bytes", 2.5 * C * B * 16)     # ~2 subints per sub-batch
-    try:
+    with eng.options(max_work_bytes=2.5 * C * B * 16):     # ~2 subints per sub-batch
         parts = eng.fit_batch(data, freqs, P, np.array(x0), **kw)
-    finally:
-        eng.set_option("max_work_bytes", 96e9)
     for k in ("params", "param_errs", "nu_refs", "chi2", "snr", "scales", "nfeval", "npass"):
         np.testing.assert_array_equal(whole[k], parts[k])
     # the scaled template changes the amplitudes, not the timing
@@ -1743,11 +1726,8 @@ def test_headline_shape_matches_oracle_raw(dtype):
     assert 2 * e.model_nharm(0) < B // 2          # (the truncated-template plan: k_xspec_q1024)
     if dtype == "f32":
         data = data.to(torch.float32)
-    e.set_option("profile", 1)
-    e.kernel_times(reset=True)
-    r = e.fit_batch(data, freqs, P, x0, **kw)
-    kt = e.kernel_times(reset=True)
-    e.set_option("profile", 0)
+    with e.profiled() as kt:
+        r = e.fit_batch(data, freqs, P, x0, **kw)
     assert kt["xspec"][1] == 1 and kt.get("eval", (0, 0))[1] == 0      # one pass, nothing stored
     assert (r["return_code"] == 2).all() and (r["npass"] == 1).all()
     worst = [0.0, 0.0]
@@ -1978,32 +1958,27 @@ def test_pilot_seed_matches_full_seed(eng):
     x0[:, 0] = 0.123           # ignored by the seed
     mask = np.ones((nsub, len(freqs)), dtype=np.uint8)
     mask[:, ::3] = 0
-    try:
-        for method, tol in (("newton", 1e-12), ("trust-ncg", PHI_BAR)):
-            eng.set_option("seed_chan_stride", 1)
+    for method, tol in (("newton", 1e-12), ("trust-ncg", PHI_BAR)):
+        with eng.options(seed_chan_stride=1):
             full = eng.fit_batch(data, freqs, P, x0, seed_ns=100, method=method, **kw)
-            eng.set_option("seed_chan_stride", 8)
+        with eng.options(seed_chan_stride=8):
             pilot = eng.fit_batch(data, freqs, P, x0, seed_ns=100, method=method, **kw)
-            eng.set_option("seed_min_snr", 1e30)      # every pilot seed "weak"
-            weak = eng.fit_batch(data, freqs, P, x0, seed_ns=100, method=method, **kw)
-            eng.set_option("seed_min_snr", 8.0)
-            for name, r in (("pilot", pilot), ("weak", weak)):
-                dphi = _dphi_common(r, full, P)
-                assert dphi < tol, (method, name, dphi)
-                assert np.max(np.abs(r["params"][:, 1] - full["params"][:, 1])) < 1e3 * tol
-                np.testing.assert_allclose(r["chi2"], full["chi2"], rtol=1e-11)
-                assert (r["return_code"] == 2).all() and (r["npass"] == 1).all()
-        # a third of the channels masked, measured noise: same agreement
-        kw2 = dict(kw, errs=None, chan_mask=mask)
-        eng.set_option("seed_chan_stride", 1)
+            with eng.options(seed_min_snr=1e30):      # every pilot seed "weak"
+                weak = eng.fit_batch(data, freqs, P, x0, seed_ns=100, method=method, **kw)
+        for name, r in (("pilot", pilot), ("weak", weak)):
+            dphi = _dphi_common(r, full, P)
+            assert dphi < tol, (method, name, dphi)
+            assert np.max(np.abs(r["params"][:, 1] - full["params"][:, 1])) < 1e3 * tol
+            np.testing.assert_allclose(r["chi2"], full["chi2"], rtol=1e-11)
+            assert (r["return_code"] == 2).all() and (r["npass"] == 1).all()
+    # a third of the channels masked, measured noise: same agreement
+    kw2 = dict(kw, errs=None, chan_mask=mask)
+    with eng.options(seed_chan_stride=1):
         full = eng.fit_batch(data, freqs, P, x0, seed_ns=100, method="newton", **kw2)
-        eng.set_option("seed_chan_stride", 8)
+    with eng.options(seed_chan_stride=8):
         pilot = eng.fit_batch(data, freqs, P, x0, seed_ns=100, method="newton", **kw2)
-        assert _dphi_common(pilot, full, P) < 1e-12
-        np.testing.assert_allclose(pilot["chi2"], full["chi2"], rtol=1e-11)
-    finally:
-        eng.set_option("seed_chan_stride", 16)
-        eng.set_option("seed_min_snr", 8.0)
+    assert _dphi_common(pilot, full, P) < 1e-12
+    np.testing.assert_allclose(pilot["chi2"], full["chi2"], rtol=1e-11)
 
 
 def test_device_spline_portrait_matches_reference(eng):
@@ -2085,11 +2060,8 @@ def test_float_cross_spectrum_option(name):
     from pulseportraiture_amd.engine import default_engine
     g = _load(name)
     b = _golden_fit(g, 'Newton-CG')
-    default_engine().set_option("x_f32", 1)
-    try:
+    with default_engine().options(x_f32=1):
         a = _golden_fit(g, 'Newton-CG')
-    finally:
-        default_engine().set_option("x_f32", 0)
     assert _dphi(a.phi, b.phi) < 1e-10 and abs(a.DM - b.DM) < 1e-8
     assert (a.phi, a.DM) != (b.phi, b.DM)                # (the option did take effect)
     np.testing.assert_allclose(np.asarray(a.params)[2:], np.asarray(b.params)[2:], rtol=1e-6, atol=1e-8)
@@ -2132,9 +2104,8 @@ def test_reference_seed_formed_inside_the_single_pass(dtype, flags):
     # one pass
     xb = x0.copy(); xb[:, 0] = 0.123                      # (ignored)
     rs = dict(weights=w, model_profs=mprof, nu_mean=nu_mean, Ns=100, finish='simplex')
-    e.set_option("profile", 1); e.kernel_times(reset=True)
-    one = e.fit_batch(data, freqs, P, xb, ref_seed=rs, **kw)
-    kt = e.kernel_times(reset=True); e.set_option("profile", 0)
+    with e.profiled() as kt:
+        one = e.fit_batch(data, freqs, P, xb, ref_seed=rs, **kw)
     assert kt["xspec"][1] == 2 and kt.get("eval", (0, 0))[1] == 0        # the pilot + ONE pass over the portraits
     assert np.abs(_dphi_arr(one["seed_phase"], g2)).max() < 1e-12, (one["seed_phase"], g2)
     # (raw: the same iterates; a phase-only walk has marginal exits -- a last step worth one ulp of
@@ -2203,9 +2174,8 @@ def test_reference_seed_single_pass_scattering_fit(dtype, l10):
     two = e.fit_batch(data, freqs, P, xa, **kw)
     xb = x0.copy(); xb[:, 0] = -0.321                     # (ignored)
     rs = dict(weights=w, model_profs=mprof, nu_mean=nu_mean, Ns=100, finish='simplex')
-    e.set_option("profile", 1); e.kernel_times(reset=True)
-    one = e.fit_batch(data, freqs, P, xb, ref_seed=rs, **kw)
-    kt = e.kernel_times(reset=True); e.set_option("profile", 0)
+    with e.profiled() as kt:
+        one = e.fit_batch(data, freqs, P, xb, ref_seed=rs, **kw)
     assert kt["xspec"][1] == 1                            # ONE pass over the portraits
     assert np.abs(_dphi_arr(one["seed_phase"], g2)).max() < 1e-12, (one["seed_phase"], g2)
     assert np.abs(_dphi_arr(one["params"][:, 0], two["params"][:, 0])).max() < 1e-11
@@ -2292,18 +2262,12 @@ def test_get_TOAs_default_flow_reads_the_portraits_once_at_2048_bins(fit_scat):
     eng = default_engine()
     runs = []
     for single in (True, False):
-        eng.set_option("one_exchange", 1 if single else 0)
-        eng.set_option("profile", 1); eng.kernel_times(reset=True)
-        try:
+        with eng.options(one_exchange=1 if single else 0), eng.profiled() as kt:
             gt = GetTOAs(data, os.path.join(GOLDEN, "example.gmodel"), quiet=True)
             if fit_scat:
                 gt.get_TOAs(quiet=True, fit_scat=True, scat_guess=[75e-6, 1500.0, -4.0])
             else:
                 gt.get_TOAs(quiet=True)
-            kt = eng.kernel_times(reset=True)
-        finally:
-            eng.set_option("profile", 0)
-            eng.set_option("one_exchange", 1)
         runs.append((gt, kt))
     (a, kta), (b, ktb) = runs
     # (pilot +) the one pass; fit_phase_shift on the channel mean
@@ -2341,15 +2305,10 @@ def test_first_evaluation_of_a_scattering_fit_rides_in_the_transform(flags, l10)
     nsub = 6
     e, data, freqs, model, P, x0, errs, nu_fit, kw = _full_shape_case(64, 2048, flags, l10, nsub=nsub, tau_us=25.0,
                                                                       gm=bool(flags[2]), seed=31)
-    e.set_option("profile", 1); e.kernel_times(reset=True)
-    a = e.fit_batch(data, freqs, P, x0, objective=True, **kw)
-    kta = e.kernel_times(reset=True)
-    e.set_option("fuse_scat", 0)
-    try:
+    with e.profiled() as kta:
+        a = e.fit_batch(data, freqs, P, x0, objective=True, **kw)
+    with e.options(fuse_scat=0), e.profiled() as ktb:
         b = e.fit_batch(data, freqs, P, x0, objective=True, **kw)
-    finally:
-        e.set_option("fuse_scat", 1)
-    ktb = e.kernel_times(reset=True); e.set_option("profile", 0)
     assert kta["accum"][1] == 1 and ktb.get("accum", (0, 0))[1] == 0
     assert kta["eval"][1] + kta["scat_model"][1] // 2 == ktb["eval"][1] + ktb["scat_model"][1] // 2 - 1
     np.testing.assert_allclose(a["obj_f"], b["obj_f"], rtol=1e-13)
@@ -2471,14 +2430,9 @@ def test_coarse_phase_dm_grid_recovers_a_poor_dm_guess(eng):
     x0[:, 0] = 0.0
     x0[:, 1] += 0.02
     kw = dict(kw, method="newton")
-    try:
-        one = eng.fit_batch(data, freqs, P, x0, seed_ns=100, **kw)
-        eng.set_option("seed_ndm", 41)
-        eng.set_option("seed_dm_step", 1e-3)
+    one = eng.fit_batch(data, freqs, P, x0, seed_ns=100, **kw)
+    with eng.options(seed_ndm=41, seed_dm_step=1e-3):
         grid = eng.fit_batch(data, freqs, P, x0, seed_ns=100, **kw)
-    finally:
-        eng.set_option("seed_ndm", 1)
-        eng.set_option("seed_dm_step", 0.0)
     assert (one["npass"] > 1).all() and (grid["npass"] == 1).all()
     assert (one["return_code"] == 2).all() and (grid["return_code"] == 2).all()
     assert _dphi_common(grid, one, P) < 1e-11
@@ -2506,16 +2460,12 @@ def test_scattering_model_of_the_closing_iterations_walks_the_same_iteration(l10
     mask = np.ones((24, 256), dtype=np.uint8)
     mask[:, 17] = 0; mask[3, 100:140] = 0
     res, evals, passes = {}, {}, {}
-    e.set_option("profile", 1)
     for sm in (0, 1):
-        e.set_option("scat_model", sm)
-        e.kernel_times(reset=True)
-        # (phases referred to a fixed frequency, so that they compare across runs)
-        res[sm] = e.fit_batch(data, freqs, P, x0, chan_mask=mask, nu_outs=np.full((24, 3), nu_fit), **kw)
-        kt = e.kernel_times(reset=True)
+        with e.options(scat_model=sm), e.profiled() as kt:
+            # (phases referred to a fixed frequency, so that they compare across runs)
+            res[sm] = e.fit_batch(data, freqs, P, x0, chan_mask=mask, nu_outs=np.full((24, 3), nu_fit), **kw)
         evals[sm] = kt["eval"][1]
         passes[sm] = kt.get("scat_model", (0.0, 0))[1]
-    e.set_option("profile", 0)
     a, b = res[0], res[1]
     assert passes[0] == 0 and passes[1] > 0
     # (launches are counted while ANY subint iterates; passes per subint say who took the model)
@@ -2555,17 +2505,11 @@ def test_scattering_model_evaluations_that_fail_their_certificate_are_made_over_
     flags, l10 = [1, 1, 0, 1, 1], True
     e, data, freqs, model, P, x0, errs, nu_fit, kw = _full_shape_case(256, 1024, flags, l10, nsub=16,
                                                                       tau_us=30.0, seed=10)
-    e.set_option("scat_model", 0)
-    ref = e.fit_batch(data, freqs, P, x0, **kw)
-    refn = e.fit_batch(data, freqs, P, x0, method='newton', **kw)
-    e.set_option("scat_model", 1)
-    e.set_option("scat_model_tol", 1e300)
-    e.set_option("profile", 1)
-    e.kernel_times(reset=True)
-    r = e.fit_batch(data, freqs, P, x0, **kw)
-    kt = e.kernel_times(reset=True)
-    e.set_option("profile", 0)
-    e.set_option("scat_model_tol", 1e-10)
+    with e.options(scat_model=0):
+        ref = e.fit_batch(data, freqs, P, x0, **kw)
+        refn = e.fit_batch(data, freqs, P, x0, method='newton', **kw)
+    with e.options(scat_model=1, scat_model_tol=1e300), e.profiled() as kt:
+        r = e.fit_batch(data, freqs, P, x0, **kw)
     np.testing.assert_array_equal(ref["nfeval"], r["nfeval"])
     # (evaluations on the model and over the data alternate here: same iterates, rounding apart)
     assert np.abs(_dphi_arr(ref["params"][:, 0], r["params"][:, 0])).max() < 1e-11
@@ -2574,9 +2518,8 @@ def test_scattering_model_evaluations_that_fail_their_certificate_are_made_over_
     # early model passes were abandoned: more passes over the data than evaluations the
     # default setting needs, yet the model still ran
     assert kt["scat_model"][1] > 0
-    e.set_option("scat_model", 2)
-    rn = e.fit_batch(data, freqs, P, x0, method='newton', **kw)
-    e.set_option("scat_model", 1)
+    with e.options(scat_model=2):
+        rn = e.fit_batch(data, freqs, P, x0, method='newton', **kw)
     np.testing.assert_array_equal(refn["nfeval"], rn["nfeval"])
     assert np.abs(_dphi_arr(refn["params"][:, 0], rn["params"][:, 0])).max() < 2e-12
     np.testing.assert_allclose(refn["params"][:, 3:], rn["params"][:, 3:], rtol=1e-10)
@@ -2625,11 +2568,8 @@ def test_auxiliary_entry_points_split_host_inputs_that_exceed_the_work_budget(en
     d = _aux_split_inputs(B, dtype, freqs_per_subint, slots)
     whole = _aux_split_calls(eng, d)
     # three subints (or a few profiles) at a time
-    eng.set_option("max_work_bytes", 3.4 * d["C"] * B * np.dtype(dtype).itemsize)
-    try:
+    with eng.options(max_work_bytes=3.4 * d["C"] * B * np.dtype(dtype).itemsize):
         split = _aux_split_calls(eng, d)
-    finally:
-        eng.set_option("max_work_bytes", 96e9)
     np.testing.assert_array_equal(whole[0][:, :6], split[0][:, :6])     # (column 6 is the duration)
     np.testing.assert_array_equal(whole[1], split[1])
     np.testing.assert_allclose(whole[2][0], split[2][0], rtol=1e-13, atol=1e-13)
@@ -2694,16 +2634,11 @@ def test_scattering_fits_in_sub_batches_with_model_slots_and_the_model_path(eng)
     data = np.array(data); P = np.full(N, inp["P"]); x0 = np.array(x0)
     kw = dict(errs=np.full((N, C), 0.03), nu_fits=nuf, fit_flags=[1, 1, 0, 1, 1], log10_tau=True,
               model_slot=slots)
-    eng.set_option("profile", 1)
-    eng.kernel_times(reset=True)
-    whole = eng.fit_batch(data, freqs, P, x0, **kw)
-    assert eng.kernel_times(reset=True).get("scat_model", (0, 0))[1] > 0
-    eng.set_option("profile", 0)
-    eng.set_option("max_work_bytes", 2.5 * C * B * 16)
-    try:
+    with eng.profiled() as kt:
+        whole = eng.fit_batch(data, freqs, P, x0, **kw)
+    assert kt.get("scat_model", (0, 0))[1] > 0
+    with eng.options(max_work_bytes=2.5 * C * B * 16):
         parts = eng.fit_batch(data, freqs, P, x0, **kw)
-    finally:
-        eng.set_option("max_work_bytes", 96e9)
     for k in ("params", "param_errs", "nu_refs", "chi2", "snr", "scales", "nfeval", "npass"):
         np.testing.assert_array_equal(whole[k], parts[k])
     assert (whole["return_code"] == 2).all() and (whole["nfeval"] > 5).all()
@@ -2713,11 +2648,8 @@ def test_scattering_fits_in_sub_batches_with_model_slots_and_the_model_path(eng)
                                model_slot=slots[i:i + 1])
         np.testing.assert_array_equal(single["params"][0], whole["params"][i])
     # against the ordinary path
-    eng.set_option("scat_model", 0)
-    try:
+    with eng.options(scat_model=0):
         plain = eng.fit_batch(data, freqs, P, x0, **kw)
-    finally:
-        eng.set_option("scat_model", 1)
     d = _dphi_arr(plain["params"][:, 0], whole["params"][:, 0])
     assert np.median(d) < 2e-12 and d.max() < 2e-9
     np.testing.assert_allclose(plain["chi2"], whole["chi2"], rtol=1e-11)
@@ -2837,16 +2769,10 @@ def test_poor_dm_guesses_get_one_more_expansion_instead_of_evaluations(eng):
     x1 = x0.copy()
     x1[poor, 1] += np.where(np.arange(len(poor)) % 2, 5e-3, -4.5e-3)
     # (the phase guess refers to nu_fit: a DM error tilts the channels about it)
-    eng.set_option("profile", 1)
-    eng.kernel_times(reset=True)
-    r = eng.fit_batch(data, freqs, P, x1, objective=True, **kw)
-    kt = eng.kernel_times(reset=True)
-    eng.set_option("profile", 0)
-    eng.set_option("taylor_recentre", 0)
-    try:
+    with eng.profiled() as kt:
+        r = eng.fit_batch(data, freqs, P, x1, objective=True, **kw)
+    with eng.options(taylor_recentre=0):
         loop = eng.fit_batch(data, freqs, P, x1, objective=True, **kw)
-    finally:
-        eng.set_option("taylor_recentre", 1)
     ok = np.setdiff1d(np.arange(nsub), poor)
     assert (r["npass"][ok] == 1).all() and (r["npass"][poor] == 2).all(), r["npass"][poor]
     assert (loop["npass"][poor] >= 3).all()
@@ -2919,7 +2845,6 @@ def test_one_exchange_transform_matches_general_kernel_and_oracle(dtype):
     x0[:, 1] = 34.56789
     errs = np.full((nsub, C), 0.05)
     kw = dict(errs=errs, nu_fits=np.full((nsub, 3), nu_fit), fit_flags=[1, 1, 0, 0, 0])
-    e.set_option("profile", 1)
     e.set_option("one_exchange", 0)
     a = e.fit_batch(data, freqs, P, x0, **kw)
     e.set_option("one_exchange", 1)
@@ -2978,11 +2903,8 @@ def test_fused_reference_seed_2048_bins_one_exchange_kernel(eng, dtype):
     nu_mean = np.array([freqs[w[i] > 0].mean() for i in range(N)])
     kw = dict(phi=-orc.Dconst * 12.5 / P * nu_mean ** -2.0, DM=np.full(N, 12.5), Ns=100, finish='simplex')
     got = eng.reference_phase_seed(ports, freqs, P, w, mprof, **kw)
-    eng.set_option("one_exchange", 0)
-    try:
+    with eng.options(one_exchange=0):
         old = eng.reference_phase_seed(ports, freqs, P, w, mprof, **kw)
-    finally:
-        eng.set_option("one_exchange", 1)
     profs = np.array([np.average(orc.rotate_data(ports[i].astype(np.float64), 0.0, 12.5, P[i], freqs, nu_mean[i]),
                                  axis=0, weights=w[i]) for i in range(N)])
     want = eng.fit_phase_shift_batch(profs, np.tile(mprof, (N, 1)), Ns=100, finish='simplex')
@@ -3005,12 +2927,9 @@ def test_one_exchange_1024_bin_rows_in_the_list_and_seed_flows(eng):
     x1[poor, 1] += np.where(np.arange(len(poor)) % 2, 5e-3, -4.5e-3)
     runs = {}
     for oe in (0, 1):
-        eng.set_option("one_exchange", oe)
-        try:
+        with eng.options(one_exchange=oe):
             runs[oe] = (eng.fit_batch(data, freqs, P, x1, **kw),
                         eng.fit_batch(data, freqs, P, x0, seed_ns=100, method="newton", **kw))
-        finally:
-            eng.set_option("one_exchange", 1)
     for a, b in zip(runs[0], runs[1]):
         assert (a["return_code"] == 2).all() and (b["return_code"] == 2).all()
         np.testing.assert_array_equal(a["npass"], b["npass"])
@@ -3548,37 +3467,30 @@ def test_solve_and_postfit_widths_agree(eng, C, flags):
     rng = np.random.default_rng(C)
     mask = (rng.random((nsub, C)) > 0.1).astype(np.uint8)
     kw = dict(kw, fit_flags=flags, chan_mask=mask)
-    keys = ("solve_threads", "solve_cache", "finalize_regs")
-    saved = {k: eng.get_option(k) for k in keys}
-    try:
-        for method in ("trust-ncg", "newton"):
-            ref = eng.fit_batch(data, freqs, P, x0, method=method, **kw)
-            assert (ref["return_code"] == 2).all() and (ref["npass"] == 1).all()
-            variants = [dict(solve_threads=256, finalize_regs=0), dict(solve_cache=0), dict(solve_threads=64, finalize_regs=512),
-                        dict(solve_threads=128, solve_cache=100, finalize_regs=256), dict(solve_threads=512)]
-            for v in variants:
-                for k in keys:
-                    eng.set_option(k, v.get(k, saved[k]))
+    for method in ("trust-ncg", "newton"):
+        ref = eng.fit_batch(data, freqs, P, x0, method=method, **kw)
+        assert (ref["return_code"] == 2).all() and (ref["npass"] == 1).all()
+        variants = [dict(solve_threads=256, finalize_regs=0), dict(solve_cache=0), dict(solve_threads=64, finalize_regs=512),
+                    dict(solve_threads=128, solve_cache=100, finalize_regs=256), dict(solve_threads=512)]
+        for v in variants:
+            with eng.options(**v):
                 r = eng.fit_batch(data, freqs, P, x0, method=method, **kw)
-                # (a GM fit's optimum is ill-conditioned in (phi, DM, GM) at the fit frequencies: rounding moves it ~1e-12)
-                moved = np.abs(_dphi_arr(r["params"][:, 0], ref["params"][:, 0])) > (1e-11 if flags[2] else 1e-13)
-                # (SciPy's walk ends on a +-1 ulp(f) decision: another summation order can stop it one closing
-                # step away, ~1e-10 rot -- up to 4e-9 for GM fits, where a third of the exits are that marginal)
-                allowed = 0 if method == "newton" else (4 if flags[2] else 1)
-                assert moved.sum() <= allowed, (v, method, int(moved.sum()))
-                assert np.abs(_dphi_arr(r["params"][:, 0], ref["params"][:, 0])).max() < (1e-8 if flags[2] else PHI_BAR)
-                same = ~moved
-                np.testing.assert_array_equal(r["nfeval"][same], ref["nfeval"][same], err_msg=str(v))
-                np.testing.assert_allclose(r["params"][same, 1:3], ref["params"][same, 1:3], rtol=0,
-                                           atol=(1e-9 if flags[2] else 1e-12), err_msg=str(v))
-                for key in ("param_errs", "chi2", "red_chi2", "snr", "nu_refs"):
-                    np.testing.assert_allclose(r[key][same], ref[key][same], rtol=1e-10, err_msg=key + str(v))
-                for key in ("scales", "scale_errs", "channel_snrs"):
-                    np.testing.assert_allclose(r[key][same], ref[key][same], rtol=1e-10, atol=1e-14, err_msg=key + str(v))
-                assert (r["scales"][mask == 0] == 0).all()
-    finally:
-        for k in keys:
-            eng.set_option(k, saved[k])
+            # (a GM fit's optimum is ill-conditioned in (phi, DM, GM) at the fit frequencies: rounding moves it ~1e-12)
+            moved = np.abs(_dphi_arr(r["params"][:, 0], ref["params"][:, 0])) > (1e-11 if flags[2] else 1e-13)
+            # (SciPy's walk ends on a +-1 ulp(f) decision: another summation order can stop it one closing
+            # step away, ~1e-10 rot -- up to 4e-9 for GM fits, where a third of the exits are that marginal)
+            allowed = 0 if method == "newton" else (4 if flags[2] else 1)
+            assert moved.sum() <= allowed, (v, method, int(moved.sum()))
+            assert np.abs(_dphi_arr(r["params"][:, 0], ref["params"][:, 0])).max() < (1e-8 if flags[2] else PHI_BAR)
+            same = ~moved
+            np.testing.assert_array_equal(r["nfeval"][same], ref["nfeval"][same], err_msg=str(v))
+            np.testing.assert_allclose(r["params"][same, 1:3], ref["params"][same, 1:3], rtol=0,
+                                       atol=(1e-9 if flags[2] else 1e-12), err_msg=str(v))
+            for key in ("param_errs", "chi2", "red_chi2", "snr", "nu_refs"):
+                np.testing.assert_allclose(r[key][same], ref[key][same], rtol=1e-10, err_msg=key + str(v))
+            for key in ("scales", "scale_errs", "channel_snrs"):
+                np.testing.assert_allclose(r[key][same], ref[key][same], rtol=1e-10, atol=1e-14, err_msg=key + str(v))
+            assert (r["scales"][mask == 0] == 0).all()
 
 
 def test_transport_and_prefetch_options_change_nothing(eng):
@@ -3587,27 +3499,21 @@ def test_transport_and_prefetch_options_change_nothing(eng):
     bytes move: every output is bitwise the same, synchronous and enqueued, odd batch sizes (the staged
     blocks are padded to whole words) and the reference-seed flow (its phase guesses ride in the output
     block) included."""
-    keys = ("copy_kernels", "solve_prefetch")
-    saved = {k: eng.get_option(k) for k in keys}
-    try:
-        for nsub, C, B in ((7, 2304, 256), (5, 256, 2048)):
-            data, freqs, P, x0, kw = _medium_batch(eng, nsub, C=C, B=B, seed=nsub)
-            model_prof = None
-            outs = []
-            for ck, pf in ((1, 0), (0, 0), (1, 1), (0, 1)):
-                eng.set_option("copy_kernels", ck); eng.set_option("solve_prefetch", pf)
+    for nsub, C, B in ((7, 2304, 256), (5, 256, 2048)):
+        data, freqs, P, x0, kw = _medium_batch(eng, nsub, C=C, B=B, seed=nsub)
+        model_prof = None
+        outs = []
+        for ck, pf in ((1, 0), (0, 0), (1, 1), (0, 1)):
+            with eng.options(copy_kernels=ck, solve_prefetch=pf):
                 r = eng.fit_batch(data, freqs, P, x0, **kw)
                 eng.enqueue(data, freqs, P, x0, **kw)
                 q = eng.collect()
-                outs.append((r, q))
-            for r, q in outs:
-                for key in ("params", "param_errs", "nu_refs", "cov", "chi2", "red_chi2", "snr", "nfeval", "npass", "return_code",
-                            "scales", "scale_errs", "channel_snrs"):
-                    np.testing.assert_array_equal(r[key], outs[0][0][key], err_msg=key)
-                    np.testing.assert_array_equal(q[key], outs[0][0][key], err_msg=key)
-    finally:
-        for k in keys:
-            eng.set_option(k, saved[k])
+            outs.append((r, q))
+        for r, q in outs:
+            for key in ("params", "param_errs", "nu_refs", "cov", "chi2", "red_chi2", "snr", "nfeval", "npass", "return_code",
+                        "scales", "scale_errs", "channel_snrs"):
+                np.testing.assert_array_equal(r[key], outs[0][0][key], err_msg=key)
+                np.testing.assert_array_equal(q[key], outs[0][0][key], err_msg=key)
 
 
 @pytest.mark.parametrize("C,B,flags", [(2304, 2048, [1, 1, 0, 0, 0]), (640, 2048, [1, 1, 1, 0, 0]), (300, 2048, [1, 0, 0, 0, 0])])
@@ -3648,60 +3554,56 @@ def test_tail_inside_the_next_transform_returns_the_synchronous_bits(eng, C, B, 
                  ("refseed3", data, x0, dict(kw, ref_seed=rs))]
     keys = ("params", "param_errs", "nu_refs", "cov", "chi2", "red_chi2", "snr", "nfeval", "npass", "return_code",
             "scales", "scale_errs", "channel_snrs")
-    saved = eng.get_option("fuse_tail")
-    try:
-        eng.set_option("fuse_tail", 0)
+    with eng.options(fuse_tail=0):
         sync = [eng.fit_batch(d, freqs, P[:len(x)], x, **k) for _, d, x, k in jobs]
-        assert (sync[2]["npass"][[3, 17]] > 1).all()
-        for ft, depth in ((1, 3), (1, 2), (0, 3)):
-            eng.set_option("fuse_tail", ft)
-            got = []
+    assert (sync[2]["npass"][[3, 17]] > 1).all()
+    for ft, depth in ((1, 3), (1, 2), (0, 3)):
+        got = []
+        with eng.options(fuse_tail=ft):
             for j, (_, d, x, k) in enumerate(jobs):
                 eng.enqueue(d, freqs, P[:len(x)], x, **k)
                 if j >= depth - 1:
                     got.append(eng.collect())
             while len(got) < len(jobs):
                 got.append(eng.collect())
-            for (name, _, _, _), a, g in zip(jobs, sync, got):
-                for key in keys + (("seed_phase",) if "seed_phase" in a else ()):
-                    np.testing.assert_array_equal(a[key], g[key], err_msg="fuse_tail=%d depth %d %s %s" % (ft, depth, name, key))
-        # other flows in between -- a 1024-bin batch (its transform carries no tail) and a scattering fit --: the
-        # pending tail goes out by the stand-alone kernels, every batch still returns the synchronous bits
-        import torch
-        from pulseportraiture_amd import gmodel
-        from pulseportraiture_amd.pplib import Dconst
-        freqs1, model1, _ = gmodel.example_model(C, 1024)
-        eng.set_model(model1, slot=1)
-        inj = np.zeros((nsub, 3))
-        inj[:, 0] = rng.uniform(-0.5, 0.5, nsub)
-        inj[:, 1] = 34.56789 + rng.normal(3e-4, 2e-4, nsub)
-        data1 = torch.empty((nsub, C, 1024), dtype=torch.float64, device="cuda:0")
-        eng.synth_portraits(data1, freqs, P, inj, 0.05, 4242, 0, slot=1)
-        nu_fit = float(np.asarray(kw["nu_fits"])[0, 0])
-        x1 = np.zeros((nsub, 5))
-        x1[:, 0] = (inj[:, 0] + Dconst * inj[:, 1] / P / nu_fit ** 2 + 0.5) % 1 - 0.5
-        x1[:, 1] = 34.56789
-        kw1 = dict(kw, fit_flags=[1, 1, 0, 0, 0], model_slot=np.ones(nsub, dtype=np.int32))
-        xs = x0.copy()
-        xs[:, 3], xs[:, 4] = 1e-3, -4.0
-        kws = dict(kw, fit_flags=[1, 1, 0, 1, 0], log10_tau=False)
-        mixed = [("plain", data, x0, kw), ("1024 bins", data1, x1, kw1), ("plain", data, x0, kw), ("scattering", data, xs, kws),
-                 ("masked", data, x0, kw_m)]
-        eng.set_option("fuse_tail", 0)
+        for (name, _, _, _), a, g in zip(jobs, sync, got):
+            for key in keys + (("seed_phase",) if "seed_phase" in a else ()):
+                np.testing.assert_array_equal(a[key], g[key], err_msg="fuse_tail=%d depth %d %s %s" % (ft, depth, name, key))
+    # other flows in between -- a 1024-bin batch (its transform carries no tail) and a scattering fit --: the
+    # pending tail goes out by the stand-alone kernels, every batch still returns the synchronous bits
+    import torch
+    from pulseportraiture_amd import gmodel
+    from pulseportraiture_amd.pplib import Dconst
+    freqs1, model1, _ = gmodel.example_model(C, 1024)
+    eng.set_model(model1, slot=1)
+    inj = np.zeros((nsub, 3))
+    inj[:, 0] = rng.uniform(-0.5, 0.5, nsub)
+    inj[:, 1] = 34.56789 + rng.normal(3e-4, 2e-4, nsub)
+    data1 = torch.empty((nsub, C, 1024), dtype=torch.float64, device="cuda:0")
+    eng.synth_portraits(data1, freqs, P, inj, 0.05, 4242, 0, slot=1)
+    nu_fit = float(np.asarray(kw["nu_fits"])[0, 0])
+    x1 = np.zeros((nsub, 5))
+    x1[:, 0] = (inj[:, 0] + Dconst * inj[:, 1] / P / nu_fit ** 2 + 0.5) % 1 - 0.5
+    x1[:, 1] = 34.56789
+    kw1 = dict(kw, fit_flags=[1, 1, 0, 0, 0], model_slot=np.ones(nsub, dtype=np.int32))
+    xs = x0.copy()
+    xs[:, 3], xs[:, 4] = 1e-3, -4.0
+    kws = dict(kw, fit_flags=[1, 1, 0, 1, 0], log10_tau=False)
+    mixed = [("plain", data, x0, kw), ("1024 bins", data1, x1, kw1), ("plain", data, x0, kw), ("scattering", data, xs, kws),
+             ("masked", data, x0, kw_m)]
+    with eng.options(fuse_tail=0):
         sync = [eng.fit_batch(d, freqs, P, x, **k) for _, d, x, k in mixed]
-        eng.set_option("fuse_tail", 1)
-        got = []
+    got = []
+    with eng.options(fuse_tail=1):
         for j, (_, d, x, k) in enumerate(mixed):
             eng.enqueue(d, freqs, P, x, **k)
             if j >= 2:
                 got.append(eng.collect())
         while len(got) < len(mixed):
             got.append(eng.collect())
-        for (name, _, _, _), a, g in zip(mixed, sync, got):
-            for key in keys:
-                np.testing.assert_array_equal(a[key], g[key], err_msg="mixed flows: %s %s" % (name, key))
-    finally:
-        eng.set_option("fuse_tail", saved)
+    for (name, _, _, _), a, g in zip(mixed, sync, got):
+        for key in keys:
+            np.testing.assert_array_equal(a[key], g[key], err_msg="mixed flows: %s %s" % (name, key))
 
 
 @pytest.mark.parametrize("C,nsub", [(256, 7), (512, 33), (1024, 5)])
@@ -3776,9 +3678,8 @@ def test_post_fit_stage_on_its_own_stream_changes_nothing(eng):
     sync = [eng.fit_batch(data, freqs, P, x, **k) for x, k in jobs]
     keys = ("params", "param_errs", "nu_refs", "cov", "chi2", "red_chi2", "snr", "nfeval", "npass", "return_code",
             "scales", "scale_errs", "channel_snrs")
-    try:
-        for ov in (1, 0, 1):
-            eng.set_option("overlap_post", ov)
+    for ov in (1, 0, 1):
+        with eng.options(overlap_post=ov):
             got = []
             for j, (x, k) in enumerate(jobs * 2):
                 eng.enqueue(data, freqs, P, x, **k)
@@ -3790,8 +3691,6 @@ def test_post_fit_stage_on_its_own_stream_changes_nothing(eng):
                     np.testing.assert_array_equal(a[key], b[key], err_msg="overlap_post=%d %s" % (ov, key))
                 if "seed_phase" in a:
                     np.testing.assert_array_equal(a["seed_phase"], b["seed_phase"])
-    finally:
-        eng.set_option("overlap_post", 0)
 
 
 @pytest.mark.parametrize("seed", ["reference", "device"])

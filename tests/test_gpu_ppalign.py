@@ -14,6 +14,8 @@ point), which is what the restatement does with np.add.at."""
 import numpy as np
 import pytest
 
+from tests.gpu_support import eng, run_module  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 NBINS = [32, 256, 2048, 4096, 8192, 100, 1000]
@@ -24,14 +26,6 @@ MAPS = {
     "many_to_one": np.array([[0, 0, 1, 2, 3, 4, 4], [0, 1, 1, 2, 3, 3, 4], [4, 3, 2, 2, 1, 0, 0]], dtype=np.int32),
     "row_never_hit": np.array([[0, 0, 1, 1, 2, 4, 4], [0, 1, 1, 2, 2, 4, 4], [0, 0, 0, 1, 2, 2, 4]], dtype=np.int32),
 }
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pulseportraiture_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
 
 
 def _pow2(nbin):
@@ -154,12 +148,8 @@ def test_a_host_input_cut_into_runs_gives_the_same_bits(eng):
     ports, freqs, Ps, phases, DMs, nu_refs, w = _inputs(nbin, 4, NCHAN, np.float64, False)
     cmap = MAPS["row_never_hit"]
     al, tw = _accumulate(eng, ports, freqs, Ps, phases, DMs, nu_refs, w, cmap, NCHAN_MODEL)
-    budget = eng.get_option("max_work_bytes")
-    try:
-        eng.set_option("max_work_bytes", 1.4 * ports[0].nbytes)
+    with eng.options(max_work_bytes=1.4 * ports[0].nbytes):
         al2, tw2 = _accumulate(eng, ports, freqs, Ps, phases, DMs, nu_refs, w, cmap, NCHAN_MODEL)
-    finally:
-        eng.set_option("max_work_bytes", budget)
     assert al2.tobytes() == al.tobytes() and tw2.tobytes() == tw.tobytes()
 
 
@@ -242,9 +232,6 @@ def test_misuse_is_refused_not_faulted():
 # =====================================================================================================
 import json      # noqa: E402
 import os        # noqa: E402
-import signal    # noqa: E402
-import subprocess   # noqa: E402
-import sys       # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -324,28 +311,6 @@ def test_align_archives_matches_the_reference(fname, case, capsys):
 # =====================================================================================================
 # the command line, in child processes
 # =====================================================================================================
-def _run(module, args, cwd, timeout=300):
-    """`python -m pulseportraiture_amd.<module> args` in a session of its own; on timeout its process group gets
-    SIGTERM, then SIGKILL."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    env["PYTHONPATH"] = ROOT
-    cmd = [sys.executable, "-m", "pulseportraiture_amd." + module] + list(args)
-    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
-
-
 def _npz_fields(g, name):
     return {k: v for k, v in _archive_fields(g, name).items() if k != "filename"}
 
@@ -369,8 +334,8 @@ def test_ppalign_run_equals_the_golden(tmp_path):
     from pulseportraiture_amd.archive import load_bunch as _load
     g, gc = _golden("ppalign_same"), _golden("ppalign_same_norms")
     meta = _write_archives(g, str(tmp_path))
-    out = _run("ppalign_run", ["-M", meta, "-I", "init.npz", "--niter", "2", "-N", "prof", "-C", "10", "-o", "out.npz"],
-               tmp_path)
+    out = run_module("ppalign_run", ["-M", meta, "-I", "init.npz", "--niter", "2", "-N", "prof", "-C", "10", "-o", "out.npz"],
+                     tmp_path, 300)
     assert _lines(out) == ["Doing iteration 1...", "Doing iteration 2..."]
     d, _ = _load(str(tmp_path / "out.npz"))
     want = gc["norm_prof_niter2_amps"]
@@ -390,8 +355,8 @@ def test_ppalign_run_with_a_gaussian_guess_and_with_none(tmp_path):
     from pulseportraiture_amd.archive import load_bunch as _load
     g = _golden("ppalign_mapped")
     meta = _write_archives(g, str(tmp_path))
-    _run("ppalign_run", ["-M", meta, "-g", "0.05", "-o", "gauss.npz"], tmp_path)
-    _run("ppalign_run", ["-M", meta], tmp_path)
+    run_module("ppalign_run", ["-M", meta, "-g", "0.05", "-o", "gauss.npz"], tmp_path, 300)
+    run_module("ppalign_run", ["-M", meta], tmp_path, 300)
     for name in ("gauss.npz", "list.txt.algnd.npz"):
         d, _ = _load(str(tmp_path / name))
         assert d.subints.shape == (1, 1, 24, 128) and np.isfinite(d.subints).all() and d.subints.any()
@@ -431,9 +396,9 @@ def test_the_chain_from_archives_to_toas(tmp_path):
         np.savez(str(tmp_path / names[-1]), subints=sub, freqs=np.tile(freqs, (2, 1)), Ps=np.full(2, P_EXAMPLE),
                  epochs=56000.0 + ia + 0.01 * np.arange(2), weights=np.ones((2, 16)), DM=0.0, dmc=0, nu0=1500.0, bw=800.0)
     (tmp_path / "list.txt").write_text("\n".join(names) + "\n")
-    _run("ppalign_run", ["-M", "list.txt", "--niter", "2", "-o", "avg.npz"], tmp_path)
-    _run("ppspline_run", ["-d", "avg.npz", "-o", "t.spl", "--quiet"], tmp_path)
-    out = _run("pptoas_run", ["-d", "list.txt", "-m", "t.spl", "--quiet"], tmp_path)
+    run_module("ppalign_run", ["-M", "list.txt", "--niter", "2", "-o", "avg.npz"], tmp_path, 300)
+    run_module("ppspline_run", ["-d", "avg.npz", "-o", "t.spl", "--quiet"], tmp_path, 300)
+    out = run_module("pptoas_run", ["-d", "list.txt", "-m", "t.spl", "--quiet"], tmp_path, 300)
     toas = [ln for ln in out.splitlines() if "-pp_dm " in ln]
     assert len(toas) == 6, out
 

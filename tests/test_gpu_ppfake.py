@@ -8,28 +8,18 @@ reversal of the channel order (0 here: its rows do not depend on each other, so 
 their variance by sqrt(2 / N), and the sample correlation of two independent sets, or of a set with itself one bin on,
 by 1 / sqrt(N).  All were fixed before the first run; every measured figure is printed beside its bar."""
 import os
-import signal
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import ppfake_cases as pc
+from tests.gpu_support import eng, run_module  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NSUB, NCHAN = 3, 5
 PARITY_BAR = 1e-12
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pulseportraiture_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
 
 
 def _template(nchan, nbin):
@@ -291,28 +281,6 @@ def test_misuse_is_refused_not_faulted():
 # =====================================================================================================
 # the closed loop of the reference's example, commands in child processes
 # =====================================================================================================
-def _run(module, args, cwd, timeout=300):
-    """`python -m pulseportraiture_amd.<module> args` in a session of its own; on timeout its process group gets
-    SIGTERM, then SIGKILL."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    env["PYTHONPATH"] = ROOT
-    cmd = [sys.executable, "-m", "pulseportraiture_amd." + module] + list(args)
-    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
-
-
 def _flag(line, key):
     parts = line.split()
     return float(parts[parts.index(key) + 1])
@@ -337,13 +305,13 @@ def test_the_examples_closed_loop(tmp_path, leg):
             "--nbin", "256", "--dDM", ",".join("%g" % v for v in DDMS), "--phase", "%g" % PHASE, "--noise_std",
             "%.6g" % (0.02 * peak), "--seed", "4", "--metafile", "list.txt", "--quiet"]
     args += {"dispersed": [], "dedispersed": ["--dedispersed"], "npol4_scint": ["--npol", "4", "--scint"]}[leg]
-    out = _run("ppfake_run", args, tmp_path, timeout=120)
+    out = run_module("ppfake_run", args, tmp_path, 120)
     lines = [ln for ln in out.splitlines() if "dDM" in ln]
     assert [ln.split()[0] for ln in lines] == ["fake-1.npz", "fake-2.npz", "fake-3.npz"], out
     assert [float(ln.split()[-1]) for ln in lines] == DDMS
     assert (tmp_path / "list.txt").read_text().split() == ["fake-1.npz", "fake-2.npz", "fake-3.npz"]
-    out = _run("pptoas_run", ["-d", "list.txt", "-m", pc.GMODEL, "--DM", "34.56789", "--print_phase", "--quiet"], tmp_path,
-               timeout=120)
+    out = run_module("pptoas_run", ["-d", "list.txt", "-m", pc.GMODEL, "--DM", "34.56789", "--print_phase", "--quiet"],
+                     tmp_path, 120)
     toas = [ln for ln in out.splitlines() if "-pp_dm " in ln]
     assert len(toas) == 6, out
     if leg == "npol4_scint":

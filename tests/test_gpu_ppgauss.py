@@ -15,39 +15,20 @@ Bars
                   parameters (one parameter's difference between two solves is a single draw and can be near zero
                   by chance; the largest is what the two reference solves guarantee of each other)
 With PP_PPGAUSS_PARITY_OUT set, the achieved distances are written there as JSON (profiles/ppgauss_parity.json)."""
-import json
 import math
 import os
-import signal
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+from tests.gpu_support import eng, measured_writer, run_module  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-MEASURED = {}
+MEASURED, _write_measured = measured_writer("PP_PPGAUSS_PARITY_OUT")
 PHI_BAR, DM_BAR = 1e-9, 1e-6        # the legacy fit_portrait golden test's bars (tests/test_gpu_parity.py)
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pulseportraiture_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_measured():
-    yield
-    out = os.environ.get("PP_PPGAUSS_PARITY_OUT")
-    if out and MEASURED:
-        with open(out, "w") as fh:
-            json.dump(MEASURED, fh, indent=1, sort_keys=True)
 
 
 def _g(name):
@@ -215,13 +196,10 @@ def test_golden_fits_through_the_engine(eng, name):
     from pulseportraiture_amd.pplib import fit_gaussian_portrait, get_bin_centers
     g = _g("ppgauss_fit_" + name)
     nchan, nbin = g["data"].shape
-    eng.set_option("profile", 1)
-    eng.kernel_times(reset=True)
-    r = fit_gaussian_portrait(str(g["code"]), g["data"], g["init_params"], float(g["scattering_index_in"]),
-                              np.outer(g["errs"], np.ones(nbin)), g["fit_flags"], False, get_bin_centers(nbin), g["freqs"],
-                              float(g["nu_ref"]), engine=eng)
-    kt = eng.kernel_times(reset=True)
-    eng.set_option("profile", 0)
+    with eng.profiled() as kt:
+        r = fit_gaussian_portrait(str(g["code"]), g["data"], g["init_params"], float(g["scattering_index_in"]),
+                                  np.outer(g["errs"], np.ones(nbin)), g["fit_flags"], False, get_bin_centers(nbin),
+                                  g["freqs"], float(g["nu_ref"]), engine=eng)
     # one iteration is one gauss_residuals plus one gauss_normal, plus one of each per trial step
     lm = r.lm_results
     assert kt["gauss_resid"][1] == lm.niter + lm.nfev + 1 and kt["gauss_normal"][1] == lm.niter + lm.nfev
@@ -285,26 +263,6 @@ def test_make_gaussian_model_rotates_and_refits_to_convergence(eng, tmp_path):
     np.testing.assert_allclose(mdl["params"], dp.model_params, rtol=0, atol=6e-9)
 
 
-def _run(args, cwd, timeout=300):
-    """`python -m pulseportraiture_amd.ppgauss_run args` in a session of its own, under a time limit."""
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    cmd = [sys.executable, "-m", "pulseportraiture_amd.ppgauss_run"] + args
-    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
-
-
 def test_command_line_round_trip_to_toas(tmp_path):
     """archive -> ppgauss_run --gauss ... -> .gmodel -> GetTOAs: the pipeline README describes."""
     from pulseportraiture_amd import gmodel
@@ -314,8 +272,8 @@ def test_command_line_round_trip_to_toas(tmp_path):
     P = gmodel.EXAMPLE_PERIOD
     np.savez(tmp_path / "case.npz", subints=g["data"][None, None], freqs=g["freqs"][None], Ps=np.array([P]),
              epochs=np.array([55000.0]), noise_stds=np.full((1, 1, nchan), 0.05), bw=800.0, source="PSR_1234-5678")
-    out = _run(["-d", "case.npz", "--gauss", "0.22,0.05,4.0", "--gauss", "0.234,0.016,7.0", "--gauss", "0.258,0.024,2.4",
-                "-o", "out.gmodel", "-m", "made_here"], tmp_path)
+    out = run_module("ppgauss_run", ["-d", "case.npz", "--gauss", "0.22,0.05,4.0", "--gauss", "0.234,0.016,7.0", "--gauss",
+                                     "0.258,0.024,2.4", "-o", "out.gmodel", "-m", "made_here"], tmp_path, 300)
     assert "Fitting Gaussian model portrait..." in out
     mdl = gmodel.read_gmodel(str(tmp_path / "out.gmodel"))
     assert mdl["name"] == "made_here" and mdl["ngauss"] == 3 and mdl["code"] == "000"

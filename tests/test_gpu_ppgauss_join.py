@@ -15,39 +15,20 @@ Bars
                   parameters; model and data with the offsets taken out again against NumPy at 8e-14 of the peak
 With PP_PPGAUSS_JOIN_PARITY_OUT set, the achieved distances are written there as JSON
 (profiles/ppgauss_join_parity.json)."""
-import json
 import os
-import signal
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+from tests.gpu_support import eng, measured_writer, run_module  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-MEASURED = {}
+MEASURED, _write_measured = measured_writer("PP_PPGAUSS_JOIN_PARITY_OUT")
 PHI_BAR, DM_BAR = 1e-9, 1e-6        # the legacy fit_portrait golden test's bars (tests/test_gpu_parity.py)
 Dconst = 0.000241 ** -1
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pulseportraiture_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_measured():
-    yield
-    out = os.environ.get("PP_PPGAUSS_JOIN_PARITY_OUT")
-    if out and MEASURED:
-        with open(out, "w") as fh:
-            json.dump(MEASURED, fh, indent=1, sort_keys=True)
 
 
 def _g(name):
@@ -262,14 +243,12 @@ def test_golden_joined_fits_through_the_engine(eng, name):
     from pulseportraiture_amd.pplib import fit_gaussian_portrait, get_bin_centers
     g = _g("ppgauss_join_fit_" + name)
     nchan, nbin = g["data"].shape
-    eng.set_option("profile", 1)
-    eng.kernel_times(reset=True)
-    r = fit_gaussian_portrait(str(g["code"]), g["data"], g["init_params"], float(g["scattering_index_in"]),
-                              np.outer(g["errs"], np.ones(nbin)), g["fit_flags"], False, get_bin_centers(nbin), g["freqs"],
-                              float(g["nu_ref"]), join_params=[join_ichans_of(g), g["join_init"], g["join_flags"]],
-                              P=float(g["P"]), engine=eng)
-    kt = eng.kernel_times(reset=True)
-    eng.set_option("profile", 0)
+    with eng.profiled() as kt:
+        r = fit_gaussian_portrait(str(g["code"]), g["data"], g["init_params"], float(g["scattering_index_in"]),
+                                  np.outer(g["errs"], np.ones(nbin)), g["fit_flags"], False, get_bin_centers(nbin),
+                                  g["freqs"], float(g["nu_ref"]),
+                                  join_params=[join_ichans_of(g), g["join_init"], g["join_flags"]], P=float(g["P"]),
+                                  engine=eng)
     # one iteration is one gauss_residuals plus one gauss_normal, plus one of each per trial step
     lm = r.lm_results
     assert kt["gauss_resid"][1] == lm.niter + lm.nfev + 1 and kt["gauss_normal"][1] == lm.niter + lm.nfev
@@ -377,26 +356,6 @@ def test_make_gaussian_model_on_two_bands(eng, tmp_path):
                                      port_max_abs=float(np.abs(dp.port - m["port_out"]).max()))
 
 
-def _run(module, args, cwd, timeout=300):
-    """`python -m pulseportraiture_amd.<module> args` in a session of its own, under a time limit."""
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    cmd = [sys.executable, "-m", "pulseportraiture_amd." + module] + args
-    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
-
-
 def test_command_line_round_trip_to_toas(tmp_path):
     """two band archives -> ppgauss_join_run -M -> .gmodel + .join -> pptoas_run on one of the bands: the joined route
     README describes."""
@@ -408,7 +367,8 @@ def test_command_line_round_trip_to_toas(tmp_path):
                  epochs=np.array([55000.0]), noise_stds=np.full((1, 1, nchan), 0.05), bw=-400.0, source="PSR_1234-5678")
     (tmp_path / "bands.txt").write_text("band1.npz\nband2.npz\n")
     (tmp_path / "start.gmodel").write_bytes(m["start_gmodel"].tobytes())
-    out = _run("ppgauss_join_run", ["-M", "bands.txt", "-I", "start.gmodel", "-o", "out.gmodel", "-m", "joined_here"], tmp_path)
+    out = run_module("ppgauss_join_run", ["-M", "bands.txt", "-I", "start.gmodel", "-o", "out.gmodel", "-m", "joined_here"],
+                     tmp_path, 300)
     assert "Fitting Gaussian model portrait..." in out
     mdl = gmodel.read_gmodel(str(tmp_path / "out.gmodel"))
     assert mdl["name"] == "joined_here" and mdl["ngauss"] == 3 and os.path.exists(str(tmp_path / "out.gmodel_errs"))
@@ -418,6 +378,6 @@ def test_command_line_round_trip_to_toas(tmp_path):
     lines = (tmp_path / "joined_here.join").read_text().splitlines()
     assert len(lines) == 3 and lines[0].startswith("# archive name") and [ln.split()[0] for ln in lines[1:]] == ["band1.npz", "band2.npz"]
     assert float(lines[1].split()[1]) == 0.0 and abs(float(lines[2].split()[1]) - float(g["fitted_params"][-2])) < 1e-9
-    toas = _run("pptoas_run", ["-d", "band2.npz", "-m", "out.gmodel", "-o", "band2.tim"], tmp_path)
+    toas = run_module("pptoas_run", ["-d", "band2.npz", "-m", "out.gmodel", "-o", "band2.tim"], tmp_path, 300)
     tim = (tmp_path / "band2.tim").read_text().splitlines()
     assert len([ln for ln in tim if "band2.npz" in ln]) == 1, (toas, tim)

@@ -8,13 +8,12 @@ inputs.  Total weights, the identity and the four ways of cutting a call up: bit
 rot and DM within the same relative bar (the README's caller-level parity bar), TOA strings identical."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import scrunch_refs as sr
+from tests.gpu_support import eng, run_module  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,14 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NSUB, NCHAN = 5, 6
 T_OFF, F_OFF = [0, 3, 5], [0, 1, 4, 6]
 POLS = [(1, "keep"), (1, "first"), (2, "keep"), (2, "sum01"), (2, "first"), (4, "keep"), (4, "sum01"), (4, "first")]
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pulseportraiture_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
 
 
 _inputs = {}
@@ -104,12 +95,8 @@ def test_scrunch_bits_do_not_depend_on_runs_device_or_other_groups(eng, npol, po
     # runs of two subints: [0, 1] [2, 3] [4] -- both time groups straddle a run boundary
     npo = npol if pol_mode == "keep" else 1
     per_sub = npol * NCHAN * nbin * x.itemsize + npo * (len(F_OFF) - 1) * nbin * 8 + 24 * NCHAN
-    before = eng.get_option("max_work_bytes")
-    eng.set_option("max_work_bytes", 2.5 * per_sub)
-    try:
+    with eng.options(max_work_bytes=2.5 * per_sub):
         cut, wcut = eng.scrunch(x, w, T_OFF, F_OFF, pol_mode)
-    finally:
-        eng.set_option("max_work_bytes", before)
     assert np.array_equal(cut, one) and np.array_equal(wcut, wone)
     dev, wdev = eng.scrunch(torch.from_numpy(x).to("cuda:0"), w, T_OFF, F_OFF, pol_mode)
     assert dev.is_cuda and dev.dtype == torch.float64
@@ -216,27 +203,6 @@ def _periods_apart(a, b, P):
     return (d.intday() * 86400.0 + d.fracday() * 86400.0) / P
 
 
-def _run(module, args, cwd, timeout=300):
-    import signal
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    env["PYTHONPATH"] = ROOT
-    cmd = [sys.executable, "-m", "pulseportraiture_amd." + module] + list(args)
-    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
-
-
 def test_get_TOAs_tscrunch_end_to_end(tmp_path):
     from pulseportraiture_amd import archive, pptoas, scrunch
     from pulseportraiture_amd.engine import default_engine
@@ -274,10 +240,10 @@ def test_get_TOAs_tscrunch_end_to_end(tmp_path):
     print("anchor subint %d: %.9f periods apart, tolerance %.3e" % (anchor, turns, tol))
     assert abs(turns - np.round(turns)) <= tol and np.round(turns) != 0
     # ... and through the commands, in child processes
-    _run("ppscrunch_run", ["-d", name, "-T", "--quiet"], tmp_path, timeout=120)
+    run_module("ppscrunch_run", ["-d", name, "-T", "--quiet"], tmp_path, 120)
     scr = str(tmp_path / "fake.scr.npz")
     assert os.path.exists(scr)
-    out = _run("pptoas_run", ["-d", scr, "-m", GMODEL, "--nu_ref", "%g" % NU_REF, "--quiet"], tmp_path, timeout=120)
+    out = run_module("pptoas_run", ["-d", scr, "-m", GMODEL, "--nu_ref", "%g" % NU_REF, "--quiet"], tmp_path, 120)
     lines = [ln for ln in out.splitlines() if "-pp_dm " in ln]
     assert len(lines) == 1, out
     day, frac = _mjd_string(lines[0]).split(".")

@@ -8,7 +8,6 @@ restatement's two inverse forms (time-domain even/odd averaging against the fram
 to max |row|: the device's adjoint form is one more rearrangement of that kind.  With PP_PPSMOOTH_PARITY_OUT set, both
 figures of every case are written there as JSON (profiles/ppsmooth_parity.json).
 """
-import json
 import os
 
 import numpy as np
@@ -16,31 +15,18 @@ import pytest
 
 from tests import ppsmooth_cases as sc
 from tests import wavelet_ref as wr
+from tests.gpu_support import default_eng, measured_writer
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 TIE = 1e-9
-MEASURED = {}
+MEASURED, _write_measured = measured_writer("PP_PPSMOOTH_PARITY_OUT")
 
 
 def _g(name):
     return np.load(os.path.join(GOLDEN, "ppsmooth_%s.npz" % name))
-
-
-def _eng():
-    from pulseportraiture_amd.engine import default_engine
-    return default_engine()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _parity_file():
-    yield
-    path = os.environ.get("PP_PPSMOOTH_PARITY_OUT")
-    if path and MEASURED:
-        with open(path, "w") as f:
-            json.dump(MEASURED, f, indent=1, sort_keys=True)
 
 
 def _record(key, dev, forms):
@@ -58,7 +44,7 @@ def test_wavelet_smooth_matches_the_reference(nbin, nlevel):
     rows = np.tile(x, (len(sc.FACTS), 1))
     worst = 0.0
     for tt in sc.THRESHTYPES:
-        got = _eng().wavelet_smooth(rows, nlevel=nlevel, threshtype=tt, fact=np.array(sc.FACTS))
+        got = default_eng().wavelet_smooth(rows, nlevel=nlevel, threshtype=tt, fact=np.array(sc.FACTS))
         for i, fact in enumerate(sc.FACTS):
             want = g["out_%d_%d_%s_%g" % (nbin, nlevel, tt, fact)]
             worst = max(worst, np.abs(got[i] - want).max() / np.abs(x).max())
@@ -133,7 +119,7 @@ def test_a_row_gives_the_same_bits_alone_and_in_a_batch():
     rows[5] = 0.0
     rows[11] *= 1e-6
     rows[17] = rng.standard_normal(256)
-    eng = _eng()
+    eng = default_eng()
     all_out, all_info = eng.smart_smooth(rows, 8)
     for i in (0, 5, 11, 17, 37):
         one_out, one_info = eng.smart_smooth(rows[i:i + 1], 8)
@@ -148,7 +134,7 @@ def test_a_row_gives_the_same_bits_alone_and_in_a_batch():
 
 def test_f32_and_device_tensor_input():
     import torch
-    eng = _eng()
+    eng = default_eng()
     x32 = np.array([sc.profile(256, 30.0, 4400 + i) for i in range(3)], dtype=np.float32)
     x64 = x32.astype(np.float64)
     want = eng.wavelet_smooth(x64, nlevel=4, fact=1.0)
@@ -165,7 +151,7 @@ def test_f32_and_device_tensor_input():
 
 def test_argument_checks():
     from pulseportraiture_amd.engine import EngineError
-    eng = _eng()
+    eng = default_eng()
     x = sc.profile(256, 30.0, 1)[None]
     with pytest.raises(EngineError):
         eng.wavelet_smooth(x[:, :255], nlevel=1)                 # odd nbin

@@ -16,15 +16,13 @@ the reference's column (smoothing is odd).
 """
 import os
 import pickle
-import signal
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import ppsmooth_cases as sc
 from tests import ppspline_cases as pc
+from tests.gpu_support import run_module
 
 pytestmark = pytest.mark.gpu
 
@@ -136,25 +134,6 @@ def test_make_smooth_spline_model_against_the_reference(name):
     assert not hasattr(dp, "smooth_eigvec") and not hasattr(dp, "smooth_mean_prof")
 
 
-def _run(args, cwd, timeout=300):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    cmd = [sys.executable, "-m", "pulseportraiture_amd.ppspline_smooth_run"] + args
-    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
-
-
 @pytest.mark.parametrize("name", sc.MODEL_CASES)
 def test_command_line_writes_the_references_smoothed_model(name, tmp_path):
     from pulseportraiture_amd.splmodel import read_spline_model
@@ -162,7 +141,7 @@ def test_command_line_writes_the_references_smoothed_model(name, tmp_path):
     np.savez(tmp_path / "avg.npz", subints=_port(name)[None, None], freqs=g["freqs"][None], Ps=np.array([P0]),
              epochs=np.array([55000.0]), weights=g["weights"][None], noise_stds=g["noise_stds"][None, None],
              bw=float(g["bw"]), source="fake", SNRs=g["SNRs"][None, None])
-    out = _run(["-d", "avg.npz", "-N", "None", "-l", "the model", "-s"], tmp_path)
+    out = run_module("ppspline_smooth_run", ["-d", "avg.npz", "-N", "None", "-l", "the model", "-s"], tmp_path, 300)
     assert "Wrote modelfile avg.npz.spl." in out and "uses %d basis" % len(g["ieig"]) in out
     model_name, source, datafile, mean_prof, eigvec, tck = read_spline_model(str(tmp_path / "avg.npz.spl"), quiet=True)
     assert (model_name, source, datafile) == ("the model", "fake", "avg.npz")

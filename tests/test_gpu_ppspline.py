@@ -6,24 +6,21 @@ quantity's scale: the device's summation order is one more reordering of that ki
 arbitrary sign in both implementations; signs are aligned by the dot product with the reference's column.
 With PP_PPSPLINE_PARITY_OUT set, the measured deviations are written there as JSON (profiles/ppspline_parity.json).
 """
-import json
 import os
 import pickle
-import signal
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import ppspline_cases as pc
+from tests.gpu_support import default_eng, measured_writer, run_module
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 P0 = 0.003
-MEASURED = {}
+MEASURED, _write_measured = measured_writer("PP_PPSPLINE_PARITY_OUT")
 
 
 def _g(name):
@@ -37,11 +34,6 @@ def _port(name):
         return port
     g = _g(name)
     return g["port"] if "port" in g.files else _g("64x256")["port"]
-
-
-def _eng():
-    from pulseportraiture_amd.engine import default_engine
-    return default_engine()
 
 
 def _bunch(name, port=None, with_snrs=True):
@@ -120,15 +112,6 @@ def _compare(name, g, mean_prof, eigval, eigvec, stats, ieig, proj_port, tck, fp
     return bad
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _write_measured():
-    yield
-    out = os.environ.get("PP_PPSPLINE_PARITY_OUT")
-    if out and MEASURED:
-        with open(out, "w") as f:
-            json.dump(MEASURED, f, indent=1, sort_keys=True)
-
-
 @pytest.mark.parametrize("name", list(pc.CASES))
 def test_make_spline_model_against_the_reference(name):
     g, kw = _g(name), pc.CASES[name][5]
@@ -153,18 +136,18 @@ def test_channel_snrs_against_get_SNR(name, dtype, rtol):
     from pulseportraiture_amd.pplib import get_SNR
     g, port = _g(name), _port(name)
     ok = g["weights"] > 0
-    snrs = _eng().channel_snrs(port[ok].astype(dtype))
+    snrs = default_eng().channel_snrs(port[ok].astype(dtype))
     np.testing.assert_allclose(snrs, g["SNRs"][ok], rtol=rtol, atol=0)
     if dtype is np.float64:
         n = int(np.where(ok)[0][3])
         np.testing.assert_allclose(get_SNR(port[n]), g["SNRs"][n], rtol=rtol, atol=0)
         np.testing.assert_allclose(get_SNR(port[n], fudge=1.0), 3.25 * g["SNRs"][n], rtol=rtol, atol=0)
-        cube = _eng().channel_snrs(port[None, ok])
+        cube = default_eng().channel_snrs(port[None, ok])
         assert cube.shape == (1, ok.sum()) and np.array_equal(cube[0], snrs)
     # a profile whose sum is not positive (its maximum is) has no S/N (get_SNR's mask)
     low = port[ok][:2] - 1.5 * port[ok][:2].mean(axis=1, keepdims=True)
     assert low.sum(axis=1).max() < 0 < low.max(axis=1).min()
-    assert _eng().channel_snrs(low.astype(dtype)).tolist() == [0.0, 0.0]
+    assert default_eng().channel_snrs(low.astype(dtype)).tolist() == [0.0, 0.0]
 
 
 def test_normalize_portrait_side_effects():
@@ -205,7 +188,7 @@ def test_gram_matrix_exact_on_small_integers_and_the_same_bits_twice(nchan, nbin
     half = rng.integers(-8, 9, size=(nchan // 2, nbin)).astype(np.float64)
     port = np.concatenate([half, -half])[rng.permutation(nchan)]
     w = np.ones(nchan)
-    eng = _eng()
+    eng = default_eng()
     mean_prof, gram, fact = eng.pca_gram(port, w)
     assert fact == nchan - 1.0 and not mean_prof.any()
     want = (np.dot(port, port.T) if nchan < nbin else np.dot(port.T, port)) * (1.0 / fact)
@@ -236,7 +219,7 @@ def test_f32_and_device_tensor_input(name):
     ok = g["weights"] > 0
     x, snrs = port[ok], g["SNRs"][ok]
     w = snrs / snrs.sum()
-    eng = _eng()
+    eng = default_eng()
     m64, g64, _ = eng.pca_gram(x, w)
     x32 = x.astype(np.float32)
     m32, g32, _ = eng.pca_gram(x32, w)
@@ -257,26 +240,6 @@ def test_f32_and_device_tensor_input(name):
     dp32.make_spline_model(smooth=False, quiet=True, **kw)
     np.testing.assert_array_equal(dp32.ieig, dp64.ieig)
     np.testing.assert_allclose(dp32.model, dp64.model, rtol=0, atol=1e-5 * np.abs(dp64.model).max())
-
-
-def _run(args, cwd, timeout=300):
-    """`python -m pulseportraiture_amd.ppspline_run args` in a session of its own, under a time limit."""
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    cmd = [sys.executable, "-m", "pulseportraiture_amd.ppspline_run"] + args
-    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
 
 
 def _write_archive(path, name, with_snrs=True):
@@ -300,7 +263,7 @@ def test_command_line_writes_the_references_model(name, tmp_path):
     for opt, key in (("-n", "max_ncomp"), ("-S", "snr_cutoff"), ("-k", "k"), ("-f", "sfac"), ("-t", "max_nbreak")):
         if key in kw:
             argv += [opt, repr(kw[key])]
-    out = _run(argv, tmp_path)
+    out = run_module("ppspline_run", argv, tmp_path, 300)
     assert "Wrote modelfile avg.npz.spl." in out and "B-spline interpolation model the model uses %d basis" % len(g["ieig"]) in out
     model_name, source, datafile, mean_prof, eigvec, tck = read_spline_model(str(tmp_path / "avg.npz.spl"), quiet=True)
     assert (model_name, source, datafile) == ("the model", "fake", "avg.npz")
@@ -323,13 +286,13 @@ def test_command_line_writes_the_references_model(name, tmp_path):
     # without SNRs in the archive: the device's get_SNR (1e-12 of the reference's) weights the same model
     _write_archive(tmp_path / "bare.npz", name, with_snrs=False)
     (tmp_path / "meta.txt").write_text("bare.npz\n")
-    assert _run(argv[2:] + ["-d", "meta.txt", "-o", "bare.spl", "--quiet"], tmp_path) == ""
+    assert run_module("ppspline_run", argv[2:] + ["-d", "meta.txt", "-o", "bare.spl", "--quiet"], tmp_path, 300) == ""
     bare = read_spline_model(str(tmp_path / "bare.spl"), quiet=True)
     assert bare[:3] == ("the model", "fake", "bare.npz")
     np.testing.assert_allclose(bare[3], mean_prof, rtol=0, atol=1e-10 * np.abs(mean_prof).max())
     np.testing.assert_array_equal(bare[5][0], tck[0])
     # the default normalisation ('prof') runs through
-    assert _run(["-d", "avg.npz", "-o", "other.spl", "--quiet", "-n", "2"], tmp_path) == ""
+    assert run_module("ppspline_run", ["-d", "avg.npz", "-o", "other.spl", "--quiet", "-n", "2"], tmp_path, 300) == ""
     assert read_spline_model(str(tmp_path / "other.spl"), quiet=True)[4].shape[1] <= 2
 
 

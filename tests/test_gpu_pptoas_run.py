@@ -6,12 +6,12 @@ its own under a time limit; a failure or a timeout ends the test."""
 import json
 import os
 import pickle
-import signal
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from tests.gpu_support import child_env, run_command, run_module
 
 pytestmark = pytest.mark.gpu
 
@@ -50,33 +50,8 @@ finally:
 ''' % (LISTS,)
 
 
-def _env(extra_path=None):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    env["PYTHONPATH"] = os.pathsep.join([p for p in (ROOT, extra_path) if p])
-    return env
-
-
-def _run(cmd, timeout, env):
-    """A child in a session of its own; on timeout its process group gets SIGTERM (the launcher
-    forwards it to the ranks), then SIGKILL."""
-    p = subprocess.Popen(cmd, cwd=ROOT, env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
-
-
 def _cli(args, timeout=420):
-    return _run([sys.executable, "-m", "pulseportraiture_amd.pptoas_run"] + list(args), timeout, _env())
+    return run_module("pptoas_run", args, ROOT, timeout)
 
 
 def _api(tmp, nproc, listfile, kw, tag, timeout=420):
@@ -85,7 +60,8 @@ def _api(tmp, nproc, listfile, kw, tag, timeout=420):
     out = tmp / ("lists_%s.pkl" % tag)
     code = ("import sys; from pulseportraiture_amd.pptoas_run import launch; "
             "sys.exit(launch(%d, sys.argv[1:], module='pp_api_driver'))" % nproc)
-    _run([sys.executable, "-c", code, str(listfile), MODEL, json.dumps(kw), str(out)], timeout, _env(str(tmp)))
+    run_command([sys.executable, "-c", code, str(listfile), MODEL, json.dumps(kw), str(out)], ROOT, timeout,
+                child_env(str(tmp)))
     with open(out, "rb") as f:
         return pickle.load(f)
 

@@ -4,12 +4,11 @@ f32, host and device input (and nbin 4096 against NumPy); the clip's zap lists; 
 on two ranks sharing the GPU over gloo; a subint's noise and zap row independent of its batch.  Every child
 runs in a session of its own under a time limit."""
 import os
-import signal
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+from tests.gpu_support import default_eng, run_module
 
 pytestmark = pytest.mark.gpu
 
@@ -19,11 +18,6 @@ MODEL = os.path.join(GOLDEN, "example.gmodel")
 G = np.load(os.path.join(GOLDEN, "ppzap_noise.npz"))
 NORMS = ["none", "mean", "max", "prof", "rms", "abs"]
 CLIPPED = ["none", "mean", "max", "prof", "abs"]     # (rms: every normalised noise is 1, the clip decides nothing)
-
-
-def _eng():
-    from pulseportraiture_amd.engine import default_engine
-    return default_engine()
 
 
 def _ok(ia):
@@ -40,7 +34,7 @@ def _norm(name):
 @pytest.mark.parametrize("dtype,rtol", [(np.float64, 1e-12), (np.float32, 1e-5)])
 def test_channel_noise_against_the_reference(ia, norm, dtype, rtol):
     ports, w = _ok(ia)
-    noise, norms = _eng().channel_noise(ports.astype(dtype), norm=_norm(norm), weights=w)
+    noise, norms = default_eng().channel_noise(ports.astype(dtype), norm=_norm(norm), weights=w)
     np.testing.assert_allclose(noise, G["a%d_noise_%s" % (ia, norm)], rtol=rtol, atol=0)
     np.testing.assert_allclose(norms, G["a%d_norms_%s" % (ia, norm)], rtol=rtol, atol=0)
 
@@ -61,7 +55,7 @@ def test_zap_lists_against_the_reference(ia, norm, nstd):
     if norm != "none":          # (the command line's -N; without it the bunch has no noise: measured on the device)
         ports, w = _ok(ia)
         ns = np.zeros((d.nsub, 1, d.nchan))
-        ns[d.ok_isubs, 0] = _eng().channel_noise(ports, norm=norm, weights=w)[0]
+        ns[d.ok_isubs, 0] = default_eng().channel_noise(ports, norm=norm, weights=w)[0]
         d.noise_stds = ns
     want = [[int(c) for c in np.nonzero(r)[0]] for r in G["a%d_zap_%s_%d" % (ia, norm, nstd)]]
     assert get_zap_channels(d, nstd=nstd) == want
@@ -69,7 +63,7 @@ def test_zap_lists_against_the_reference(ia, norm, nstd):
 
 @pytest.mark.parametrize("ia", [1, 2])
 def test_a_subints_noise_and_zap_row_do_not_depend_on_its_batch(ia):
-    eng = _eng()
+    eng = default_eng()
     x, w = _ok(ia)
     good = w > 0
     noise = eng.channel_noise(x)[0]
@@ -92,8 +86,8 @@ def test_device_tensor_input_gives_the_host_bits(norm, ia, dtype):
     import torch
     ports, w = _ok(ia)
     ports = ports.astype(dtype)
-    host = _eng().channel_noise(ports, norm=norm, weights=w)
-    dev = _eng().channel_noise(torch.as_tensor(ports, device="cuda"), norm=norm, weights=w)
+    host = default_eng().channel_noise(ports, norm=norm, weights=w)
+    dev = default_eng().channel_noise(torch.as_tensor(ports, device="cuda"), norm=norm, weights=w)
     for a, b in zip(host, dev):
         assert a.tobytes() == b.tobytes()
 
@@ -108,7 +102,7 @@ def test_nbin_4096_several_waves_per_row(dtype):
     x = 40.0 * np.exp(-0.5 * ((ph - 0.4) / 0.01) ** 2) + rng.standard_normal((3, 8, 4096)) * rng.uniform(1, 9, (3, 8, 1))
     x[1, 3] = 0.0
     x = x.astype(dtype)
-    eng = _eng()
+    eng = default_eng()
     p = np.abs(np.fft.rfft(x.astype(np.float64), axis=-1)) ** 2 / 4096
     want = np.sqrt(p[..., int(0.75 * 2049):].mean(axis=-1))
     for norm, ref in ((None, np.ones(x.shape[:2])), ("mean", x.astype(np.float64).mean(-1)),
@@ -125,28 +119,6 @@ def test_nbin_4096_several_waves_per_row(dtype):
         assert one[0][0].tobytes() == noise[1].tobytes() and one[1][0].tobytes() == norms[1].tobytes()
 
 
-def _run(args, cwd, timeout=600):
-    """`python -m pulseportraiture_amd.ppzap_run args` in a session of its own; on timeout its process group
-    gets SIGTERM (the launcher forwards it to the ranks), then SIGKILL."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    env["PYTHONPATH"] = ROOT
-    cmd = [sys.executable, "-m", "pulseportraiture_amd.ppzap_run"] + list(args)
-    p = subprocess.Popen(cmd, cwd=str(cwd), env=env, start_new_session=True, stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGTERM)
-        try:
-            p.communicate(timeout=30)
-        except subprocess.TimeoutExpired:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.communicate()
-        pytest.fail("timed out after %d s: %s" % (timeout, " ".join(cmd)))
-    assert p.returncode == 0, (" ".join(cmd), err[-4000:])
-    return out
-
-
 def _paz(tmp):
     p = tmp / "paz.txt"
     return p.read_text() if p.exists() else ""
@@ -159,7 +131,7 @@ def test_noise_method_command_line_bytes(k, tmp_path):
         np.savez(tmp_path / ("arch%d.npz" % ia), subints=x, freqs=G["a%d_freqs" % ia], Ps=G["a%d_Ps" % ia],
                  epochs=np.zeros(len(x)), weights=G["a%d_weights" % ia])
     (tmp_path / "list.txt").write_text("arch0.npz\narch1.npz\narch2.npz\n")
-    out = _run(["-d", "list.txt"] + [str(a) for a in G["cli%d_argv" % k]], tmp_path)
+    out = run_module("ppzap_run", ["-d", "list.txt"] + [str(a) for a in G["cli%d_argv" % k]], tmp_path, 600)
     assert out == str(G["cli%d_stdout" % k])
     assert _paz(tmp_path) == str(G["cli%d_file" % k])
 
@@ -188,7 +160,7 @@ def test_model_method_command_line_bytes_on_one_and_two_ranks(tmp_path):
             (1, ["--gpus", "2", "--backend", "gloo"])]
     for k, ranks in runs:
         (tmp_path / "paz.txt").unlink(missing_ok=True)
-        out = _run(["-d", "list.txt", "-m", MODEL] + [str(a) for a in gm["cli%d_argv" % k]] + ranks, tmp_path,
-                   timeout=900)
+        out = run_module("ppzap_run", ["-d", "list.txt", "-m", MODEL] + [str(a) for a in gm["cli%d_argv" % k]] + ranks,
+                         tmp_path, 900)
         assert out == str(gm["cli%d_stdout" % k]), ranks
         assert _paz(tmp_path) == str(gm["cli%d_file" % k]), ranks

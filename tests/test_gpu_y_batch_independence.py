@@ -18,6 +18,8 @@ import argparse
 import numpy as np
 import pytest
 
+from tests.gpu_support import eng  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 NBIG = 512
@@ -30,14 +32,6 @@ def _args(**kw):
              measured_noise=False, method="trust-ncg")
     d.update(kw)
     return argparse.Namespace(**d)
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pulseportraiture_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
 
 
 def _fit(eng, b, lo, hi, x0=None, **kw):
@@ -170,8 +164,7 @@ def test_wide_band_small_shapes_do_not_depend_on_the_batch(eng):
         flags = [1, 1, 0, 1, 1] if scat else [1, 1, 0, 0, 0]
         for method in ("trust-ncg", "newton"):
             for taylor in ((1,) if scat else (1, 0)):
-                eng.set_option("taylor", taylor)
-                try:
+                with eng.options(taylor=taylor):
                     kw = dict(errs=np.full((N, C), 0.05), chan_mask=masks, nu_fits=nuf, fit_flags=flags,
                               log10_tau=scat, method=method)
                     whole = eng.fit_batch(data, freqs, P, x0, **kw)
@@ -179,5 +172,3 @@ def test_wide_band_small_shapes_do_not_depend_on_the_batch(eng):
                         k1 = dict(kw, errs=kw["errs"][i:i + 1], chan_mask=masks[i:i + 1], nu_fits=nuf[i:i + 1])
                         one = eng.fit_batch(data[i:i + 1], freqs, P[i:i + 1], x0[i:i + 1], **k1)
                         _same(whole, one, i, i + 1, "%dx%d scat=%s %s taylor=%d subint %d" % (C, B, scat, method, taylor, i))
-                finally:
-                    eng.set_option("taylor", 1)

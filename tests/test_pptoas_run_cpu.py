@@ -13,6 +13,7 @@ import pytest
 
 from pulseportraiture_amd import archive, pptoas, pptoas_run
 from pulseportraiture_amd.dist import shard_range
+from tests.gpu_support import kill_group
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL = os.path.join(ROOT, "tests", "golden", "example.gmodel")
@@ -357,8 +358,7 @@ def test_launcher_leaves_no_rank_behind_after_sigterm(tmp_path):
         assert not any(_alive(x) for x in pids)
     finally:
         if p.poll() is None:
-            os.killpg(p.pid, signal.SIGKILL)
-            p.wait()
+            kill_group(p)
 
 
 @pytest.mark.timeout(180)
