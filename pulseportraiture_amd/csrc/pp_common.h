@@ -77,7 +77,9 @@ __device__ __forceinline__ double kconst(double v) {
     return v;
 }
 // SC: polynomial coefficients from scalar registers (k_xspec: -30 VALU per row)
-template <bool SC = false>
+// ISGN: the quadrant's signs go into the high dwords as integers -- (x << 31) keeps bit 0 of x, and adding it flips the
+// sign bit exactly as the negation does -- instead of a compare, a negated copy and a select for each of the two
+template <bool SC = false, bool ISGN = false>
 __device__ __forceinline__ void sincos_turns(double t, double* sn, double* cs) {
     const double q = rint(4.0 * t);
     const double y = fma(-0.25, q, t);          // exact
@@ -104,6 +106,12 @@ __device__ __forceinline__ void sincos_turns(double t, double* sn, double* cs) {
     const int qi = (int)q;
     const bool odd = qi & 1;
     const double so = odd ? c0 : s0, co = odd ? s0 : c0;
+    if (ISGN) {
+        const unsigned uq = (unsigned)qi;
+        *sn = __hiloint2double((int)((unsigned)__double2hiint(so) + ((uq >> 1) << 31)), __double2loint(so));
+        *cs = __hiloint2double((int)((unsigned)__double2hiint(co) + (((uq + 1u) >> 1) << 31)), __double2loint(co));
+        return;
+    }
     *sn = (qi & 2) ? -so : so;
     *cs = ((qi + 1) & 2) ? -co : co;
 }
@@ -111,14 +119,14 @@ __device__ __forceinline__ void sincos_turns(double t, double* sn, double* cs) {
 // exp(2 pi i k phi) with the product reduced modulo 1 before the sincos:
 // k*phi is formed exactly (fma residual), so large non-dedispersed phase
 // shifts do not lose the fraction.
-template <bool SC = false>
+template <bool SC = false, bool ISGN = false>
 __device__ __forceinline__ cplx unit_phasor(double k, double phi) {
     double pfrac = phi - rint(phi);          // exact
     double prod = k * pfrac;
     double err = fma(k, pfrac, -prod);       // exact residual of the product
     double r = (prod - rint(prod)) + err;
     double s, c;
-    sincos_turns<SC>(r, &s, &c);
+    sincos_turns<SC, ISGN>(r, &s, &c);
     return make_double2(c, s);
 }
 
@@ -173,19 +181,42 @@ __device__ __forceinline__ double wave_reduce16(const double (&s)[NS], int lane)
 // finish.  ~3 NS + 22 instructions instead of ~230; `buf` holds NS * 68 doubles
 // (rows padded so that the strided reads spread over the banks).  On return lane l
 // holds the wave total of s[(l >> 2)] for l < 4 NS (same indexing as above).
-template <int NS>
+//
+// LEAN: the same stores, the same sixteen additions in the same order and the same two quad exchanges, with fewer
+// instructions around them.  The positions are the identities (l >> 4) 17 + (l & 15) = l + (l >> 4) and
+// 68 q + 17 p = 17 (4 q + p) -- shifts and additions where the products above become v_mul_lo_u32, a quarter-rate
+// instruction each --, and the partner of a quad exchange comes by DPP (quad_perm: two v_mov_b32 a value) instead of
+// ds_bpermute_b32, which computes the partner's lane number first (mbcnt, xor, compare, select, shift) and goes
+// through the LDS unit.  a + b = b + a: the bits are the same.
+template <int X>   // the value of lane l ^ X, X = 1 or 2
+__device__ __forceinline__ double quad_xor(double v) {
+    static_assert(X == 1 || X == 2, "inside a quad");
+    constexpr int ctrl = X == 1 ? 0xB1 : 0x4E;      // quad_perm:[1,0,3,2] | [2,3,0,1]
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    // (every lane is written and every source lane is inside its quad: no old value to keep, no copy in front)
+    lo = __builtin_amdgcn_mov_dpp(lo, ctrl, 0xF, 0xF, false);
+    hi = __builtin_amdgcn_mov_dpp(hi, ctrl, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+template <int NS, bool LEAN = false>
 __device__ __forceinline__ double wave_reduce_lds(const double (&s)[NS], int lane, double* buf) {
     static_assert(NS <= 16, "one value per lane quad");
-    const int wpos = (lane >> 4) * 17 + (lane & 15);
+    const unsigned l = (unsigned)lane & 63u;
+    const int wpos = LEAN ? (int)(l + (l >> 4)) : (lane >> 4) * 17 + (lane & 15);
 #pragma unroll
     for (int q = 0; q < NS; ++q) buf[q * 68 + wpos] = s[q];
     const int q = min(lane >> 2, NS - 1), part = lane & 3;
-    const double* src = buf + q * 68 + part * 17;
+    const double* src = LEAN ? buf + 17u * (4u * min(l >> 2, (unsigned)(NS - 1)) + (l & 3u)) : buf + q * 68 + part * 17;
     double v = 0.0;
 #pragma unroll
     for (int t = 0; t < 16; ++t) v += src[t];
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
+    if (LEAN) {
+        v += quad_xor<1>(v);
+        v += quad_xor<2>(v);
+    } else {
+        v += __shfl_xor(v, 1, 64);
+        v += __shfl_xor(v, 2, 64);
+    }
     return v;
 }
 #define PP_WRED_DOUBLES(NS) ((NS) * 68)

@@ -59,7 +59,9 @@ constexpr int FFTQ_LDS_ELEMS = 4 * 272;      // four rows of 16 lanes x (16 x 17
 // fftq1024_from takes the two twiddles as callables, each called ONCE where its value is first wanted (in front of
 // the second half of stage 1's butterflies; in front of the lane swaps): a kernel that keeps its lane constants in
 // LDS reads them there instead of holding eight registers from the top of the row.
-template <int WHEN = 0, typename T1, typename T2, typename Mid>
+// LEAN: the transpose's write position (tid >> 4) 272 + 17 (tid & 15) taken as what it is, 17 tid: a shift and an
+// addition where the two products cost a v_mul_lo_u32 (quarter rate) and a v_mad_u32_u24.
+template <int WHEN = 0, bool LEAN = false, typename T1, typename T2, typename Mid>
 __device__ __forceinline__ void fftq1024_from(cplx (&v)[16], cplx* lds, T1 get_t1, T2 get_t2, int tid,
                                               double* power, Mid mid) {
     // ---- stage 1 ----
@@ -110,11 +112,11 @@ __device__ __forceinline__ void fftq1024_from(cplx (&v)[16], cplx* lds, T1 get_t
     }
     // ---- 16 x 16 transpose inside every row of 16 lanes ----
     {
-        cplx* wbase = lds + (tid >> 4) * 272 + 17 * (tid & 15);
+        cplx* wbase = LEAN ? lds + 17u * ((unsigned)tid & 63u) : lds + (tid >> 4) * 272 + 17 * (tid & 15);
 #pragma unroll
         for (int j = 0; j < 16; ++j) wbase[j] = v[j];
         lds_sync<64>();
-        const cplx* rbase = lds + (tid >> 4) * 272 + (tid & 15);
+        const cplx* rbase = LEAN ? wbase - 16u * ((unsigned)tid & 15u) : lds + (tid >> 4) * 272 + (tid & 15);
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] = rbase[17 * j];
         lds_sync<64>();

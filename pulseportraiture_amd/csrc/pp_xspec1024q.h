@@ -59,10 +59,22 @@ constexpr int FFTQ_FREE_ELEM0 = 3 * 272 + 16, FFTQ_FREE_PITCH = 17;
 // it.  (Stores that only some lanes issue are branched around when none does; behind them the number of accesses in
 // flight is unknown, and the next row's wait for its data has to be one for the store's acknowledgement as well.)
 // ONE = false (the kernels that also measure the noise): the two or three one-lane stores.
-template <int M, bool TAIL, bool ONE = true>
+// LEAN (ONE, noise given): the sign of total q <= 10 is bit 1 of q + 1 (+ - - + + - - + + - -, and + for the remainder
+// coefficient), added to the high dword as (x << 31) instead of a negated copy chosen by two compares; the Taylor
+// sums' address is formed for every q and replaced as a whole for S_d.  The same values to the same places.
+template <int M, bool TAIL, bool ONE = true, bool LEAN = false>
 __device__ __forceinline__ void store_row_results(const XspecArgs& a, const size_t rc, const int tid, double tv) {
     constexpr int H = M + 1, kc = (int)(0.75 * H);   // get_noise_PS: int((1 - 1/4) * len(pows))
-  if constexpr (ONE) {
+  if constexpr (ONE && LEAN) {
+    static_assert(!TAIL && PP_TJ == 10 && PP_TSTRIDE == 12, "sign pattern of totals 0..11; S_d in the quads behind them");
+    const unsigned q = (unsigned)wave_reduce16_index(tid);
+    const double th = 0.5 * tv;
+    double val = __hiloint2double((int)((unsigned)__double2hiint(th) + (((q + 1u) >> 1) << 31)), __double2loint(th));
+    double* dst = a.tay + tay_idx(rc, 0) + q;
+    if (q >= (unsigned)PP_TSTRIDE) { val = tv; dst = a.sdraw + rc; }
+    typedef double __attribute__((address_space(1)))* gdp_t;
+    *(gdp_t)(uintptr_t)dst = val;
+  } else if constexpr (ONE) {
     const int q = wave_reduce16_index(tid);
     const double th = 0.5 * tv;
     // Re(i^q z): +Re, -Im, -Re, +Im, ...   (x 1/2: unhalved template against 2 d_k)
@@ -215,6 +227,14 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
     // The walk is kept whole, so a wave back from tail_work finishes its chunk with general rows)
     unsigned fast_left = 0u;
     size_t rc_prev = 0;
+    // (TWL: what a row needs of lambda -- kb and the partner's place in the published image -- in one register carried
+    // across the rows, bits 0..9 the byte offset 16 fftq_lane_of((64 - lambda) & 63), bits 10..16 kb: two
+    // instructions a row to unpack against fourteen to derive them from the lane number.  lambda = 0 is lane 0.)
+    unsigned lanepk = 0u;
+    if (TWL) {
+        const int lamp = fftq_lambda(tid);
+        lanepk = 16u * (unsigned)fftq_lane_of((64 - lamp) & 63) | (unsigned)(lamp ? lamp : 64) << 10;
+    }
     for (; rw.more && tail_after != 0; rw.advance(), row = rw.row, i = i_nx, n = n_nx, --tail_after) {
         // (FASTROW: the walk's steps sit in the general branch of the row top below.  The kernels without it keep
         // theirs where they were measured)
@@ -222,12 +242,16 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
             rw.draw(a.ticket);
             rw.peek(nrows, a.ticket_base, a.mwords);
         }
-        // (everything derived from the lane number is recomputed per row: held across
-        // the row it would cost the registers the prefetched row needs)
+        // (what is derived from the lane number is recomputed per row: held across the row it would cost the
+        // registers the prefetched row needs -- all but TWL's one packed word, lanepk)
         asm volatile("" : "+v"(tid));
-        const int lam = fftq_lambda(tid);
-        const bool l0 = (lam == 0);
-        const int kb = l0 ? 64 : lam;
+        if (TWL) {
+            asm volatile("" : "+v"(lanepk));
+            __builtin_assume((unsigned)tid < 64u);      // (behind the barrier the compiler has forgotten it: masks, range tests)
+        }
+        const int lam = TWL ? 0 : fftq_lambda(tid);       // (TWL: not used)
+        const bool l0 = TWL ? (tid == 0) : (lam == 0);
+        const int kb = TWL ? (int)(lanepk >> 10) : (l0 ? 64 : lam);
         if (TWR) {
             t1 = as_global(a.twB)[2 * tid];
             t2 = as_global(a.twB)[32 * (tid & 15)];
@@ -303,7 +327,7 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
             load_some(0, HALVES ? R1 / 2 : R1);
             __builtin_amdgcn_sched_barrier(0);
         };
-        fftq1024_from<(sizeof(Tin) == 8 ? Q_PREFETCH_F64 : Q_PREFETCH_F32)>(
+        fftq1024_from<(sizeof(Tin) == 8 ? Q_PREFETCH_F64 : Q_PREFETCH_F32), TWL>(
             v, lds, [&]() { return NTW ? ldtw[tid] : t1; }, [&]() { return TWL ? ldt2[FFTQ_FREE_PITCH * (tid & 15)] : t2; },
             tid, &sd, prefetch);
         __builtin_amdgcn_sched_barrier(0);
@@ -342,20 +366,25 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
             load_some(R1 / 2, R1);
             __builtin_amdgcn_sched_barrier(0);
         }
-        const cplx* pc = lds + fftq_lane_of((64 - lam) & 63);   // slot j: register 15 - j -> pc[64 (6 - j)]
+        // slot j: register 15 - j -> pc[64 (6 - j)]
+        const cplx* pc = TWL ? reinterpret_cast<const cplx*>(reinterpret_cast<const char*>(lds) + (lanepk & 0x3ffu))
+                             : lds + fftq_lane_of((64 - lam) & 63);
         // ---- phasors: e^{2 pi i kb phi}; lane 0 (kb = 64) holds the step ----
-        const cplx el = unit_phasor<true>((double)kb, phin);
+        const cplx el = unit_phasor<true, TWL>((double)kb, phin);
         const cplx wst = make_double2(bcast_lane0(el.x), bcast_lane0(el.y));
         cplx e = el, wb = wb0;
         const int ktu = __builtin_amdgcn_readfirstlane(ktn);
         const double kap0 = PP_TWO_PI * (double)kb;
         double tm[PP_TSTRIDE];
-        cplx zc_nx = pc[64 * 6];
+        // (the partner value of the slot in hand and of the next one: TWL alternates between two registers' worth --
+        // carried in one variable the hand-over is two v_mov_b64 a slot)
+        cplx zq[2];
+        zq[0] = pc[64 * 6];
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
             if (j > 0 && !(64 * j < ktu)) break;     // (kept slots are a prefix)
-            const cplx zc = zc_nx;
-            if (j + 1 < NSL && 64 * (j + 1) < ktu) zc_nx = pc[64 * (5 - j)];
+            const cplx zc = zq[TWL ? (j & 1) : 0];
+            if (j + 1 < NSL && 64 * (j + 1) < ktu) zq[TWL ? ((j + 1) & 1) : 0] = pc[64 * (5 - j)];
             // the template cut is a multiple of 64: a slot is kept or dropped as a whole
             if (j == 0 || 64 * j < ktu) {
                 const cplx dd = split_pair(csel(l0, v[j + 1], v[j]), zc, wb);
@@ -377,8 +406,8 @@ __global__ __launch_bounds__(64, 2) void k_xspec_q1024(XspecArgs a) {
         tr[PP_TSTRIDE] = sd;
         if (TAIL) tr[NRED - 1] = tail;
         lds_sync<T>();      // (the partner reads are older than the reduction's writes)
-        double tv = wave_reduce_lds(tr, tid, reinterpret_cast<double*>(lds));
-        store_row_results<M, TAIL, ROWTOP>(a, rc, tid, tv);
+        double tv = wave_reduce_lds<NRED, TWL>(tr, tid, reinterpret_cast<double*>(lds));
+        store_row_results<M, TAIL, ROWTOP, TWL>(a, rc, tid, tv);
         lds_sync<T>();
     }
     }

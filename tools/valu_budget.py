@@ -205,9 +205,10 @@ Operation-count bounds, block by block (one lane's share of a 2048-bin row: 16 c
 an instruction = one VALU issue slot; FMA counted as one):
 
   block                          built   bound   where the difference goes
-  fft stage 1                     296     ~215   DFT16 144-150 (split-radix: 144 adds, the 24 multiplies fused) + 15 twiddle products 60
-                                                 = ~210; built: DFT16 158, products 60, the powers t1^2..t1^15 by a product tree 49 (7
-                                                 squarings at 3 + 7 products at 4), 29 moves / selects.  The tree trades VALU for registers
+  fft stage 1                     292     ~215   DFT16 144-150 (split-radix: 144 adds, the 24 multiplies fused) + 15 twiddle products 60
+                                                 = ~210; built: 289 f64 instructions (DFT16 158, products 60, the powers t1^2..t1^15 by a
+                                                 product tree 49: 7 squarings at 3 + 7 products at 4; the other 22 are f64 too -- the
+                                                 butterflies' own products, not moves) + 3 address instructions.  The tree trades VALU for registers
                                                  and memory: the powers read from a table measured slower (14.25 against 14.07 ms, round 2:
                                                  fifteen 16-byte loads per lane and row, behind the prefetched row).
   fft stage 2                     120      112   4 radix-4 butterflies (64 adds) + 12 twiddle products (48); w2, w3 from t2: 7
@@ -220,14 +221,18 @@ an instruction = one VALU issue slot; FMA counted as one):
                                                  the ONE lane that owns lambda = 0 (its harmonic 64 (j + 1) sits in register j + 1): 28 a row.
                                                  Taking that lane's value through the partner exchange instead costs an 8th slot for the whole
                                                  wave (49); a DFT16 with rotated outputs costs 60.
-  phasor (sincos of kb phi_n)      46      ~40   range reduction + two degree-8 polynomials (coefficients from scalar registers)
-  reduction + stores               51      ~30   13 values x (store, 16-term column sum shared by 4 lanes), 2 quad exchanges, scaling, signs
-  row top + row walk               87      ~25   18 loads' 64-bit addresses (v_add_co / v_addc pairs: 4 groups of 4 KB reach), lambda, kb,
-                                                 the chunk's ticket and mask word; everything that can is scalar (341 s_ instructions a row,
-                                                 each taking an issue slot of its wave: DESIGN.md section 4)
+  phasor (sincos of kb phi_n)      43      ~40   range reduction + two degree-8 polynomials (coefficients from scalar registers); the quadrant's
+                                                 signs as integer additions to the high dwords (46 with a compare, a negated copy and a select each)
+  reduction + stores               47      ~30   13 values x (store, 16-term column sum shared by 4 lanes), 2 quad exchanges by DPP (4 v_mov_b32
+                                                 where ds_bpermute_b32 took 4 LDS instructions and ~12 VALU for the partner's lane number), positions
+                                                 by shifts and additions (three v_mul_lo_u32, quarter rate, before), scaling, signs: 57 before
+  row top + row walk               66      ~25   both row tops, the once-per-chunk one with its 64-bit addresses, ticket and mask word; kb and the
+                                                 partner's LDS offset unpacked from one register carried across the rows (2 instructions; 14 to
+                                                 derive them from the lane number); everything that can is scalar (each s_ instruction takes an
+                                                 issue slot of its wave: DESIGN.md section 4)
   -----------------------------------------------------------------------------------------------
-  k_xspec_q1024<double, false>   1103 (4.5 slots kept; SQ_INSTS_VALU / rows = 1044 measured) against ~930 + the 64 lane swaps:
-  the kernel is within 6 - 11 % of its operation count; no block is more than ~80 instructions (7 % of a row) above its bound and
+  k_xspec_q1024<double, false>   1059 (4.5 slots kept; 1103 before the selects, moves and lane index arithmetic of the row loop were
+  reworked, profiles/row_valu_ab.txt) against ~930 + the 64 lane swaps: the kernel is within 5 - 7 % of its operation count; no block is more than ~80 instructions (7 % of a row) above its bound and
   each of those gaps is a measured trade (registers for the twiddle tree, the LDS unit for the lane swaps).
 
   k_xspec_q1024<double, true> (noise measured, what load_data always asks for): + 87 for |2 d_k|^2 of k = 768 .. 1024 (4 slots x
@@ -241,7 +246,9 @@ an instruction = one VALU issue slot; FMA counted as one):
 Conclusion (round-5 verdict, item 5): every block is within ~10 % of its operation-count bound except FFT stage 1 (+38 %, of which
 the twiddle-power tree is 49 instructions), the reduction (+21 instructions) and the row top (+60); together ~130 instructions = 12 % of a
 row, each a trade measured in rounds 2 - 5 (profiles/README.md).  The 28 v_cndmask of the lambda = 0 lane are the one item this table
-turned up that had not been looked at; both ways around them cost more than they save.  Closed: the transform kernels are f64-issue
+turned up that had not been looked at; both ways around them cost more than they save, and so does a third: moving that lane's
+registers 1..7 down by one under a one-lane EXEC takes 14 v_mov_b64 (a complex value is two), the compiler adds 14 copies of
+its own around them and spills inside the row loop -- 1183 static VALU with it and without.  Closed: the transform kernels are f64-issue
 bound at ~1.1 x their operation count, at the power-capped clock.
 """
 
