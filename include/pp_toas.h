@@ -140,6 +140,14 @@ void* pp_stream(pp_ctx* ctx);
  *                  once (first exchange by lane swaps) and whose split reads only the partner
  *                  harmonics -- k_xspec_q1024 / k_xspec_qf<1024> / k_xspec_qf<512> --, and the
  *                  single-pass reference seed (pp_seed_ref) exists; 0 = the kernels above
+ *   "cu_tables"    1 (default) = f64 2048-bin rows with the noise given, a template cut below 512
+ *                  harmonics and neither a channel mask, an `act` list nor per-subint templates take
+ *                  k_xspec_cu1024: k_xspec_q1024's row with the CU's eight waves in one workgroup
+ *                  that shares LDS tables of the row-invariant twiddle powers (bitwise the same
+ *                  results); 0 = k_xspec_q1024.  A device that does not grant the kernel its 161 792 B
+ *                  of LDS keeps k_xspec_q1024 whatever the option says
+ *   "cu_grid_cap"  k_xspec_cu1024: at most this many workgroups; 0 (default) = one per CU.  For tests
+ *                  (with one workgroup every wave of a small batch has rows and works tickets between them)
  *   "scat_model"   scattering fits: 1 (default) = once the trust-ncg iteration is
  *                  predicted to stay within its range, ONE more pass over the
  *                  cross-spectrum leaves a degree-8 polynomial model of every channel's

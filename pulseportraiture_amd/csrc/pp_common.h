@@ -221,6 +221,19 @@ __device__ __forceinline__ double wave_reduce_lds(const double (&s)[NS], int lan
 }
 #define PP_WRED_DOUBLES(NS) ((NS) * 68)
 
+// The barrier of the threads that work on one thing together.  WV = false: the workgroup (__syncthreads()).
+// WV: ONE wave of a workgroup whose waves each work on something of their own and must not wait for one another
+// (k_xspec_cu1024's waves inside a ticket, pp_tail.h) -- the same two fences around a barrier of the wave alone, which
+// is what __syncthreads() comes to in a workgroup of one wave.
+template <bool WV>
+__device__ __forceinline__ void team_sync() {
+    if constexpr (WV) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    } else __syncthreads();
+}
+
 // block-wide sum of NV values held by every thread; result valid in all
 // threads.  scratch must hold (blockDim.x/64)*NV doubles.
 template <int NV>

@@ -943,7 +943,7 @@ __device__ inline int block_argmin256(double v, int j, double* shv, int* shj) {
 // Block-wide sums of k_fps's 256 threads.  NVW = 1: 256 real threads (block_sum).  NVW = 4: ONE real wave plays the
 // four waves in turn -- lane l is threads l, l + 64, l + 128, l + 192 -- and adds the four wave totals in block_sum's
 // order: bitwise its results (what a transform wave runs as a ticket, pp_tail.h).  part(vt, v): thread vt's values.
-template <int NV, int NVW, typename F>
+template <int NV, int NVW, bool WV = false, typename F>
 __device__ __forceinline__ void fps_bsum(double (&out)[NV], double* scratch, int tid, F&& part) {
     if constexpr (NVW == 1) {
         part(tid, out);
@@ -962,14 +962,14 @@ __device__ __forceinline__ void fps_bsum(double (&out)[NV], double* scratch, int
                 for (int q = 0; q < NV; ++q) scratch[vw * NV + q] = v[q];
             }
         }
-        __syncthreads();
+        team_sync<WV>();
 #pragma unroll
         for (int q = 0; q < NV; ++q) {
             double t = 0.0;
             for (int w = 0; w < NVW; ++w) t += scratch[w * NV + q];
             out[q] = t;
         }
-        __syncthreads();
+        team_sync<WV>();
     }
 }
 
@@ -1019,13 +1019,13 @@ __device__ __forceinline__ double nelder_mead_1d(const double x0, F&& feval, dou
 
 // The 1-D fit of profile pair i: dspec(k) = the data profile's harmonic k, m[k] the model's, X[0 .. M) the work array
 // of their cross-spectrum (LDS where it fits).  Threads: 256 (NVW = 1) or one wave standing in for them (NVW = 4).
-template <int NVW, typename DF>
+template <int NVW, bool WV = false, typename DF>
 __device__ __forceinline__ void fps_body(const FpsArgs& a, const int i, const int tid, const int M, DF&& dspec,
                                          const cplx* m, cplx* X, double* scratch, double* shv, int* shj) {
     constexpr int RT = 256 / NVW;        // real threads
     const int H = M + 1, kc = (int)(0.75 * H);
     double v[3];   // sum |d|^2, sum |m|^2, tail of |d|^2
-    fps_bsum<3, NVW>(v, scratch, tid, [&](const int vt, double (&u)[3]) __attribute__((always_inline)) {
+    fps_bsum<3, NVW, WV>(v, scratch, tid, [&](const int vt, double (&u)[3]) __attribute__((always_inline)) {
         u[0] = u[1] = u[2] = 0.0;
         for (int k = 1 + vt; k <= M; k += 256) {
             const cplx dk = dspec(k), mk = m[k];
@@ -1069,7 +1069,7 @@ __device__ __forceinline__ void fps_body(const FpsArgs& a, const int i, const in
     double f = 0.0, f2 = 0.0;
     // the three sums at one phase, the same in every thread
     auto sums_at = [&](double x, double (&s)[3]) __attribute__((always_inline)) {
-        fps_bsum<3, NVW>(s, scratch, tid, [&](const int vt, double (&u)[3]) __attribute__((always_inline)) {
+        fps_bsum<3, NVW, WV>(s, scratch, tid, [&](const int vt, double (&u)[3]) __attribute__((always_inline)) {
             fps_sums(X, M, x, vt, 256, u[0], u[1], u[2]);
         });
     };

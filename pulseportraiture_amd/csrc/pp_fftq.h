@@ -61,12 +61,31 @@ constexpr int FFTQ_LDS_ELEMS = 4 * 272;      // four rows of 16 lanes x (16 x 17
 // LDS reads them there instead of holding eight registers from the top of the row.
 // LEAN: the transpose's write position (tid >> 4) 272 + 17 (tid & 15) taken as what it is, 17 tid: a shift and an
 // addition where the two products cost a v_mul_lo_u32 (quarter rate) and a v_mad_u32_u24.
-template <int WHEN = 0, bool LEAN = false, typename T1, typename T2, typename Mid>
+// TAB: the powers t1^1 .. t1^15 come from a table that holds what the product tree gives -- get_t1(j), called once for
+// each j where the power is used -- instead of being formed again for every row (k_xspec_cu1024, pp_xspec1024cu.h).
+template <int WHEN = 0, bool LEAN = false, bool TAB = false, typename T1, typename T2, typename Mid>
 __device__ __forceinline__ void fftq1024_from(cplx (&v)[16], cplx* lds, T1 get_t1, T2 get_t2, int tid,
                                               double* power, Mid mid) {
     // ---- stage 1 ----
     dft16_first(v);
     if (WHEN == 0) mid();
+    if constexpr (TAB) {
+        // (the reads run AHEAD products in front of their use -- the first AHEAD are issued in front of the second half
+        // of the butterflies, which hides their latency; all fifteen from there would be 60 registers held through it)
+        constexpr int AHEAD = 8;
+        cplx wq[16];
+#pragma unroll
+        for (int j = 1; j <= AHEAD; ++j) wq[j] = get_t1(j);
+        __builtin_amdgcn_sched_barrier(0);
+        dft16_second(v);
+#pragma unroll
+        for (int j = 1; j < 16; ++j) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (j + AHEAD < 16) wq[j + AHEAD] = get_t1(j + AHEAD);
+            v[j] = cmul(v[j], wq[j]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
     const cplx t1 = get_t1();
     dft16_second(v);
     {
@@ -82,6 +101,7 @@ __device__ __forceinline__ void fftq1024_from(cplx (&v)[16], cplx* lds, T1 get_t
         }
 #pragma unroll
         for (int j = 1; j < 16; ++j) v[j] = cmul(v[j], wq[j]);
+    }
     }
     if (WHEN == 1) mid();
     const cplx t2 = get_t2();

@@ -39,7 +39,15 @@ struct ModelFftArgs {
 struct TailArgs;
 #define PP_TAIL_LDS_DOUBLES 2176     // LDS of the carrying kernels (k_xspec_q1024, k_xspec_qf<1024>: 1088 complex), in doubles
 #define PP_TAIL_CACHE ((PP_TAIL_LDS_DOUBLES - 536) / 4)     // channels whose invariants the in-kernel solve keeps there
-__device__ void tail_work(const TailArgs* t, double* lds, int nlds, int tid, int max_tickets);
+// (WV: the caller is ONE wave of a workgroup of several, in its own share of the LDS -- k_xspec_cu1024)
+template <bool WV>
+__device__ void tail_work_as(const TailArgs* t, double* lds, int nlds, int tid, int max_tickets);
+__device__ __forceinline__ void tail_work(const TailArgs* t, double* lds, int nlds, int tid, int max_tickets) {
+    tail_work_as<false>(t, lds, nlds, tid, max_tickets);
+}
+__device__ __forceinline__ void tail_work_wave(const TailArgs* t, double* lds, int nlds, int tid, int max_tickets) {
+    tail_work_as<true>(t, lds, nlds, tid, max_tickets);
+}
 
 struct XspecArgs {
     const void* data;         // [nsub][nchan][B]
@@ -271,8 +279,16 @@ constexpr int PP_ROW_CHUNK = 32;
 // NEXT chunk is fetched (one scalar load) while the current one is walked, as soon as the ticket
 // that names it has arrived; an empty chunk costs its visitor one more (synchronous) ticket.  Every
 // in-range chunk draws exactly one ticket.
-template <bool DYN>
+// CU: the walker is one WAVE of a workgroup of eight (k_xspec_cu1024) and takes the place of a one-wave workgroup:
+// number 8 blockIdx.x + wave of 8 gridDim.x, its lane 0 draws the tickets.
+template <bool DYN, bool CU = false>
 struct RowWalk {
+    static __device__ __forceinline__ unsigned me() {
+        if constexpr (CU) return 8u * blockIdx.x + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        else return blockIdx.x;
+    }
+    static __device__ __forceinline__ unsigned walkers() { if constexpr (CU) return 8u * gridDim.x; else return gridDim.x; }
+    static __device__ __forceinline__ unsigned lane() { if constexpr (CU) return threadIdx.x & 63u; else return threadIdx.x; }
     unsigned row, row_nx;      // this row, the row after it
     unsigned bits;             // rows of this chunk still to come (after `row`)
     unsigned wnx, cnx;         // masked walk: the next chunk's word and index, once fetched
@@ -295,10 +311,10 @@ struct RowWalk {
     static __device__ __forceinline__ unsigned chunk_after(unsigned c, unsigned* ticket, unsigned base) {
         if (DYN) {
             unsigned t = 0;
-            if (threadIdx.x == 0) t = atomicAdd(ticket, 1u);
-            return gridDim.x + (__builtin_amdgcn_readfirstlane(t) - base);
+            if (lane() == 0u) t = atomicAdd(ticket, 1u);
+            return walkers() + (__builtin_amdgcn_readfirstlane(t) - base);
         }
-        return c + gridDim.x;
+        return c + walkers();
     }
     __device__ __forceinline__ void enter(unsigned c, unsigned w, unsigned nrows) {
         more_nx = (c * PP_ROW_CHUNK < nrows) ? 1u : 0u;
@@ -310,7 +326,7 @@ struct RowWalk {
         static_assert(PP_ROW_CHUNK == 32, "one 32-bit word per chunk");
         const unsigned nrows = (unsigned)nrows_;
         wnx = 0; cnx = 0; have_wnx = 0u;
-        unsigned c = blockIdx.x;
+        unsigned c = me();
         unsigned w = word_of(mw, c, nrows);
         // the first chunk with a row in use (an empty one still owes its ticket)
         while (w == 0u && c * PP_ROW_CHUNK < nrows) {
@@ -319,18 +335,18 @@ struct RowWalk {
         }
         enter(c, __builtin_amdgcn_readfirstlane(w), nrows);
         row = row_nx; more = more_nx;
-        tick = threadIdx.x;
+        tick = lane();
         fresh = 1u;
     }
     // top of a row: draw the ticket of the chunk after this one
     __device__ __forceinline__ void draw(unsigned* ticket) {
-        if (DYN && fresh && threadIdx.x == 0) tick = atomicAdd(ticket, 1u);
+        if (DYN && fresh && lane() == 0u) tick = atomicAdd(ticket, 1u);
     }
     // masked walk, top of a row that is not the first of its chunk: the ticket has long arrived --
     // fetch the word of the chunk it names, to be looked at when this chunk runs out
     __device__ __forceinline__ void peek(long long nrows_, unsigned base, const unsigned* mw) {
         if (mw && !fresh && !have_wnx) {
-            cnx = DYN ? gridDim.x + (__builtin_amdgcn_readfirstlane(tick) - base) : (row >> 5) + gridDim.x;
+            cnx = DYN ? walkers() + (__builtin_amdgcn_readfirstlane(tick) - base) : (row >> 5) + walkers();
             wnx = word_of(mw, cnx, (unsigned)nrows_);
             have_wnx = 1u;
         }
@@ -356,7 +372,7 @@ struct RowWalk {
         // keeps the whole walk in scratch memory)
         if (have_wnx) { c = cnx; w = wnx; have_wnx = 0u; }
         else {
-            c = DYN ? gridDim.x + (__builtin_amdgcn_readfirstlane(tick) - base) : (row >> 5) + gridDim.x;
+            c = DYN ? walkers() + (__builtin_amdgcn_readfirstlane(tick) - base) : (row >> 5) + walkers();
             w = word_of(mw, c, nrows);
         }
         while (w == 0u && c * PP_ROW_CHUNK < nrows) {
@@ -379,7 +395,7 @@ struct RowWalk {
             more_nx = 1u;
             return;
         }
-        unsigned c = DYN ? gridDim.x + (__builtin_amdgcn_readfirstlane(tick) - base) : (row >> 5) + gridDim.x;
+        unsigned c = DYN ? walkers() + (__builtin_amdgcn_readfirstlane(tick) - base) : (row >> 5) + walkers();
         unsigned w = word_of(mw, c, nrows);
         while (w == 0u && c * PP_ROW_CHUNK < nrows) {
             c = chunk_after(c, ticket, base);
@@ -1639,7 +1655,7 @@ constexpr int PP_TAYLOR_WAVES = 2;     // waves per SIMD the kernel is compiled 
 // NT-thread kernel from a workgroup of 64 threads (k_taylor_solve_v; what a transform wave could run between rows).
 // `tid`: the real thread (0 .. NT / NVW - 1).  scratch: PP_BSUM_DOUBLES(NT / 64, 10) doubles of LDS; inv_lds:
 // 4 a.solve_cache doubles of LDS.
-template <int NV, int NVMAX, int NT, int NVW, typename F>
+template <int NV, int NVMAX, int NT, int NVW, bool WV = false, typename F>
 __device__ __forceinline__ void vblock_sum(double (&out)[NV], double* scratch, int& flip, double* mx, int tid, F&& accumulate) {
     static_assert(NV <= NVMAX, "scratch sized for NVMAX values");
     constexpr int NWV = NT / 64, RT = NT / NVW;      // virtual waves, real threads
@@ -1663,7 +1679,7 @@ __device__ __forceinline__ void vblock_sum(double (&out)[NV], double* scratch, i
 #pragma unroll 1
         for (int k = 0; k < NVW; ++k) one_wave(rw + (RT / 64) * k);   // the virtual wave this real wave plays now
     }
-    __syncthreads();
+    team_sync<WV>();
     // (the waves' totals are added one wave at a time, as block_sum_t's run-time loop does: with the wave loop
     // unrolled too, 8 x 31 LDS reads are in flight at once and the post-fit kernels spill hundreds of registers)
 #pragma unroll
@@ -1681,7 +1697,7 @@ __device__ __forceinline__ void vblock_sum(double (&out)[NV], double* scratch, i
     }
 }
 
-template <int NT, int PF, int NVW>
+template <int NT, int PF, int NVW, bool WV = false>
 __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i, const int tid, double* scratch, double* inv_lds) {
     constexpr int RT = NT / NVW;         // real threads
     static_assert(NT % 64 == 0 && RT % 64 == 0 && NT % RT == 0, "whole waves");
@@ -1716,7 +1732,7 @@ __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i,
             phase_geom(freqs[n], P, nuDM, nuGM, p1, p2);
             inv_w[n] = wts[n]; inv_p1[n] = p1; inv_p2[n] = p2; inv_S[n] = msum[n];
         }
-        __syncthreads();
+        team_sync<WV>();
     }
     auto chan_inv = [&](int n, double& w, double& p1, double& p2, double& S0) {
         if (n < ncache) { w = inv_w[n]; p1 = inv_p1[n]; p2 = inv_p2[n]; S0 = inv_S[n]; }
@@ -1782,7 +1798,7 @@ __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i,
         double dmax = 0.0;
         // (a channel out of the fit adds zeros instead of branching around the work: the two channels a thread
         // has in hand then interleave -- with one wave per SIMD a dependent chain costs its full latency)
-        vblock_sum<10, 10, NT, NVW>(acc, scratch, flip, &dmax, tid, [&](const int vt, double (&ac)[10], double& dm) __attribute__((always_inline)) {
+        vblock_sum<10, 10, NT, NVW, WV>(acc, scratch, flip, &dmax, tid, [&](const int vt, double (&ac)[10], double& dm) __attribute__((always_inline)) {
             auto add = [&](double w, double p1, double p2, double S0, double A0, double A1, double A2) {
                 const bool in = (w != 0.0);
                 const double r = A0 / S0;
@@ -1949,7 +1965,7 @@ __device__ __forceinline__ void taylor_solve_body(const FitArgs& a, const int i,
         double ev[4];                          // err bounds g_phi, g_DM, g_GM; f at the accepted point
         double jf = 1.0;
         for (int j = 2; j <= PP_TJ; ++j) jf *= (double)j;   // PP_TJ!
-        vblock_sum<4, 10, NT, NVW>(ev, scratch, flip, nullptr, tid, [&](const int vt, double (&e4)[4], double&) __attribute__((always_inline)) {
+        vblock_sum<4, 10, NT, NVW, WV>(ev, scratch, flip, nullptr, tid, [&](const int vt, double (&e4)[4], double&) __attribute__((always_inline)) {
             for_channels(vt, [&](int n, const double (&t)[PP_TSTRIDE]) {
                 double w, p1, p2, S0;
                 chan_inv(n, w, p1, p2, S0);
@@ -2356,7 +2372,7 @@ __device__ __forceinline__ double py_wrap_half(double x) {
 // NVW > 1 (CPT = 0 only): NT / NVW real threads walk the NT / 64 waves of the NT-thread kernel in turn and form its
 // block-wide sums from the same per-wave totals in the same order (vblock_sum, as taylor_solve_body): bitwise its results.
 // `tid`: the real thread.  scratch: PP_BSUM_DOUBLES(NT / 64, 31) doubles of LDS; sh: one double.
-template <int CPT, int NT, int NVW>
+template <int CPT, int NT, int NVW, bool WV = false>
 __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, const int tid, double* scratch, double* sh) {
     static_assert(NVW == 1 || CPT == 0, "channels held in registers belong to real threads");
     constexpr int RT = NT / NVW;
@@ -2418,7 +2434,7 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
     };
     // ---- pass 0: Sd, mean frequency, used channels -------------------------
     double v3[3];
-    vblock_sum<3, 31, NT, NVW>(v3, scratch, flip, nullptr, tid, [&](const int vt, double (&u3)[3], double&) __attribute__((always_inline)) {
+    vblock_sum<3, 31, NT, NVW, WV>(v3, scratch, flip, nullptr, tid, [&](const int vt, double (&u3)[3], double&) __attribute__((always_inline)) {
         for_channels(vt, [&](int n, int q) {
             const double w = wt_of(n, q);
             double sd;
@@ -2440,7 +2456,7 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
         // sums over channels of local terms times powers of frequency
         // v[0..]: see per-pattern use below
         double v[20];
-        vblock_sum<20, 31, NT, NVW>(v, scratch, flip, nullptr, tid, [&](const int vt, double (&v)[20], double&) __attribute__((always_inline)) {
+        vblock_sum<20, 31, NT, NVW, WV>(v, scratch, flip, nullptr, tid, [&](const int vt, double (&v)[20], double&) __attribute__((always_inline)) {
         for_channels(vt, [&](int n, int q) {
             const double w = wt_of(n, q);
             if (w == 0.0) return;
@@ -2524,9 +2540,9 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
                 // coefficients of nu^6, nu^4, nu^2, 1 -> cubic in y = nu^2
                 double co[4] = {A * C - E * G, E * Hh - A * D, F * G - B * C, B * D - F * Hh};
                 if (tid == 0) sh[0] = pick_poly_root(co, 3, fmean, true);
-                __syncthreads();
+                team_sync<WV>();
                 nzDM = nzGM = sh[0];
-                __syncthreads();
+                team_sync<WV>();
             }
             break;
         case 0x1B: {
@@ -2561,9 +2577,9 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
                     deg = 4;
                 }
                 if (tid == 0) sh[0] = pick_poly_root(co, deg, fmean, true);
-                __syncthreads();
+                team_sync<WV>();
                 nzDM = nzGM = sh[0];
-                __syncthreads();
+                team_sync<WV>();
             }
             break;
         default: break;
@@ -2586,7 +2602,7 @@ __device__ __forceinline__ void finalize_body(const FitArgs& a, const int i, con
     // A_ij (15 upper) + Schur correction sum_n U_i U_j/(2 S_n) (15) -> 30 sums,
     // then snr^2
     double m[31];
-    vblock_sum<31, 31, NT, NVW>(m, scratch, flip, nullptr, tid, [&](const int vt, double (&m)[31], double&) __attribute__((always_inline)) {
+    vblock_sum<31, 31, NT, NVW, WV>(m, scratch, flip, nullptr, tid, [&](const int vt, double (&m)[31], double&) __attribute__((always_inline)) {
     for_channels(vt, [&](int n, int q) {
         const double w = wt_of(n, q);
         if (w == 0.0) return;

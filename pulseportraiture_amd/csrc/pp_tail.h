@@ -50,6 +50,7 @@ struct TailArgs {
 // the reference's phase guess of subint i by ONE wave: k_refseed_finish's harmonics feed k_fps's fit directly (no
 // spectrum in global memory), the fit's 256 threads are walked as four virtual waves (fps_body<4>: bitwise k_fps),
 // k_refseed_start's arithmetic closes it.  LDS: [0, 16) block sums, [128, 128 + 2 * 1024) the cross-spectrum.
+template <bool WV = false>
 __device__ __forceinline__ void refseed_ticket(const RefTailArgs& r, const int nsub, const int i, const int tid, double* lds) {
     constexpr int M = 1024;
     static_assert(128 + 2 * M <= PP_TAIL_LDS_DOUBLES, "the fit's cross-spectrum in the carrying kernel's image");
@@ -97,16 +98,18 @@ __device__ __forceinline__ void refseed_ticket(const RefTailArgs& r, const int n
             if (k > 448) X[k - 1] = make_double2(0.0, 0.0);
         }
     }
-    __syncthreads();
+    team_sync<WV>();
     const cplx* m = r.mspec + (size_t)i * r.mstride;
     auto dv = [&](const int k) __attribute__((always_inline)) { return X[k - 1]; };
-    fps_body<4>(r.fps, i, tid, M, dv, m, X, lds, nullptr, nullptr);
-    __syncthreads();             // (out7[i] written by lane 0, read by lane 0: ordered anyway; the LDS is free again)
+    fps_body<4, WV>(r.fps, i, tid, M, dv, m, X, lds, nullptr, nullptr);
+    team_sync<WV>();             // (out7[i] written by lane 0, read by lane 0: ordered anyway; the LDS is free again)
     if (tid == 0) refseed_start_one(r.fps.out7, i, r.xs, r.seed_phase);
-    __syncthreads();
+    team_sync<WV>();
 }
 
-__device__ __noinline__ void tail_work(const TailArgs* t, double* lds, int nlds, int tid, int max_tickets) {
+// WV: the caller is one wave of a workgroup of several (tail_work_wave): every barrier is the wave's own (team_sync)
+template <bool WV>
+__device__ __noinline__ void tail_work_as(const TailArgs* t, double* lds, int nlds, int tid, int max_tickets) {
     TailArgs* tw = const_cast<TailArgs*>(t);
     const int nsub = t->nsub;
     for (int round = 0; round < max_tickets; ++round) {
@@ -124,19 +127,19 @@ __device__ __noinline__ void tail_work(const TailArgs* t, double* lds, int nlds,
         double* sh = lds + 528;
         double* inv = lds + 536;
         (void)nlds;
-        if (t->rs.on) refseed_ticket(t->rs, nsub, i, tid, lds);
+        if (t->rs.on) refseed_ticket<WV>(t->rs, nsub, i, tid, lds);
         const int snt = t->solve_nt, spf = t->solve_pf, fnt = t->fin_nt;
-        if (snt == 64) taylor_solve_body<64, PP_SOLVE_PF, 1>(a, i, tid, scratch, inv);
-        else if (snt == 128) taylor_solve_body<128, PP_SOLVE_PF, 2>(a, i, tid, scratch, inv);
-        else if (snt == 512) taylor_solve_body<512, PP_SOLVE_PF, 8>(a, i, tid, scratch, inv);
-        else if (spf == 0) taylor_solve_body<256, 0, 4>(a, i, tid, scratch, inv);
-        else taylor_solve_body<256, PP_SOLVE_PF, 4>(a, i, tid, scratch, inv);
-        __syncthreads();             // (one wave: orders its LDS and global writes before the post-fit stage reads them)
-        if (fnt == 64) finalize_body<8, 64, 1>(a, i, tid, scratch, sh);
-        else if (fnt == 128) finalize_body<0, 128, 2>(a, i, tid, scratch, sh);
-        else if (fnt == 512) finalize_body<0, 512, 8>(a, i, tid, scratch, sh);
-        else finalize_body<0, 256, 4>(a, i, tid, scratch, sh);
-        __syncthreads();
+        if (snt == 64) taylor_solve_body<64, PP_SOLVE_PF, 1, WV>(a, i, tid, scratch, inv);
+        else if (snt == 128) taylor_solve_body<128, PP_SOLVE_PF, 2, WV>(a, i, tid, scratch, inv);
+        else if (snt == 512) taylor_solve_body<512, PP_SOLVE_PF, 8, WV>(a, i, tid, scratch, inv);
+        else if (spf == 0) taylor_solve_body<256, 0, 4, WV>(a, i, tid, scratch, inv);
+        else taylor_solve_body<256, PP_SOLVE_PF, 4, WV>(a, i, tid, scratch, inv);
+        team_sync<WV>();             // (one wave: orders its LDS and global writes before the post-fit stage reads them)
+        if (fnt == 64) finalize_body<8, 64, 1, WV>(a, i, tid, scratch, sh);
+        else if (fnt == 128) finalize_body<0, 128, 2, WV>(a, i, tid, scratch, sh);
+        else if (fnt == 512) finalize_body<0, 512, 8, WV>(a, i, tid, scratch, sh);
+        else finalize_body<0, 256, 4, WV>(a, i, tid, scratch, sh);
+        team_sync<WV>();
         // the last ticket to finish publishes the count of unfinished subints (the stand-alone post-fit kernel
         // runs after the whole solve kernel: its subint 0 does it)
         if (tid == 0) {

@@ -237,6 +237,11 @@ struct pp_ctx {
     int fps_finish = 0;         // pp_fit_phase_shift_batch: 0 = Newton polish, 1 = SciPy brute's simplex finish
     int paired_split = 1;       // 2048-bin rows: last FFT stage + split in registers (k_xspec_p1024)
     int one_exchange = 1;       // 2048-bin rows, mode 2, noise given: one-exchange FFT (k_xspec_q1024)
+    int cu_tables = 1;          // ... f64 rows, no mask / `act` list / per-subint templates: one workgroup per CU with the
+                                // row-invariant twiddle powers in shared LDS tables (k_xspec_cu1024); 0 = k_xspec_q1024
+    int cu_grid_cap = 0;        // k_xspec_cu1024: at most this many workgroups (0 = one per CU).  For tests: with few
+                                // workgroups the waves of a small batch all have rows and take their tickets between them
+    bool cu_ready = false;      // the device granted k_xspec_cu1024 its LDS block (ctx_init); otherwise k_xspec_q1024 serves
     int seed_chan_stride = 16;  // device phase seed: pilot pass over every n-th channel (1 = all channels)
     int tail_virtual = 0;       // experiments: solve (and post-fit stage) by ONE real wave per subint that walks the
                                 // waves of the multi-wave kernels in turn (bitwise the same results)
@@ -344,6 +349,10 @@ static int ctx_busy(pp_ctx* c, const char* who) {
 extern "C" int pp_abi_version(void) { return PP_ABI_VERSION; }
 extern "C" const char* pp_last_error(void) { return g_err.c_str(); }
 
+// k_xspec_cu1024 (pp_xspec1024cu.h) is a translation unit of its own, pp_xspec_cu.hip: its two host entry points
+extern "C" __attribute__((visibility("hidden"))) int pp_cu1024_prepare(void);
+extern "C" __attribute__((visibility("hidden"))) void pp_cu1024_launch(const void* xspec_args, long long nrows, int ncu, hipStream_t stream);
+
 static int ctx_init(pp_ctx* c) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     {
@@ -371,6 +380,9 @@ static int ctx_init(pp_ctx* c) {
     int rc = c->ticket.reserve(64);
     if (rc) return rc;
     HIP_TRY(hipMemset(c->ticket.p, 0, 64));
+    // (a device that refuses the kernel its 158 KB of LDS keeps every fit on k_xspec_q1024)
+    c->cu_ready = pp_cu1024_prepare() == (int)hipSuccess;
+    if (!c->cu_ready) (void)hipGetLastError();
     return PP_OK;
 }
 
@@ -469,7 +481,8 @@ static bool option_ref(pp_ctx* c, const std::string& n, OptRef* out) {
         {"solve_threads", 'i', &c->solve_threads, 0}, {"copy_kernels", 'i', &c->copy_kernels, INT32_MIN},
         {"solve_prefetch", 'i', &c->solve_prefetch, INT32_MIN}, {"overlap_post", 'i', &c->overlap_post, INT32_MIN},
         {"refseed_stride", 'i', &c->refseed_stride, 0}, {"tail_virtual", 'i', &c->tail_virtual, INT32_MIN},
-        {"fuse_tail", 'i', &c->fuse_tail, INT32_MIN},
+        {"fuse_tail", 'i', &c->fuse_tail, INT32_MIN}, {"cu_tables", 'i', &c->cu_tables, INT32_MIN},
+        {"cu_grid_cap", 'i', &c->cu_grid_cap, 0},
     };
     for (const OptRef& o : tab)
         if (n == o.name) { *out = o; return true; }
@@ -871,6 +884,14 @@ static int upload(pp_ctx* c, DevBuf& b, const void* src, size_t bytes) {
 // persistent grid of exactly the resident capacity of this instantiation (its
 // register / LDS footprint decides how many workgroups a CU holds): a larger grid
 // would run its surplus workgroups in a second, mostly idle round
+static int cu_count(pp_ctx* c) {
+    if (!c->ncu) {
+        hipDeviceProp_t prop;
+        c->ncu = (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
+                     ? prop.multiProcessorCount : 256;
+    }
+    return c->ncu;
+}
 template <typename K>
 static int resident_grid(pp_ctx* c, K kernel, int T, long long nrows, int fallback) {
     const void* key = reinterpret_cast<const void*>(kernel);
@@ -884,12 +905,7 @@ static int resident_grid(pp_ctx* c, K kernel, int T, long long nrows, int fallba
         }
         c->occ_cache[key] = per_cu;
     }
-    if (!c->ncu) {
-        hipDeviceProp_t prop;
-        c->ncu = (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
-                     ? prop.multiProcessorCount : 256;
-    }
-    const long long g = per_cu > 0 ? (long long)per_cu * c->ncu : (long long)fallback;
+    const long long g = per_cu > 0 ? (long long)per_cu * cu_count(c) : (long long)fallback;
     return (int)std::max(1LL, std::min(nrows, g));
 }
 
@@ -913,8 +929,18 @@ static void launch_xspec(pp_ctx* c, const XspecArgs& xa_in, bool tail, int mode)
     if constexpr (MM == 1024) {
         // 2048-bin rows, Taylor sums only (noise given or measured): the one-exchange transform
         // (pp_xspec1024q.h) -- a third of the LDS traffic of the general kernel
-        if (c->one_exchange && mode == 2 && 2 * xa.Kt < MM)
+        if (c->one_exchange && mode == 2 && 2 * xa.Kt < MM) {
+            // f64 rows, noise given, every row of every subint against the one template set: the CU's eight waves as ONE
+            // workgroup that shares the row-invariant twiddle tables (pp_xspec1024cu.h); a wave of it walks rows and
+            // draws tickets as a workgroup of k_xspec_q1024 does
+            if constexpr (sizeof(TIN) == 8) {
+                if (c->cu_tables && c->cu_ready && !tail && !xa.mwords && !xa.act && !xa.slot) {
+                    const int ncu = cu_count(c);
+                    return pp_cu1024_launch(&xa, nrows, c->cu_grid_cap > 0 ? std::min(ncu, c->cu_grid_cap) : ncu, c->stream);
+                }
+            }
             return with_flag(tail, [&](auto TL) { launch(k_xspec_q1024<TIN, decltype(TL)::value>); });
+        }
         // ... and with a template that keeps 512 harmonics or more (mode 3)
         if (c->one_exchange && mode == 3)
             return with_flag(tail, [&](auto TL) { launch(k_xspec_qf<1024, TIN, decltype(TL)::value>); });

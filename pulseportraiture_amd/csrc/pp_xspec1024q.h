@@ -34,9 +34,11 @@ namespace pp {
 // a wave asks for its ticket after a wave-specific number of rows, uniform over this fraction of its share of the launch
 // (every wave asks, the first `tickets` to ask get one: with 3/4 and four waves per ticket they are gone after the first fifth)
 constexpr unsigned PP_TICKET_WINDOW_NUM = 3u, PP_TICKET_WINDOW_DEN = 4u;
+// (CU: the wave is one of a workgroup's eight and counts as a one-wave workgroup, see RowWalk)
+template <bool CU = false>
 __device__ __forceinline__ int ticket_moment(const long long nrows) {
-    const unsigned share = (unsigned)(nrows / (long long)gridDim.x) + 1u;
-    return 1 + (int)(((blockIdx.x * 2654435761u) >> 8) % (share * PP_TICKET_WINDOW_NUM / PP_TICKET_WINDOW_DEN + 1u));
+    const unsigned share = (unsigned)(nrows / (long long)RowWalk<true, CU>::walkers()) + 1u;
+    return 1 + (int)(((RowWalk<true, CU>::me() * 2654435761u) >> 8) % (share * PP_TICKET_WINDOW_NUM / PP_TICKET_WINDOW_DEN + 1u));
 }
 
 // where the row after this one starts: (subint i_nx of the list, channel n_nx of the subset), or this row again (rc)

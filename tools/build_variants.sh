@@ -7,7 +7,7 @@ mkdir -p ../../variants
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -mllvm -disable-machine-licm -mllvm -amdgpu-atomic-optimizer-strategy=None"
 while [ $# -ge 2 ]; do
   n=$1; ex=$2; shift 2
-  ( eval hipcc $F $ex -Rpass-analysis=kernel-resource-usage -o ../../variants/$n.so pp_toas.hip > ../../variants/$n.res 2>&1 \
+  ( eval hipcc $F $ex -Rpass-analysis=kernel-resource-usage -o ../../variants/$n.so pp_toas.hip pp_xspec_cu.hip > ../../variants/$n.res 2>&1 \
       && echo "built $n" || echo "FAILED $n" ) &
   while [ $(jobs -r | wc -l) -ge 4 ]; do sleep 1; done
 done

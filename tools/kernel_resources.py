@@ -22,12 +22,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def code_object(so, tmp):
-    fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")
+def code_objects(so, tmp):
+    """The gfx950 code objects of the library, one per translation unit (pp_toas.hip's first; pp_xspec_cu.hip's kernels
+    carry their unit's namespace, pp_cu_unit::, in their names)."""
+    fat = os.path.join(tmp, "fat.bin")
     subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", so, fat], check=True)
-    subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
-    return co
+    blob, magic, cos = open(fat, "rb").read(), b"__CLANG_OFFLOAD_BUNDLE__", []
+    starts = [m.start() for m in re.finditer(re.escape(magic), blob)]
+    for i, (lo, hi) in enumerate(zip(starts, starts[1:] + [len(blob)])):
+        part, co = os.path.join(tmp, "fat%d.bin" % i), os.path.join(tmp, "dev%d.co" % i)
+        with open(part, "wb") as f:
+            f.write(blob[lo:hi])
+        subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + part,
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+        cos.append(co)
+    return cos
+
+
+def _objdump(so, tmp):
+    return "".join(subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True,
+                                  check=True).stdout for co in code_objects(so, tmp))
 
 
 def loop_scratch(so=None, pat=""):
@@ -35,9 +49,7 @@ def loop_scratch(so=None, pat=""):
     kernels whose name contains `pat`."""
     so = so or os.path.join(ROOT, "pulseportraiture_amd", "csrc", "libpptoas_hip.so")
     with tempfile.TemporaryDirectory() as tmp:
-        co = code_object(so, tmp)
-        full = subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True,
-                              check=True).stdout
+        full = _objdump(so, tmp)
         blocks, cur = {}, None
         for ln in full.splitlines():
             m = re.match(r"^([0-9a-f]+) <([^>]+)>:", ln)
@@ -50,7 +62,7 @@ def loop_scratch(so=None, pat=""):
         dem = subprocess.run(["c++filt"], input="\n".join(want), capture_output=True, text=True).stdout.split("\n")
         out = {}
         for sym, name in zip(want, dem):
-            short = re.sub(r"\(.*\)$", "", re.sub(r"^(void )?pp::", "", name))
+            short = re.sub(r"\(.*\)$", "", re.sub(r"^(void )?(pp::)?", "", name))
             if pat and pat not in short:
                 continue
             if not short.startswith("k_"):
@@ -94,12 +106,10 @@ def row_loop(so=None, kernel=""):
     loops inside the row -- ticket draws, mask words -- are not it)."""
     so = so or os.path.join(ROOT, "pulseportraiture_amd", "csrc", "libpptoas_hip.so")
     with tempfile.TemporaryDirectory() as tmp:
-        co = code_object(so, tmp)
-        full = subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True,
-                              check=True).stdout
-    syms = re.findall(r"^[0-9a-f]+ <(_ZN2pp[^>]+)>:", full, re.M)
+        full = _objdump(so, tmp)
+    syms = re.findall(r"^[0-9a-f]+ <(_ZN\d+pp[^>]+)>:", full, re.M)
     dem = subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True).stdout.split("\n")
-    want = [sy for sy, name in zip(syms, dem) if re.sub(r"\(.*\)$", "", re.sub(r"^(void )?pp::", "", name)) == kernel]
+    want = [sy for sy, name in zip(syms, dem) if re.sub(r"\(.*\)$", "", re.sub(r"^(void )?(pp::)?", "", name)) == kernel]
     if len(want) != 1:
         raise KeyError(kernel)
     ins, start, on = [], None, False          # (address, text, branch target or None)
@@ -134,8 +144,8 @@ def metadata(so=None, pat=""):
     """{kernel (demangled, short): dict(vgpr, agpr, sgpr, vspill, sspill, lds, scratch)} from the code object's notes."""
     so = so or os.path.join(ROOT, "pulseportraiture_amd", "csrc", "libpptoas_hip.so")
     with tempfile.TemporaryDirectory() as tmp:
-        notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", code_object(so, tmp)], capture_output=True, text=True,
-                               check=True).stdout
+        notes = "".join(subprocess.run([LLVM + "/llvm-readelf", "--notes", co], capture_output=True, text=True,
+                                       check=True).stdout for co in code_objects(so, tmp))
     keys = dict(vgpr="vgpr_count", agpr="agpr_count", sgpr="sgpr_count", vspill="vgpr_spill_count",
                 sspill="sgpr_spill_count", lds="group_segment_fixed_size", scratch="private_segment_fixed_size")
     rows = []
@@ -146,7 +156,7 @@ def metadata(so=None, pat=""):
     names = subprocess.run(["c++filt"], input="\n".join(r[0] for r in rows), capture_output=True, text=True).stdout.split("\n")
     out = {}
     for (sym, d), n in zip(rows, names):
-        n = re.sub(r"\(.*\)$", "", re.sub(r"^(void )?pp::", "", n))
+        n = re.sub(r"\(.*\)$", "", re.sub(r"^(void )?(pp::)?", "", n))
         if not pat or pat in n:
             out[n] = d
     return out
@@ -155,8 +165,7 @@ def metadata(so=None, pat=""):
 def disassembly(so):
     """{kernel symbol (mangled): [instruction text, ...]} of the code object, addresses stripped."""
     with tempfile.TemporaryDirectory() as tmp:
-        full = subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", code_object(so, tmp)],
-                              capture_output=True, text=True, check=True).stdout
+        full = _objdump(so, tmp)
     out, cur = {}, None
     for ln in full.splitlines():
         m = re.match(r"^[0-9a-f]+ <([^>]+)>:", ln)
@@ -193,7 +202,7 @@ def compare(so_a, so_b):
     import difflib
     ma, mb = metadata(so_a), metadata(so_b)
     da, db = disassembly(so_a), disassembly(so_b)
-    short = lambda n: re.sub(r"\(.*\)$", "", re.sub(r"^(void )?pp::", "", n))
+    short = lambda n: re.sub(r"\(.*\)$", "", re.sub(r"^(void )?(pp::)?", "", n))
     syms = sorted(set(da) | set(db))
     names = dict(zip(syms, (short(n) for n in subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True,
                                                              text=True).stdout.split("\n"))))
