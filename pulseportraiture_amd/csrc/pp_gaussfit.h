@@ -88,6 +88,17 @@ __global__ __launch_bounds__(256) void k_gauss_fit_rows(GaussFitArgs f, int B) {
     const GaussArgs a = gauss_fit_set(f, s);
     gauss_plain_row(a, f.freqs[n], B, gc, threadIdx.x, 256, GaussRowOut{f.R + ((size_t)s * f.nchan + n) * B});
 }
+// general row lengths, an unscattered set of a joined fit with a rotation somewhere: all its rows went through their
+// harmonics, and a row whose own rotation is zero came back moved by a rounding; it is written again, so that such a
+// row has the bits it has without a band map -- as at the power-of-two lengths, where it never sees a transform
+__global__ __launch_bounds__(256) void k_gauss_fit_unrotated(GaussFitArgs f, int B, int s) {
+    __shared__ GaussComp gc[PP_MAX_GAUSS];
+    const int n = blockIdx.x;
+    const double nu = f.freqs[n];
+    if (gauss_fit_rotation(f, s, n, nu) != 0.0) return;       // (the same for every thread of the workgroup)
+    const GaussArgs a = gauss_fit_set(f, s);
+    gauss_plain_row(a, nu, B, gc, threadIdx.x, 256, GaussRowOut{f.R + ((size_t)s * f.nchan + n) * B});
+}
 __global__ __launch_bounds__(256) void k_gauss_resid_finish(GaussFitArgs f, int B) {
     const int n = blockIdx.x, s = blockIdx.y;
     double* row = f.R + ((size_t)s * f.nchan + n) * B;
@@ -327,6 +338,10 @@ extern "C" int pp_gauss_residuals(pp_ctx* c, const char* code, double nu_ref, in
                                        (const double*)F.freqs.as<double>(), nu_ref, tau_rot[s], alpha[s], M);
                 HIP_TRY(hipGetLastError());
                 if ((rc = irfft_any(c, nbin, harm, nchan, rows))) return rc;
+                if (rot && tau_rot[s] == 0.0) {
+                    hipLaunchKernelGGL(k_gauss_fit_unrotated, dim3((unsigned)nchan), dim3(256), 0, c->stream, f, nbin, s);
+                    HIP_TRY(hipGetLastError());
+                }
             }
             hipLaunchKernelGGL(k_gauss_resid_finish, grid, dim3(256), 0, c->stream, f, nbin);
         } else {

@@ -138,7 +138,8 @@ def test_rows_of_a_set_do_not_depend_on_the_launch(eng, nbin):
     """The rows of a set are the same bits alone, in a triple and among all seven -- also where the neighbours differ
     in tau, in alpha and in which bands they rotate; and a channel whose rotation is zero in a set keeps the bits it has
     without a band map (64 bins: no transform at all for such a row when tau is zero too; at 100 bins a set with a
-    rotation anywhere takes all its rows through their harmonics, so such a row moves by a rounding there)."""
+    rotation anywhere takes all its rows through their harmonics, and an unscattered set's rows without a rotation are
+    written again afterwards: tests/test_gpu_gauss_kernels.py holds them to the unjoined bits at every row length)."""
     g = _g("ppgauss_join_rows")
     data, errs, freqs, band = _rows_case(g, nbin)
     nu_ref = float(g["nu_ref"])
