@@ -236,14 +236,14 @@ __global__ __launch_bounds__(FftPlan<L>::T) void k_rotate_any(RotateArgs a, AnyA
         };
         const cplx z0 = buf[0];
         const double y0 = z0.x + z0.y;
-        const double yM = (z0.x - z0.y) * unit_phasor((double)M, phin).x;
+        const double yM = (z0.x - z0.y) * turn_phasor((double)M, phin).x;
         // rotated harmonics -> packed spectrum of the inverse, conjugated; parked in the (free) image
         for (int k = tid; k < M; k += T) {
             cplx yk, ym;
             if (k == 0) { yk = make_double2(y0, 0.0); ym = make_double2(yM, 0.0); }
             else {
-                yk = cmul(harm(k), unit_phasor((double)k, phin));
-                ym = cmul(harm(M - k), unit_phasor((double)(M - k), phin));
+                yk = cmul(harm(k), turn_phasor((double)k, phin));
+                ym = cmul(harm(M - k), turn_phasor((double)(M - k), phin));
             }
             ym.y = -ym.y;
             const cplx ev = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y + ym.y));

@@ -5,6 +5,22 @@
 
 namespace pp {
 
+// exp(2 pi i k phi) for the rotation kernels, with k phi reduced modulo 1 by ONE fused operation.  unit_phasor
+// (pp_common.h) writes the reduction as (prod - rint(prod)) + err, err being the exact residual of prod = k * pfrac.
+// The compiler contracts that subtraction with the product into fma(k, pfrac, -rint(prod)) -- which already IS the
+// exact fraction, rounded once -- so adding err counts the residual twice and the phasor is off by the rounding of
+// k * phi: 3.4e-13 rad at k = 4095, phi = -0.31, NumPy's own error with the sign turned
+// (tests/test_gpu_rot_kernels.py: the k = M - 1 cosine at nbin 4096 and 8192).  Here the fused form is written out and
+// nothing is left to contract.  unit_phasor itself stays as it is: the fit's kernels use it, and their bits are pinned.
+__device__ __forceinline__ cplx turn_phasor(double k, double phi) {
+    const double pfrac = phi - rint(phi);          // exact
+    const double whole = rint(k * pfrac);
+    const double r = fma(k, pfrac, -whole);        // the exact product less a whole number: one rounding
+    double s, c;
+    sincos_turns(r, &s, &c);
+    return make_double2(c, s);
+}
+
 // --------------------------------------------------------------------------
 // counter-based RNG: Philox4x32-10 (Salmon et al. 2011), keyed on the seed,
 // counter = (bin pair, channel, subint lo, subint hi)
@@ -137,13 +153,13 @@ __global__ __launch_bounds__(FftPlan<M>::T) void k_rotate(RotateArgs a) {
         // rotated harmonics Y_k, k = 0..M, then the packed spectrum of the inverse
         const cplx z0 = lds[0];
         const double y0 = z0.x + z0.y;                                   // DC, unchanged
-        const double yM = (z0.x - z0.y) * unit_phasor((double)M, phin).x; // Nyquist: real part kept
+        const double yM = (z0.x - z0.y) * turn_phasor((double)M, phin).x; // Nyquist: real part kept
         for (int k = tid; k < M; k += T) {
             cplx yk, ym;
             if (k == 0) { yk = make_double2(y0, 0.0); ym = make_double2(yM, 0.0); }
             else {
-                yk = cmul(rfft_harmonic<M>(lds, a.twB, k), unit_phasor((double)k, phin));
-                ym = cmul(rfft_harmonic<M>(lds, a.twB, M - k), unit_phasor((double)(M - k), phin));
+                yk = cmul(rfft_harmonic<M>(lds, a.twB, k), turn_phasor((double)k, phin));
+                ym = cmul(rfft_harmonic<M>(lds, a.twB, M - k), turn_phasor((double)(M - k), phin));
             }
             ym.y = -ym.y;
             const cplx ev = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y + ym.y));

@@ -1170,7 +1170,8 @@ def test_rotate_functions_match_oracle():
     assert np.abs(d[:, :-1]).max() < 1e-9 and np.abs(d[:, -1]).max() > 1e-3
 
 
-@pytest.mark.parametrize("nbin,dtype", [(256, np.float64), (2048, np.float64), (512, np.float32)])
+@pytest.mark.parametrize("nbin,dtype", [(256, np.float64), (2048, np.float64), (512, np.float32), (64, np.float64),
+                                        (128, np.float64), (512, np.float64), (1024, np.float64)])
 def test_align_accumulate_matches_oracle(eng, nbin, dtype):
     """ppalign's weighted accumulation of rotated subints (ppalign.py:199-206):
     per-subint phase, DM and reference frequency, ragged zero-weight channels, a

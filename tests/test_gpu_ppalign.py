@@ -18,7 +18,7 @@ from tests.gpu_support import eng, run_module  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-NBINS = [32, 256, 2048, 4096, 8192, 100, 1000]
+NBINS = [32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 100, 1000]
 NSUB, NCHAN, NCHAN_MODEL = 3, 7, 5
 MAPS = {
     # data channel -> accumulator row, per subint
