@@ -78,6 +78,12 @@ extern "C" {
 #define PP_NORM_RMS 4
 #define PP_NORM_ABS 5
 
+/* pp_channel_noise_fit: what the rows are, and find_kc's model function (pplib.py:1448-1463) */
+#define PP_NOISEFIT_ROWS 0    /* profiles [nrows][nbin] */
+#define PP_NOISEFIT_POWS 1    /* power spectra [nrows][nbin / 2 + 1], f64 */
+#define PP_KC_EXP_DC 0        /* b exp(-a k) + dc */
+#define PP_KC_HALF_TRI 1      /* half_triangle_function (pplib.py:1436-1446) */
+
 typedef struct pp_ctx pp_ctx;
 
 /* Streams.  A context launches everything on its own non-blocking HIP stream
@@ -590,6 +596,33 @@ int pp_zap_median(pp_ctx* ctx, const double* noise, const unsigned char* good, i
  * the row.  snrs: [nrows] host array. */
 int pp_channel_snrs(pp_ctx* ctx, const void* src, int dtype, int on_device, int nrows,
                     int nbin, double fudge, double* snrs);
+
+/* ---- the 'fit' noise method -------------------------------------------------- */
+/* pplib.get_noise_fit(row, fact) (pplib.py:2255-2287) of every row of src [nrows][nbin] (`dtype`, host or
+ * device), with pplib.find_kc(pows, fn=fn) (pplib.py:1465-1495) inside it: pows = |rfft(row)|^2 / nbin, the
+ * 20 x 20 x 20 opt.brute grid over (a, b, dc) of b f_a(k) + dc against log10(pows) in closed form, NumPy's
+ * argmin (a slowest, dc fastest, the first minimum), kc of the winning a, then sqrt(mean(pows[int(k):])) with
+ * k = fact kc, clipped to int(0.99 H) from H = nbin / 2 + 1 on.  A row with a harmonic of exactly zero power
+ * (log10 = -inf: the reference's grid is all NaN) takes cell 0 and kc = H - 1; an all-zero row has noise 0.
+ * input_kind PP_NOISEFIT_POWS: src holds H f64 powers per row, find_kc's own input (PP_F64, PP_NORM_NONE).
+ * norm_method, divisor, norms, noise: as pp_channel_noise, noise(row) / |norm| (PP_NORM_RMS: the fitted noise);
+ * scaling a row shifts log10(pows) and the grid alike, so the cell does not move.  kc: int32 [nrows] or NULL;
+ * cell: int32 [nrows][3] = (ia, ib, idc) or NULL.  A row's bits do not depend on the rest of the call.
+ * nbin: even, 8 ... 4096; fact >= 0. */
+int pp_channel_noise_fit(pp_ctx* ctx, const void* src, int dtype, int on_device, int nrows, int nbin,
+                         int input_kind, int fn, double fact, int norm_method, const double* divisor,
+                         double* norms, double* noise, int32_t* kc, int32_t* cell);
+
+/* pplib.get_SNR(row, fudge) (pplib.py:2289-2308) of every row with get_noise(row, method='fit')
+ * (pplib.py:2221-2222) as its noise: pp_channel_snrs with pp_channel_noise_fit's estimator, one pass. */
+int pp_channel_snrs_fit(pp_ctx* ctx, const void* src, int dtype, int on_device, int nrows, int nbin,
+                        int fn, double fact, double fudge, double* snrs);
+
+/* find_kc's width axis for H harmonics (host only, no context): the 20 values np.mgrid[lo:hi:20j] gives
+ * opt.brute (pplib.py:1476-1485; i * ((hi - lo) / 19) + lo, (lo, hi) = (1 / H, 1) for PP_KC_EXP_DC and (1, H)
+ * for PP_KC_HALF_TRI) and the kc find_kc returns for each (pplib.py:1487-1493): the smallest k < H with
+ * exp(-a k) < 0.005, H - 1 where there is none; floor(a) for the half triangle. */
+int pp_noise_fit_grid(int H, int fn, double* a20, int32_t* kc20);
 
 /* The device side of pplib.pca (pplib.py:1497-1534) up to the eigen-solve, for the portrait src
  * [nchan][nbin] (`dtype`, host or device) and the weights w[nchan] (host; sumw = sum w, fact = sumw -

@@ -20,6 +20,9 @@ ABI_VERSION = 11
 PP_METHOD_TRUST_NCG, PP_METHOD_NEWTON = 0, 1
 PP_POL = {'keep': 0, 'sum01': 1, 'first': 2}
 PP_NORMS = {None: 0, 'mean': 1, 'max': 2, 'prof': 3, 'rms': 4, 'abs': 5}
+PP_NOISEFIT_ROWS, PP_NOISEFIT_POWS = 0, 1
+PP_KC_FNS = {'exp_dc': 0, 'half_tri': 1}
+NOISE_METHODS = ("PS", "fit")          # pplib.get_noise's methods (pplib.py:2206-2225)
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -132,6 +135,11 @@ SYMBOLS = {
                                 c_uint8_p]),
     "pp_channel_snrs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                   c_double_p]),
+    "pp_channel_noise_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_double, C.c_int, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "pp_channel_snrs_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                      C.c_double, c_double_p]),
+    "pp_noise_fit_grid": (C.c_int, [C.c_int, C.c_int, c_double_p, c_int32_p]),
     "pp_pca_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p,
                               C.c_double, C.c_double, c_double_p, c_double_p]),
     "pp_pca_basis": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p]),

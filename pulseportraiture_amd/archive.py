@@ -6,10 +6,12 @@ The format is stated once, in ARRAY_FIELDS, SCALAR_FIELDS and EXTRA_FIELDS; `loa
 errors) read it, `write_archive` writes it.  This module
 stands below every command and every library module that touches an archive: it imports none of them.
 """
+import contextlib
 import zipfile
 
 import numpy as np
 
+from ._lib import NOISE_METHODS as _NOISE_METHODS
 from .pplib import DataBunch, default_engine, get_bin_centers
 
 # ---- the format: the arguments of data_from_arrays ... ----
@@ -170,44 +172,109 @@ def load_bunch(datafile):
     return _read(datafile)[:2]
 
 
-def measure(eng, data, noise_stds=True, SNRs=True):
+# ---------------------------------------------------------------------------
+# the noise estimator
+# ---------------------------------------------------------------------------
+# pplib.get_noise's methods (pplib.py:2206-2225).  The reference has one module constant; here every function that
+# measures noise takes noise_method=None, and None means whatever noise_method_scope has put in force -- nothing,
+# unless a command line said --noise_method: today's power-spectrum estimate wherever the archive stores no value.
+NOISE_METHODS = _NOISE_METHODS
+_IN_FORCE = [None]
+
+
+def add_noise_method_option(ap):
+    """--noise_method for a command's parser (its value is checked by noise_method_refusal, through the command's
+    own refusal())."""
+    ap.add_argument("--noise_method", default=None, metavar="{PS,fit}",
+                    help="Noise estimator: 'PS', the mean of the top quarter of the power spectrum, or 'fit', the "
+                         "mean above a fitted noise-floor harmonic (get_noise_fit).  Given, it is measured anew "
+                         "even where the archive stores noise_stds and SNRs. [default: stored values, else 'PS']")
+
+
+def noise_method_refusal(opts):
+    """The message for a --noise_method that is no estimator, or None."""
+    value = getattr(opts, "noise_method", None)
+    if value is not None and value not in NOISE_METHODS:
+        return "--noise_method %s: unknown estimator (one of %s)" % (value, ", ".join(NOISE_METHODS))
+    return None
+
+
+@contextlib.contextmanager
+def noise_method_scope(method):
+    """Inside the block, every noise_method=None means `method` (None: no change).  The one place a command line's
+    --noise_method is applied: the commands run their work inside it.  The setting is the process's, as the
+    reference's module constant is: the commands are single-threaded, and a library caller with threads passes
+    noise_method to the functions instead."""
+    if method is not None and method not in NOISE_METHODS:
+        raise ValueError("noise method must be one of %s, not %r" % (", ".join(NOISE_METHODS), method))
+    before = _IN_FORCE[0]
+    if method is not None:
+        _IN_FORCE[0] = method
+    try:
+        yield
+    finally:
+        _IN_FORCE[0] = before
+
+
+def noise_method_in_force(noise_method=None):
+    """The estimator a function called with noise_method should use: its argument, else the scope's, else None
+    (stored values where there are any, 'PS' where something has to be measured)."""
+    if noise_method is not None and noise_method not in NOISE_METHODS:
+        raise ValueError("noise method must be one of %s, not %r" % (", ".join(NOISE_METHODS), noise_method))
+    return noise_method if noise_method is not None else _IN_FORCE[0]
+
+
+def noise_kwargs(noise_method=None):
+    """Engine.channel_noise / channel_snrs keywords of the estimator in force: none at all for None."""
+    method = noise_method_in_force(noise_method)
+    return {} if method is None else {"method": method}
+
+
+def measure(eng, data, noise_stds=True, SNRs=True, noise_method=None):
     """data.noise_stds and data.SNRs [nsub,npol,nchan] measured from its subints (NumPy or a device tensor) on the
     device: get_noise and get_SNR of every row, shaped like subints without its last axis.  A row of zeros has no
-    noise to divide by: its S/N is NaN (scrunch.measured makes it 0)."""
+    noise to divide by: its S/N is NaN (scrunch.measured makes it 0).  noise_method: 'PS' or 'fit' (None: the
+    scope's, else 'PS')."""
     sub = data.subints if hasattr(data.subints, "is_cuda") else np.asarray(data.subints)
     rows = sub.reshape(-1, sub.shape[-1])
     shape = tuple(int(n) for n in sub.shape[:-1])
+    kw = noise_kwargs(noise_method)
     if noise_stds:
-        data.noise_stds = eng.channel_noise(rows)[0].reshape(shape)
+        data.noise_stds = eng.channel_noise(rows, **kw)[0].reshape(shape)
     if SNRs:
-        data.SNRs = eng.channel_snrs(rows).reshape(shape)
+        data.SNRs = eng.channel_snrs(rows, **kw).reshape(shape)
     return data
 
 
-def _completed(read, engine):
-    """(DataBunch, name) of what _read returned, the noise and S/N per channel that the archive lacks measured."""
+def _completed(read, engine, noise_method=None):
+    """(DataBunch, name) of what _read returned, the noise and S/N per channel that the archive lacks measured --
+    or, with an estimator in force, all of them measured with it: stored values of another estimator would
+    otherwise win silently."""
     data, name, has_snrs = read
-    return measure(engine or default_engine(), data, data.noise_stds is None, not has_snrs or data.SNRs is None), name
+    forced = noise_method_in_force(noise_method) is not None
+    return measure(engine or default_engine(), data, forced or data.noise_stds is None,
+                   forced or not has_snrs or data.SNRs is None, noise_method), name
 
 
-def load_archive(datafile, engine=None):
+def load_archive(datafile, engine=None, noise_method=None):
     """(DataBunch, name) of an archive ready to be worked on: load_bunch, with the noise and S/N per channel that the
-    archive lacks measured on the device.  RuntimeError: it cannot be loaded."""
+    archive lacks measured on the device (noise_method given, or in force: all of them, with that estimator).
+    RuntimeError: it cannot be loaded."""
     try:
         read = _read(datafile)
     except LOAD_ERRORS + (TypeError, KeyError) as err:
         raise RuntimeError("Cannot load_data(%s): %s" % (datafile, err))
-    return _completed(read, engine)
+    return _completed(read, engine, noise_method)
 
 
-def load_archive_file(datafile, engine=None):
+def load_archive_file(datafile, engine=None, noise_method=None):
     """load_archive for the commands that fit one file and report what reading it raised: NumPy is asked to open the
     file whatever its name, so one that is missing or is no .npz inside raises NumPy's own error, and only a file that
     NumPy can open but whose name is not an .npz's raises load_bunch's RuntimeError."""
     if not str(datafile).endswith(".npz"):
         with np.load(datafile, allow_pickle=True):
             pass
-    return _completed(_read(datafile), engine)
+    return _completed(_read(datafile), engine, noise_method)
 
 
 def good_channel_counts(datafile, tscrunch=False):

@@ -98,9 +98,9 @@ __global__ void k_copy_words(unsigned long long* dst, const unsigned long long* 
 static int staged_copy(pp_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st = nullptr);
 __global__ void k_publish_int(int* host_dst, const int* dev_src) { *host_dst = *dev_src; }
 static int publish_int(pp_ctx* c, int* host_dst, const int* dev_src);
-enum KernelFamily { KF_MODEL = 0, KF_XSPEC, KF_PREP, KF_SEED, KF_ACCUM, KF_EVAL, KF_TAYLOR, KF_STEP, KF_FINAL, KF_SYNTH, KF_FPS, KF_SCATMODEL, KF_PCA, KF_GAUSSRES, KF_GAUSSNORM, KF_NBSFFT, KF_NBSFIT, KF_SCRUNCH, KF_COUNT };
+enum KernelFamily { KF_MODEL = 0, KF_XSPEC, KF_PREP, KF_SEED, KF_ACCUM, KF_EVAL, KF_TAYLOR, KF_STEP, KF_FINAL, KF_SYNTH, KF_FPS, KF_SCATMODEL, KF_PCA, KF_GAUSSRES, KF_GAUSSNORM, KF_NBSFFT, KF_NBSFIT, KF_SCRUNCH, KF_NOISEFIT, KF_COUNT };
 static const char* kFamilyNames[KF_COUNT] = {"model_fft", "xspec", "prep", "seed", "accum", "eval", "taylor_solve", "step", "finalize",
-                                            "synth", "fit_phase_shift", "scat_model", "pca_gram", "gauss_resid", "gauss_normal", "nbscat_fft", "nbscat_fit", "scrunch"};
+                                            "synth", "fit_phase_shift", "scat_model", "pca_gram", "gauss_resid", "gauss_normal", "nbscat_fft", "nbscat_fit", "scrunch", "noise_fit"};
 
 #define PP_NSTAGE 3     // enqueued batches that may be pending at once (staging blocks, work-buffer sets)
 struct pp_ctx {
@@ -109,6 +109,7 @@ struct pp_ctx {
     std::map<int, DevBuf> twiddles;   // by nbin
     struct AnyPlan { int L = 0; DevBuf chirp, bft; };
     std::map<int, AnyPlan> anyplans;  // Bluestein tables of row lengths that are no power of two (pp_anybin.h)
+    std::map<int, DevBuf> nftabs;     // find_kc's width tables, by 2 H + fn (pp_noisefit.h)
     ModelSlot slots[PP_MAX_SLOTS];
     DevBuf mft_table, msum_table, kt_table, mdc_table, msq_table;   // device arrays of slot base pointers
     // work buffers of the context itself: what only the transform stage touches, and the aux entry points' scratch
@@ -420,6 +421,7 @@ extern "C" int pp_destroy(pp_ctx* c) {
     for (void*& h : c->tail_host) { if (h) (void)hipHostFree(h); h = nullptr; }
     for (auto& kv : c->twiddles) kv.second.release();
     for (auto& kv : c->anyplans) { kv.second.chirp.release(); kv.second.bft.release(); }
+    for (auto& kv : c->nftabs) kv.second.release();
     for (auto& s : c->slots) { s.mft.release(); s.msum.release(); s.mmax.release(); s.mdc.release(); s.kt.release(); s.msq.release(); }
     for (auto& sg : c->stage) {
         if (sg.o_host) (void)hipHostFree(sg.o_host);
@@ -2204,6 +2206,7 @@ extern "C" int pp_fit_wait(pp_ctx* c) {
 
 #include "pp_extra_api.h"
 #include "pp_zap.h"
+#include "pp_noisefit.h"
 #include "pp_pca.h"
 #include "pp_gaussfit.h"
 #include "pp_nbscat.h"

@@ -42,13 +42,12 @@ __device__ __forceinline__ void chan_noise_reduce(double* red, double v[5]) {
 }
 
 // normalize_portrait (pplib.py:2462-2507): rows with no non-zero sample keep norm 1 (and noise 0)
-__device__ __forceinline__ void chan_noise_store(const ChanNoiseArgs& a, long long r, const double v[5]) {
-    const int M = a.M, H = M + 1, kc = (int)(0.75 * H);    // get_noise_PS: int((1 - 1/4) * len(pows))
-    const double noise = sqrt(v[4] / (2.0 * M) / (double)(H - kc));
+// (noise: the row's own, by whichever estimator)
+__device__ __forceinline__ void chan_noise_finish(const ChanNoiseArgs& a, long long r, const double v[5], double noise) {
     double norm = 1.0;
     if (v[3] != 0.0) {
         switch (a.method) {
-            case PP_NORM_MEAN: norm = v[0] / (2.0 * M); break;
+            case PP_NORM_MEAN: norm = v[0] / (2.0 * a.M); break;
             case PP_NORM_MAX: norm = v[1]; break;
             case PP_NORM_PROF: norm = a.divisor[r]; break;
             case PP_NORM_RMS: norm = noise; break;
@@ -66,6 +65,11 @@ __device__ __forceinline__ void chan_noise_store(const ChanNoiseArgs& a, long lo
         if (Weq <= 0.0) Weq = 1.0;
         a.snr[r] = v[0] / (noise * sqrt(Weq)) * keep / a.fudge;
     }
+}
+
+__device__ __forceinline__ void chan_noise_store(const ChanNoiseArgs& a, long long r, const double v[5]) {
+    const int M = a.M, H = M + 1, kc = (int)(0.75 * H);    // get_noise_PS: int((1 - 1/4) * len(pows))
+    chan_noise_finish(a, r, v, sqrt(v[4] / (2.0 * M) / (double)(H - kc)));
 }
 
 __device__ __forceinline__ void chan_noise_start(double v[5]) {

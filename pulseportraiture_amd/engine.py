@@ -98,6 +98,16 @@ def _dp(a):
     return None if a is None else a.ctypes.data_as(c_double_p)
 
 
+NOISE_METHODS = _lib.NOISE_METHODS
+
+
+def _noise_method(method, fn='exp_dc'):
+    if method not in NOISE_METHODS:
+        raise ValueError("noise method must be 'PS' or 'fit', not %r" % (method,))
+    if fn not in _lib.PP_KC_FNS:
+        raise ValueError("fn must be 'exp_dc' or 'half_tri', not %r" % (fn,))
+
+
 def _f64(a, shape=None):
     if a is None:
         return None
@@ -774,15 +784,18 @@ class Engine(object):
             _dp(params), _dp(nu_refs), _dp(scales), _dp(errs), _dp(out)), "pp_channel_red_chi2")
         return out
 
-    def channel_noise(self, ports, norm=None, weights=None):
+    def channel_noise(self, ports, norm=None, weights=None, method='PS', fact=1.1, fn='exp_dc'):
         """ppzap's channel noise (ppzap.py:222-230): every row normalised as
         normalize_portrait(port, method=norm, weights) does (pplib.py:2462-2507), then
-        get_noise_PS(row, frac=4).  ports: [nsub,nchan,nbin] or [nrows,nbin] (one
-        portrait), NumPy or a device tensor; weights: [nsub,nchan] (norm 'prof').
-        Returns (noise, norms) shaped like ports without the bin axis; rows with no
-        non-zero sample keep norm 1 and noise 0."""
+        get_noise(row, method).  method 'PS' is get_noise_PS(row, frac=4); 'fit' is
+        get_noise_fit(row, fact) (pplib.py:2255-2287) with find_kc(pows, fn=fn) inside it,
+        all of it on the device (norm 'rms' then divides by the fitted noise).  ports:
+        [nsub,nchan,nbin] or [nrows,nbin] (one portrait), NumPy or a device tensor;
+        weights: [nsub,nchan] (norm 'prof').  Returns (noise, norms) shaped like ports
+        without the bin axis; rows with no non-zero sample keep norm 1 and noise 0."""
         if norm not in _lib.PP_NORMS:
             raise ValueError("norm must be one of None, 'mean', 'max', 'prof', 'rms', 'abs'")
+        _noise_method(method, fn)
         shape = tuple(int(v) for v in ports.shape)
         if len(shape) not in (2, 3):
             raise ValueError("ports must be [nsub,nchan,nbin] or [nrows,nbin]")
@@ -793,9 +806,62 @@ class Engine(object):
         if norm == 'prof':
             div = self._prof_norms(ports, weights)
         norms, noise = np.empty(nrows), np.empty(nrows)
-        _check(self._lib.pp_channel_noise(self._ctx, src, dtype, on_dev, nrows, nbin, _lib.PP_NORMS[norm],
-                                          _dp(div), _dp(norms), _dp(noise)), "pp_channel_noise")
+        if method == 'PS':
+            _check(self._lib.pp_channel_noise(self._ctx, src, dtype, on_dev, nrows, nbin, _lib.PP_NORMS[norm],
+                                              _dp(div), _dp(norms), _dp(noise)), "pp_channel_noise")
+        else:
+            _check(self._lib.pp_channel_noise_fit(self._ctx, src, dtype, on_dev, nrows, nbin, _lib.PP_NOISEFIT_ROWS,
+                                                  _lib.PP_KC_FNS[fn], float(fact), _lib.PP_NORMS[norm], _dp(div),
+                                                  _dp(norms), _dp(noise), None, None), "pp_channel_noise_fit")
         return noise.reshape(shape[:-1]), norms.reshape(shape[:-1])
+
+    def find_kc(self, pows, fn='exp_dc', return_cell=False, fact=1.1, return_noise=False):
+        """pplib.find_kc (pplib.py:1465-1495) of every row of pows [..., H] (power spectra, NumPy
+        or an f64 device tensor; 5 <= H <= 2049): the cut-off harmonic where the noise floor of
+        log10(pows) starts, from the 20 x 20 x 20 opt.brute grid of fn ('exp_dc' or 'half_tri')
+        evaluated in closed form on the device.  Returns kc (int32, shaped like pows without its
+        last axis); return_cell adds the winning grid cell [..., 3] = (ia, ib, idc), and
+        return_noise adds sqrt(mean(pows[int(k):])) of get_noise_fit (pplib.py:2273-2277) for
+        k = fact kc."""
+        _noise_method('fit', fn)
+        if not _is_device_array(pows):
+            pows = np.ascontiguousarray(pows, dtype=np.float64)
+        src, dtype, on_dev, shape, keep = _array_arg(pows, "find_kc: device power spectra")
+        if dtype != PP_F64:
+            raise ValueError("find_kc: power spectra must be float64")
+        if len(shape) < 1 or not 5 <= shape[-1] <= 2049:
+            raise ValueError("find_kc: pows must be [..., H] with 5 <= H <= 2049")
+        H = int(shape[-1])
+        nrows = int(np.prod(shape[:-1]))
+        norms, noise = np.empty(nrows), np.empty(nrows)
+        kc, cell = np.empty(nrows, dtype=np.int32), np.empty((nrows, 3), dtype=np.int32)
+        _check(self._lib.pp_channel_noise_fit(self._ctx, src, dtype, on_dev, nrows, 2 * (H - 1), _lib.PP_NOISEFIT_POWS,
+                                              _lib.PP_KC_FNS[fn], float(fact), _lib.PP_NORMS[None], None, _dp(norms),
+                                              _dp(noise), kc.ctypes.data_as(c_int32_p), cell.ctypes.data_as(c_int32_p)),
+               "pp_channel_noise_fit")
+        out = (kc.reshape(shape[:-1]),)
+        if return_cell:
+            out += (cell.reshape(shape[:-1] + (3,)),)
+        if return_noise:
+            out += (noise.reshape(shape[:-1]),)
+        return out[0] if len(out) == 1 else out
+
+    def noise_fit(self, ports, fact=1.1, fn='exp_dc'):
+        """Everything pp_channel_noise_fit measures of the rows of ports [..., nbin] (NumPy or a
+        device tensor, f64 or f32): (noise, kc, cell) = get_noise_fit(row, fact), find_kc's cut-off
+        and its winning grid cell (ia, ib, idc), shaped like ports without the bin axis."""
+        _noise_method('fit', fn)
+        src, dtype, on_dev, shape, keep = _array_arg(ports, "noise_fit: device rows")
+        if len(shape) < 2:
+            raise ValueError("ports must be [..., nbin]")
+        nrows = int(np.prod(shape[:-1]))
+        norms, noise = np.empty(nrows), np.empty(nrows)
+        kc, cell = np.empty(nrows, dtype=np.int32), np.empty((nrows, 3), dtype=np.int32)
+        _check(self._lib.pp_channel_noise_fit(self._ctx, src, dtype, on_dev, nrows, int(shape[-1]), _lib.PP_NOISEFIT_ROWS,
+                                              _lib.PP_KC_FNS[fn], float(fact), _lib.PP_NORMS[None], None, _dp(norms),
+                                              _dp(noise), kc.ctypes.data_as(c_int32_p), cell.ctypes.data_as(c_int32_p)),
+               "pp_channel_noise_fit")
+        return noise.reshape(shape[:-1]), kc.reshape(shape[:-1]), cell.reshape(shape[:-1] + (3,))
 
     # host bytes of f64 rows _prof_norms holds at a time (and as many again for their mean profiles)
     PROF_RUN_BYTES = 256 << 20
@@ -833,18 +899,24 @@ class Engine(object):
                 self.fit_phase_shift_batch(rows[live], means[sub_of], finish='simplex')[:, 2]
         return div.reshape(-1)
 
-    def channel_snrs(self, ports, fudge=3.25):
+    def channel_snrs(self, ports, fudge=3.25, method='PS', fact=1.1, fn='exp_dc'):
         """pplib.get_SNR (pplib.py:2289-2308) of every row of ports [..., nbin] (NumPy or a
-        device tensor, f64 or f32): the row's sum, maximum and power-spectrum noise come
-        from one pass over it on the device.  Returns an array shaped like ports without
-        the bin axis."""
+        device tensor, f64 or f32): the row's sum, maximum and noise come from one pass over
+        it on the device.  method: the noise estimator, 'PS' (the power spectrum's top
+        quarter) or 'fit' (get_noise_fit with find_kc(fn=fn), as channel_noise).  Returns an
+        array shaped like ports without the bin axis."""
+        _noise_method(method, fn)
         src, dtype, on_dev, shape, keep = _array_arg(ports, "channel_snrs: device rows")
         if len(shape) < 2:
             raise ValueError("ports must be [..., nbin]")
         nrows = int(np.prod(shape[:-1]))
         snrs = np.empty(nrows)
-        _check(self._lib.pp_channel_snrs(self._ctx, src, dtype, on_dev, nrows, shape[-1], float(fudge),
-                                         _dp(snrs)), "pp_channel_snrs")
+        if method == 'PS':
+            _check(self._lib.pp_channel_snrs(self._ctx, src, dtype, on_dev, nrows, shape[-1], float(fudge),
+                                             _dp(snrs)), "pp_channel_snrs")
+        else:
+            _check(self._lib.pp_channel_snrs_fit(self._ctx, src, dtype, on_dev, nrows, shape[-1], _lib.PP_KC_FNS[fn],
+                                                 float(fact), float(fudge), _dp(snrs)), "pp_channel_snrs_fit")
         return snrs.reshape(shape[:-1])
 
     # eigenvectors find_significant_eigvec examines (check_max = 10, pplib.py:1584)

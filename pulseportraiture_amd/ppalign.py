@@ -14,15 +14,17 @@ archive to the last of the last one (Engine.align_begin / align_add / align_fini
 """
 import numpy as np
 
-from .archive import data_from_arrays, load_archive, named_datafiles, write_archive as write_npz
+from .archive import (data_from_arrays, load_archive, named_datafiles, noise_kwargs, noise_method_in_force,
+                      noise_method_scope, write_archive as write_npz)
 from .engine import default_engine
 from .pplib import Dconst, guess_fit_freq, fit_phase_shift, gaussian_profile, get_noise, get_SNR
 from .pptoas import _to_device_once
 from .scrunch import tscrunch as _tscrunch
 
 
-def normalize_portrait(port, method="rms", weights=None, return_norms=False):
-    """Normalise every profile of a portrait (pplib.py:2462-2507)."""
+def normalize_portrait(port, method="rms", weights=None, return_norms=False, noise_method=None):
+    """Normalise every profile of a portrait (pplib.py:2462-2507).  noise_method: the estimator behind 'rms'
+    (get_noise's method; None: archive's scope, else 'PS')."""
     if method not in ("mean", "max", "prof", "rms", "abs"):
         print("Unknown method for normalize_portrait(...), '%s'." % method)
         return None
@@ -42,7 +44,7 @@ def normalize_portrait(port, method="rms", weights=None, return_norms=False):
             elif method == "prof":
                 norm = fit_phase_shift(port[ichan], mean_prof).scale
             elif method == "rms":
-                norm = get_noise(port[ichan])
+                norm = get_noise(port[ichan], method=noise_method_in_force(noise_method) or "PS")
             else:
                 norm = (port[ichan] ** 2.0).sum() ** 0.5
             norm_port[ichan] = port[ichan] / norm
@@ -269,7 +271,7 @@ def write_archive(outfile, aligned_port, total_weights, model_data):
 
 def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunch=True,
                    SNR_cutoff=0.0, outfile=None, norm=None, rot_phase=0.0, place=None,
-                   niter=1, quiet=False, engine=None):
+                   niter=1, quiet=False, engine=None, noise_method=None):
     """Iteratively align and average archives (ppalign.py:54-243).
 
     Each archive is fitted for a phase, a DM and channel amplitudes against initial_guess; the
@@ -284,7 +286,16 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunc
     returns the average Stokes portraits (alignment and weights from total intensity; archives
     of one polarisation are skipped).  SNR_cutoff filters archives by prof_SNR.  outfile defaults
     to <metafile>.algnd.npz.  norm, rot_phase, place (overrides rot_phase), niter, quiet as in the
-    reference.  Returns (aligned_port[npol,nchan,nbin], total_weights[nchan])."""
+    reference.  noise_method ('PS' or 'fit'): the estimator of the archives' noise_stds and SNRs, measured anew
+    with it, and of the 'rms' norm; None keeps stored values and the power-spectrum estimate.
+    Returns (aligned_port[npol,nchan,nbin], total_weights[nchan])."""
+    with noise_method_scope(noise_method):
+        return _align_archives(metafile, initial_guess, fit_dm, tscrunch, pscrunch, SNR_cutoff, outfile, norm, rot_phase,
+                               place, niter, quiet, engine)
+
+
+def _align_archives(metafile, initial_guess, fit_dm, tscrunch, pscrunch, SNR_cutoff, outfile, norm, rot_phase, place,
+                    niter, quiet, engine):
     eng = engine or default_engine()
     if isinstance(metafile, str):
         datafiles = named_datafiles(metafile)
@@ -355,7 +366,7 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunc
     if norm in ("mean", "max", "prof", "rms", "abs"):
         # normalize_portrait(aligned_port[ipol], norm, weights=None) (ppalign.py:216-219): the norms on the device
         for ipol in range(npol):
-            norms = eng.channel_noise(aligned_port[ipol], norm=norm)[1]
+            norms = eng.channel_noise(aligned_port[ipol], norm=norm, **noise_kwargs())[1]
             aligned_port[ipol] = aligned_port[ipol] / norms[:, None]
     # rot_phase, then place (ppalign.py:220-226).  While the host rows are still the accumulator's (no norm) the
     # turn is one more finish -- in the spectrum, one inverse transform per row; normalised rows are turned as

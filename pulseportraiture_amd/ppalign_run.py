@@ -12,6 +12,8 @@ import sys
 
 import numpy as np
 
+from .archive import add_noise_method_option, noise_method_refusal, noise_method_scope
+
 MODULE = "pulseportraiture_amd.ppalign_run"
 BANNER = "\nppalign.py - Aligns and averages homogeneous archives by fitting DMs and phases\n"
 
@@ -57,8 +59,17 @@ def parser():
     return ap
 
 
+def full_parser():
+    """parser(), the reference's options, with the options that are this package's own."""
+    ap = parser()
+    add_noise_method_option(ap)
+    return ap
+
+
 def refusal(opts):
     """The message for an option this command cannot honour, or None."""
+    if noise_method_refusal(opts) is not None:
+        return noise_method_refusal(opts)
     if opts.tscrunch:
         return "-T/--tscr needs PSRCHIVE, which this package does not use: scrunch the archives with ppscrunch_run -T first"
     if opts.palign:
@@ -86,7 +97,7 @@ def initial_guess(opts, datafiles):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    ap = parser()
+    ap = full_parser()
     opts = ap.parse_args(argv)
     if opts.metafile is None or not int(opts.niter):
         print(BANNER)
@@ -97,26 +108,27 @@ def main(argv=None):
     if msg is not None:
         print("ppalign_run: " + msg, file=sys.stderr)
         return 2
-    from . import ppalign
-    from .archive import named_datafiles
-    rot_phase = np.float64(opts.rot_phase)
-    place = None
-    if opts.place is not None:
-        rot_phase, place = 0.0, np.float64(opts.place)
-    datafiles = named_datafiles(opts.metafile)
-    outfile = opts.metafile + ".algnd.npz" if opts.outfile is None else opts.outfile
-    if not datafiles:
-        print("ppalign_run: %s names no archive" % opts.metafile, file=sys.stderr)
-        return 1
-    try:
-        guess = initial_guess(opts, datafiles)
-    except RuntimeError as err:         # (the archive the guess is made from cannot be loaded)
-        print("ppalign_run: no initial guess: %s" % err, file=sys.stderr)
-        return 1
-    ppalign.align_archives(datafiles, guess, fit_dm=opts.fit_dm, tscrunch=False, pscrunch=opts.pscrunch,
-                           SNR_cutoff=float(opts.SNR_cutoff), outfile=outfile, norm=opts.norm, rot_phase=rot_phase,
-                           place=place, niter=int(opts.niter), quiet=opts.quiet)
-    return 0
+    with noise_method_scope(opts.noise_method):
+        from . import ppalign
+        from .archive import named_datafiles
+        rot_phase = np.float64(opts.rot_phase)
+        place = None
+        if opts.place is not None:
+            rot_phase, place = 0.0, np.float64(opts.place)
+        datafiles = named_datafiles(opts.metafile)
+        outfile = opts.metafile + ".algnd.npz" if opts.outfile is None else opts.outfile
+        if not datafiles:
+            print("ppalign_run: %s names no archive" % opts.metafile, file=sys.stderr)
+            return 1
+        try:
+            guess = initial_guess(opts, datafiles)
+        except RuntimeError as err:         # (the archive the guess is made from cannot be loaded)
+            print("ppalign_run: no initial guess: %s" % err, file=sys.stderr)
+            return 1
+        ppalign.align_archives(datafiles, guess, fit_dm=opts.fit_dm, tscrunch=False, pscrunch=opts.pscrunch,
+                               SNR_cutoff=float(opts.SNR_cutoff), outfile=outfile, norm=opts.norm, rot_phase=rot_phase,
+                               place=place, niter=int(opts.niter), quiet=opts.quiet)
+        return 0
 
 
 if __name__ == "__main__":

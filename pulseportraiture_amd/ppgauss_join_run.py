@@ -12,7 +12,7 @@ directory); a joinfile given with -j also provides the parameters to start from.
 import sys
 
 from . import ppgauss_run
-from .archive import named_datafiles
+from .archive import named_datafiles, noise_method_scope
 
 MODULE = ppgauss_run.JOIN_MODULE
 MAX_BANDS = 16          # Engine.GAUSS_FIT_MAX_JOIN
@@ -52,12 +52,13 @@ def main(argv=None):
     if msg is not None:
         print("ppgauss_join_run: " + msg, file=sys.stderr)
         return 2
-    try:
-        dp = load_portrait(datafiles, opts.joinfile, opts.metafile)
-    except (ValueError, OSError) as e:
-        print("ppgauss_join_run: %s" % e, file=sys.stderr)
-        return 2
-    return ppgauss_run.fit_and_write(dp, opts, opts.metafile + ".gmodel")
+    with noise_method_scope(opts.noise_method):
+        try:
+            dp = load_portrait(datafiles, opts.joinfile, opts.metafile)
+        except (ValueError, OSError) as e:
+            print("ppgauss_join_run: %s" % e, file=sys.stderr)
+            return 2
+        return ppgauss_run.fit_and_write(dp, opts, opts.metafile + ".gmodel")
 
 
 if __name__ == "__main__":

@@ -17,7 +17,8 @@ import sys
 
 import numpy as np
 
-from .archive import load_archive_file, named_datafiles
+from .archive import (add_noise_method_option, load_archive_file, named_datafiles, noise_method_refusal,
+                      noise_method_scope)
 from .pplib import default_model
 
 MODULE = "pulseportraiture_amd.ppgauss_run"
@@ -94,6 +95,7 @@ def parser(joined=False):
                          "sqrt{vector modulus} ('mean', 'max', 'prof', 'rms', 'abs').")
     ap.add_argument("--figure", default=False, metavar="figurename", help="Not available: no plotting.")
     ap.add_argument("--verbose", dest="quiet", action="store_false", default=True, help="More to stdout.")
+    add_noise_method_option(ap)
     return ap
 
 
@@ -131,6 +133,8 @@ def refusal(opts, datafiles=None):
 
 def fit_refusal(opts):
     """The message for a request about the fit itself that neither command honours, or None."""
+    if noise_method_refusal(opts) is not None:
+        return noise_method_refusal(opts)
     if opts.figure:
         return "--figure: plots are not available"
     if opts.normalize is not None and opts.normalize not in ("mean", "max", "prof", "rms", "abs"):
@@ -169,7 +173,8 @@ def main(argv=None):
     if msg is not None:
         print("ppgauss_run: " + msg, file=sys.stderr)
         return 2
-    return fit_and_write(load_portrait(datafiles[0]), opts, opts.datafile + ".gmodel")
+    with noise_method_scope(opts.noise_method):
+        return fit_and_write(load_portrait(datafiles[0]), opts, opts.datafile + ".gmodel")
 
 
 def fit_and_write(dp, opts, default_outfile):

@@ -355,20 +355,96 @@ def weighted_mean(data, errs=1.0):
     return (data[ii] * w).sum() / w.sum(), w.sum() ** -0.5
 
 
-def get_noise(data, method=default_noise_method, frac=4, chans=False):
-    """Off-pulse noise from the mean of the top 1/frac of the power spectrum
-    (get_noise / get_noise_PS, pplib.py:2206-2253; only the "PS" method).  Host
-    helper for normalisation; inside a fit the engine measures the same quantity
+def get_noise(data, method=default_noise_method, **kwargs):
+    """Off-pulse noise of data, 1- or 2-D (get_noise, pplib.py:2206-2225).  method "PS" is the mean of the
+    top 1/frac of the power spectrum (get_noise_PS; frac=4, chans=False); "fit" finds the harmonic where the
+    noise floor starts (get_noise_fit; fact=1.1, chans=False), on the device.  **kwargs go to the selected
+    function.  An unknown method prints and returns 0, as the reference."""
+    if method == "PS":
+        return get_noise_PS(data, **kwargs)
+    if method == "fit":
+        return get_noise_fit(data, **kwargs)
+    print("Unknown get_noise method.")
+    return 0
+
+
+def get_noise_PS(data, frac=4, chans=False):
+    """Off-pulse noise from the mean of the top 1/frac of the power spectrum (get_noise_PS,
+    pplib.py:2227-2253).  Host helper for normalisation; inside a fit the engine measures the same quantity
     itself when errs is None."""
-    if method != "PS":
-        print("Unknown get_noise method.")
-        return 0
     a = np.asarray(data, dtype=np.float64)
     rows = a if chans else a.reshape(1, -1)
     power = np.abs(np.fft.rfft(rows, axis=-1)) ** 2.0 / rows.shape[-1]
     kc = int((1 - frac ** -1) * power.shape[-1])
     noise = np.sqrt(power[:, kc:].mean(axis=-1))
     return noise if chans else noise[0]
+
+
+# points of one transform on the device (Engine.channel_noise: nbin <= 4096)
+NOISE_FIT_MAX_POINTS = 4096
+
+
+def get_noise_fit(data, fact=1.1, chans=False):
+    """Off-pulse noise from the mean of the power spectrum above fact * find_kc(pows) (get_noise_fit,
+    pplib.py:2255-2287), on the device (Engine.channel_noise(method='fit')).  data: 1-D, or 2-D with chans=True
+    for one value per row.  2-D data with chans=False is the reference's transform of the ravelled nchan x nbin
+    points: NotImplementedError beyond NOISE_FIT_MAX_POINTS points (and for an odd number of them).
+
+    One departure: a row whose power above DC is nothing but the transform's rounding residue (a constant row).  At
+    row lengths that are a power of two the device, like the reference, finds exact zeros there and takes kc = H - 1;
+    at other lengths the reference's transform leaves exact zeros in some harmonics and the device's in none, so the
+    fitted kc can differ.  The noise is 0 to 1e-12 of the row either way."""
+    a = np.asarray(data)
+    if a.dtype != np.float32:
+        a = a.astype(np.float64, copy=False)
+    if chans:
+        return default_engine().channel_noise(a.reshape(len(a), -1), method='fit', fact=fact)[0]
+    flat = a.reshape(1, -1)
+    if flat.shape[1] > NOISE_FIT_MAX_POINTS or flat.shape[1] % 2 or flat.shape[1] < 8:
+        raise NotImplementedError(
+            "get_noise_fit(chans=False) transforms the ravelled data as one row: %d points, and the device takes an "
+            "even number from 8 to %d (chans=True measures every row)" % (flat.shape[1], NOISE_FIT_MAX_POINTS))
+    return default_engine().channel_noise(flat, method='fit', fact=fact)[0][0]
+
+
+def half_triangle_function(a, b, dc, N):
+    """A half triangle of base floor(a) and height b on the baseline dc, N points (half_triangle_function,
+    pplib.py:1436-1446): find_kc's 'half_tri' model, as a definition."""
+    fn = np.zeros(N) + dc
+    a = int(np.floor(a))
+    fn[:a] += -(np.float64(b) / a) * np.arange(a) + b
+    return fn
+
+
+def find_kc_function(params, data, errs=1.0, fn='exp_dc'):
+    """The (weighted) chi-squared of find_kc's model (a, b, dc) against data (find_kc_function,
+    pplib.py:1448-1463): b exp(-a k) + dc for fn 'exp_dc', half_triangle_function for 'half_tri'.  The
+    definition of what Engine.find_kc minimises over its grid, not a route around it."""
+    a, b, dc = params[0], params[1], params[2]
+    if fn == 'exp_dc':
+        model = b * np.exp(-a * np.arange(len(data))) + dc
+    elif fn == 'half_tri':
+        model = half_triangle_function(a, b, dc, len(data))
+    else:
+        return 0.0
+    return np.sum(((data - model) / errs) ** 2.0)
+
+
+def find_kc(pows, errs=1.0, fn='exp_dc'):
+    """The critical cut-off harmonic where the noise floor of the power spectrum pows (1-D) starts
+    (find_kc, pplib.py:1465-1495), from the reference's 20 x 20 x 20 brute grid, searched on the device
+    (Engine.find_kc).  A scalar errs scales every chi-squared alike and does not move the minimum; an array
+    of errs is not supported.  An unknown fn returns 0, as the reference.  (Spectra are taken as given: a harmonic
+    of exactly zero power gives kc = len(pows) - 1, as in the reference; whether a transform leaves exact zeros in
+    harmonics that hold only rounding residue is the transform's business -- see get_noise_fit.)"""
+    if np.ndim(errs) != 0:
+        raise NotImplementedError("find_kc: errs must be a scalar (per-harmonic uncertainties are not supported)")
+    if fn not in ('exp_dc', 'half_tri'):
+        return 0
+    pows = np.asarray(pows, dtype=np.float64)
+    if pows.ndim != 1:
+        raise ValueError("find_kc: pows is a 1-D power spectrum (Engine.find_kc takes rows of them)")
+    return int(default_engine().find_kc(pows[None], fn=fn)[0])
 
 
 # ---- wavelet smoothing -----------------------------------------------------------
@@ -481,12 +557,14 @@ def gaussian_profile(nbin, loc, wid):
     return np.exp(-0.5 * ((x[ipk] - loc) / sigma) ** 2.0) / out[ipk] * out
 
 
-def get_SNR(prof, fudge=3.25):
+def get_SNR(prof, fudge=3.25, noise_method=None):
     """Estimate of a profile's signal-to-noise ratio, baseline removed (pplib.py:2289-2308):
     sum / (noise sqrt(Weq)) / fudge with Weq = sum / max.  The profile's sum, maximum and
-    power-spectrum noise are taken in one pass on the device (Engine.channel_snrs, which
-    takes whole portraits)."""
-    return default_engine().channel_snrs(np.asarray(prof, dtype=np.float64)[None], fudge=fudge)[0]
+    noise are taken in one pass on the device (Engine.channel_snrs, which takes whole
+    portraits).  noise_method: get_noise's method, 'PS' or 'fit' (None: archive's scope, else 'PS')."""
+    from .archive import noise_kwargs
+    return default_engine().channel_snrs(np.asarray(prof, dtype=np.float64)[None], fudge=fudge,
+                                         **noise_kwargs(noise_method))[0]
 
 
 def fit_phase_shift(data, model, noise=None, bounds=[-0.5, 0.5], Ns=100, finish='simplex'):
@@ -770,7 +848,7 @@ def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.npz", nsub=1, np
 
 def load_data(filename, state=None, dedisperse=False, dededisperse=False, tscrunch=False, pscrunch=False,
               fscrunch=False, rm_baseline=False, flux_prof=False, refresh_arch=True, return_arch=True, quiet=False,
-              engine=None):
+              engine=None, noise_method=None):
     """Load an .npz archive (or take a DataBunch) and apply the operations the reference's load_data hands to
     PSRCHIVE, in its order (pplib.py:2650-2814): state, dedisperse / dededisperse, tscrunch, pscrunch, fscrunch --
     pulseportraiture_amd.scrunch, on the device.  Returns the DataBunch with the reference's fields; prof, prof_noise,
@@ -779,9 +857,21 @@ def load_data(filename, state=None, dedisperse=False, dededisperse=False, tscrun
 
     Departures.  rm_baseline defaults to False and True raises NotImplementedError: an .npz holds what PSRCHIVE
     returned after remove_baseline, and the fit ignores the DC term.  state conversions other than to 'Intensity'
-    raise.  refresh_arch and return_arch have nothing to act on."""
+    raise.  refresh_arch and return_arch have nothing to act on.
+
+    noise_method ('PS' or 'fit'; the reference's default_noise_method constant): given, noise_stds and SNRs are measured
+    anew with it -- stored values too -- here and after every scrunch; None keeps stored values and measures the rest
+    from the power spectrum."""
+    from .archive import noise_method_scope
+    with noise_method_scope(noise_method):
+        return _load_data(filename, state, dedisperse, dededisperse, tscrunch, pscrunch, fscrunch, rm_baseline,
+                          flux_prof, quiet, engine)
+
+
+def _load_data(filename, state, dedisperse, dededisperse, tscrunch, pscrunch, fscrunch, rm_baseline, flux_prof, quiet,
+               engine):
     from . import scrunch as sc
-    from .archive import load_archive
+    from .archive import load_archive, noise_method_in_force
     if rm_baseline:
         raise NotImplementedError("load_data(rm_baseline=True): baseline removal is PSRCHIVE's; an .npz archive holds "
                                   "the data it returned after remove_baseline")
@@ -789,7 +879,7 @@ def load_data(filename, state=None, dedisperse=False, dededisperse=False, tscrun
     if isinstance(filename, dict):
         data = DataBunch(**{k: v for k, v in filename.items()})
         data.setdefault("filename", "arrays")
-        if data.get("noise_stds") is None or data.get("SNRs") is None:
+        if data.get("noise_stds") is None or data.get("SNRs") is None or noise_method_in_force() is not None:
             sc.measured(eng, data)      # (S/N 0 for a dead row, as in the scrunched bunches that follow)
     else:
         data, _ = load_archive(filename, eng)

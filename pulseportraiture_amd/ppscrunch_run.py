@@ -31,11 +31,14 @@ def parser():
     ap.add_argument("-o", "--outfile", default=None, metavar="outfile", help="Name of the output archive (one archive only).")
     ap.add_argument("--metafile", default=None, metavar="out.txt", help="Write the names of the output archives here.")
     ap.add_argument("--quiet", action="store_true", help="Suppress output.")
+    archive.add_noise_method_option(ap)
     return ap
 
 
 def refusal(opts):
     """The message for a combination this command cannot honour, or None."""
+    if archive.noise_method_refusal(opts) is not None:
+        return archive.noise_method_refusal(opts)
     if opts.tscrunch and opts.setnsub is not None:
         return "-T and --setnsub exclude each other"
     if opts.fscrunch and opts.setnchn is not None:
@@ -82,37 +85,38 @@ def main(argv=None):
     if msg is not None:
         print("ppscrunch_run: " + msg, file=sys.stderr)
         return 2
-    from .engine import default_engine
-    from .scrunch import state_of
-    datafiles = archive.named_datafiles(opts.datafiles)
-    if opts.outfile is not None and len(datafiles) != 1:
-        print("ppscrunch_run: -o names one output, %s names %d archives" % (opts.datafiles, len(datafiles)), file=sys.stderr)
-        return 2
-    eng = default_engine()
-    written = []
-    for datafile in datafiles:
-        try:
-            data, _ = archive.load_archive(datafile, eng)
-        except RuntimeError as err:
+    with archive.noise_method_scope(opts.noise_method):
+        from .engine import default_engine
+        from .scrunch import state_of
+        datafiles = archive.named_datafiles(opts.datafiles)
+        if opts.outfile is not None and len(datafiles) != 1:
+            print("ppscrunch_run: -o names one output, %s names %d archives" % (opts.datafiles, len(datafiles)), file=sys.stderr)
+            return 2
+        eng = default_engine()
+        written = []
+        for datafile in datafiles:
+            try:
+                data, _ = archive.load_archive(datafile, eng)
+            except RuntimeError as err:
+                if not opts.quiet:
+                    print("Cannot load_data(%s).  Skipping it." % datafile)
+                    print(err)
+                continue
+            try:
+                data.state = state_of(data)
+                data = scrunched(data, opts, eng)
+            except ValueError as err:            # (more groups asked for than the archive has members)
+                if not opts.quiet:
+                    print("%s: %s.  Skipping it." % (datafile, err))
+                continue
+            out = write_archive(opts.outfile or output_name(datafile, opts.ext), data)
+            written.append(out)
             if not opts.quiet:
-                print("Cannot load_data(%s).  Skipping it." % datafile)
-                print(err)
-            continue
-        try:
-            data.state = state_of(data)
-            data = scrunched(data, opts, eng)
-        except ValueError as err:            # (more groups asked for than the archive has members)
-            if not opts.quiet:
-                print("%s: %s.  Skipping it." % (datafile, err))
-            continue
-        out = write_archive(opts.outfile or output_name(datafile, opts.ext), data)
-        written.append(out)
-        if not opts.quiet:
-            print("Unloaded %s: %d subint(s) x %d pol x %d channel(s) x %d bins." % (out, data.nsub, data.npol, data.nchan, data.nbin))
-    if opts.metafile is not None:
-        with open(opts.metafile, "w") as f:
-            f.write("".join(name + "\n" for name in written))
-    return 0 if written else 1
+                print("Unloaded %s: %d subint(s) x %d pol x %d channel(s) x %d bins." % (out, data.nsub, data.npol, data.nchan, data.nbin))
+        if opts.metafile is not None:
+            with open(opts.metafile, "w") as f:
+                f.write("".join(name + "\n" for name in written))
+        return 0 if written else 1
 
 
 if __name__ == "__main__":

@@ -21,6 +21,7 @@ import numpy as np
 import scipy.interpolate as si
 
 from . import pplib
+from .archive import noise_kwargs
 from .engine import default_engine
 
 CHECK_MAX = 10      # find_significant_eigvec's check_max as make_spline_model calls it
@@ -87,11 +88,13 @@ class DataPortrait(pplib.DataPortrait):
     """The data a spline model is made from (built from arrays, like the parent), with
     the reference's methods for modelling profile evolution with a B-spline curve."""
 
-    def normalize_portrait(self, method="rms"):
+    def normalize_portrait(self, method="rms", noise_method=None):
         """Normalize each channel's profile (pplib.py:357-382), with the reference's side
         effects: port, portx, norm_values, noise_stds[0,0], noise_stdsxs, flux_prof,
         flux_profx and the unnorm_* copies.  Norms and the noise of the normalised rows are
-        measured on the device (Engine.channel_noise)."""
+        measured on the device (Engine.channel_noise), with the estimator noise_method ('PS' or
+        'fit'; None: archive's scope, else 'PS')."""
+        kw = noise_kwargs(noise_method)
         if method not in ("mean", "max", "prof", "rms", "abs"):
             print("Unknown method for normalize_portrait(...), '%s'." % method)
             return
@@ -102,18 +105,18 @@ class DataPortrait(pplib.DataPortrait):
             weightsx = np.asarray(self.weights)[np.asarray(self.weights) > 0]
         if self.noise_stds is None:
             self.noise_stds = np.zeros((self.nsub, self.npol, self.nchan))
-            self.noise_stds[0, 0] = eng.channel_noise(self.port)[0]
+            self.noise_stds[0, 0] = eng.channel_noise(self.port, **kw)[0]
             self.noise_stdsxs = self.noise_stds[0, 0, self.ok_ichans[0]]
         self.unnorm_noise_stds = np.copy(self.noise_stds)
         noise, norms = eng.channel_noise(self.port, norm=method,
-                                         weights=None if weights is None else weights[None])
+                                         weights=None if weights is None else weights[None], **kw)
         self.port = self.port / norms[:, None]
         self.norm_values = norms
         self.noise_stds[0, 0] = noise
         self.flux_prof = self.port.mean(axis=1)
         self.unnorm_noise_stdsxs = np.copy(self.noise_stdsxs)
         noisex, normsx = eng.channel_noise(self.portx, norm=method,
-                                           weights=None if weightsx is None else weightsx[None])
+                                           weights=None if weightsx is None else weightsx[None], **kw)
         self.portx = self.portx / normsx[:, None]
         self.noise_stdsxs = noisex
         self.flux_profx = self.portx.mean(axis=1)

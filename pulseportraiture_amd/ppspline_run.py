@@ -8,7 +8,8 @@ DataPortrait.make_spline_model(smooth=False) on the device and written as a .spl
 import argparse
 import sys
 
-from .archive import load_archive_file, named_datafiles
+from .archive import (add_noise_method_option, load_archive_file, named_datafiles, noise_method_refusal,
+                      noise_method_scope)
 
 MODULE = "pulseportraiture_amd.ppspline_run"
 SMOOTH_MODULE = "pulseportraiture_amd.ppspline_smooth_run"
@@ -55,11 +56,14 @@ def parser(smooth=False):
                     help="The maximum number of unique knots.")
     ap.add_argument("--plots", dest="make_plots", action="store_true", help="Not available: no plotting.")
     ap.add_argument("--quiet", action="store_true", help="Suppresses output.")
+    add_noise_method_option(ap)
     return ap
 
 
 def refusal(opts, datafiles=None, smooth=False):
     """The message for a request this command cannot honour, or None."""
+    if noise_method_refusal(opts) is not None:
+        return noise_method_refusal(opts)
     if opts.smooth and not smooth:
         return ("-s/--smooth: the wavelet smoothing was pinned without PyWavelets and lives beside this "
                 "command; run python -m %s (DataPortrait.make_smooth_spline_model) with the same "
@@ -92,20 +96,21 @@ def main(argv=None, smooth=False):
     if msg is not None:
         print(("ppspline_smooth_run: " if smooth else "ppspline_run: ") + msg, file=sys.stderr)
         return 2
-    datafile = datafiles[0]
-    max_nbreak = None if opts.max_nbreak is None else int(opts.max_nbreak)
-    dp = load_portrait(datafile)
-    if opts.norm in ("mean", "max", "prof", "rms", "abs"):
-        dp.normalize_portrait(opts.norm)
-    kw = dict(max_ncomp=int(opts.max_ncomp), snr_cutoff=float(opts.snr_cutoff), rchi2_tol=float(opts.rchi2_tol),
-              k=int(opts.k), sfac=float(opts.sfac), max_nbreak=max_nbreak, model_name=opts.model_name, quiet=opts.quiet)
-    if smooth:
-        dp.make_smooth_spline_model(**kw)
-    else:
-        dp.make_spline_model(smooth=False, **kw)
-    modelfile = opts.datafile + ".spl" if opts.modelfile is None else opts.modelfile
-    dp.write_model(modelfile, quiet=opts.quiet)
-    return 0
+    with noise_method_scope(opts.noise_method):
+        datafile = datafiles[0]
+        max_nbreak = None if opts.max_nbreak is None else int(opts.max_nbreak)
+        dp = load_portrait(datafile)
+        if opts.norm in ("mean", "max", "prof", "rms", "abs"):
+            dp.normalize_portrait(opts.norm)
+        kw = dict(max_ncomp=int(opts.max_ncomp), snr_cutoff=float(opts.snr_cutoff), rchi2_tol=float(opts.rchi2_tol),
+                  k=int(opts.k), sfac=float(opts.sfac), max_nbreak=max_nbreak, model_name=opts.model_name, quiet=opts.quiet)
+        if smooth:
+            dp.make_smooth_spline_model(**kw)
+        else:
+            dp.make_spline_model(smooth=False, **kw)
+        modelfile = opts.datafile + ".spl" if opts.modelfile is None else opts.modelfile
+        dp.write_model(modelfile, quiet=opts.quiet)
+        return 0
 
 
 if __name__ == "__main__":

@@ -13,6 +13,10 @@ def parser():
     return ppspline_run.parser(smooth=True)
 
 
+def refusal(opts, datafiles=None):
+    return ppspline_run.refusal(opts, datafiles, smooth=True)
+
+
 def main(argv=None):
     return ppspline_run.main(argv, smooth=True)
 

@@ -18,7 +18,8 @@ import time
 import numpy as np
 
 from . import gmodel, scrunch
-from .archive import MJD, data_from_arrays, good_channel_counts, load_bunch  # noqa: F401  (the first two: public here)
+from .archive import (MJD, data_from_arrays, good_channel_counts, load_bunch,  # noqa: F401  (the first two: public here)
+                      noise_method_in_force)
 from .engine import EngineNotSupported, default_engine
 from .pplib import DataBunch, Dconst, get_noise, guess_fit_freq, phase_transform, scattering_alpha, weighted_mean
 
@@ -138,7 +139,8 @@ def _noise_rows(d, isubs):
     if d.noise_stds is not None:
         return np.ascontiguousarray(np.asarray(d.noise_stds)[isubs, 0], dtype=np.float64)
     sub = np.asarray(d.subints)
-    return np.array([get_noise(sub[i, 0], chans=True) for i in isubs], dtype=np.float64)
+    return np.array([get_noise(sub[i, 0], method=noise_method_in_force() or "PS", chans=True) for i in isubs],
+                    dtype=np.float64)
 
 
 def _take_subints(subints, ok_isubs):

@@ -15,6 +15,8 @@ import sys
 import threading
 import time
 
+from .archive import add_noise_method_option, noise_method_refusal, noise_method_scope
+
 MODULE = "pulseportraiture_amd.pptoas_run"
 GRACE_S = 10.0
 PG_TIMEOUT_S = 1800.0
@@ -179,11 +181,14 @@ def parser():
     ap.add_argument("--backend", choices=("auto", "nccl", "gloo"), default="auto",
                     help="Process-group backend for --gpus > 1: auto = nccl when every rank has a GPU of "
                          "its own, gloo when ranks share one.")
+    add_noise_method_option(ap)
     return ap
 
 
 def refusal(opts):
     """The message for an option this command cannot honour, or None."""
+    if noise_method_refusal(opts) is not None:
+        return noise_method_refusal(opts)
     if opts.psrchive:
         return "--psrchive needs PSRCHIVE, which this package does not use"
     if opts.tscrunch:
@@ -268,11 +273,12 @@ def run(opts):
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
         dist.init_process_group(backend, timeout=timedelta(seconds=PG_TIMEOUT_S))
     try:
-        gt = GetTOAs(opts.datafiles, opts.modelfile, quiet=opts.quiet)
-        if opts.narrowband:
-            gt.get_narrowband_TOAs(**get_narrowband_kwargs(opts))
-        else:
-            gt.get_TOAs(distributed=world > 1, **get_toas_kwargs(opts))
+        with noise_method_scope(opts.noise_method):
+            gt = GetTOAs(opts.datafiles, opts.modelfile, quiet=opts.quiet)
+            if opts.narrowband:
+                gt.get_narrowband_TOAs(**get_narrowband_kwargs(opts))
+            else:
+                gt.get_TOAs(distributed=world > 1, **get_toas_kwargs(opts))
         if rank == 0:
             toas = one_DM_toas(gt) if (opts.one_DM and not opts.narrowband) else gt.TOA_list
             write_TOAs(toas, inf_is_zero=True, SNR_cutoff=opts.snr_cutoff, outfile=opts.outfile, append=True)

@@ -47,7 +47,13 @@ def fit_portrait_full(data_port, model_port, init_params, P, freqs,
     like the reference (pptoaslib.py:995-997 drops them for the other methods): the
     box-constrained optimum is found by an active-set iteration over device fits
     (_fit_with_bounds); an unknown method exits like the reference does
-    (pptoaslib.py:1008-1010)."""
+    (pptoaslib.py:1008-1010).
+
+    errs=None: the fit measures each channel's noise itself, in the pass that transforms
+    the row, and that measurement is always the power-spectrum estimate (get_noise
+    method "PS") whatever noise method is chosen elsewhere.  For the "fit" estimator pass
+    errs (pplib.get_noise(port, method="fit", chans=True)); get_TOAs passes the bunch's
+    noise_stds, which load_data(noise_method="fit") measures that way."""
     if method not in _METHODS:
         print("Method '%s' is not implemented." % method)
         sys.exit()

@@ -8,6 +8,7 @@ import sys
 
 import numpy as np
 
+from .archive import noise_kwargs
 from .engine import default_engine
 
 
@@ -18,22 +19,26 @@ def _good_mask(data, isubs):
     return good
 
 
-def get_zap_channels(data, nstd=3):
+def get_zap_channels(data, nstd=3, noise_method=None):
     """Proposed channels to zap by the median algorithm (ppzap.py:18-47): in every good
     subint, channels whose noise is more than nstd standard deviations above the median
     of the good channels' noise are flagged and removed, until a round flags none.
 
     data is a DataBunch; its noise_stds[isub, 0] are used, or the power-spectrum noise
-    of its portraits measured on the device when it has none.  Returns one sorted list
+    of its portraits measured on the device when it has none -- with the estimator in force
+    (archive.noise_method_scope), else 'PS'.  noise_stds that the bunch carries are the
+    caller's and are clipped as they are, whatever is in force: ppzap_run puts the noise of
+    the NORMALISED rows there, which a second measurement here would undo.  Only an
+    explicit noise_method ('PS' or 'fit') measures anew over them.  Returns one sorted list
     of channel indices per entry of data.ok_isubs, in that order."""
     isubs = np.asarray(data.ok_isubs, dtype=int)
     if not len(isubs):
         return []
     eng = default_engine()
-    if data.noise_stds is not None:
+    if data.noise_stds is not None and noise_method is None:
         noise = np.asarray(data.noise_stds, dtype=np.float64)[isubs, 0]
     else:
-        noise = eng.channel_noise(np.asarray(data.subints)[isubs, 0])[0]
+        noise = eng.channel_noise(np.asarray(data.subints)[isubs, 0], **noise_kwargs(noise_method))[0]
     zap = eng.zap_median(noise, _good_mask(data, isubs), nstd)
     return [[int(n) for n in np.nonzero(row)[0]] for row in zap]
 

@@ -14,7 +14,8 @@ import sys
 
 import numpy as np
 
-from .archive import LOAD_ERRORS, list_datafiles, load_bunch
+from .archive import (LOAD_ERRORS, add_noise_method_option, list_datafiles, load_bunch, noise_kwargs, noise_method_refusal,
+                      noise_method_scope)
 from .pptoas_run import PG_TIMEOUT_S, _backend, launch
 
 MODULE = "pulseportraiture_amd.ppzap_run"
@@ -59,11 +60,14 @@ def parser():
     ap.add_argument("--backend", choices=("auto", "nccl", "gloo"), default=None,
                     help="With -m and --gpus > 1: process-group backend; auto = nccl when every rank has "
                          "a GPU of its own, gloo when ranks share one. [default=auto]")
+    add_noise_method_option(ap)
     return ap
 
 
 def refusal(opts):
     """The message for an option this command cannot honour, or None."""
+    if noise_method_refusal(opts) is not None:
+        return noise_method_refusal(opts)
     if opts.tscrunch:
         return "-T/--tscrunch needs PSRCHIVE, which this package does not use: scrunch the archives with ppscrunch_run -T first"
     if opts.hist:
@@ -102,12 +106,13 @@ def noise_method(opts):
             continue
         nchan += int(sum(len(c) for c in data.ok_ichans))
         isubs = np.asarray(data.ok_isubs, dtype=int)
-        if opts.norm is not None and len(isubs):
+        # (an estimator in force is measured whatever the archive stores)
+        if (opts.norm is not None or noise_kwargs()) and len(isubs):
             noise = np.zeros((data.nsub, 1, data.nchan)) if data.noise_stds is None else \
                 np.array(data.noise_stds, dtype=np.float64)
             noise[isubs, 0] = default_engine().channel_noise(
                 np.asarray(data.subints)[isubs, 0], norm=opts.norm,
-                weights=np.asarray(data.weights)[isubs])[0]
+                weights=np.asarray(data.weights)[isubs], **noise_kwargs())[0]
             data.noise_stds = noise
         names.append(datafile)
         zap_channels.append(get_zap_channels(data, nstd=nstd))
@@ -177,11 +182,13 @@ def main(argv=None):
         print("ppzap_run: " + msg, file=sys.stderr)
         return 2
     if opts.modelfile is None:
-        return noise_method(opts)
+        with noise_method_scope(opts.noise_method):
+            return noise_method(opts)
     if opts.gpus > 1 and "RANK" not in os.environ:
         # (before torch is imported or a GPU is touched: the ranks are a child process)
         return launch(opts.gpus, argv, module=MODULE)
-    return model_method(opts)
+    with noise_method_scope(opts.noise_method):
+        return model_method(opts)
 
 
 if __name__ == "__main__":

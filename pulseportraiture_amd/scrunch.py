@@ -66,11 +66,11 @@ def group_epoch(epochs, Ws, P):
     return epochs[r] + MJD(0, float(k * P / 86400.0))
 
 
-def measured(eng, d):
-    """noise_stds and SNRs [nsub,npol,nchan] of d's rows, on the device (archive.measure).  Here, and for the bunch that
-    pplib.load_data is handed, a row of zeros -- a dead cell, with no noise to divide by -- has S/N 0, not the NaN
-    that a loaded archive gets."""
-    measure(eng, d)
+def measured(eng, d, noise_method=None):
+    """noise_stds and SNRs [nsub,npol,nchan] of d's rows, on the device (archive.measure; noise_method: its
+    estimator).  Here, and for the bunch that pplib.load_data is handed, a row of zeros -- a dead cell, with no noise
+    to divide by -- has S/N 0, not the NaN that a loaded archive gets."""
+    measure(eng, d, noise_method=noise_method)
     shape = (d.nsub, d.npol, d.nchan)
     d.noise_stds = d.noise_stds.reshape(shape)
     d.SNRs = np.nan_to_num(d.SNRs, nan=0.0).reshape(shape)

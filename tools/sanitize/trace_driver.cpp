@@ -350,6 +350,27 @@ static void aux_rows_calls(pp_ctx* c, const AuxCfg& k, const char* tag) {
     }
     { Outs o; double* snrs = o.d(nrows);
       AUX(o, name("pp_channel_snrs"), pp_channel_snrs(c, in.src(), in.dtype(), k.dev, nrows, B, 3.25, snrs)); }
+    // the 'fit' noise method: both model functions, with and without the optional outputs
+    for (int fn : {PP_KC_EXP_DC, PP_KC_HALF_TRI}) {
+        Outs o; double* norms = o.d(nrows); double* noise = o.d(nrows);
+        int32_t* kc = (int32_t*)o.raw(nrows, 4); int32_t* cell = (int32_t*)o.raw((size_t)nrows * 3, 4);
+        AUX(o, name(fn == PP_KC_EXP_DC ? "pp_channel_noise_fit exp_dc" : "pp_channel_noise_fit half_tri"),
+            pp_channel_noise_fit(c, in.src(), in.dtype(), k.dev, nrows, B, PP_NOISEFIT_ROWS, fn, 1.1, PP_NORM_RMS, nullptr, norms, noise, kc, cell));
+    }
+    { Outs o; double* norms = o.d(nrows); double* noise = o.d(nrows);
+      AUX(o, name("pp_channel_noise_fit prof"),
+          pp_channel_noise_fit(c, in.src(), in.dtype(), k.dev, nrows, B, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, 1.1, PP_NORM_PROF, in.scales.data(), norms, noise,
+                               nullptr, nullptr)); }
+    { Outs o; double* snrs = o.d(nrows);
+      AUX(o, name("pp_channel_snrs_fit"), pp_channel_snrs_fit(c, in.src(), in.dtype(), k.dev, nrows, B, PP_KC_EXP_DC, 1.1, 3.25, snrs)); }
+    if (!k.f32) {       // rows that already are power spectra: H = B / 2 + 1 f64 values each, read from the front of the rows
+        const int H = B / 2 + 1;
+        const int np_ = (int)((size_t)nrows * B / H);
+        Outs o; double* norms = o.d(np_); double* noise = o.d(np_);
+        int32_t* kc = (int32_t*)o.raw(np_, 4); int32_t* cell = (int32_t*)o.raw((size_t)np_ * 3, 4);
+        AUX(o, name("pp_channel_noise_fit pows"),
+            pp_channel_noise_fit(c, in.src(), PP_F64, k.dev, np_, B, PP_NOISEFIT_POWS, PP_KC_EXP_DC, 1.1, PP_NORM_NONE, nullptr, norms, noise, kc, cell));
+    }
     // pca: the first C rows as a portrait (C < B: the dual side), then, for the shortest rows, 80 of them (nchan >= nbin)
     for (int nchan : {C, 80}) {
         if (nchan > nrows || (nchan == 80 && B != 64)) continue;
@@ -506,6 +527,8 @@ static void aux_refusals(int C, int B) {
         REF("pp_rfft_rows nbin", pp_rfft_rows(c, src, PP_F64, ns, B2, out));
         REF("pp_channel_noise nbin", pp_channel_noise(c, src, PP_F64, 0, ns, B2, PP_NORM_NONE, nullptr, out, out));
         REF("pp_channel_snrs nbin", pp_channel_snrs(c, src, PP_F64, 0, ns, B2, 3.25, out));
+        REF("pp_channel_noise_fit nbin", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B2, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, 1.1, PP_NORM_NONE, nullptr, out, out, nullptr, nullptr));
+        REF("pp_channel_snrs_fit nbin", pp_channel_snrs_fit(c, src, PP_F64, 0, ns, B2, PP_KC_EXP_DC, 1.1, 3.25, out));
         REF("pp_pca_gram nbin", pp_pca_gram(c, src, PP_F64, 0, C, B2, w, (double)C, C - 1.0, out, out));
         REF("pp_gaussian_portrait nbin", pp_gaussian_portrait(c, C, B2, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5, out, 0));
         REF("pp_model_set_gaussian nbin", pp_model_set_gaussian(c, 2, C, B2, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5));
@@ -532,6 +555,23 @@ static void aux_refusals(int C, int B) {
     REF("pp_channel_noise prof without divisors", pp_channel_noise(c, src, PP_F64, 0, ns, B, PP_NORM_PROF, nullptr, out, out));
     REF("pp_channel_snrs nrows", pp_channel_snrs(c, src, PP_F64, 0, 0, B, 3.25, out));
     REF("pp_channel_snrs null", pp_channel_snrs(c, src, PP_F64, 0, ns, B, 3.25, nullptr));
+    REF("pp_channel_noise_fit nrows", pp_channel_noise_fit(c, src, PP_F64, 0, 0, B, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, 1.1, PP_NORM_NONE, nullptr, out, out, nullptr, nullptr));
+    REF("pp_channel_noise_fit kind", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B, 2, PP_KC_EXP_DC, 1.1, PP_NORM_NONE, nullptr, out, out, nullptr, nullptr));
+    REF("pp_channel_noise_fit fn", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B, PP_NOISEFIT_ROWS, 2, 1.1, PP_NORM_NONE, nullptr, out, out, nullptr, nullptr));
+    REF("pp_channel_noise_fit fact", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, -1.0, PP_NORM_NONE, nullptr, out, out, nullptr, nullptr));
+    REF("pp_channel_noise_fit method", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, 1.1, 9, nullptr, out, out, nullptr, nullptr));
+    REF("pp_channel_noise_fit prof without divisors", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, 1.1, PP_NORM_PROF, nullptr, out, out, nullptr, nullptr));
+    REF("pp_channel_noise_fit pows f32", pp_channel_noise_fit(c, src, PP_F32, 0, ns, B, PP_NOISEFIT_POWS, PP_KC_EXP_DC, 1.1, PP_NORM_NONE, nullptr, out, out, nullptr, nullptr));
+    REF("pp_channel_noise_fit pows norm", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B, PP_NOISEFIT_POWS, PP_KC_EXP_DC, 1.1, PP_NORM_RMS, nullptr, out, out, nullptr, nullptr));
+    REF("pp_channel_noise_fit null", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, 1.1, PP_NORM_NONE, nullptr, nullptr, out, nullptr, nullptr));
+    REF("pp_channel_snrs_fit null", pp_channel_snrs_fit(c, src, PP_F64, 0, ns, B, PP_KC_EXP_DC, 1.1, 3.25, nullptr));
+    { double a20[20]; int32_t kc20[20];
+      REF("pp_noise_fit_grid fn", pp_noise_fit_grid(33, 5, a20, kc20));
+      REF("pp_noise_fit_grid null", pp_noise_fit_grid(33, PP_KC_EXP_DC, nullptr, kc20));
+      mark("case aux pp_noise_fit_grid"); ++g_ncase;
+      for (int H : {5, 33, 2049})
+          for (int fn : {PP_KC_EXP_DC, PP_KC_HALF_TRI})
+              if (pp_noise_fit_grid(H, fn, a20, kc20) != PP_OK || kc20[0] < 1 || kc20[19] > H) { fprintf(stderr, "pp_noise_fit_grid(%d, %d)\n", H, fn); exit(1); } }
     REF("pp_zap_median shape", pp_zap_median(c, sc, (const unsigned char*)src, 0, C, 5.0, (unsigned char*)out));
     REF("pp_zap_median channels", pp_zap_median(c, sc, (const unsigned char*)src, ns, 5000, 5.0, (unsigned char*)out));
     REF("pp_pca_gram nchan", pp_pca_gram(c, src, PP_F64, 0, 1, B, w, 1.0, 1.0, out, out));
@@ -544,6 +584,7 @@ static void aux_refusals(int C, int B) {
         REF("pp_synth_portraits dtype", pp_synth_portraits(c, 0, out, dt, ns, f, P, p3, nullptr, 0.05, 7, 0));
         REF("pp_channel_noise dtype", pp_channel_noise(c, src, dt, 0, ns, B, PP_NORM_NONE, nullptr, out, out));
         REF("pp_channel_snrs dtype", pp_channel_snrs(c, src, dt, 0, ns, B, 3.25, out));
+        REF("pp_channel_noise_fit dtype", pp_channel_noise_fit(c, src, dt, 0, ns, B, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, 1.1, PP_NORM_NONE, nullptr, out, out, nullptr, nullptr));
         REF("pp_pca_gram dtype", pp_pca_gram(c, src, dt, 0, C, B, w, (double)C, C - 1.0, out, out));
         REF("pp_model_set dtype", pp_model_set(c, 2, src, dt, 0, C, B));
     }
@@ -656,6 +697,7 @@ static void aux_refusals(int C, int B) {
         REF("pending pp_rfft_rows", pp_rfft_rows(c, src, PP_F64, ns, B, out));
         REF("pending pp_channel_noise", pp_channel_noise(c, src, PP_F64, 0, ns, B, PP_NORM_NONE, nullptr, out, out));
         REF("pending pp_channel_snrs", pp_channel_snrs(c, src, PP_F64, 0, ns, B, 3.25, out));
+        REF("pending pp_channel_noise_fit", pp_channel_noise_fit(c, src, PP_F64, 0, ns, B, PP_NOISEFIT_ROWS, PP_KC_EXP_DC, 1.1, PP_NORM_NONE, nullptr, out, out, nullptr, nullptr));
         REF("pending pp_zap_median", pp_zap_median(c, sc, (const unsigned char*)src, ns, C, 5.0, (unsigned char*)out));
         REF("pending pp_pca_gram", pp_pca_gram(c, src, PP_F64, 0, C, B, w, (double)C, C - 1.0, out, out));
         REF("pending pp_pca_basis", pp_pca_basis(c, vecs.data(), lam.data(), 3, out, out));
