@@ -570,6 +570,28 @@ int pp_channel_red_chi2(pp_ctx* ctx, const void* src, int dtype, int on_device,
                         const double* params5, const double* nu_refs3,
                         const double* scales, const double* errs, double* red_chi2);
 
+/* The fit's residual portrait: what GetTOAs.show_fit(..., return_fit=True) returns
+ * (pptoas.py:1317-1419) and their difference.  With phi_in and tau_in as for
+ * pp_channel_red_chi2, B_k = 1 / (1 + 2 pi i k tau_in), d = rfft(src[i][n]), m the
+ * template of the subint's model slot (null: slot 0) and a = scales[i][n]:
+ *   frame 0 ("model"): D_k = d_k e^{2 pi i k phi_in},  Mo_k = a B_k m_k
+ *   frame 1 ("data"):  D_k = d_k,                      Mo_k = a B_k m_k e^{-2 pi i k phi_in}
+ * (DC is not rotated; the Nyquist harmonic keeps its real part, as irfft does) and
+ *   port = irfft(D), model = irfft(Mo), resid = irfft(D - Mo)   [nsub][nchan][nbin] of `dtype`
+ *   red_chi2[nsub][nchan] = sum_bins resid^2 / errs^2 / (nbin - 2), by Parseval, the same
+ *   figure in both frames and bit for bit pp_channel_red_chi2's.
+ * Every output may be null (not formed, not stored), at least one must be given; errs may be
+ * null unless red_chi2 is asked for.  mask[nsub][nchan] (host, may be null): rows of weight 0
+ * or NaN are not read, their port / model / resid rows are zeros and their red_chi2 NaN.
+ * Host input gives host outputs; a device input (`on_device`) gives device outputs, red_chi2
+ * included, with no copy to the host.  The per-subint arrays are host arrays either way. */
+int pp_fit_residuals(pp_ctx* ctx, const void* src, int dtype, int on_device, int nsub,
+                     int nchan, int nbin, const int32_t* model_slot, const double* freqs,
+                     int64_t freqs_stride, const double* P, const double* params5,
+                     const double* nu_refs3, const double* scales, const double* errs,
+                     const double* mask, int frame, void* port, void* model, void* resid,
+                     double* red_chi2);
+
 /* ---- ppzap ---------------------------------------------------------------- */
 /* The channel noise of ppzap's noise method (ppzap.py:200-241): for every row of src
  * [nrows][nbin] (`dtype`, host or device) the norm of normalize_portrait (pplib.py:2462-2507)

@@ -129,6 +129,10 @@ SYMBOLS = {
                                       C.c_int, C.c_int, C.POINTER(C.c_int32), c_double_p,
                                       C.c_int64, c_double_p, c_double_p, c_double_p,
                                       c_double_p, c_double_p, c_double_p]),
+    "pp_fit_residuals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   c_int32_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                   c_double_p, c_double_p, c_double_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "pp_channel_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    c_double_p, c_double_p, c_double_p]),
     "pp_zap_median": (C.c_int, [C.c_void_p, c_double_p, c_uint8_p, C.c_int, C.c_int, C.c_double,

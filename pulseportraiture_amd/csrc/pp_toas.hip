@@ -98,9 +98,9 @@ __global__ void k_copy_words(unsigned long long* dst, const unsigned long long* 
 static int staged_copy(pp_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st = nullptr);
 __global__ void k_publish_int(int* host_dst, const int* dev_src) { *host_dst = *dev_src; }
 static int publish_int(pp_ctx* c, int* host_dst, const int* dev_src);
-enum KernelFamily { KF_MODEL = 0, KF_XSPEC, KF_PREP, KF_SEED, KF_ACCUM, KF_EVAL, KF_TAYLOR, KF_STEP, KF_FINAL, KF_SYNTH, KF_FPS, KF_SCATMODEL, KF_PCA, KF_GAUSSRES, KF_GAUSSNORM, KF_NBSFFT, KF_NBSFIT, KF_SCRUNCH, KF_NOISEFIT, KF_COUNT };
+enum KernelFamily { KF_MODEL = 0, KF_XSPEC, KF_PREP, KF_SEED, KF_ACCUM, KF_EVAL, KF_TAYLOR, KF_STEP, KF_FINAL, KF_SYNTH, KF_FPS, KF_SCATMODEL, KF_PCA, KF_GAUSSRES, KF_GAUSSNORM, KF_NBSFFT, KF_NBSFIT, KF_SCRUNCH, KF_NOISEFIT, KF_RESID, KF_COUNT };
 static const char* kFamilyNames[KF_COUNT] = {"model_fft", "xspec", "prep", "seed", "accum", "eval", "taylor_solve", "step", "finalize",
-                                            "synth", "fit_phase_shift", "scat_model", "pca_gram", "gauss_resid", "gauss_normal", "nbscat_fft", "nbscat_fit", "scrunch", "noise_fit"};
+                                            "synth", "fit_phase_shift", "scat_model", "pca_gram", "gauss_resid", "gauss_normal", "nbscat_fft", "nbscat_fit", "scrunch", "noise_fit", "fit_resid"};
 
 #define PP_NSTAGE 3     // enqueued batches that may be pending at once (staging blocks, work-buffer sets)
 struct pp_ctx {
@@ -2212,3 +2212,4 @@ extern "C" int pp_fit_wait(pp_ctx* c) {
 #include "pp_nbscat.h"
 #include "pp_wavelet.h"
 #include "pp_fake.h"
+#include "pp_resid.h"

@@ -99,6 +99,8 @@ def _dp(a):
 
 
 NOISE_METHODS = _lib.NOISE_METHODS
+_RESID_OUTPUTS = ("port", "model", "resid", "red_chi2")     # what fit_residuals can return
+_RESID_FRAMES = {"model": 0, "data": 1}
 
 
 def _noise_method(method, fn='exp_dc'):
@@ -782,6 +784,54 @@ class Engine(object):
             self._ctx, src, dtype, on_dev, nsub, nchan, nbin,
             None if sl is None else sl.ctypes.data_as(c_int32_p), _dp(freqs), fstride, _dp(P),
             _dp(params), _dp(nu_refs), _dp(scales), _dp(errs), _dp(out)), "pp_channel_red_chi2")
+        return out
+
+    def fit_residuals(self, ports, freqs, P, params, nu_refs, scales, errs=None, mask=None, slots=None,
+                      frame="model", want=("resid",)):
+        """The fit's residual portrait (show_fit(..., return_fit=True), pptoas.py:1317-1419).
+        params[nsub,5] = phi, DM, GM, tau [rot, linear], alpha at nu_refs[nsub,3]; scales[nsub,nchan]
+        the fitted amplitudes; the template is the resident model slot of each subint.  frame
+        "model": `port` is the data rotated onto the template and `model` the scattered, scaled
+        template (the reference's pair); frame "data": `port` is the data as it is and `model` the
+        template rotated back onto it.  `resid` = port - model from ONE inverse transform;
+        `red_chi2`[nsub,nchan] (needs errs) is channel_red_chi2's figure, the same in both frames.
+        mask[nsub,nchan]: rows of weight 0 or NaN are not read and come back as zeros (red_chi2 NaN).
+        Returns a dict of the arrays named in `want`: NumPy for NumPy input, device tensors (new
+        ones, of the input's type; red_chi2 float64) for a device tensor."""
+        want = tuple(want)
+        if not want or any(w not in _RESID_OUTPUTS for w in want):
+            raise ValueError("want must name some of %s" % (_RESID_OUTPUTS,))
+        if frame not in _RESID_FRAMES:
+            raise ValueError("frame must be 'model' or 'data', not %r" % (frame,))
+        if "red_chi2" in want and errs is None:
+            raise ValueError("fit_residuals: red_chi2 needs errs")
+        src, dtype, on_dev, (nsub, nchan, nbin), keep = _array_arg(ports, "fit_residuals: device ports")
+        freqs, fstride, P, _ = self._subint_args(freqs, P, None, nsub, nchan)
+        params = _f64(params, (nsub, 5))
+        nu_refs = _f64(nu_refs, (nsub, 3))
+        scales = _f64(scales, (nsub, nchan))
+        errs = _f64(errs, (nsub, nchan))
+        mask = _f64(mask, (nsub, nchan))
+        sl = None
+        if slots is not None:
+            sl = np.ascontiguousarray(np.broadcast_to(np.asarray(slots, dtype=np.int32), (nsub,)))
+        out, ptr = {}, {}
+        for name in _RESID_OUTPUTS:
+            if name not in want:
+                ptr[name] = None
+            elif on_dev:
+                import torch
+                out[name] = (torch.empty((nsub, nchan), dtype=torch.float64, device=keep.device)
+                             if name == "red_chi2" else torch.empty_like(keep))
+                ptr[name] = C.c_void_p(out[name].data_ptr())
+            else:
+                out[name] = np.empty((nsub, nchan)) if name == "red_chi2" else np.empty_like(keep)
+                ptr[name] = C.c_void_p(out[name].ctypes.data)
+        _check(self._lib.pp_fit_residuals(
+            self._ctx, src, dtype, on_dev, nsub, nchan, nbin,
+            None if sl is None else sl.ctypes.data_as(c_int32_p), _dp(freqs), fstride, _dp(P),
+            _dp(params), _dp(nu_refs), _dp(scales), _dp(errs), _dp(mask), _RESID_FRAMES[frame],
+            ptr["port"], ptr["model"], ptr["resid"], ptr["red_chi2"]), "pp_fit_residuals")
         return out
 
     def channel_noise(self, ports, norm=None, weights=None, method='PS', fact=1.1, fn='exp_dc'):

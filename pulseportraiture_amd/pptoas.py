@@ -1212,3 +1212,111 @@ class GetTOAs(object):
                 zap_channels.append(bad)
             self.channel_red_chi2s.append(channel_red_chi2s)
             self.zap_channels.append(zap_channels)
+
+    # -- the fit's residual portrait -----------------------------------------
+    def _fitted_archive(self, datafile):
+        """Index among the fitted archives of `datafile` (None: the first one listed), as show_fit
+        looks it up (pptoas.py:1332-1335)."""
+        if datafile is None:
+            datafile = self.datafiles[0]
+        for iarch, idatafile in enumerate(self.ok_idatafiles):
+            f = self.datafiles[idatafile]
+            if f is datafile or (isinstance(f, str) and isinstance(datafile, str) and f == datafile):
+                return iarch
+        raise ValueError("%s is not among the fitted archives" % (datafile if isinstance(datafile, str) else "datafile"))
+
+    def _fitted_inputs(self, eng, iarch, isubs):
+        """What Engine.fit_residuals takes for the fitted subints `isubs` of fitted archive iarch,
+        rebuilt from the stored results the way get_channels_to_zap rebuilds them: the Doppler
+        factors undone, 10**tau for log10_tau, the unscattered template's slot where tau != 0,
+        the instrumental response, the scrunched archive after tscrunch=True, a dedispersed
+        archive put back.  Returns (d, port, params, nu_refs, scales, noise, slot_of, mask)."""
+        data, fname = load_bunch(self.datafiles[self.ok_idatafiles[iarch]])
+        if getattr(self, "tscrunch", False):
+            data = _tscrunched(eng, data)
+        d = data
+        isubs = np.asarray(isubs, dtype=int)
+        n = len(isubs)
+        params = np.zeros((n, 5))
+        slots, slot_of = {}, np.zeros(n, dtype=np.int32)
+        scales, mask = np.zeros((n, d.nchan)), np.zeros((n, d.nchan))
+        for j, isub in enumerate(isubs):
+            df = self.doppler_fs[iarch][isub] if self.bary else 1.0
+            tau = self.taus[iarch][isub]
+            if tau != 0.0 and self.log10_tau:
+                tau = 10.0 ** tau
+            params[j] = [self.phis[iarch][isub], self.DMs[iarch][isub] / df,
+                         self.GMs[iarch][isub] / df ** 3, tau, self.alphas[iarch][isub]]
+            scat = bool(tau != 0.0)
+            use_ird = bool(getattr(self, "add_instrumental_response", False) and
+                           (self.ird['DM'] or len(self.ird['wids'])))
+            key = (d.freqs[isub].tobytes(), scat,
+                   np.float64(d.Ps[isub]).tobytes() if use_ird else b"")
+            slot_of[j] = self._template_slot(eng, slots, key, d, isub, d.Ps.mean(), scat, use_ird)
+            scales[j] = self.scales[iarch][isub]
+            mask[j, np.asarray(d.ok_ichans[isub], dtype=int)] = 1.0
+        port = _dededisperse(eng, _take_subints(d.subints, isubs), d, isubs)
+        nu_refs = np.array([self.nu_refs[iarch][isub] for isub in isubs], dtype=np.float64)
+        return d, port, params, nu_refs, scales, _noise_rows(d, isubs), slot_of, mask
+
+    def show_fit(self, datafile=None, isub=0, rotate=0.0, show=False, return_fit=True,
+                 savefig=False, quiet=None):
+        """The fit of one subint as the reference returns it (pptoas.py:1317-1419; get_TOAs
+        must have been called first): (port, model_scaled, ok_ichans, freqs, noise_stds) --
+        the subint rotated by the fitted (phi, DM, GM) onto the template, zapped channels
+        zeroed, and the template scattered by the fitted (tau, alpha) and multiplied by the
+        fitted amplitudes; both turned by `rotate` [rot].  One device call
+        (Engine.fit_residuals).  Plots are not drawn here.  `quiet` is taken for the
+        reference's signature and has no effect: nothing is printed either way."""
+        if show or savefig:
+            raise NotImplementedError("plots are outside the accelerated path")
+        eng = self._engine(False)
+        iarch = self._fitted_archive(datafile)
+        d, port, params, nu_refs, scales, noise, slot_of, mask = self._fitted_inputs(eng, iarch, [isub])
+        fit = eng.fit_residuals(port, d.freqs[[isub]], d.Ps[[isub]], params, nu_refs, scales, mask=mask,
+                                slots=slot_of, frame="model", want=("port", "model"))
+        out = []
+        for name in ("port", "model"):
+            a = fit[name]
+            if rotate:
+                a = eng.rotate_portraits(a, np.full(d.nchan, np.inf), 1.0, phi=float(rotate))
+            out.append((a.cpu().numpy() if hasattr(a, "is_cuda") else a)[0])
+        if return_fit:
+            return (out[0], out[1], d.ok_ichans[isub], d.freqs[isub], noise[0])
+
+    def get_residuals(self, datafile=None, frame="model", on_device=False):
+        """The residual portrait -- data minus fitted model -- of every fitted subint of one
+        archive, in one device call (get_TOAs must have been called first).  frame "model": the
+        rows aligned with the template (show_fit's port - model_scaled); "data": the rows as
+        they were fitted, the model rotated back onto them.  Returns a DataBunch of
+        resid[nsub,nchan,nbin] (zero rows for subints and channels that were not fitted; a
+        device tensor with on_device), channel_red_chi2[nsub,nchan] (time domain, dof = nbin - 2;
+        NaN where nothing was fitted), the noise_stds[nsub,nchan] it was formed with, ok_isubs and
+        ok_ichans."""
+        eng = self._engine(False)
+        iarch = self._fitted_archive(datafile)
+        ok_isubs = np.asarray(self.ok_isubs[iarch], dtype=int)
+        d, port, params, nu_refs, scales, noise, slot_of, mask = self._fitted_inputs(eng, iarch, ok_isubs)
+        if on_device:
+            port = _to_device_once(eng, port)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            fit = eng.fit_residuals(port, d.freqs[ok_isubs], d.Ps[ok_isubs], params, nu_refs, scales, errs=noise,
+                                    mask=mask, slots=slot_of, frame=frame, want=("resid", "red_chi2"))
+        res, rchi2 = fit["resid"], fit["red_chi2"]
+        if hasattr(rchi2, "is_cuda"):
+            rchi2 = rchi2.cpu().numpy()
+        if hasattr(res, "is_cuda") and not on_device:
+            res = res.cpu().numpy()
+        shape = (d.nsub, d.nchan, d.nbin)
+        if hasattr(res, "is_cuda"):
+            resid = res.new_zeros(shape)
+            resid[ok_isubs.tolist()] = res
+        else:
+            resid = np.zeros(shape, dtype=res.dtype)
+            resid[ok_isubs] = res
+        channel_red_chi2 = np.full((d.nsub, d.nchan), np.nan)
+        channel_red_chi2[ok_isubs] = rchi2
+        noise_stds = np.full((d.nsub, d.nchan), np.nan)
+        noise_stds[ok_isubs] = noise
+        return DataBunch(resid=resid, channel_red_chi2=channel_red_chi2, noise_stds=noise_stds, ok_isubs=ok_isubs,
+                         ok_ichans=[np.asarray(d.ok_ichans[i], dtype=int) for i in range(d.nsub)])

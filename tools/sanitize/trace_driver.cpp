@@ -332,6 +332,25 @@ static void aux_ports_calls(pp_ctx* c, const AuxCfg& k, const char* tag) {
     { Outs o; double* rc2 = o.d(in.nrow);
       AUX(o, name("pp_channel_red_chi2"), pp_channel_red_chi2(c, in.src(), in.dtype(), k.dev, ns, C, B, in.slot(), in.freqs.data(), in.fstride(), in.P.data(),
           in.params5.data(), in.nus3.data(), in.scales.data(), in.errs.data(), rc2)); }
+    // pp_fit_residuals: all four outputs, the residual alone (no errs), and the model with chi^2 under a mask that
+    // drops the first and the last row; outputs live where the input lives
+    std::vector<double> mask(in.nrow, 1.0);
+    mask[0] = 0.0; mask[in.nrow - 1] = NAN;
+    for (int variant = 0; variant < 3; ++variant) {
+        Outs o;
+        const bool want[4] = {variant == 0, variant != 1, variant != 2, variant != 1};      // port, model, resid, red_chi2
+        void* out[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int j = 0; j < 4; ++j) {
+            if (!want[j]) continue;
+            const size_t n = j == 3 ? in.nrow : in.nrow * B, elem = j == 3 ? 8 : in.esz;
+            out[j] = k.dev ? dev_copy(nullptr, n * elem) : o.raw(n, elem);
+        }
+        static const char* names[3] = {"pp_fit_residuals all", "pp_fit_residuals resid", "pp_fit_residuals model chi2 masked"};
+        AUX(o, name(names[variant]), pp_fit_residuals(c, in.src(), in.dtype(), k.dev, ns, C, B, in.slot(), in.freqs.data(), in.fstride(), in.P.data(),
+            in.params5.data(), in.nus3.data(), in.scales.data(), variant == 1 ? nullptr : in.errs.data(), variant == 2 ? mask.data() : nullptr,
+            variant % 2, out[0], out[1], out[2], (double*)out[3]));
+        if (k.dev) for (int j = 0; j < 4; ++j) if (out[j]) dev_free(out[j]);
+    }
 }
 
 // the entry points that take rows: dtype and where the rows are
@@ -522,6 +541,7 @@ static void aux_refusals(int C, int B) {
         REF("pp_rotate_portraits nbin", pp_rotate_portraits(c, src, out, PP_F64, 0, ns, C, B2, f, 0, P, p3, INFINITY, INFINITY));
         REF("pp_align_accumulate nbin", pp_align_accumulate(c, src, PP_F64, 0, ns, C, B2, f, 0, P, p3, w, out, out));
         REF("pp_channel_red_chi2 nbin", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B2, nullptr, f, 0, P, p5, n3, sc, er, out));
+        REF("pp_fit_residuals nbin", pp_fit_residuals(c, src, PP_F64, 0, ns, C, B2, nullptr, f, 0, P, p5, n3, sc, er, nullptr, 0, out, nullptr, nullptr, nullptr));
         REF("pp_fit_phase_shift_batch nbin", pp_fit_phase_shift_batch(c, mp, mp, nullptr, ns, B2, -0.5, 0.5, 20, out));
         REF("pp_fit_phase_tau_batch nbin", pp_fit_phase_tau_batch(c, mp, mp, nullptr, mp, ns, B2, -0.5, 0.5, 20, 1, out));
         REF("pp_rfft_rows nbin", pp_rfft_rows(c, src, PP_F64, ns, B2, out));
@@ -541,6 +561,7 @@ static void aux_refusals(int C, int B) {
         REF("pp_rotate_portraits shape", pp_rotate_portraits(c, src, out, PP_F64, 0, s, ch, B, f, 0, P, p3, INFINITY, INFINITY));
         REF("pp_align_accumulate shape", pp_align_accumulate(c, src, PP_F64, 0, s, ch, B, f, 0, P, p3, w, out, out));
         REF("pp_channel_red_chi2 shape", pp_channel_red_chi2(c, src, PP_F64, 0, s, ch, B, nullptr, f, 0, P, p5, n3, sc, er, out));
+        REF("pp_fit_residuals shape", pp_fit_residuals(c, src, PP_F64, 0, s, ch, B, nullptr, f, 0, P, p5, n3, sc, er, nullptr, 0, out, nullptr, nullptr, nullptr));
     }
     REF("pp_reference_phase_seed Ns", pp_reference_phase_seed(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY, w, mp, -0.5, 0.5, 0, out));
     REF("pp_fit_phase_shift_batch nprof", pp_fit_phase_shift_batch(c, mp, mp, nullptr, 0, B, -0.5, 0.5, 20, out));
@@ -581,6 +602,7 @@ static void aux_refusals(int C, int B) {
         REF("pp_rotate_portraits dtype", pp_rotate_portraits(c, src, out, dt, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY));
         REF("pp_align_accumulate dtype", pp_align_accumulate(c, src, dt, 0, ns, C, B, f, 0, P, p3, w, out, out));
         REF("pp_channel_red_chi2 dtype", pp_channel_red_chi2(c, src, dt, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, out));
+        REF("pp_fit_residuals dtype", pp_fit_residuals(c, src, dt, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, nullptr, 0, out, nullptr, nullptr, nullptr));
         REF("pp_synth_portraits dtype", pp_synth_portraits(c, 0, out, dt, ns, f, P, p3, nullptr, 0.05, 7, 0));
         REF("pp_channel_noise dtype", pp_channel_noise(c, src, dt, 0, ns, B, PP_NORM_NONE, nullptr, out, out));
         REF("pp_channel_snrs dtype", pp_channel_snrs(c, src, dt, 0, ns, B, 3.25, out));
@@ -593,6 +615,7 @@ static void aux_refusals(int C, int B) {
         REF("pp_rotate_portraits freqs_stride", pp_rotate_portraits(c, src, out, PP_F64, 0, ns, C, B, f, fs, P, p3, INFINITY, INFINITY));
         REF("pp_align_accumulate freqs_stride", pp_align_accumulate(c, src, PP_F64, 0, ns, C, B, f, fs, P, p3, w, out, out));
         REF("pp_channel_red_chi2 freqs_stride", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B, nullptr, f, fs, P, p5, n3, sc, er, out));
+        REF("pp_fit_residuals freqs_stride", pp_fit_residuals(c, src, PP_F64, 0, ns, C, B, nullptr, f, fs, P, p5, n3, sc, er, nullptr, 0, out, nullptr, nullptr, nullptr));
     }
     // one null pointer at a time
     for (int z = 0; z < 9; ++z) {
@@ -603,6 +626,8 @@ static void aux_refusals(int C, int B) {
         REF("pp_align_accumulate null", pp_align_accumulate(NZ(8, c), NZ(0, src), PP_F64, 0, ns, C, B, NZ(1, f), 0, NZ(2, P), NZ(3, p3), NZ(4, w), NZ(6, out), NZ(7, out)));
         REF("pp_channel_red_chi2 null", pp_channel_red_chi2(NZ(8, c), NZ(0, src), PP_F64, 0, ns, C, B, nullptr, NZ(1, f), 0, NZ(2, P), NZ(3, p5), NZ(4, n3), NZ(5, sc),
                                                            NZ(7, er), NZ(6, out)));
+        REF("pp_fit_residuals null", pp_fit_residuals(NZ(8, c), NZ(0, src), PP_F64, 0, ns, C, B, nullptr, NZ(1, f), 0, NZ(2, P), NZ(3, p5), NZ(4, n3), NZ(5, sc),
+                                                     NZ(7, er), nullptr, 0, nullptr, nullptr, nullptr, NZ(6, out)));
         REF("pp_fit_phase_shift_batch null", pp_fit_phase_shift_batch(NZ(8, c), NZ(0, mp), NZ(1, mp), nullptr, ns, B, -0.5, 0.5, 20, NZ(6, out)));
         REF("pp_fit_phase_tau_batch null", pp_fit_phase_tau_batch(NZ(8, c), NZ(0, mp), NZ(1, mp), nullptr, NZ(2, mp), ns, B, -0.5, 0.5, 20, 1, NZ(6, out)));
         REF("pp_rfft_rows null", pp_rfft_rows(NZ(8, c), NZ(0, src), PP_F64, ns, B, NZ(6, out)));
@@ -643,6 +668,10 @@ static void aux_refusals(int C, int B) {
     }
     REF("pp_channel_red_chi2 unset slot", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B, badslot.data(), f, 0, P, p5, n3, sc, er, out));
     REF("pp_channel_red_chi2 slot of another shape", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C / 2, B, nullptr, f, 0, P, p5, n3, sc, er, out));
+    REF("pp_fit_residuals unset slot", pp_fit_residuals(c, src, PP_F64, 0, ns, C, B, badslot.data(), f, 0, P, p5, n3, sc, er, nullptr, 0, out, nullptr, nullptr, nullptr));
+    REF("pp_fit_residuals slot of another shape", pp_fit_residuals(c, src, PP_F64, 0, ns, C / 2, B, nullptr, f, 0, P, p5, n3, sc, er, nullptr, 0, out, nullptr, nullptr, nullptr));
+    REF("pp_fit_residuals frame", pp_fit_residuals(c, src, PP_F64, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, nullptr, 2, out, nullptr, nullptr, nullptr));
+    REF("pp_fit_residuals no output", pp_fit_residuals(c, src, PP_F64, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, nullptr, 0, nullptr, nullptr, nullptr, nullptr));
     REF("pp_model_apply_response unset slot", pp_model_apply_response(c, 9, mp, nullptr));
     REF("pp_model_apply_response slot out of range", pp_model_apply_response(c, -1, mp, nullptr));
     REF("pp_model_set slot", pp_model_set(c, PP_MAX_SLOTS, src, PP_F64, 0, C, B));
@@ -689,6 +718,7 @@ static void aux_refusals(int C, int B) {
         REF("pending pp_rotate_portraits", pp_rotate_portraits(c, src, out, PP_F64, 0, ns, C, B, f, 0, P, p3, INFINITY, INFINITY));
         REF("pending pp_align_accumulate", pp_align_accumulate(c, src, PP_F64, 0, ns, C, B, f, 0, P, p3, w, out, out));
         REF("pending pp_channel_red_chi2", pp_channel_red_chi2(c, src, PP_F64, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, out));
+        REF("pending pp_fit_residuals", pp_fit_residuals(c, src, PP_F64, 0, ns, C, B, nullptr, f, 0, P, p5, n3, sc, er, nullptr, 0, out, nullptr, nullptr, nullptr));
         REF("pending pp_gaussian_portrait", pp_gaussian_portrait(c, C, B, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5, out, 0));
         REF("pending pp_model_set_gaussian", pp_model_set_gaussian(c, 2, C, B, f, "000", 1500.0, 0.0, 0.0, -4.0, 1, p5));
         REF("pending pp_spline_portrait", pp_spline_portrait(c, C, B, f, 0, mp, 0, nullptr, nullptr, 3, out, 0));
